@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train-step samples/s of the text+vision fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no RANK in the environment) the script launches its own N ranks: before anything touches
@@ -23,7 +23,9 @@ the exchange, the clip and AdamW step batch by batch (32 samples per optimizer s
 same run's throughput with one batch per encoder pass.
 Prints ONE JSON line (rank 0) with the contract's fields plus `roofline` (the bf16 GEMM kernel,
 timed with HIP events on its stream) and `cpu_baseline` (the oracle's same step on host cores,
-bounded sample).
+bounded sample).  After --warmup W untimed steps, exactly --steps K steps are timed (one block; --repeats R: R blocks of K
+steps, the median one reported); `ms_per_step` is the reported block's time over K.  Inputs and initial weights are
+seeded: the same arguments give the same inputs in every run, and --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -152,6 +154,36 @@ def cpu_baseline(B: int, slice_b: int = 8, warm: int = 3, timed: int = 20, budge
                       f"(L={SEQ_LEN}, {FRAMES}x{IMAGE}^2 frame; per-sample work identical to B={B}){short}: {med * 1e3:.0f} ms/step "
                       f"(min {min(times) * 1e3:.0f}, max {max(times) * 1e3:.0f}); host has {os.cpu_count()} cpus"}
 
+DUMP_SAMPLE = 16384        # elements kept of a larger parameter tensor in --dump-outputs
+DUMP_LIMIT = 64 << 20      # bytes of one dump, at most
+
+
+def dump_outputs(out_dir: str, out: dict, arena) -> None:
+    """--dump-outputs: what the timed path computed in its last step, as float32 DIR/<name>.npy -- the tensors the step
+    returned (loss, logits, probs, forensic, y; the lookahead path also returns its last group's per-step losses) and every
+    tensor of the trained parameter arena after that step (param.<name>), by name, so that builds with different arena layouts
+    compare.  A parameter above DUMP_SAMPLE elements is a fixed sample of its flattened elements, the same for every run and
+    build (a function of its size only)."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, (list, tuple)):
+            v = torch.stack(list(v))
+        arrays[k] = v.detach().float().cpu().numpy()
+    for key in arena.offsets:
+        flat = arena.view(key).detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["param." + key] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def exchange_probe(tr, dev, n: int = 20):
     """What RCCL saw: the process group's world size and the time of one gradient exchange of the step -- the two-bucket
     all-reduce of the flat fp32 gradient arena, exactly as the step issues it -- alone on the GPU (median of `n`, HIP events
@@ -226,7 +258,7 @@ def bench_train_encoders(args, dev, world, rank):
         fence()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            tr.train_step(batches[i % 4])
+            out = tr.train_step(batches[i % 4])
         enq = time.perf_counter() - t0          # the host has enqueued every launch of the block (about 1,200 per step)
         fence()
         dt = time.perf_counter() - t0
@@ -236,6 +268,8 @@ def bench_train_encoders(args, dev, world, rank):
             dt = float(t.item())
         blocks.append(dt)
         host.append(enq)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, tr.arena)
     dt = sorted(blocks)[len(blocks) // 2]
     flops, _ = gemm_flops_per_step(B)
     step_ms = dt / args.steps * 1e3
@@ -312,7 +346,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE configs[1]: 32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps, back to back; the reported figures are the median block")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of --steps steps, back to back; the reported figures are the median block (default 1: --steps is "
+                         "the number of timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0; see dump_outputs)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--seq-len", type=int, default=128, help="text length (BASELINE configs[3]: 512 with --batch 128)")
     ap.add_argument("--frames", type=int, default=1, help="frames per sample (BASELINE configs[4]: 8 with --batch 8 per GPU)")
@@ -393,9 +431,11 @@ def main():
             sync()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                tr.train_step(bl[i % 2])
+                out = tr.train_step(bl[i % 2])
             sync()
             blocks.append(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out, tr.arena)
         dt = sorted(blocks)[len(blocks) // 2]
         P = tr.arena.n_grad
         gbps = 11 * 4 * P / (dt / args.steps) / 1e9
@@ -443,15 +483,17 @@ def main():
     def run(n):
         """n optimizer steps, software-pipelined: the head / exchange / optimizer of the current batches overlap the encoders of
         the next ones.  G > 1: encoders once per group of G batches (a last, partial group still encodes all G: never less work)."""
+        out = None
         if G == 1:
             tr.prefetch_features(batches[0])
             for i in range(n):
-                tr.train_step_pipelined(batches[i % 4], batches[(i + 1) % 4] if i + 1 < n else None)
-            return
+                out = tr.train_step_pipelined(batches[i % 4], batches[(i + 1) % 4] if i + 1 < n else None)
+            return out
         ng = (n + G - 1) // G
         tr.prefetch_features(batches[0], group=True)
         for gi in range(ng):
-            tr.train_group_pipelined(batches[gi % 4], batches[(gi + 1) % 4] if gi + 1 < ng else None, steps=min(G, n - gi * G))
+            out = tr.train_group_pipelined(batches[gi % 4], batches[(gi + 1) % 4] if gi + 1 < ng else None, steps=min(G, n - gi * G))
+        return out
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -471,7 +513,7 @@ def main():
     for _ in range(max(1, args.repeats)):      # every block: EXACTLY --steps steps between two barrier + synchronize fences
         fence()
         t0 = time.perf_counter()
-        run(args.steps)
+        out = run(args.steps)
         fence()
         dt = time.perf_counter() - t0
         if dist.is_initialized():
@@ -479,6 +521,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         blocks.append(dt)
+    if args.dump_outputs and rank == 0:        # (before the legs below: they reuse the step's buffers and train on)
+        dump_outputs(args.dump_outputs, out, tr.arena)
     dt = sorted(blocks)[len(blocks) // 2]      # the median block is the one reported
     final_loss = float(tr.optim.state.read().loss)
     # the same steps with ONE batch per encoder pass (lookahead 1), in the same run, for comparison: not the headline
@@ -496,7 +540,7 @@ def main():
         torch.cuda.synchronize(dev)
         run1(args.warmup)
         b1 = []
-        for _ in range(3):
+        for _ in range(max(1, args.repeats)):
             fence()
             t0 = time.perf_counter()
             run1(args.steps)
@@ -507,9 +551,9 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 d1 = float(t.item())
             b1.append(d1)
-        d1 = sorted(b1)[1]
+        d1 = sorted(b1)[len(b1) // 2]
         la1 = {"value": round(world * B * args.steps / d1, 2), "ms_per_step": round(d1 / args.steps * 1e3, 4),
-               "what": "the same optimizer steps with one batch per encoder pass (lookahead 1), median of 3 blocks, same process"}
+               "what": f"the same optimizer steps with one batch per encoder pass (lookahead 1), median of {len(b1)} block(s), same process"}
 
     # ---- roofline of the dominant kernel (bf16 GEMM): HIP events around every launch, instrumented pass
     roof = None
