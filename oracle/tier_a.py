@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE (see oracle/__init__.py) -- Tier-A oracle.
 
-Functional torch-fp32 CPU restatement of the reference's trainable hot path:
+Functional torch CPU restatement of the reference's trainable hot path (fp32 as the reference, or fp64 as the
+yardstick the HIP kernels are measured against -- it follows the parameters' dtype):
 
   CrossModalTransformer.forward   src/models/fusion/cross_modal_transformer.py:134-210
   ForensicCoAttention.forward     src/models/fusion/cross_modal_transformer.py:39-55
@@ -91,15 +92,18 @@ def no_grad_keys_fusion():
     return [k for k in fusion_shapes() if k.startswith("semantic.") or k.startswith("classifier.")]
 
 
-def no_grad_keys_clf():
-    return ["temperature"] + [f"node.trees.{t}.tau" for t in range(TREES)]
+def no_grad_keys_clf(trees: int = TREES):
+    return ["temperature"] + [f"node.trees.{t}.tau" for t in range(trees)]
 
 
-def seeded_params(seed: int, use_gnn: bool = True) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+def seeded_params(seed: int, use_gnn: bool = True, hidden: int = HIDDEN, trees: int = TREES, depth: int = DEPTH,
+                  aux_dim: int = AUX_DIM, use_aux: bool = True) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
     """Deterministic, *perturbed* parameters (NODE leaves/gates non-zero so the
     tree path is exercised -- SURVEY.md 8c).  Regenerated from the seed on both
     sides of every comparison so fixtures stay small; a checksum of the result is
-    stored in each fixture to catch generator drift."""
+    stored in each fixture to catch generator drift.  The geometry arguments are classifier.yaml's hidden_dim /
+    node_trees / node_depth / aux_dim / use_aux (pre.0 is hidden + aux_dim wide only with use_aux); at the defaults
+    the draw order is the one every fixture was minted with."""
     g = torch.Generator().manual_seed(seed)
 
     def gen(key: str, shape) -> torch.Tensor:
@@ -117,13 +121,14 @@ def seeded_params(seed: int, use_gnn: bool = True) -> Tuple[Dict[str, torch.Tens
             return torch.randn(shape, generator=g) * (1.0 / math.sqrt(shape[1]))
         return torch.randn(shape, generator=g) * 0.05
 
-    fus = OrderedDict((k, gen(k, s)) for k, s in fusion_shapes(use_gnn=use_gnn).items())
-    clf = OrderedDict((k, gen(k, s)) for k, s in clf_shapes().items())
+    fus = OrderedDict((k, gen(k, s)) for k, s in fusion_shapes(hidden=hidden, use_gnn=use_gnn).items())
+    clf = OrderedDict((k, gen(k, s)) for k, s in clf_shapes(hidden=hidden, in_dim=hidden, aux_dim=aux_dim if use_aux else 0,
+                                                            trees=trees, depth=depth).items())
     return fus, clf
 
 
-def seeded_batch(seed: int, B: int) -> Dict[str, torch.Tensor]:
-    """FakeSV-shaped synthetic feature batch (SURVEY.md 8c 'Golden vectors')."""
+def seeded_batch(seed: int, B: int, aux_dim: int = AUX_DIM) -> Dict[str, torch.Tensor]:
+    """FakeSV-shaped synthetic feature batch (SURVEY.md 8c 'Golden vectors'); `aux` is (B, aux_dim)."""
     g = torch.Generator().manual_seed(seed)
     return {
         "text_features": torch.randn(B, TEXT_DIM, generator=g),
@@ -131,7 +136,7 @@ def seeded_batch(seed: int, B: int) -> Dict[str, torch.Tensor]:
         "visual_features": torch.randn(B, VISUAL_DIM, generator=g),
         "temporal_features": torch.randn(B, TEMPORAL_DIM, generator=g),
         "gnn_feat": torch.randn(B, GNN_DIM, generator=g),
-        "aux": torch.rand(B, AUX_DIM, generator=g),
+        "aux": torch.rand(B, aux_dim, generator=g),
         "label": torch.randint(0, 2, (B,), generator=g),
     }
 
@@ -153,17 +158,28 @@ def _co_attention(p: Dict[str, torch.Tensor], blk: str, x, y, evidence):
     return gated * (attn * v) + (1.0 - gated) * (0.5 * (x + y))
 
 
-def _drop(x, p: float, train: bool):
+def _drop(x, p: float, train: bool, mask: Optional[torch.Tensor] = None):
+    """nn.Dropout(p) in train mode, or -- with `mask` -- the given multipliers (0 or 1/(1-p)) instead of a fresh draw."""
+    if mask is not None:
+        return x * mask.to(x.dtype)
     return F.dropout(x, p, training=train) if (train and p > 0) else x
 
 
+def _mask(masks: Optional[Dict[str, torch.Tensor]], site: str) -> Optional[torch.Tensor]:
+    return None if masks is None else masks[site]
+
+
 def fusion_forward(p: Dict[str, torch.Tensor], feats: Dict[str, torch.Tensor],
-                   dropout: float = 0.1, train: bool = False) -> Dict[str, torch.Tensor]:
-    """CrossModalTransformer.forward, cross_modal_transformer.py:134-210."""
-    t = F.linear(feats["text_features"].float(), p["text_proj.weight"], p["text_proj.bias"])
-    a = F.linear(feats["audio_features"].float(), p["audio_proj.weight"], p["audio_proj.bias"])
-    v = F.linear(feats["visual_features"].float(), p["visual_proj.weight"], p["visual_proj.bias"])
-    u = F.linear(feats["temporal_features"].float(), p["temporal_proj.weight"], p["temporal_proj.bias"])
+                   dropout: float = 0.1, train: bool = False,
+                   masks: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """CrossModalTransformer.forward, cross_modal_transformer.py:134-210.  Runs in the parameters' dtype (float32 as in
+    the reference, or float64 as a high-precision yardstick).  `masks`: explicit dropout multipliers for the sites
+    "fuse0" (B, 2H) and "fuse3" (B, H) in place of F.dropout."""
+    dt = p["text_proj.weight"].dtype
+    t = F.linear(feats["text_features"].to(dt), p["text_proj.weight"], p["text_proj.bias"])
+    a = F.linear(feats["audio_features"].to(dt), p["audio_proj.weight"], p["audio_proj.bias"])
+    v = F.linear(feats["visual_features"].to(dt), p["visual_proj.weight"], p["visual_proj.bias"])
+    u = F.linear(feats["temporal_features"].to(dt), p["temporal_proj.weight"], p["temporal_proj.bias"])
 
     with torch.no_grad():  # :153-164
         def cos01(x1, x2):
@@ -181,11 +197,11 @@ def fusion_forward(p: Dict[str, torch.Tensor], feats: Dict[str, torch.Tensor],
     pairs = [t + a, t * a, (t - a).abs(), t + v, t * v, (t - v).abs(), t + u, v + u]  # :172-178
     cat = [t, a, v, u, *pairs, tv, ta, vu]
     if feats.get("gnn_feat") is not None and "gnn_proj.weight" in p:  # :184-187 (`use_gnn: false`: no gnn_proj, gnn_feat ignored)
-        cat.append(F.linear(feats["gnn_feat"].float(), p["gnn_proj.weight"], p["gnn_proj.bias"]))
+        cat.append(F.linear(feats["gnn_feat"].to(dt), p["gnn_proj.weight"], p["gnn_proj.bias"]))
     fused_cat = torch.cat(cat, dim=-1)
 
-    h = _drop(F.gelu(F.linear(fused_cat, p["fuse_mlp.0.weight"], p["fuse_mlp.0.bias"])), dropout, train)
-    fused = _drop(F.gelu(F.linear(h, p["fuse_mlp.3.weight"], p["fuse_mlp.3.bias"])), dropout, train)
+    h = _drop(F.gelu(F.linear(fused_cat, p["fuse_mlp.0.weight"], p["fuse_mlp.0.bias"])), dropout, train, _mask(masks, "fuse0"))
+    fused = _drop(F.gelu(F.linear(h, p["fuse_mlp.3.weight"], p["fuse_mlp.3.bias"])), dropout, train, _mask(masks, "fuse3"))
     logits = F.linear(fused, p["classifier.weight"], p["classifier.bias"])
     return {"fused": fused, "logits": logits, "fused_cat": fused_cat,
             "forensic": {"emotion_intensity": emo.squeeze(-1),
@@ -193,15 +209,30 @@ def fusion_forward(p: Dict[str, torch.Tensor], feats: Dict[str, torch.Tensor],
                          "temporal_delay": delay.squeeze(-1)}}
 
 
+def clf_geometry(p: Dict[str, torch.Tensor]) -> Tuple[int, int, int]:
+    """(trees, depth, aux width of pre.0) of a classifier parameter dict."""
+    trees = sum(1 for k in p if k.endswith(".tau") and k.startswith("node.trees."))
+    depth = sum(1 for k in p if k.startswith("node.trees.0.gates."))
+    return trees, depth, p["pre.0.weight"].shape[1] - p["pre.3.weight"].shape[1]
+
+
 def classifier_forward(p: Dict[str, torch.Tensor], fused, aux: Optional[torch.Tensor],
                        dropout: float = 0.1, node_dropout: float = 0.3, train: bool = False,
-                       trees: int = TREES, depth: int = DEPTH) -> Dict[str, torch.Tensor]:
-    """DeepTruthClassifier.forward, deep_truth_classifier.py:148-171."""
-    x = fused.float()
-    if aux is not None:
-        x = torch.cat([x, aux.float()], dim=-1)
-    h = _drop(F.gelu(F.linear(x, p["pre.0.weight"], p["pre.0.bias"])), dropout, train)
-    h = _drop(F.gelu(F.linear(h, p["pre.3.weight"], p["pre.3.bias"])), dropout, train)
+                       trees: Optional[int] = None, depth: Optional[int] = None,
+                       masks: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """DeepTruthClassifier.forward, deep_truth_classifier.py:148-171.  trees / depth default to the parameter dict's;
+    a classifier built with `use_aux: false` (pre.0 is hidden wide) ignores `aux` (:142-146).  Runs in the parameters'
+    dtype.  `masks`: explicit dropout multipliers for "pre0", "pre3" (B, H) and "tree" (B, 2 * trees; tree t's (B, 2)
+    logits take columns 2t, 2t + 1)."""
+    p_trees, p_depth, aux_w = clf_geometry(p)
+    trees = p_trees if trees is None else trees
+    depth = p_depth if depth is None else depth
+    dt = p["pre.0.weight"].dtype
+    x = fused.to(dt)
+    if aux is not None and aux_w > 0:
+        x = torch.cat([x, aux.to(dt)], dim=-1)
+    h = _drop(F.gelu(F.linear(x, p["pre.0.weight"], p["pre.0.bias"])), dropout, train, _mask(masks, "pre0"))
+    h = _drop(F.gelu(F.linear(h, p["pre.3.weight"], p["pre.3.bias"])), dropout, train, _mask(masks, "pre3"))
 
     outs = []
     for t in range(trees):  # _ObliviousTree.forward :54-74
@@ -212,17 +243,19 @@ def classifier_forward(p: Dict[str, torch.Tensor], fused, aux: Optional[torch.Te
             feat = (h * alpha).sum(dim=-1, keepdim=True)
             s = torch.sigmoid(tau * (feat - p[f"node.trees.{t}.thresh.{k}"]))
             probs = torch.cat([probs * (1.0 - s), probs * s], dim=1)
-        outs.append(_drop(probs @ p[f"node.trees.{t}.leaf_logits"], node_dropout, train))
+        tm = None if masks is None else masks["tree"][:, 2 * t:2 * t + 2]
+        outs.append(_drop(probs @ p[f"node.trees.{t}.leaf_logits"], node_dropout, train, tm))
     logits = torch.stack(outs, 0).mean(0) + F.linear(h, p["bypass.weight"], p["bypass.bias"])
     T = torch.clamp(p["temperature"], min=0.5, max=5.0)
     return {"logits": logits, "probs": F.softmax(logits / T, dim=-1), "temperature": T, "h": h}
 
 
-def forward_batch(fus, clf, batch, train: bool = False, dropout: float = 0.1):
-    """ForensicTrainer._forward_batch (forensic_trainer.py:238-271) on a ready batch."""
-    fo = fusion_forward(fus, batch, dropout=dropout, train=train)
+def forward_batch(fus, clf, batch, train: bool = False, dropout: float = 0.1, masks: Optional[Dict[str, torch.Tensor]] = None):
+    """ForensicTrainer._forward_batch (forensic_trainer.py:238-271) on a ready batch.  The geometry (hidden width, trees,
+    depth, aux width) is the parameter dicts'; `masks` (fusion_forward / classifier_forward) replaces every dropout draw."""
+    fo = fusion_forward(fus, batch, dropout=dropout, train=train, masks=masks)
     co = classifier_forward(clf, fo["fused"], batch["aux"], dropout=dropout,
-                            node_dropout=0.3 if dropout > 0 else 0.0, train=train)
+                            node_dropout=0.3 if dropout > 0 else 0.0, train=train, masks=masks)
     return {"logits": co["logits"], "probs": co["probs"], "y": batch["label"],
             "forensic": fo["forensic"], "fused": fo["fused"], "fusion_logits": fo["logits"]}
 
@@ -278,14 +311,16 @@ def clip_grads_(grads: Dict[str, Optional[torch.Tensor]], max_norm: float) -> fl
     return float(total)
 
 
-def loss_and_grads(fus, clf, batch, train: bool = False, dropout: float = 0.1):
+def loss_and_grads(fus, clf, batch, train: bool = False, dropout: float = 0.1,
+                   masks: Optional[Dict[str, torch.Tensor]] = None, label_smoothing: float = 0.0):
     """Forward + F.cross_entropy(mean) + autograd backward.  Returns
-    (out, loss, grads_fusion, grads_clf) with None for keys that get no grad."""
+    (out, loss, grads_fusion, grads_clf) with None for keys that get no grad.  `label_smoothing` is
+    F.cross_entropy's (the integrated variant's criterion)."""
     fl = {k: v.detach().clone().requires_grad_(v.dtype.is_floating_point) for k, v in fus.items()}
     cl = {k: v.detach().clone().requires_grad_(v.dtype.is_floating_point and not k.endswith("tau"))
           for k, v in clf.items()}
-    out = forward_batch(fl, cl, batch, train=train, dropout=dropout)
-    loss = F.cross_entropy(out["logits"], batch["label"])
+    out = forward_batch(fl, cl, batch, train=train, dropout=dropout, masks=masks)
+    loss = F.cross_entropy(out["logits"], batch["label"], label_smoothing=label_smoothing)
     loss.backward()
     gf = {k: v.grad for k, v in fl.items()}
     gc = {k: v.grad for k, v in cl.items()}
@@ -293,10 +328,10 @@ def loss_and_grads(fus, clf, batch, train: bool = False, dropout: float = 0.1):
 
 
 def train_step(fus, clf, batch, opt: AdamWState, grad_clip: float = 5.0,
-               train: bool = False, dropout: float = 0.1):
+               train: bool = False, dropout: float = 0.1, masks: Optional[Dict[str, torch.Tensor]] = None):
     """One iteration of ForensicTrainer._epoch_loop's train branch
     (forensic_trainer.py:285-298).  Mutates fus/clf in place."""
-    out, loss, gf, gc = loss_and_grads(fus, clf, batch, train=train, dropout=dropout)
+    out, loss, gf, gc = loss_and_grads(fus, clf, batch, train=train, dropout=dropout, masks=masks)
     grads = {**{"fusion." + k: g for k, g in gf.items()}, **{"clf." + k: g for k, g in gc.items()}}
     total = clip_grads_(grads, grad_clip) if grad_clip and grad_clip > 0 else float("nan")
     params = {**{"fusion." + k: v for k, v in fus.items()}, **{"clf." + k: v for k, v in clf.items()}}

@@ -14,6 +14,9 @@ What it does
            (dropout p=0) at B in {2,4,32}; asserts the oracle restatement agrees
            element-for-element, and stores the reference's outputs (full for the small
            tensors, per-tensor digests for grads/params) in tier_a_B*.npz.
+  tier_a_geom builds the reference's CrossModalTransformer / DeepTruthClassifier from temporary YAMLs at four other
+           head geometries (hidden_dim, node_trees, node_depth, aux_dim / use_aux: false), eval forward + one backward
+           (dropout p=0) against the oracle -> tier_a_geom.npz.
   metrics  runs the reference's forensic_metrics on known inputs -> metrics_kat.json.
   temporal runs the reference's TemporalSyncNet.align on seeded weights -> temporal.npz.
   temporal_seq runs the reference's TemporalSyncNet(use_tcn=True).forward (eval, and train with dropout p=0) on seeded
@@ -229,6 +232,77 @@ def tier_a_nognn():
     store["step1/loss"] = np.float64(loss.item())
     np.savez_compressed(HERE / "tier_a_nognn_B4.npz", **store)
     print(f"tier_a_nognn B={B}: ok  loss={loss.item():.6f}  ({len(nograd)} tensors without gradient)")
+
+
+# (hidden, trees, depth, aux_dim, use_aux, B): every branch the geometry drives in the head's kernels has a case here
+GEOMS = [(256, 16, 2, 4, True, 5), (1024, 5, 6, 2, False, 3), (512, 1, 1, 2, True, 4), (256, 3, 6, 2, False, 6)]
+
+
+def tier_a_geom():
+    """The oracle's geometry arguments pinned to the reference's own modules built from YAMLs of that geometry."""
+    import tempfile
+    sys.modules["transformers"] = None
+    os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
+    sys.dont_write_bytecode = True
+    sys.path.insert(0, str(REF))
+    os.chdir(REF)
+    import torch.nn as nn
+    import torch.nn.functional as F
+    from src.models.fusion.cross_modal_transformer import CrossModalTransformer
+    from src.models.fusion.deep_truth_classifier import DeepTruthClassifier
+    from oracle import tier_a as O
+    store = {"geoms": np.array(json.dumps(GEOMS))}
+    tmp = Path(tempfile.mkdtemp())
+    for i, (H, T, D, A, use_aux, B) in enumerate(GEOMS):
+        pre = f"g{i}/"
+        fy, cy = tmp / f"fusion{i}.yaml", tmp / f"classifier{i}.yaml"
+        fy.write_text(f"hidden_dim: {H}\ndropout: 0.1\nuse_gnn: true\ngnn_dim: 128\n")
+        cy.write_text(f"input_dim: {H}\nhidden_dim: {H}\ndropout: 0.1\nnum_classes: 2\nuse_aux: {str(use_aux).lower()}\naux_dim: {A}\n"
+                      f"node_trees: {T}\nnode_depth: {D}\nnode_tau: 10.0\ntemperature: 1.0\n")
+        pseed, bseed = PARAM_SEED + 20 + i, 40 + i
+        fus_sd, clf_sd = O.seeded_params(pseed, hidden=H, trees=T, depth=D, aux_dim=A, use_aux=use_aux)
+        torch.manual_seed(0)
+        fusion, clf = CrossModalTransformer(str(fy)).to("cpu"), DeepTruthClassifier(str(cy)).to("cpu")
+        assert list(fusion.state_dict().keys()) == list(fus_sd.keys()) and list(clf.state_dict().keys()) == list(clf_sd.keys())
+        assert all(tuple(v.shape) == tuple(fus_sd[k].shape) for k, v in fusion.state_dict().items())
+        assert all(tuple(v.shape) == tuple(clf_sd[k].shape) for k, v in clf.state_dict().items())
+        fusion.load_state_dict(fus_sd); clf.load_state_dict(clf_sd)
+        for m in list(fusion.modules()) + list(clf.modules()):
+            if isinstance(m, nn.Dropout):
+                m.p = 0.0
+        batch = O.seeded_batch(bseed, B, aux_dim=A)
+        feats = {k: batch[k] for k in ("text_features", "audio_features", "visual_features", "temporal_features", "gnn_feat")}
+        store[pre + "param_seed"], store[pre + "batch_seed"] = np.int64(pseed), np.int64(bseed)
+        store[pre + "param_checksum"] = np.float64(sum(v.double().sum() for v in list(fus_sd.values()) + list(clf_sd.values())))
+        fusion.eval(); clf.eval()
+        with torch.no_grad():
+            fo = fusion(feats)
+            co = clf(fo["fused"], batch["aux"])
+        oo = O.forward_batch(fus_sd, clf_sd, batch, train=False)
+        for name, r, o in (("fused", fo["fused"], oo["fused"]), ("logits", co["logits"], oo["logits"]), ("probs", co["probs"], oo["probs"])):
+            assert (r - o).abs().max().item() <= 1e-6, (i, name)
+            store[f"{pre}out/{name}"] = r.numpy()
+        fusion.train(); clf.train()
+        fo = fusion(feats)
+        co = clf(fo["fused"], batch["aux"])
+        loss = F.cross_entropy(co["logits"], batch["label"])
+        loss.backward()
+        _, oloss, gf, gc = O.loss_and_grads(fus_sd, clf_sd, batch, train=False)
+        assert abs(float(oloss) - loss.item()) <= 1e-6, i
+        nograd = []
+        for mp, mod, og in (("fusion.", fusion, gf), ("clf.", clf, gc)):
+            for k, p in mod.named_parameters():
+                g = og[k]
+                assert (g is None) == (p.grad is None), (i, k)
+                if p.grad is None:
+                    nograd.append(mp + k)
+                else:
+                    assert (g - p.grad).abs().max().item() <= 1e-6 * max(1.0, p.grad.abs().max().item()), (i, k)
+                    put_digest(store, f"{pre}grad/{mp}{k}", p.grad)
+        store[pre + "nograd_keys"] = np.array(json.dumps(nograd))
+        store[pre + "loss"] = np.float64(loss.item())
+        print(f"tier_a_geom {i}: hidden {H} trees {T} depth {D} aux {A if use_aux else 'off'} B={B}: ok  loss={loss.item():.6f}")
+    np.savez_compressed(HERE / "tier_a_geom.npz", **store)
 
 
 def metrics():
@@ -657,7 +731,7 @@ def gnn_model():
 if __name__ == "__main__":
     part = sys.argv[1] if len(sys.argv) > 1 else "all"
     if part == "all":
-        for p in ("tier_a", "tier_a_nognn", "metrics", "tier_b", "tier_b_grads", "temporal", "temporal_seq", "init_parity", "gcn", "gnn_model"):
+        for p in ("tier_a", "tier_a_nognn", "tier_a_geom", "metrics", "tier_b", "tier_b_grads", "temporal", "temporal_seq", "init_parity", "gcn", "gnn_model"):
             subprocess.check_call([sys.executable, str(Path(__file__).resolve()), p], cwd=str(REPO))
     else:
-        {"tier_a": tier_a, "tier_a_nognn": tier_a_nognn, "metrics": metrics, "tier_b": tier_b, "tier_b_grads": tier_b_grads, "temporal": temporal, "temporal_seq": temporal_seq, "init_parity": init_parity, "gcn": gcn, "gnn_model": gnn_model}[part]()
+        {"tier_a": tier_a, "tier_a_nognn": tier_a_nognn, "tier_a_geom": tier_a_geom, "metrics": metrics, "tier_b": tier_b, "tier_b_grads": tier_b_grads, "temporal": temporal, "temporal_seq": temporal_seq, "init_parity": init_parity, "gcn": gcn, "gnn_model": gnn_model}[part]()

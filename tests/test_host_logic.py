@@ -198,3 +198,45 @@ def test_temporal_sequence_module_init_and_delay_estimators():
         sr, max_lag = g[f"lag/{i}/args"]
         got = TemporalSyncNet.estimate_av_lag(g[f"lag/{i}/a"], torch.from_numpy(g[f"lag/{i}/m"]), sr=float(sr), max_lag_s=float(max_lag))
         assert got == float(want), (i, got, want)
+
+
+def test_head_step_sizes_aux_from_the_classifier_and_refuses_other_widths():
+    """HeadStep reads clf.eff_aux (aux_dim with use_aux, else 0): a dataset whose aux rows are not aux_dim wide is refused at
+    construction, naming the limit; without use_aux any width passes (the column is never read, deep_truth_classifier.py:142-146)."""
+    from types import SimpleNamespace
+    from ultrafnd_git_amd.head_step import HeadStep
+    cfg = SimpleNamespace(use_graph=False, head_graph=False, label_smoothing=0.0, class_weighting=False, fused_head=True)
+    for eff_aux, ok, bad in ((2, 2, 4), (4, 4, 2)):
+        hs = HeadStep(cfg, torch.device("cpu"), None, SimpleNamespace(eff_aux=eff_aux, hidden=512), None, None)
+        assert hs.aux_dim == eff_aux
+        hs.check_aux_width(ok)
+        with pytest.raises(ValueError, match=f"aux_dim: {eff_aux}"):
+            hs.check_aux_width(bad)
+    hs = HeadStep(cfg, torch.device("cpu"), None, SimpleNamespace(eff_aux=0, hidden=512), None, None)
+    assert hs.aux_dim == 0
+    hs.check_aux_width(2)
+    hs.check_aux_width(4)
+
+
+@pytest.mark.parametrize("use_aux,aux_dim", [(False, 2), (True, 2), (True, 4)])
+def test_head_step_aux_buffer_and_pointer_follow_the_classifier(tmp_path, use_aux, aux_dim):
+    """The step's aux buffer is (B, clf.eff_aux) and the head gets a null aux pointer without use_aux (both entry points refuse a
+    non-null aux when aux_dim is 0).  Host side only: the workspace sizes come from the library's host functions."""
+    from types import SimpleNamespace
+    from ultrafnd_git_amd.classifier import DeepTruthClassifier
+    from ultrafnd_git_amd.head_step import HeadStep
+    cy = tmp_path / "classifier.yaml"
+    cy.write_text(f"input_dim: 256\nhidden_dim: 256\nuse_aux: {str(use_aux).lower()}\naux_dim: {aux_dim}\nnode_trees: 3\nnode_depth: 6\n")
+    clf = DeepTruthClassifier(str(cy))
+    eff = aux_dim if use_aux else 0
+    assert clf.eff_aux == eff and clf.dims().aux_dim == eff
+    cfg = SimpleNamespace(use_graph=False, head_graph=False, label_smoothing=0.0, class_weighting=False, fused_head=True)
+    hs = HeadStep(cfg, torch.device("cpu"), SimpleNamespace(dropout=0.1, gnn_dim=128, hidden=256), clf, None, None)
+    b = hs.bufs(5, True)
+    assert tuple(b["aux"].shape) == (5, eff)
+    io = hs._io(b)
+    assert (io.aux is None) == (eff == 0)
+    aux = torch.rand(5, aux_dim)
+    hs.stage_aux(b, aux)
+    if eff:
+        assert torch.equal(b["aux"], aux)

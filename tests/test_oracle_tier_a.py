@@ -102,3 +102,54 @@ def test_oracle_without_the_gnn_slot_matches_the_reference_fixture():
     for k, g in grads.items():
         if g is not None:
             assert_digest_close(z, f"grad/{k}", g, rtol=1e-5, atol=1e-9)
+
+
+def _geoms():
+    import json
+    return json.loads(str(load_npz("tier_a_geom.npz")["geoms"]))
+
+
+@pytest.mark.parametrize("i", range(4))
+def test_oracle_at_other_head_geometries_matches_the_reference_fixture(i):
+    """hidden_dim / node_trees / node_depth / aux_dim / use_aux: false: the oracle's geometry arguments against the reference's own modules
+    built from YAMLs of that geometry (tests/golden/tier_a_geom.npz; make_golden.py tier_a_geom) -- eval forward and one backward, in
+    float32 as minted, and the float64 oracle (the yardstick of the GPU tests) within float32 rounding of it."""
+    import json
+    z = load_npz("tier_a_geom.npz")
+    H, T, D, A, use_aux, B = _geoms()[i]
+    pre = f"g{i}/"
+    fus, clf = O.seeded_params(int(z[pre + "param_seed"]), hidden=H, trees=T, depth=D, aux_dim=A, use_aux=use_aux)
+    assert tuple(clf["pre.0.weight"].shape) == (H, H + (A if use_aux else 0))
+    assert sum(1 for k in clf if k.endswith("leaf_logits")) == T and tuple(clf["node.trees.0.leaf_logits"].shape) == (1 << D, 2)
+    assert abs(float(sum(v.double().sum() for v in list(fus.values()) + list(clf.values()))) - float(z[pre + "param_checksum"])) < 1e-6
+    batch = O.seeded_batch(int(z[pre + "batch_seed"]), B, aux_dim=A)
+    for dt, tol, gtol in ((torch.float32, 1e-6, 1e-5), (torch.float64, 2e-6, 2e-5)):
+        f, c = ({k: v.to(dt) for k, v in d.items()} for d in (fus, clf))
+        out = O.forward_batch(f, c, batch, train=False)
+        assert out["logits"].dtype == dt
+        for name in ("fused", "logits", "probs"):
+            assert np.abs(out[name].double().numpy() - z[f"{pre}out/{name}"]).max() <= tol, (dt, name)
+        _, loss, gf, gc = O.loss_and_grads(f, c, batch, train=False)
+        assert abs(float(loss) - float(z[pre + "loss"])) <= tol
+        grads = {**{"fusion." + k: g for k, g in gf.items()}, **{"clf." + k: g for k, g in gc.items()}}
+        assert sorted(k for k, g in grads.items() if g is None) == sorted(json.loads(str(z[pre + "nograd_keys"])))
+        assert sorted(k for k, g in gc.items() if g is None) == sorted(O.no_grad_keys_clf(T))
+        for k, g in grads.items():
+            if g is not None:
+                assert_digest_close(z, f"{pre}grad/{k}", g, rtol=gtol, atol=1e-9, what=str(dt))
+
+
+def test_oracle_masks_equal_dropout_draws_and_a_wrong_mask_shows():
+    """masks= replaces F.dropout with the given multipliers: all-ones masks reproduce the eval forward bit for bit, and one dropped
+    column of the pre.3 mask moves the logits."""
+    fus, clf = O.seeded_params(5, hidden=256, trees=3, depth=2, aux_dim=4)
+    b = O.seeded_batch(6, 3, aux_dim=4)
+    H, T = 256, 3
+    ones = {"fuse0": torch.ones(3, 2 * H), "fuse3": torch.ones(3, H), "pre0": torch.ones(3, H), "pre3": torch.ones(3, H),
+            "tree": torch.ones(3, 2 * T)}
+    a = O.forward_batch(fus, clf, b, train=False)["logits"]
+    assert torch.equal(O.forward_batch(fus, clf, b, train=True, masks=ones)["logits"], a)
+    m = dict(ones)
+    m["pre3"] = ones["pre3"].clone()
+    m["pre3"][:, 7] = 0.0
+    assert (O.forward_batch(fus, clf, b, train=True, masks=m)["logits"] - a).abs().max() > 1e-6

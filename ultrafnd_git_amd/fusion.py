@@ -119,6 +119,9 @@ class CrossModalTransformer(ArenaModule):
 
     # ------------------------------------------------------------------ C tables
     def dims(self, clf=None) -> L.Dims:
+        """The fusion entry points' dims.  aux_dim / trees / depth / clf_dropout / node_dropout are placeholders that only pass
+        check_dims: no fusion entry point reads them (the classifier's input panel is prepared only by the fused head step,
+        whose dims are DeepTruthClassifier.dims())."""
         d = L.Dims()
         d.hidden, d.text_dim, d.audio_dim, d.visual_dim, d.temporal_dim = self.hidden, 768, 128, 512, 256
         d.gnn_dim, d.aux_dim, d.trees, d.depth, d.classes = (self.gnn_dim if self.use_gnn else 0), 2, 6, 4, 2      # gnn_dim 0 = no GNN slot

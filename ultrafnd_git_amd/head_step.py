@@ -31,6 +31,16 @@ class HeadStep:
         self.fused_entries = not (cfg.label_smoothing > 0.0 or cfg.class_weighting) and bool(getattr(cfg, "fused_head", True))
         self._dw_stream: Optional[torch.cuda.Stream] = None
         self._iota: Optional[torch.Tensor] = None
+        # aux columns the classifier reads per row: aux_dim with use_aux, else none (the reference ignores aux then,
+        # deep_truth_classifier.py:142-146); the step's aux buffer has this width and the kernels get no aux pointer at 0
+        self.aux_dim = int(clf.eff_aux)
+
+    def check_aux_width(self, width: int) -> None:
+        """Refuse a dataset whose aux rows are not the classifier's aux_dim wide (the reference fails on the shape of
+        pre.0 at its first forward).  Without use_aux the aux column is never read, whatever its width."""
+        if self.aux_dim and int(width) != self.aux_dim:
+            raise ValueError(f"aux features are {int(width)} wide but classifier.yaml has use_aux: true, aux_dim: {self.aux_dim} "
+                             f"(pre.0 is {self.clf.hidden}+{self.aux_dim} wide): give the dataset aux rows of that width")
 
     # ------------------------------------------------------------------ buffers
     def bufs(self, B: int, train: bool, slot: int = 0) -> dict:
@@ -50,7 +60,7 @@ class HeadStep:
                 "text": torch.empty(B, 768, dtype=f32, device=dev), "audio": torch.empty(B, 128, dtype=f32, device=dev),
                 "visual": torch.empty(B, 512, dtype=f32, device=dev), "temporal": torch.empty(B, 256, dtype=f32, device=dev),
                 "gnn": torch.empty(B, self.fusion.gnn_dim, dtype=f32, device=dev),
-                "aux": torch.empty(B, 2, dtype=f32, device=dev), "label": torch.empty(B, dtype=torch.int64, device=dev),
+                "aux": torch.empty(B, self.aux_dim, dtype=f32, device=dev), "label": torch.empty(B, dtype=torch.int64, device=dev),
                 "logits": torch.empty(B, 2, dtype=f32, device=dev), "probs": torch.empty(B, 2, dtype=f32, device=dev),
                 "forensic": torch.empty(3, B, dtype=f32, device=dev), "dlogits": torch.empty(B, 2, dtype=f32, device=dev),
                 "dfused": torch.empty(B, self.fusion.hidden, dtype=f32, device=dev), "graph": None}
@@ -78,6 +88,8 @@ class HeadStep:
         pairs = []
         for src, dst in ((ds.T, b["text"]), (ds.A, b["audio"]), (ds.V, b["visual"]), (ds.U, b["temporal"]), (ds.AUX, b["aux"]),
                          (ds.y, b["label"]), (ds.G, b["gnn"])):
+            if dst is b["aux"] and not self.aux_dim:
+                continue
             rb = src[0].numel() * src.element_size()
             if not src.is_contiguous() or src.dtype != dst.dtype or rb != dst[0].numel() * dst.element_size() or src.device != dst.device:
                 raise RuntimeError(f"cached tensor {tuple(src.shape)} {src.dtype} does not match its batch buffer {tuple(dst.shape)} {dst.dtype}")
@@ -89,6 +101,8 @@ class HeadStep:
         pairs = []
         for src, dst in ((grp["text"], b["text"]), (grp["visual"], b["visual"]), (group["audio_features"], b["audio"]), (group["aux"], b["aux"]),
                          (group["label"], b["label"]), (group["gnn_feat"], b["gnn"])):
+            if dst is b["aux"] and not self.aux_dim:
+                continue
             if not (src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and tuple(src.shape[1:]) == tuple(dst.shape[1:]) and
                     (src[0].numel() * src.element_size()) % 8 == 0):
                 raise RuntimeError(f"lookahead group tensor {tuple(src.shape)} {src.dtype} does not match its step buffer {tuple(dst.shape)} {dst.dtype}")
@@ -100,7 +114,8 @@ class HeadStep:
         """audio / aux / label / gnn rows of a raw batch into the step's static buffers: ONE ufnd_gather_rows launch (identity
         index) instead of four copy kernels on the head -> exchange -> optimizer chain; torch copies when a tensor does not
         have the buffer's dtype / layout."""
-        pairs = [(batch["audio_features"], b["audio"]), (batch["aux"], b["aux"]), (batch["label"], b["label"]), (batch["gnn_feat"], b["gnn"])]
+        pairs = [(batch["audio_features"], b["audio"])] + ([(batch["aux"], b["aux"])] if self.aux_dim else []) + \
+            [(batch["label"], b["label"]), (batch["gnn_feat"], b["gnn"])]
         ok = all(isinstance(src, torch.Tensor) and src.device == dst.device and src.dtype == dst.dtype and src.is_contiguous() and
                  tuple(src.shape) == tuple(dst.shape) and (src[0].numel() * src.element_size()) % 8 == 0 for src, dst in pairs)
         if not ok:
@@ -111,11 +126,19 @@ class HeadStep:
                      [(src.data_ptr(), dst, src[0].numel() * src.element_size(), src.shape[0]) for src, dst in pairs], "ufnd_gather_rows")
 
     # ------------------------------------------------------------------ launches
+    def _aux_ptr(self, b: dict) -> Optional[int]:
+        return b["aux"].data_ptr() if self.aux_dim else None
+
+    def stage_aux(self, b: dict, aux: torch.Tensor) -> None:
+        """A batch's aux rows into the step's buffer (nothing to stage without use_aux)."""
+        if self.aux_dim:
+            b["aux"].copy_(aux)
+
     def _io(self, b: dict) -> "L.HeadIO":
         if "io" not in b:
             io = L.HeadIO()
             io.text, io.audio, io.visual, io.temporal = (b[k].data_ptr() for k in ("text", "audio", "visual", "temporal"))
-            io.gnn, io.aux, io.labels = b["gnn"].data_ptr(), b["aux"].data_ptr(), b["label"].data_ptr()
+            io.gnn, io.aux, io.labels = b["gnn"].data_ptr(), self._aux_ptr(b), b["label"].data_ptr()
             io.fusion_workspace, io.clf_workspace = b["fws"].data_ptr(), b["cws"].data_ptr()
             io.logits, io.probs, io.forensic, io.d_logits = (b[k].data_ptr() for k in ("logits", "probs", "forensic", "dlogits"))
             b["io"] = io
@@ -133,7 +156,7 @@ class HeadStep:
                                         b["gnn"].data_ptr(), B, int(train), b["fws"].data_ptr(), b["xin"], b["ldx"], None,
                                         b["forensic"].data_ptr(), st, s), "ufnd_fusion_forward")
         L.check(lib.ufnd_classifier_forward(C.byref(d), C.byref(self.clf.param_table()), b["xin"], b["ldx"],
-                                            b["aux"].data_ptr(), B, int(train), b["cws"].data_ptr(), b["logits"].data_ptr(),
+                                            self._aux_ptr(b), B, int(train), b["cws"].data_ptr(), b["logits"].data_ptr(),
                                             b["probs"].data_ptr(), st, s), "ufnd_classifier_forward")
         if self.cfg.label_smoothing > 0.0 or self.cfg.class_weighting:
             L.check(lib.ufnd_softmax_ce_weighted(b["logits"].data_ptr(), b["label"].data_ptr(), B, self.ce_w[0], self.ce_w[1],

@@ -219,6 +219,7 @@ class ForensicTrainer:
             raise ValueError("encode_inline=True needs text_encoder= and visual_encoder=")
         self.head = HeadStep(cfg, self.device, self.fusion, self.clf, self.optim, self.reducer, ce_w,
                              gnn_dims=416 if self.gnn_model is not None else None)
+        self.head.check_aux_width(np.shape(cache["aux"])[1])
         self.pipe = EncoderPipeline(cfg, self.device, self.head, self.reducer, self.optim, text_encoder, visual_encoder, temporal_net)
 
         self.best_val_auc = -1.0
@@ -296,7 +297,7 @@ class ForensicTrainer:
             self.temporal_net.align_batch(b["text"], b["visual"], out=b["temporal"], training=None if split == "train" else False)
         else:
             b["temporal"].copy_(batch["temporal_features"])
-        b["aux"].copy_(batch["aux"])
+        self.head.stage_aux(b, batch["aux"])
         b["label"].copy_(batch["label"])
         ds = self._dataset(split)
         if "gnn_feat" in batch and batch["gnn_feat"] is not None:
@@ -364,7 +365,7 @@ class ForensicTrainer:
             self.temporal_net.align_batch(b["text"], b["visual"], out=b["temporal"])
         else:
             b["temporal"].copy_(batch["temporal_features"])
-        b["aux"].copy_(batch["aux"])
+        self.head.stage_aux(b, batch["aux"])
         b["label"].copy_(batch["label"])
         if "gnn_feat" in batch and batch["gnn_feat"] is not None:
             b["gnn"].copy_(batch["gnn_feat"])
