@@ -11,6 +11,10 @@
   --mode world2   two ranks sharing cuda:0 over gloo (device tensors staged through host memory by tests/host_staged.py's
                   Collectives subclass -- the product has no such path, its exchange is RCCL): sharded batches + summed gradients + 1/world == the single-process
                   full-batch step; then fit() / test() with sharded loaders, gathered metrics, the rank-0 checkpoint.
+  --mode enc2     two ranks sharing cuda:0 over gloo (host-staged like world2), TrainConfig.train_encoders with 2-layer encoders that
+                  every rank builds from a DIFFERENT seed: construction broadcasts rank 0's masters and refreshes every bf16 operand
+                  copy; two sharded steps against the single-process full-batch step; a rank-0 checkpoint that _load_checkpoint()
+                  restores on every rank after the masters moved (and rank 1's were perturbed).
 Prints one JSON line on rank 0."""
 import argparse
 import json
@@ -296,10 +300,158 @@ def variants(out_dir):
     dist.destroy_process_group()
 
 
+def _enc_raw_batches(B, n, seed):
+    """Full batches with raw encoder inputs (token ids, attention mask, frames) beside the cached head features."""
+    from oracle import encoders_ref as E
+    out = []
+    for k in range(n):
+        d = dict_batches(B, 1, seed + k)[0]
+        ids, mask = E.synthetic_tokens(seed + 10 + k, B, 32, vocab=500, min_len=8)
+        d.update({"input_ids": ids.to(DEV), "attention_mask": mask.to(torch.int32).to(DEV), "frames": E.synthetic_frames(seed + 20 + k, B, 1).to(DEV)})
+        out.append(d)
+    return out
+
+
+def _enc_trainer(out_dir, B, weight_seed, group=None):
+    """ForensicTrainer(train_encoders=True) over 2-layer encoders (vocab 500) whose weights come from `weight_seed`; dropout off."""
+    from oracle import encoders_ref as E
+    from ultrafnd_git_amd.encoders import BertTextEncoder, ClipVisualEncoder
+    from ultrafnd_git_amd.trainer import ForensicTrainer, TrainConfig, synthetic_cache
+    tenc, venc = BertTextEncoder(layers=2, vocab_size=500), ClipVisualEncoder(layers=2)
+    tenc.load_state_dict(E.seeded_weights(E.bert_shapes(layers=2, vocab=500), weight_seed))
+    venc.load_state_dict(E.seeded_weights(E.vit_shapes(layers=2), weight_seed + 1))
+    tenc, venc = tenc.to(DEV), venc.to(DEV)
+    torch.manual_seed(5)
+    cfg = TrainConfig(data_root="", ocr_phrase_pkl=None, out_dir=out_dir, batch_size=B, device="cuda:0", use_graph=False, encode_inline=True,
+                      train_encoders=True)
+    tr = ForensicTrainer(cfg, cache=synthetic_cache(32, seed=1), text_encoder=tenc, visual_encoder=venc, group=group)
+    tr.fusion.dropout = tr.clf.dropout = tr.clf.node_dropout = 0.0
+    tr.head.step_bufs.clear()
+    tr.fusion.train(); tr.clf.train()
+    return tr
+
+
+def _frozen_logits(tr, batch):
+    """Features and logits of the frozen fast path (packed operands), as validation / test() run it."""
+    tr.fusion.eval(); tr.clf.eval()
+    out = tr._forward_batch(batch, "val")
+    torch.cuda.synchronize()
+    b = tr.head.bufs(int(batch["label"].shape[0]), False)
+    res = torch.cat([b["text"].flatten(), b["visual"].flatten(), out["logits"].float().flatten()]).cpu()
+    tr.fusion.train(); tr.clf.train()
+    return res
+
+
+def enc2(out_dir):
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    B = 8                                            # global batch; every rank takes B / world rows
+    batches = _enc_raw_batches(B, 3, 300)
+    probe = {k: v[:4].contiguous() for k, v in batches[2].items()}
+    ranges = {}
+    ref = None
+    if rank == 0:                                    # single-process full-batch reference, BEFORE the group exists
+        tr0 = _enc_trainer(os.path.join(out_dir, "ref"), B, 11)
+        a = tr0.arena
+        enc_lo = a.offsets["text." + tr0.text_bp.groups()[0][0][0]][0]
+        vis_lo = a.offsets["vis." + tr0.vis_bp.groups()[0][0][0]][0]
+        ranges = {"head": (0, enc_lo), "text": (enc_lo, vis_lo), "vis": (vis_lo, a.n_grad)}
+        ref = {"init": a.data.clone(), "data": [], "grad": [], "norm": []}
+        for b in batches[:2]:
+            tr0.train_step(b)
+            torch.cuda.synchronize()
+            ref["data"].append(a.data.clone())
+            ref["grad"].append(a.grad.clone())
+            ref["norm"].append(float(tr0.optim.state.read().grad_norm))
+        del tr0, a
+        torch.cuda.synchronize()
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from host_staged import HostStagedCollectives
+    from ultrafnd_git_amd.dp import save_checkpoint
+    comm = HostStagedCollectives()
+    res = {}
+
+    def agree(t):
+        """Whether every rank holds exactly these bits."""
+        mine = t.detach().cpu()
+        other = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(other, mine)
+        return bool(all(torch.equal(o, other[0]) for o in other))
+
+    def every(flag):
+        """Whether `flag` holds on every rank."""
+        t = torch.tensor([int(bool(flag))])
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        return bool(t.item())
+
+    # construction: the masters every rank built itself (seed 11 + 100 x rank) are replaced by rank 0's, and so are the bf16 operands
+    tr = _enc_trainer(out_dir, B // world, 11 + 100 * rank, group=comm)
+    assert tr.world == world and tr.reducer.active and len(tr.reducer.buckets) == 4
+    res["init_ranks_agree"] = agree(tr.arena.data)
+    if rank == 0:
+        res["init_equals_fresh"] = bool(torch.equal(tr.arena.data, ref["init"]))
+    res["frozen_path_ranks_agree"] = agree(_frozen_logits(tr, probe))
+    # two sharded steps against the full-batch step
+    rel = lambda a, b: float(((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item())
+    res["steps"] = []
+    for i, b in enumerate(batches[:2]):
+        tr.train_step({k: v[rank::world].contiguous() for k, v in b.items()})
+        torch.cuda.synchronize()
+        step = {"ranks_agree": agree(tr.arena.data)}
+        if rank == 0:
+            g = tr.arena.grad * tr.reducer.grad_scale          # the summed gradient of the two half batches, as a full-batch mean
+            rg = ref["grad"][i]
+            step["grad_rel"] = {n: rel(g[lo:hi], rg[lo:hi]) for n, (lo, hi) in ranges.items()}
+            step["grad_rel_l2"] = {n: float((g[lo:hi] - rg[lo:hi]).norm() / rg[lo:hi].norm()) for n, (lo, hi) in ranges.items()}
+            per = {}
+            for k in tr.arena.grad_keys:
+                o, shp = tr.arena.offsets[k]
+                n = int(torch.Size(shp).numel())
+                per[k] = float((g[o:o + n] - rg[o:o + n]).norm() / rg[o:o + n].norm().clamp_min(1e-30))
+            step["worst_tensors_rel_l2"] = sorted(per.items(), key=lambda kv: -kv[1])[:6]
+            step["grad_norm"], step["grad_norm_ref"] = float(tr.optim.state.read().grad_norm), ref["norm"][i]
+            step["param_max_abs_err"] = (tr.arena.data - ref["data"][i]).abs().max().item()
+            step["param_scale"] = ref["data"][i].abs().max().item()
+            # the same, over the elements whose full-batch gradient is clear of zero in every step so far (>= 1e-3 of its tensor's
+            # largest): AdamW moves an element by ~lr in the direction of its gradient's SIGN, so an element whose gradient is
+            # rounding noise around zero (the key bias's, by softmax's shift invariance) may step either way in the two runs
+            clear = torch.ones_like(tr.arena.data, dtype=torch.bool)
+            for k in tr.arena.grad_keys:
+                o, shp = tr.arena.offsets[k]
+                n = int(torch.Size(shp).numel())
+                for rgj in ref["grad"][:i + 1]:
+                    gk = rgj[o:o + n].abs()
+                    clear[o:o + n] &= gk >= 1e-3 * gk.max()
+            d = (tr.arena.data - ref["data"][i]).abs()
+            step["param_max_abs_err_clear"] = d[clear].max().item()
+            step["clear_fraction"] = float(clear[:tr.arena.n_grad].float().mean())
+        res["steps"].append(step)
+    # checkpoint: rank 0 saves; every rank steps on, rank 1's masters are also perturbed; _load_checkpoint() restores rank 0's file
+    save_checkpoint(tr._checkpoint_state(), tr.ckpt_path, comm)
+    saved = tr.arena.data.clone()
+    want = _frozen_logits(tr, probe)
+    tr.train_step({k: v[rank::world].contiguous() for k, v in batches[2].items()})
+    if rank == 1:
+        with torch.no_grad():
+            tr.text_bp.master(tr.text_bp.linears()["0.qkv"][0]).add_(1e-2)
+            tr.vis_bp.master(tr.vis_bp.linears()["1.w1"][0]).mul_(1.5)
+    torch.cuda.synchronize()
+    res["ckpt_moved_on_every_rank"] = every(not torch.equal(tr.arena.data, saved) and not torch.equal(_frozen_logits(tr, probe), want))
+    found = tr._load_checkpoint()
+    torch.cuda.synchronize()
+    got = _frozen_logits(tr, probe)
+    res["ckpt_found"] = bool(found) if rank == 0 else None
+    res["ckpt_restored_on_every_rank"] = every(torch.equal(tr.arena.data, saved) and torch.equal(got, want))
+    res["ckpt_ranks_agree"] = agree(got) and agree(tr.arena.data)
+    res["ranges"] = {n: list(r) for n, r in ranges.items()}
+    if rank == 0:
+        print(json.dumps(res))
+    dist.destroy_process_group()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     torch.cuda.set_device(0)
-    {"force1": force1, "world2": world2, "variants": variants, "factors2": factors2}[a.mode](a.out)
+    {"force1": force1, "world2": world2, "variants": variants, "factors2": factors2, "enc2": enc2}[a.mode](a.out)

@@ -61,3 +61,46 @@ def hidden_errors(got, ref):
     g, r = got.double().cpu(), ref.double().cpu()
     d = g - r
     return {"rel_rms": (d.pow(2).mean().sqrt() / r.pow(2).mean().sqrt()).item(), "max_abs": d.abs().max().item()}
+
+
+def outlier_text_problem(gain: float):
+    """The outlier-shaped 4-layer BERT of tests/test_gpu_encoder_train.py (four hidden dimensions with `gain` x LayerNorm gains, every
+    LayerNorm bias offset by half a standard deviation) and its token batch: (weights, ids, mask, loss seed)."""
+    from oracle import encoders_ref as E
+    w = E.seeded_weights(E.bert_shapes(layers=4, vocab=800), 93)
+    hot = [7, 300, 511, 640]
+    for k in list(w):
+        if k.endswith("LayerNorm.weight"):
+            w[k] = w[k].clone()
+            w[k][hot] *= gain
+        if k.endswith("LayerNorm.bias"):
+            w[k] = w[k] + 0.5
+    ids, mask = E.synthetic_tokens(193, 4, 96, vocab=800)
+    return w, ids, mask, 7
+
+
+def grad_rel_errors(got: dict, ref: dict, floor_frac: float = 2e-3):
+    """Relative L2 error of every gradient tensor of `got` against `ref`, and the absolute floor test_gpu_encoder_train.py's
+    _compare grants a tensor whose own gradient is (nearly) zero: floor_frac x the largest per-element gradient scale x sqrt(numel).
+    Returns ({name: (rel, err, floor, ref norm)}, worst rel over the tensors whose error exceeds their floor, its name)."""
+    top = max(g.norm().item() / max(1, g.numel()) ** 0.5 for g in ref.values())
+    out, worst = {}, ("", 0.0)
+    for k, r in ref.items():
+        err = (got[k].double() - r.double()).norm().item()
+        rn = r.double().norm().item()
+        rel = err / max(rn, 1e-30)
+        floor = floor_frac * top * max(1, r.numel()) ** 0.5
+        out[k] = (rel, err, floor, rn)
+        if err > floor and rel > worst[1]:
+            worst = (k, rel)
+    return out, worst[1], worst[0]
+
+
+def qk_weight_rel_l2(got: dict, ref: dict) -> float:
+    """Relative L2 error of all query / key weight gradients taken together (the tensors a saturated softmax hits)."""
+    num = den = 0.0
+    for k, r in ref.items():
+        if k.endswith(("attention.self.query.weight", "attention.self.key.weight")):
+            num += float((got[k].double() - r.double()).pow(2).sum())
+            den += float(r.double().pow(2).sum())
+    return (num / max(den, 1e-300)) ** 0.5

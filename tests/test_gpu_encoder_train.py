@@ -100,6 +100,64 @@ def test_visual_encoder_gradients_vs_oracle_autograd(tag):
     _compare(arena, ref, 1.6e-2, f"{tag} (2 layers)")
 
 
+@pytest.mark.parametrize("B,Lq", [(3, 77), (5, 40)])
+def test_text_encoder_gradients_at_unaligned_token_counts(B, Lq):
+    """B x L not a multiple of 64 (231 and 200 tokens): the ragged 64-row tails of forward_train / backward and the split-K weight
+    gradients over a ragged token count; at L = 77 one row has a single real token (its [CLS] only).  2 layers, the bound of the
+    aligned cases, and a bit-identical rerun."""
+    from oracle import encoders_ref as E
+    from ultrafnd_git_amd.encoder_train import TextBackprop
+    from ultrafnd_git_amd.encoders import BertTextEncoder
+    w = E.seeded_weights(E.bert_shapes(layers=2, vocab=1000), 24)
+    ids, mask = E.synthetic_tokens(300 + Lq, B, Lq, vocab=1000)
+    if Lq == 77:
+        mask[1] = 0
+        mask[1, 0] = 1
+    assert (B * Lq) % 64 != 0
+    enc = BertTextEncoder(layers=2, vocab_size=1000)
+    enc.load_state_dict(w)
+    enc = enc.to(DEV)
+    bp, arena = _standalone(TextBackprop, enc)
+    feat = bp.forward_train(ids, mask).clone()
+    ref_feat, ref = E.text_feature_grads(w, ids, mask, 78)
+    assert (feat.cpu() - ref_feat).abs().max().item() <= 1.2e-3
+    dfeat = torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(78)).to(DEV)
+    bp.backward(dfeat)
+    _compare(arena, ref, 1.6e-2, f"B={B} L={Lq} ({B * Lq} tokens, 2 layers)")
+    first = arena.grad.clone()
+    arena.grad.fill_(float("nan"))
+    bp.forward_train(ids, mask)
+    bp.backward(dfeat)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.nan_to_num(arena.grad, nan=-7.0), torch.nan_to_num(first, nan=-7.0))
+
+
+def test_visual_encoder_gradients_three_frames():
+    """ViT with F = 3 frames per sample at B = 3: 9 images, 450 tokens (not a multiple of 64), the frame mean + L2 of the
+    multi-frame pooling in the backward; 2 layers, the bound of the aligned cases, and a bit-identical rerun."""
+    from oracle import encoders_ref as E
+    from ultrafnd_git_amd.encoder_train import VisualBackprop
+    from ultrafnd_git_amd.encoders import ClipVisualEncoder
+    w = E.seeded_weights(E.vit_shapes(layers=2), 25)
+    frames = E.synthetic_frames(326, 3, 3)
+    enc = ClipVisualEncoder(layers=2)
+    enc.load_state_dict(w)
+    enc = enc.to(DEV)
+    bp, arena = _standalone(VisualBackprop, enc)
+    feat = bp.forward_train(frames).clone()
+    ref_feat, ref = E.visual_feature_grads(w, frames, 79)
+    assert (feat.cpu() - ref_feat).abs().max().item() <= 1.5e-3
+    dfeat = torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(79)).to(DEV)
+    bp.backward(dfeat)
+    _compare(arena, ref, 1.6e-2, "ViT B=3 F=3 (450 tokens, 2 layers)")
+    first = arena.grad.clone()
+    arena.grad.fill_(float("nan"))
+    bp.forward_train(frames)
+    bp.backward(dfeat)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.nan_to_num(arena.grad, nan=-7.0), torch.nan_to_num(first, nan=-7.0))
+
+
 def test_full_depth_text_encoder_gradients_sampled_tensors():
     """12 layers (BERT-base geometry, small vocabulary so that the CPU autograd stays quick): first, middle and last layer's
     tensors and the embeddings."""
@@ -170,13 +228,9 @@ BERT12_LAYER_BOUNDS = {11: 1.85e-2, 6: 2.4e-2, 0: 3.0e-2}       # measured 9.1e-
 def test_outlier_shaped_weights_through_the_backward_path():
     """Outlier-shaped weights (four hidden dimensions with 5x LayerNorm gains, every LayerNorm bias offset by half a standard
     deviation) through forward_train + backward of a 4-layer BERT: the gradients hold the bound of the Gaussian-weight tests.
-    Why 5x and not the forward test's 20x (tests/test_gpu_fullsize.py): with Gaussian projections behind them, 20x gains in EVERY
-    LayerNorm let the hot dimensions dominate each next LayerNorm's variance, the other dimensions shrink 16-fold per sublayer and
-    the attention logits reach ~100 (measured on this construction: |q.k| / 8 ~ 120): the softmax saturates and its gradient
-    P (dP - delta) becomes a small difference of rounded numbers -- the q / k weight gradients of ANY implementation with bf16
-    operands are then 60 % off the fp32 autograd (measured here: 0.64 relative L2; the pooled forward features still agree to
-    9e-4).  That is a property of the synthetic network (trained encoders keep their logits at O(10)), recorded in DESIGN section 2,
-    not a case a bf16 backward can be held to."""
+    Why 5x and not the forward test's 20x (tests/test_gpu_fullsize.py): with 20x gains the softmax saturates and the q / k weight
+    gradients of a bf16 backward are ~0.55 relative L2 off the fp32 autograd -- the bf16 rounding of the forward's GEMM operands
+    alone does that; the 20x case is checked against the bf16 emulation by the next test."""
     from oracle import encoders_ref as E
     from ultrafnd_git_amd.encoder_train import TextBackprop
     from ultrafnd_git_amd.encoders import BertTextEncoder
@@ -201,9 +255,59 @@ def test_outlier_shaped_weights_through_the_backward_path():
     assert fe["rel_l2"] <= 3.0e-3 and fe["one_minus_cos"] <= 3.0e-6, fe      # (measured 1.2e-3 / 7.6e-7)
     bp.backward(torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(7)).to(DEV))
     _compare(arena, ref, OUTLIER_BWD_BOUND, "outlier-shaped weights (4 layers, 5x gains), backward")
+    # against the emulation of the kernel's own roundings (oracle/encoders_bf16.py, every point)
+    from oracle import encoders_bf16 as EB
+    _, emu = EB.text_feature_grads(w, ids, mask, 7)
+    _compare(arena, emu, OUTLIER_EMU_BOUND, "outlier-shaped weights (4 layers, 5x gains), backward vs the bf16 emulation")
 
 
 OUTLIER_BWD_BOUND = 6.0e-3      # 3 x measured on MI355X (2.1e-3)
+OUTLIER_EMU_BOUND = 5.0e-3      # 2 x measured on MI355X (2.4e-3: no closer than to fp32 -- the HIP and the emulation round at the same points, but
+                                # fp32-level differences between them flip individual bf16 roundings)
+
+
+def test_outlier_shaped_weights_20x_against_the_bf16_emulation():
+    """The outlier test's construction with the forward test's 20x gains (tests/test_gpu_fullsize.py): the softmax saturates (attention
+    logits ~100) and the q / k weight gradients of the HIP backward are ~0.55 relative L2 off the fp32 autograd.
+
+    The CPU ablation (tests/encoder_bf16_ablation.py) puts that error on the bf16 rounding of the Linear operands
+    of the FORWARD -- the LayerNorm outputs and the weights alone reproduce it; no rounding of the attention kernels carries it.  At
+    these gains a bf16-rounded encoder is discontinuous in its inputs: its gradients move by ~0.4 relative L2 under a 1e-6 relative
+    perturbation of the weights (fp32 autograd: ~1e-3), so no bf16 implementation can be held to an emulation of its own roundings
+    element by element (the kernel's distance from the emulation is what a 1e-6 perturbation of the emulation's own weights gives).
+    What is asserted instead: the forward features agree (well conditioned); the HIP gradients are no farther from fp32 than the
+    emulation's own (a backward fault on saturated softmax rows would add to the emulation's error, not sit beside it); and the HIP
+    gradients are no farther from the emulation than the perturbed emulation is."""
+    from oracle import encoders_bf16 as EB
+    from oracle import encoders_ref as E
+    from tests.helpers import feature_errors, outlier_text_problem, qk_weight_rel_l2
+    from ultrafnd_git_amd.encoder_train import TextBackprop
+    from ultrafnd_git_amd.encoders import BertTextEncoder
+    w, ids, mask, seed = outlier_text_problem(20.0)
+    enc = BertTextEncoder(layers=4, vocab_size=800)
+    enc.load_state_dict(w)
+    enc = enc.to(DEV)
+    bp, arena = _standalone(TextBackprop, enc)
+    feat = bp.forward_train(ids, mask).clone().cpu()
+    ref_feat, ref = E.text_feature_grads(w, ids, mask, seed)
+    emu_feat, emu = EB.text_feature_grads(w, ids, mask, seed)
+    g = torch.Generator().manual_seed(1)
+    _, emu_p = EB.text_feature_grads({k: v * (1 + 1e-6 * torch.randn(v.shape, generator=g)) for k, v in w.items()}, ids, mask, seed)
+    bp.backward(torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(seed)).to(DEV))
+    got = {k: arena.grad_view(k).cpu() for k in ref}
+    assert all(torch.isfinite(v).all() for v in got.values())
+    fe, fe_emu = feature_errors(feat, emu_feat), feature_errors(feat, ref_feat)
+    hip_ref, emu_ref, hip_emu, emu_emu_p = qk_weight_rel_l2(got, ref), qk_weight_rel_l2(emu, ref), qk_weight_rel_l2(got, emu), qk_weight_rel_l2(emu_p, emu)
+    print(f"20x gains, features: vs the emulation {fe}, vs fp32 {fe_emu}")
+    print(f"20x gains, q/k weight gradients, relative L2: HIP vs fp32 {hip_ref:.3e}, emulation vs fp32 {emu_ref:.3e}; "
+          f"HIP vs emulation {hip_emu:.3e}, emulation with 1e-6-perturbed weights vs emulation {emu_emu_p:.3e}")
+    print("20x gains, per-layer relative L2 against the emulation:", {k: f"{v:.3e}" for k, v in _per_layer(arena, emu, "encoder.layer.{}.", (0, 1, 2, 3)).items()})
+    assert fe["rel_l2"] <= OUTLIER20_FEAT_REL_L2, fe
+    assert hip_ref <= 1.25 * emu_ref, (hip_ref, emu_ref)            # (measured 0.538 vs 0.577)
+    assert hip_emu <= 2.0 * emu_emu_p, (hip_emu, emu_emu_p)         # (measured 0.433 vs 0.328)
+
+
+OUTLIER20_FEAT_REL_L2 = 1.8e-3  # 2 x measured on MI355X (8.9e-4)
 
 
 def test_trainer_step_with_trainable_encoders_vs_oracle(tmp_path):
@@ -254,7 +358,8 @@ def test_trainer_step_with_trainable_encoders_vs_oracle(tmp_path):
     head_norm = sum(float(v.grad.double().pow(2).sum()) for d in (fl, cl) for v in d.values() if v.requires_grad and v.grad is not None) ** 0.5
     total = (enc_norm ** 2 + head_norm ** 2) ** 0.5
     print(f"loss {float(st.loss):.6f} (oracle {float(loss):.6f}); grad norm {float(st.grad_norm):.5f} (oracle {total:.5f}: head {head_norm:.5f}, encoders {enc_norm:.5f})")
-    assert abs(float(st.grad_norm) - total) <= 2e-2 * total
+    print(f"global norm relative error {abs(float(st.grad_norm) - total) / total:.3e}")
+    assert abs(float(st.grad_norm) - total) <= 1e-5 * total         # 2 x measured on MI355X (4.7e-6; was 2e-2)
     _compare(tr.arena, grads, 2.5e-2, "trainer step, encoder gradients (2 + 2 layers behind the fp32 head)")
     # every parameter moved against its gradient by about lr (AdamW's first step): compare the signs where the gradient is clear
     moved = (tr.arena.data - before).cpu()
@@ -272,6 +377,127 @@ def test_trainer_step_with_trainable_encoders_vs_oracle(tmp_path):
     tr._load_batch(tr.head.bufs(B, False), gb, "val")
     torch.cuda.synchronize()
     assert (tr.head.bufs(B, False)["text"] - f_train).abs().max().item() <= 2e-3
+
+
+def test_three_clipped_trainer_steps_with_trainable_encoders_vs_float64_replay(tmp_path):
+    """ForensicTrainer(train_encoders=True), three steps with the default grad_clip (5.0) at lr 2e-3: the first step's global norm is
+    ~2.7, the next two are above 5 (measured on the oracle: 12.2 and 6.3), so the clip coefficient taken from the JOINT norm of head
+    and encoder gradients applies.  After every step:
+      * gradients at the HIP's own pre-step parameters (no drift accumulates): the head's against the float64 head oracle fed with
+        the HIP's own encoder features (the Tier-A bounds of tests/test_gpu_head_geometry.py); the encoders' against fp32 autograd
+        through both encoders and the head (_compare, 2.5e-2); the global norm against that autograd's;
+      * the optimizer: the HIP gradients, in float64, through oracle.tier_a.clip_grads_ + AdamWState over the joint parameter set
+        (head, text and visual ranges, none excluded; weight decay, step count and bias correction carried from the first step);
+        every parameter within 2e-7 x max(1, |p|) of that update applied to the HIP's pre-step parameters.  (Applied to the
+        replay's own parameters instead, fp32 storage of the arena adds up to ~1 ulp per step -- 1.2e-7 relative at the LayerNorm
+        gains near 1 -- which three steps of do not fit in 2e-7; the cumulative difference is printed.)
+    After the last step the encoders' bf16 W and W^T operands equal a fresh cast / transpose of the final masters."""
+    import torch.nn.functional as F
+    from oracle import encoders_ref as E
+    from oracle import tier_a as O
+    from ultrafnd_git_amd.encoders import BertTextEncoder, ClipVisualEncoder
+    from ultrafnd_git_amd.trainer import ForensicTrainer, TrainConfig, synthetic_cache
+    B, Lq = 4, 64
+    wt = E.seeded_weights(E.bert_shapes(layers=2, vocab=500), 11)
+    wv = E.seeded_weights(E.vit_shapes(layers=2), 12)
+    tenc, venc = BertTextEncoder(layers=2, vocab_size=500), ClipVisualEncoder(layers=2)
+    tenc.load_state_dict(wt); venc.load_state_dict(wv)
+    tenc, venc = tenc.to(DEV), venc.to(DEV)
+    fus_sd, clf_sd = O.seeded_params(1234)
+    cfg = TrainConfig(data_root="", ocr_phrase_pkl=None, out_dir=str(tmp_path), batch_size=B, device=DEV, use_graph=False, encode_inline=True,
+                      train_encoders=True, lr=2e-3)
+    assert cfg.grad_clip == 5.0
+    tr = ForensicTrainer(cfg, cache=synthetic_cache(16, seed=1), text_encoder=tenc, visual_encoder=venc)
+    tr.fusion.load_state_dict(fus_sd); tr.clf.load_state_dict(clf_sd)
+    tr.fusion.dropout = tr.clf.dropout = tr.clf.node_dropout = 0.0
+    tr.head.step_bufs.clear()
+    tr.fusion.train(); tr.clf.train()
+    a = tr.arena
+    keys = list(a.grad_keys)
+    view = lambda buf, k: buf[a.offsets[k][0]:a.offsets[k][0] + a.view(k).numel()].view(a.view(k).shape)
+    replay = {k: a.view(k).detach().cpu().double().clone() for k in keys}        # the cumulative float64 replay
+    opt = O.AdamWState(lr=cfg.lr, weight_decay=cfg.weight_decay)
+    opt_restart = O.AdamWState(lr=cfg.lr, weight_decay=cfg.weight_decay)
+    clipped = []
+    for step in range(3):
+        ids, mask = E.synthetic_tokens(13 + step, B, Lq, vocab=500, min_len=8)
+        frames = E.synthetic_frames(14 + step, B, 1)
+        batch = O.seeded_batch(15 + step, B)
+        gb = {k: v.to(DEV) for k, v in batch.items()}
+        gb.update({"input_ids": ids.to(DEV), "attention_mask": mask.to(torch.int32).to(DEV), "frames": frames.to(DEV)})
+        before = a.data.detach().cpu().clone()
+        fus_now, clf_now = {k: v.cpu() for k, v in tr.fusion.state_dict().items()}, {k: v.cpu() for k, v in tr.clf.state_dict().items()}
+        wt_now, wv_now = ({k: v.cpu() for k, v in enc.state_dict().items()} for enc in (tenc, venc))
+        tr.train_step(gb)
+        st = tr.optim.state.read()
+        hb = tr.head.bufs(B, True)
+        got = {k: a.grad_view(k).detach().cpu().clone() for k in keys}
+        # the head: float64 oracle on the HIP's own features
+        hbatch = dict(batch)
+        hbatch["text_features"], hbatch["visual_features"] = hb["text"].cpu().double(), hb["visual"].cpu().double()
+        hbatch = {k: (v.double() if v.is_floating_point() else v) for k, v in hbatch.items()}
+        f64 = [{k: v.double() for k, v in d.items()} for d in (fus_now, clf_now)]
+        out, hloss, gf, gc_ = O.loss_and_grads(*f64, hbatch, train=False)
+        assert abs(float(st.loss) - float(hloss)) <= 2e-5, (step, float(st.loss), float(hloss))
+        worst = (0.0, "")
+        for k, r in [("fusion." + k, g) for k, g in gf.items()] + [("clf." + k, g) for k, g in gc_.items()]:
+            if r is None:
+                continue
+            scale = max(r.abs().max().item(), r.norm().item() / max(1.0, r.numel() ** 0.5), 1e-9)
+            err = (got[k].double() - r).abs().max().item() / scale
+            worst = max(worst, (err, k))
+        print(f"step {step + 1}: head gradients, worst max-abs / scale {worst[0]:.2e} ({worst[1]})")
+        assert worst[0] <= 5e-4, (step, worst)
+        # the encoders (and the norm): fp32 autograd through both encoders and the head
+        wtl = {k: v.clone().requires_grad_(True) for k, v in wt_now.items()}
+        wvl = {k: v.clone().requires_grad_(True) for k, v in wv_now.items()}
+        fl = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in fus_now.items()}
+        cl = {k: v.clone().requires_grad_(v.is_floating_point() and not k.endswith("tau")) for k, v in clf_now.items()}
+        rb = dict(batch)
+        rb["text_features"], rb["visual_features"] = E.text_features(wtl, ids, mask), E.visual_features(wvl, frames)
+        F.cross_entropy(O.forward_batch(fl, cl, rb)["logits"], batch["label"]).backward()
+        enc_ref = {"text." + k: v.grad for k, v in wtl.items()}
+        enc_ref.update({"vis." + k: v.grad for k, v in wvl.items()})
+        total = (sum(float(g.double().pow(2).sum()) for g in enc_ref.values()) +
+                 sum(float(v.grad.double().pow(2).sum()) for d in (fl, cl) for v in d.values() if v.requires_grad and v.grad is not None)) ** 0.5
+        print(f"step {step + 1}: grad norm {st.grad_norm:.5f} (oracle {total:.5f}, rel {abs(st.grad_norm - total) / total:.2e}), clip {st.clip_coef:.4f}")
+        assert abs(st.grad_norm - total) <= TRAINER_NORM_REL * total, (step, st.grad_norm, total)
+        _compare(a, enc_ref, 2.5e-2, f"step {step + 1}: encoder gradients")
+        # the optimizer, float64
+        gnorm = sum(float(g.double().pow(2).sum()) for g in got.values()) ** 0.5
+        assert abs(st.grad_norm - gnorm) <= 1e-5 * gnorm, (st.grad_norm, gnorm)
+        coef = min(1.0, cfg.grad_clip / (gnorm + 1e-6))
+        assert abs(st.clip_coef - coef) <= 1e-6, (st.clip_coef, coef)
+        clipped.append(coef < 1.0)
+        g64 = {k: v.double() for k, v in got.items()}
+        O.clip_grads_(g64, cfg.grad_clip)
+        opt.step(replay, {k: v.clone() for k, v in g64.items()})
+        restart = {k: view(before, k).double().clone() for k in keys}
+        opt_restart.step(restart, g64)
+        after = a.data.detach().cpu()
+        worst = {"head": 0.0, "text": 0.0, "vis": 0.0}
+        cum = 0.0
+        for k in keys:
+            p = view(after, k).double()
+            rng = "text" if k.startswith("text.") else "vis" if k.startswith("vis.") else "head"
+            worst[rng] = max(worst[rng], ((p - restart[k]).abs() / restart[k].abs().clamp_min(1.0)).max().item())
+            cum = max(cum, ((p - replay[k]).abs() / replay[k].abs().clamp_min(1.0)).max().item())
+        print(f"step {step + 1}: parameters vs the float64 AdamW step, max |diff| / max(1, |p|): " +
+              ", ".join(f"{n} {v:.2e}" for n, v in worst.items()) + f"; cumulative replay {cum:.2e}")
+        assert max(worst.values()) <= 2e-7, (step, worst)
+        assert int(st.step) == step + 1
+    assert any(clipped), clipped
+    # the bf16 operand copies were re-cast from the final masters
+    for bp in (tr.text_bp, tr.vis_bp):
+        for name, (wk, _) in bp.linears().items():
+            m = bp.master(wk)
+            m2 = m.reshape(m.shape[0], -1)
+            wb, wtr = bp._ops[name]
+            assert torch.equal(wb, m2.to(torch.bfloat16)), name
+            assert torch.equal(wtr, m2.t().contiguous().to(torch.bfloat16)), name
+
+
+TRAINER_NORM_REL = 1.3e-5       # 2 x measured on MI355X (4.7e-6 / 6.4e-6 / 6.4e-6 over the three steps)
 
 
 def test_best_checkpoint_carries_the_trained_encoders(tmp_path):

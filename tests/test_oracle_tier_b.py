@@ -92,3 +92,44 @@ def test_oracle_encoder_gradients_match_the_third_party_autograd_fixture():
     _, g = E.visual_feature_grads(w, E.synthetic_frames(meta["frame_seed"], meta["B"], meta["F"]), meta["loss_seed"])
     for k in meta["keys"]:
         assert_digest_close(z, f"vit2_F2/grad/{k}", g[k], 1e-4, 1e-7, k)
+
+
+def _bert2_problem():
+    z = load_npz("tier_b_grads.npz")
+    meta = json.loads(str(z["bert2_L64/meta"]))
+    w = E.seeded_weights(E.bert_shapes(layers=meta["layers"], vocab=meta["vocab"]), meta["weight_seed"])
+    return w, torch.from_numpy(z["bert2_L64/ids"]), torch.from_numpy(z["bert2_L64/mask"]), meta["loss_seed"]
+
+
+def test_bf16_emulation_without_rounding_is_the_fp32_autograd():
+    """oracle/encoders_bf16.py with no rounding point active performs encoders_ref's operations in the same order: features and every
+    gradient bit for bit."""
+    from oracle import encoders_bf16 as EB
+    w, ids, mask, seed = _bert2_problem()
+    f0, g0 = E.text_feature_grads(w, ids, mask, seed)
+    f1, g1 = EB.text_feature_grads(w, ids, mask, seed, points=())
+    assert torch.equal(f0, f1)
+    assert set(g0) == set(g1) and all(torch.equal(g0[k], g1[k]) for k in g0)
+    with pytest.raises(ValueError):
+        EB.text_feature_grads(w, ids, mask, seed, points=("no_such_point",))
+
+
+def test_bf16_emulation_error_is_the_bf16_estimate():
+    """Every rounding point active, Gaussian 2-layer weights: each gradient tensor within 2.5 x 2^-9 sqrt(4 n) (n = 2 layers) of the
+    fp32 autograd in relative L2, with test_gpu_encoder_train.py's absolute floor -- the bound the HIP backward is held to; and
+    every point does change the result (no rounding point is a no-op)."""
+    import math
+    from oracle import encoders_bf16 as EB
+    from tests.helpers import grad_rel_errors
+    w, ids, mask, seed = _bert2_problem()
+    _, ref = E.text_feature_grads(w, ids, mask, seed)
+    _, emu = EB.text_feature_grads(w, ids, mask, seed)
+    bound = 2.5 * 2 ** -9 * math.sqrt(4 * 2)
+    per, worst, where = grad_rel_errors(emu, ref)
+    print(f"bf16 emulation vs fp32 autograd (2 layers): worst relative L2 {worst:.3e} ({where}), bound {bound:.2e}")
+    for k, (rel, err, floor, rn) in per.items():
+        assert err <= bound * rn + floor, (k, rel, err, floor)
+    assert worst > 0.0
+    for p in EB.ALL:
+        _, one = EB.text_feature_grads(w, ids, mask, seed, points=(p,))
+        assert any(not torch.equal(one[k], ref[k]) for k in ref), p

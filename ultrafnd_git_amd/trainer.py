@@ -194,6 +194,7 @@ class ForensicTrainer:
         else:
             self.reducer = GradReducer(self.arena.ensure_grad(), group=self.comm, bounds=bounds,
                                        force=force_exchange, payload=cfg.grad_payload, algorithm=cfg.grad_exchange)
+        self.text_encoder, self.visual_encoder = text_encoder, visual_encoder     # (before the broadcast: _sync_encoder_operands reads them)
         if self.text_bp is not None and self.world > 1:
             # the encoders are built by the caller, before this constructor seeds anything: replicas may start from different RNG
             # states.  They only ever exchange gradients, so unequal masters would silently stay unequal.
@@ -213,7 +214,6 @@ class ForensicTrainer:
             pos, neg = float((y == 1).sum()), float((y == 0).sum())
             total = max(1.0, pos + neg)
             ce_w = (0.5 * total / max(1.0, neg), 0.5 * total / max(1.0, pos))
-        self.text_encoder, self.visual_encoder = text_encoder, visual_encoder
         self.temporal_net = temporal_net    # optional TemporalSyncNet: temporal = align(text, visual) inside the step
         if cfg.encode_inline and (text_encoder is None or visual_encoder is None):
             raise ValueError("encode_inline=True needs text_encoder= and visual_encoder=")
