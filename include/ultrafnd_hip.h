@@ -697,6 +697,42 @@ int ufnd_bert_embed_bwd(const int64_t* ids, const float* ds, float* dword, float
  * (the `patch_embed_bwd` of SURVEY 8b is ufnd_gemm_bf16_wgrad on dpe and the patch matrix). */
 int ufnd_vit_assemble_bwd(const float* ds, float* dcls, float* dpos, void* dpe_bf16, int N, int P, int H, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Train-mode dropout of the trainable encoders (HF BertModel / CLIPVisionModel in .train()).
+ * No mask is stored: each multiplier is regenerated from Philox4x32-10 keyed by state->seed, with counter
+ * (element / 4, tag, state->step) -- a pure function of (seed, step, tag, element).  Element numbering:
+ *   attention probabilities  ((b heads + h) L + q) Lp + k,  Lp = L rounded up to a multiple of 4
+ *   hidden states (M, H)     row H + col
+ * The host descriptor is read at enqueue time; state is a device pointer read by the kernels (graph-replay safe).
+ * Every _dropout entry requires 0 < p < 1 (p = 0 is the entry without the suffix).
+ * ---------------------------------------------------------------------------------- */
+typedef struct ufnd_dropout {
+  const ufnd_step_state* state; /* device: seed and step */
+  float p;                      /* drop probability, 0 < p < 1 */
+  uint32_t tag;                 /* the site's stream tag (ranges: csrc/common.hpp) */
+} ufnd_dropout;
+
+#define UFND_LN_BWD_DROP_DXB 1  /* the bf16 output (the dense layer's input gradient) is multiplied by the mask; the fp32 one is not */
+#define UFND_LN_BWD_DROP_DY 2   /* the incoming dy is multiplied by the mask (LayerNorm followed by dropout) */
+
+/* ufnd_attention_bf16_lse with dropout on the softmax probabilities: ctx = (m o P) V.  lse stays that of the undropped P. */
+int ufnd_attention_bf16_lse_dropout(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads,
+                                    const ufnd_dropout* drop, void* stream);
+/* ufnd_attention_bf16_bwd of the dropped forward (same mask): dV = (m o P)^T dO, dS = P o (m o dO V^T - delta). */
+int ufnd_attention_bf16_bwd_dropout(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* key_mask,
+                                    void* dqkv, float* workspace, int B, int L, int heads, const ufnd_dropout* drop, void* stream);
+/* Post-LN residual site with dropout on the dense output: y = x + m o d (d = the dense layer's output incl. bias, without its
+ * residual); y (M, H) fp32 is stored (the LayerNorm backward's input), then LayerNorm(y) -> out_bf16 and / or out_f32 (stride H). */
+int ufnd_dropout_residual_layernorm(const float* x, int ldx, const float* d, int ldd, const float* gamma, const float* beta, float* y,
+                                    void* out_bf16, float* out_f32, int M, int H, float eps, const ufnd_dropout* drop, void* stream);
+/* LayerNorm followed by dropout: out = m o LayerNorm(x) (BertEmbeddings). */
+int ufnd_layernorm_dropout(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32, int M, int H,
+                           float eps, const ufnd_dropout* drop, void* stream);
+/* ufnd_layernorm_bwd with a dropout mask (element row H + col) at `where`: UFND_LN_BWD_DROP_DXB or UFND_LN_BWD_DROP_DY. */
+int ufnd_layernorm_bwd_dropout(const float* x, int ldx, const float* gamma, const float* dy, int lddy, const float* add, int ldadd,
+                               float* dx_f32, void* dx_bf16, int lddx, float* dgamma, float* dbeta, float* workspace, int accumulate,
+                               int M, int H, float eps, const ufnd_dropout* drop, int where, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

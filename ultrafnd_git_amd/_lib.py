@@ -80,7 +80,13 @@ class RefreshItem(C.Structure):
                 ("ld_w", C.c_int), ("ld_wt", C.c_int), ("tile0", C.c_int)]
 
 
+class Dropout(C.Structure):
+    """ufnd_dropout: one train-mode dropout site of the trainable encoders (state = device ufnd_step_state: seed, step)."""
+    _fields_ = [("state", C.c_void_p), ("p", C.c_float), ("tag", C.c_uint32)]
+
+
 PARTIALS_DEFER = 2
+LN_BWD_DROP_DXB, LN_BWD_DROP_DY = 1, 2
 WGRAD_ALL, WGRAD_TRANSPOSE, WGRAD_PRODUCT = 0, 1, 2
 
 
@@ -198,6 +204,11 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_bert_embed_bwd": [P, P, P, P, P, I, I, I, I, I, I, P],
         "ufnd_vit_assemble_bwd": [P, P, P, P, I, I, I, P],
         "ufnd_act_bf16": [P, P, S, I, P],
+        "ufnd_attention_bf16_lse_dropout": [P, P, P, P, I, I, I, C.POINTER(Dropout), P],
+        "ufnd_attention_bf16_bwd_dropout": [P, P, P, P, P, P, P, I, I, I, C.POINTER(Dropout), P],
+        "ufnd_dropout_residual_layernorm": [P, I, P, I, P, P, P, P, P, I, I, F, C.POINTER(Dropout), P],
+        "ufnd_layernorm_dropout": [P, I, P, P, P, P, I, I, F, C.POINTER(Dropout), P],
+        "ufnd_layernorm_bwd_dropout": [P, I, P, P, I, P, I, P, P, I, P, P, P, I, I, I, F, C.POINTER(Dropout), I, P],
     })
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -16,6 +16,10 @@
 //        by ds_read_b64_tr_b16 (hardware transpose): 4 keys x 16 d per 16-lane group.
 // Masking follows HF: masked keys get the constant finfo.min-like score (a fully masked row
 // degenerates to a uniform average, not NaN); keys beyond L contribute exactly zero.
+// Training dropout (DROP, ufnd_attention_bf16_lse_dropout): P^T is multiplied by the mask in fp32 just before its in-place bf16
+// conversion; l and lse stay those of the undropped probabilities.  The mask is drawn, never stored: element (q, k) of (b, h) is
+// ((b heads + h) L + q) Lp + k with Lp = L rounded up to 4, so the 4 keys a lane holds per tile (4g..4g+3: aligned) are one
+// Philox evaluation.  DESIGN.md section 4.
 #include "attn_softmax.hpp"
 
 // No implicit contraction: the fused projection + attention kernel (gemm_bf16_kernel.hpp, ATT) repeats this kernel's
@@ -36,9 +40,11 @@ __device__ __forceinline__ bf16x8 k_frag(const char* tile, int row, int chunk) {
 // NW = waves per workgroup (32 queries each).  Sequences of <= 64 tokens (ViT-B/32: 50) run with NW = 2: the 4-wave form spends
 // half its waves on clamped duplicate queries there, and its 216 registers allow 8 waves per CU either way -- twice the
 // samples in flight with 2-wave workgroups (a block is one dependent chain: loads -> S -> softmax -> O -> store).
-template <int KB, int NW = 4>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2 ? 3 : 2))) void attention_kernel(const __bf16* qkv, const int32_t* mask, __bf16* ctx, int L,
-                                                        int heads, float scale_log2e, const int32_t* cu, float* lse, int nqb) {
+// DROP: the Philox draws need ~170 registers in the 2-wave form; at three waves per SIMD it spilled, so it runs at two.
+template <int KB, int NW = 4, bool DROP = false>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2 && !DROP ? 3 : 2))) void attention_kernel(const __bf16* qkv, const int32_t* mask, __bf16* ctx, int L,
+                                                        int heads, float scale_log2e, const int32_t* cu, float* lse, int nqb,
+                                                        ufnd_dropout dr) {
   __shared__ __attribute__((aligned(16))) char ks[KB * 128];
   __shared__ __attribute__((aligned(16))) char vs[KB * 128];
   __shared__ __attribute__((aligned(16))) float kbias[KB];
@@ -68,6 +74,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     const __bf16* src = qkv + (tok0 + qc) * ld + h * 64 + 8 * g;
     qf[qt][0] = *reinterpret_cast<const bf16x8*>(src);
     qf[qt][1] = *reinterpret_cast<const bf16x8*>(src + 32);
+  }
+
+  uint64_t dseed = 0, dstep = 0;
+  uint32_t drow[2] = {0u, 0u};      // DROP: the Philox counter of (query, key group 0) per query tile
+  if constexpr (DROP) {
+    dseed = dr.state->seed;
+    dstep = dr.state->step;
+    const uint32_t lp4 = (uint32_t)(L + 3) >> 2;
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) drow[qt] = ((uint32_t)(b * heads + h) * (uint32_t)L + (uint32_t)qrow[qt]) * lp4 + (uint32_t)g;
   }
 
   f32x4 o[4][2];
@@ -141,7 +157,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     bf16x8 pf[KT / 2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-      const float alpha = online_softmax_block<KT>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf);
+      f32x4 dm[KT];
+      if constexpr (DROP) {
+        // keys kb0 + 16 kt + 4 g .. +3 of this lane's query: counter (q Lp + kb0 + 16 kt + 4 g) / 4.  Queries or keys beyond L draw
+        // multipliers nobody uses (their P is 0)
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+          float m4[4];
+          dropout_mul4_ctr(dseed, dstep, dr.p, dr.tag, drow[qt] + (uint32_t)(kb0 >> 2) + 4u * kt, m4);
+          dm[kt] = f32x4{m4[0], m4[1], m4[2], m4[3]};
+        }
+      }
+      const float alpha = online_softmax_block<KT, DROP>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf, dm);
       if (!__all(alpha == 1.0f)) {       // (the running maximum rarely moves after the first blocks: skip the rescale then)
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
@@ -210,10 +237,10 @@ extern "C" int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask,
   const float scale_log2e = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
   if (L <= 64)
     hipLaunchKernelGGL((attention_kernel<64, 2>), dim3(heads * B), dim3(128), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, 1);
+                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, 1, ufnd_dropout{});
   else
     hipLaunchKernelGGL((attention_kernel<64, 4>), dim3(ufnd_cdiv(L, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB));
+                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB), ufnd_dropout{});
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -227,7 +254,26 @@ extern "C" int ufnd_attention_bf16_varlen(const void* qkv, const int32_t* cu_seq
   const float scale_log2e = 0.125f * 1.44269504088896340736f;
   hipLaunchKernelGGL((attention_kernel<64, 4>), dim3(ufnd_cdiv(max_len, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
                      (const __bf16*)qkv, (const int32_t*)nullptr, (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr,
-                     ufnd_cdiv(max_len, QB));
+                     ufnd_cdiv(max_len, QB), ufnd_dropout{});
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_attention_bf16_lse_dropout(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads,
+                                               const ufnd_dropout* drop, void* stream_) {
+  UFND_REQUIRE(qkv && ctx && lse && drop && drop->state, "attention_dropout: null operand");
+  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "attention_dropout: p=%g (0 < p < 1; p = 0 is ufnd_attention_bf16_lse)", (double)drop->p);
+  UFND_REQUIRE(B >= 1 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention_dropout: B=%d L=%d heads=%d", B, L, heads);
+  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_dropout: 16-B alignment required");
+  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(L, QB) < (1ll << 31), "attention_dropout: grid too large");
+  UFND_REQUIRE(ufnd_attn_dropout_fits(B, L, heads), "attention_dropout: B=%d L=%d heads=%d overflows the 32-bit dropout counter", B, L, heads);
+  const float scale_log2e = 0.125f * 1.44269504088896340736f;
+  if (L <= 64)
+    hipLaunchKernelGGL((attention_kernel<64, 2, true>), dim3(heads * B), dim3(128), 0, (hipStream_t)stream_,
+                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, 1, *drop);
+  else
+    hipLaunchKernelGGL((attention_kernel<64, 4, true>), dim3(ufnd_cdiv(L, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
+                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB), *drop);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

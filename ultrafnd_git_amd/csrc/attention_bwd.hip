@@ -18,6 +18,15 @@
 // pass, bitwise reproducible -- and attention is a few percent of an encoder layer's FLOPs at these lengths.
 // Masked keys (HF semantics, as the forward): score = the finfo.min-like constant, so P = 0 for them wherever a row has a
 // live key; keys / queries beyond L contribute exactly zero.
+//
+// Training dropout (DROP, ufnd_attention_bf16_bwd_dropout; the forward used O = (m o P) V with the same mask m):
+//   dV = (m o P)^T dO,  dP = m o (dO V^T),  dS = P o (dP - delta)
+// delta = rowsum(dO o O) is still right: O is the DROPPED output, and rowsum(P o m o dO V^T) = rowsum(dO o O).  The mask is
+// regenerated (attention.hip: element ((b heads + h) L + q) Lp + k, Lp = L rounded up to 4).  Pass 1 holds S^T like the forward:
+// 4 consecutive keys of one query per lane and tile -- one Philox evaluation.  Pass 2 holds S: 4 consecutive QUERIES of one key.
+// There the 4 lanes of a DPP quad (keys 4j..4j+3, same queries) each evaluate the counter of ONE of the 4 queries, which yields
+// that query's words for all 4 keys; the keep bits travel as a nibble through 4 quad_perm broadcasts -- also one evaluation
+// per 4 elements, instead of 4.
 #include "common.hpp"
 
 namespace {
@@ -75,9 +84,16 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const __bf16* dctx, con
   }
 }
 
-template <int PASS>
+// the 4 keep bits of quad lane r, broadcast to the quad (DPP quad_perm [r, r, r, r])
+template <int R>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, R * 0x55, 0xF, 0xF, false);
+}
+
+template <int PASS, bool DROP = false>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, const __bf16* dctx, const float* lse, const float* delta,
-                                                            const int32_t* mask, __bf16* dqkv, int L, int heads, float scale_log2e, float scale, int nob) {
+                                                            const int32_t* mask, __bf16* dqkv, int L, int heads, float scale_log2e, float scale, int nob,
+                                                            ufnd_dropout dr) {
   // images of the walked side's current 64-row block
   __shared__ __attribute__((aligned(16))) char imgA[64 * 128];      // pass 1: K (form 1)      pass 2: Q  (form 1)
   __shared__ __attribute__((aligned(16))) char imgB[64 * 128];      // pass 1: V (form 1)      pass 2: dO (form 1)
@@ -121,6 +137,17 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
       c0[t] = r < L ? ((!mask || mask[tok0 + rc] != 0) ? 0.0f : NEG_MASK) : -INFINITY;
       c1[t] = 0.0f;
     }
+  }
+
+  uint64_t dseed = 0, dstep = 0;
+  uint32_t lp4 = 0, bh0 = 0;
+  float kscale = 0.0f;
+  if constexpr (DROP) {
+    dseed = dr.state->seed;
+    dstep = dr.state->step;
+    lp4 = (uint32_t)(L + 3) >> 2;
+    bh0 = (uint32_t)(b * heads + h) * (uint32_t)L;
+    kscale = 1.0f / (1.0f - dr.p);
   }
 
   f32x4 acc0[4][2], acc1[4][2];      // pass 1: dQ^T (acc0); pass 2: dK^T (acc0), dV^T (acc1)
@@ -182,6 +209,20 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
         const f32x4 wv0 = *reinterpret_cast<const f32x4*>(w0 + rt * 16 + 4 * g);
         f32x4 wv1 = {0.f, 0.f, 0.f, 0.f};
         if constexpr (PASS == 2) wv1 = *reinterpret_cast<const f32x4*>(w1 + rt * 16 + 4 * g);
+        float dm[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+        if constexpr (DROP && PASS == 1) {       // rows = keys wb0 + 16 rt + 4 g + r of my query orow[t]
+          dropout_mul4_ctr(dseed, dstep, dr.p, dr.tag, (bh0 + (uint32_t)orow[t]) * lp4 + (uint32_t)(wb0 >> 2) + 4u * rt + (uint32_t)g, dm);
+        } else if constexpr (DROP) {             // rows = queries wb0 + 16 rt + 4 g + r of my key orow[t]
+          const uint32_t pq = (uint32_t)fr & 3u;
+          uint32_t w[4];
+          philox_4x32(dseed, dstep, dr.tag, (bh0 + (uint32_t)(wb0 + rt * 16 + 4 * g) + pq) * lp4 + ((uint32_t)orow[t] >> 2), w);
+          uint32_t nib = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) nib |= (dropout_keep(w[j], dr.p) != 0.0f ? 1u : 0u) << j;
+          const uint32_t nb[4] = {quad_bcast<0>(nib), quad_bcast<1>(nib), quad_bcast<2>(nib), quad_bcast<3>(nib)};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dm[r] = ((nb[r] >> pq) & 1u) ? kscale : 0.0f;
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float sc2, ls, dl;
@@ -195,9 +236,15 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
             dl = wv1[r];
           }
           const float p = fast_exp2(sc2 - ls);
-          const float dsv = p * (dp[rt][t][r] - dl) * scale;
-          pf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)p;
-          dsf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)dsv;
+          if constexpr (DROP) {
+            const float dsv = p * (dp[rt][t][r] * dm[r] - dl) * scale;
+            pf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)(p * dm[r]);
+            dsf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)dsv;
+          } else {
+            const float dsv = p * (dp[rt][t][r] - dl) * scale;
+            pf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)p;
+            dsf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)dsv;
+          }
         }
       }
 
@@ -260,10 +307,35 @@ extern "C" int ufnd_attention_bf16_bwd(const void* qkv, const void* ctx, const v
   UFND_REQUIRE((long long)nob * heads * B < (1ll << 31), "attention_bwd: grid too large");
   const dim3 grid(nob * heads * B);
   hipLaunchKernelGGL(attention_bwd_kernel<1>, grid, dim3(256), 0, stream, (const __bf16*)qkv, (const __bf16*)dctx, lse, (const float*)workspace, key_mask,
-                     (__bf16*)dqkv, L, heads, scale_log2e, scale, nob);
+                     (__bf16*)dqkv, L, heads, scale_log2e, scale, nob, ufnd_dropout{});
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(attention_bwd_kernel<2>, grid, dim3(256), 0, stream, (const __bf16*)qkv, (const __bf16*)dctx, lse, (const float*)workspace, key_mask,
-                     (__bf16*)dqkv, L, heads, scale_log2e, scale, nob);
+                     (__bf16*)dqkv, L, heads, scale_log2e, scale, nob, ufnd_dropout{});
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_attention_bf16_bwd_dropout(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* key_mask,
+                                               void* dqkv, float* workspace, int B, int L, int heads, const ufnd_dropout* drop, void* stream_) {
+  UFND_REQUIRE(qkv && ctx && dctx && lse && dqkv && workspace && drop && drop->state, "attention_bwd_dropout: null operand");
+  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "attention_bwd_dropout: p=%g (0 < p < 1; p = 0 is ufnd_attention_bf16_bwd)", (double)drop->p);
+  UFND_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention_bwd_dropout: B=%d L=%d heads=%d", B, L, heads);
+  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16) && ufnd_aligned(dctx, 16) && ufnd_aligned(dqkv, 16),
+               "attention_bwd_dropout: 16-B alignment required");
+  UFND_REQUIRE(ufnd_attn_dropout_fits(B, L, heads), "attention_bwd_dropout: B=%d L=%d heads=%d overflows the 32-bit dropout counter", B, L, heads);
+  hipStream_t stream = (hipStream_t)stream_;
+  const float scale = 0.125f, scale_log2e = 0.125f * 1.44269504088896340736f;
+  const int tokens = B * L;
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(ufnd_cdiv(tokens, 4)), dim3(256), 0, stream, (const __bf16*)dctx, (const __bf16*)ctx, workspace, tokens, heads);
+  UFND_CHECK_LAUNCH();
+  const int nob = ufnd_cdiv(L, 128);
+  UFND_REQUIRE((long long)nob * heads * B < (1ll << 31), "attention_bwd_dropout: grid too large");
+  const dim3 grid(nob * heads * B);
+  hipLaunchKernelGGL((attention_bwd_kernel<1, true>), grid, dim3(256), 0, stream, (const __bf16*)qkv, (const __bf16*)dctx, lse, (const float*)workspace,
+                     key_mask, (__bf16*)dqkv, L, heads, scale_log2e, scale, nob, *drop);
+  UFND_CHECK_LAUNCH();
+  hipLaunchKernelGGL((attention_bwd_kernel<2, true>), grid, dim3(256), 0, stream, (const __bf16*)qkv, (const __bf16*)dctx, lse, (const float*)workspace,
+                     key_mask, (__bf16*)dqkv, L, heads, scale_log2e, scale, nob, *drop);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

@@ -23,9 +23,12 @@ __device__ __forceinline__ bool masked_block_is_noop(const float* kb, int lane, 
   return __all(kb[lane] != 0.0f) && __all(m_run[0] > -1.0e30f && m_run[1] > -1.0e30f);
 }
 
-template <int KT>
+// DROP (attention.hip's training forward with dropout): pf gets exp2(score - m_new) * dm[kt][r] -- the dropout multiplier applied in fp32
+// just before the bf16 rounding -- while l_run keeps summing the UNDROPPED probabilities (HF: dropout after the softmax).
+template <int KT, bool DROP = false>
 __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const int qt, const float* kbias, const bool any_masked, const int g,
-                                                      const float scale_log2e, float& m_run, float& l_run, bf16x8 (&pf)[KT / 2][2]) {
+                                                      const float scale_log2e, float& m_run, float& l_run, bf16x8 (&pf)[KT / 2][2],
+                                                      const f32x4* dm = nullptr) {
 #pragma clang fp contract(off)
   float mx = -INFINITY, lsum = 0.0f, m_new, alpha;
   if (any_masked) {
@@ -49,7 +52,8 @@ __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const i
       for (int r = 0; r < 4; ++r) {
         const float p = fast_exp2(s[kt][qt][r] - m_new);
         lsum += p;
-        pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)p;
+        if constexpr (DROP) pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)(p * dm[kt][r]);
+        else pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)p;
       }
   } else {
 #pragma unroll
@@ -67,7 +71,8 @@ __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const i
       for (int r = 0; r < 4; ++r) {
         const float p = fast_exp2(__builtin_fmaf(s[kt][qt][r], scale_log2e, neg_m));
         lsum += p;
-        pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)p;
+        if constexpr (DROP) pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)(p * dm[kt][r]);
+        else pf[kt >> 1][qt][(kt & 1) * 4 + r] = (__bf16)p;
       }
   }
   l_run = __builtin_fmaf(l_run, alpha, lsum);

@@ -197,3 +197,27 @@ __device__ __forceinline__ void dropout_mul4(const ufnd_step_state* st, float p,
 #pragma unroll
   for (int q = 0; q < 4; ++q) m[q] = dropout_keep(w[q], p);
 }
+// the same for a counter (= element / 4) and a seed / step already loaded (kernels that draw many groups per lane)
+__device__ __forceinline__ void dropout_mul4_ctr(uint64_t seed, uint64_t step, float p, uint32_t layer, uint32_t ctr, float (&m)[4]) {
+  uint32_t w[4];
+  philox_4x32(seed, step, layer, ctr, w);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) m[q] = dropout_keep(w[q], p);
+}
+
+// Dropout stream tags (the counter's second word).  Every (module, layer, site) owns one; the ranges in use:
+//   1 .. 5         the head (tier_a.hip: LAYER_FUSE0 .. LAYER_TREE)
+//   9, 10          the GCN (gcn.hip)
+//   16 + block     the TCN (tcn.hip; open-ended upwards, far below 256 for any real depth)
+//   21             the temporal alignment (temporal.hip)
+//   256 ..         the trainable text encoder (encoder_train.py): 256 = embeddings, 257 + 3 i + s for layer i, site s = 0 attention
+//                  probabilities, 1 attention output, 2 FFN output (layers <= 1279 stay below 4096)
+//   4096 ..        the trainable visual encoder: 4096 + i = attention probabilities of layer i (CLIP has no hidden-state dropout)
+// A dropped attention probability tensor has B heads L Lp elements (Lp = L rounded up to 4): its Philox counters (element / 4)
+// must fit the 32-bit counter word.
+static inline bool ufnd_attn_dropout_fits(int B, int L, int heads) {
+  const long long lp = (L + 3) / 4 * 4;
+  return (long long)B * heads * L * lp / 4 <= (1ll << 32);
+}
+constexpr uint32_t UFND_TAG_TEXT = 256;
+constexpr uint32_t UFND_TAG_VISION = 4096;

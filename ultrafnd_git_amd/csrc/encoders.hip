@@ -72,6 +72,41 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, int ldx,
   store_row<NI>(v, ob, of, row, H, lane);
 }
 
+// Training dropout at a LayerNorm (the trainable text encoder, HF BertModel.train()); element (row, col) of the (M, H) site is
+// row H + col: a lane's 4 columns are one Philox evaluation.
+//   RESID (BertSelfOutput / BertOutput):  y = x + m o d  (d = the dense output with its bias; y stored: the backward's LayerNorm input),
+//                                         out = LayerNorm(y)
+//   !RESID (BertEmbeddings):              out = m o LayerNorm(x)
+// Same launch count as the GEMM-with-residual + ufnd_layernorm pair it replaces.
+template <int NI, bool RESID>
+__global__ __launch_bounds__(256) void dropout_layernorm_kernel(const float* x, int ldx, const float* d, int ldd, const float* gamma,
+                                                                const float* beta, float* y, __bf16* ob, float* of, int M, int H, float eps,
+                                                                ufnd_dropout dr) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const uint64_t seed = dr.state->seed, step = dr.state->step;
+  f32x4 v[NI], m[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int col = 4 * lane + 256 * i;
+    float m4[4];
+    dropout_mul4_ctr(seed, step, dr.p, dr.tag, (uint32_t)(((size_t)row * H + col) >> 2), m4);
+    m[i] = f32x4{m4[0], m4[1], m4[2], m4[3]};
+    v[i] = ld4(x + (size_t)row * ldx + col);
+    if constexpr (RESID) {
+      v[i] += m[i] * ld4(d + (size_t)row * ldd + col);
+      *reinterpret_cast<f32x4*>(y + (size_t)row * H + col) = v[i];
+    }
+  }
+  ln_row<NI>(v, H, eps, gamma, beta, lane);
+  if constexpr (!RESID) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) v[i] *= m[i];
+  }
+  store_row<NI>(v, ob, of, row, H, lane);
+}
+
 template <int NI>
 __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* ids, const float* word, const float* pos,
                                                          const float* type0, const float* gamma, const float* beta,
@@ -290,6 +325,15 @@ __global__ __launch_bounds__(256) void field_mean_l2_kernel(const float* parts, 
     else hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                    \
   } while (0)
 
+// the same over a kernel with a second template argument T
+#define NI_LAUNCH_T(H, KERNEL, T, GRID, STREAM, ...)                                                       \
+  do {                                                                                                     \
+    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);           \
+    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
+    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
+    else hipLaunchKernelGGL((KERNEL<4, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                      \
+  } while (0)
+
 inline bool h_ok(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
 
 }  // namespace
@@ -302,6 +346,35 @@ extern "C" int ufnd_layernorm(const float* x, int ldx, const float* gamma, const
                "layernorm: alignment");
   NI_LAUNCH(H, layernorm_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, x, ldx, gamma, beta, (__bf16*)out_bf16,
             out_f32, M, H, eps);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_dropout_residual_layernorm(const float* x, int ldx, const float* d, int ldd, const float* gamma, const float* beta, float* y,
+                                               void* out_bf16, float* out_f32, int M, int H, float eps, const ufnd_dropout* drop, void* stream_) {
+  UFND_REQUIRE(x && d && gamma && beta && y && (out_bf16 || out_f32) && M >= 1 && drop && drop->state, "dropout_residual_layernorm: null argument");
+  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "dropout_residual_layernorm: p=%g (0 < p < 1)", (double)drop->p);
+  UFND_REQUIRE(h_ok(H), "dropout_residual_layernorm: H=%d (supported 256/512/768/1024)", H);
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ldd % 4 == 0 && ldd >= H && ufnd_aligned(x, 16) && ufnd_aligned(d, 16) && ufnd_aligned(y, 16) &&
+                   ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16) && (!out_f32 || ufnd_aligned(out_f32, 16)) && (!out_bf16 || ufnd_aligned(out_bf16, 8)),
+               "dropout_residual_layernorm: alignment");
+  UFND_REQUIRE((long long)M * H / 4 <= (1ll << 32), "dropout_residual_layernorm: M=%d H=%d overflows the 32-bit dropout counter", M, H);
+  NI_LAUNCH_T(H, dropout_layernorm_kernel, true, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, x, ldx, d, ldd, gamma, beta, y, (__bf16*)out_bf16,
+            out_f32, M, H, eps, *drop);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_layernorm_dropout(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32, int M, int H,
+                                      float eps, const ufnd_dropout* drop, void* stream_) {
+  UFND_REQUIRE(x && gamma && beta && (out_bf16 || out_f32) && M >= 1 && drop && drop->state, "layernorm_dropout: null argument");
+  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "layernorm_dropout: p=%g (0 < p < 1)", (double)drop->p);
+  UFND_REQUIRE(h_ok(H), "layernorm_dropout: H=%d (supported 256/512/768/1024)", H);
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16) &&
+                   (!out_f32 || ufnd_aligned(out_f32, 16)) && (!out_bf16 || ufnd_aligned(out_bf16, 8)), "layernorm_dropout: alignment");
+  UFND_REQUIRE((long long)M * H / 4 <= (1ll << 32), "layernorm_dropout: M=%d H=%d overflows the 32-bit dropout counter", M, H);
+  NI_LAUNCH_T(H, dropout_layernorm_kernel, false, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, x, ldx, (const float*)nullptr, 0, gamma, beta,
+            (float*)nullptr, (__bf16*)out_bf16, out_f32, M, H, eps, *drop);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

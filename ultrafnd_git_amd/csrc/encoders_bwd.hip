@@ -13,11 +13,15 @@ __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<
 
 // y = (x - mean) rstd gamma + beta  ->  dx = rstd (g - mean(g) - xh mean(g xh)),  g = dy gamma,  xh = (x - mean) rstd
 // (+ `add`: the gradient arriving over the residual branch).  dgamma / dbeta partials per block: part[blk][0/1][H].
-template <int NI>
+// DROPAT (training dropout of the text encoder, mask regenerated: element row H + col, encoders.hip dropout_layernorm_kernel):
+//   UFND_LN_BWD_DROP_DXB  y = x_res + m o dense(..): the bf16 output (the dense layer's dgrad / wgrad / bias-gradient input) is
+//                         m o dx; the fp32 output (the residual's gradient) stays unmasked
+//   UFND_LN_BWD_DROP_DY   out = m o LayerNorm(x): dy is multiplied by m on arrival
+template <int NI, int DROPAT = 0>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                             const float* __restrict__ dy, int lddy, const float* __restrict__ add, int ldadd,
                                                             float* __restrict__ dx, __bf16* __restrict__ dxb, int lddx, float* __restrict__ part,
-                                                            int M, int H, float eps) {
+                                                            int M, int H, float eps, ufnd_dropout dr) {
   __shared__ f32x4 sh[2][4][NI][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   f32x4 dg[NI], db[NI], gm[NI];
@@ -29,12 +33,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   }
   const float inv_h = 1.0f / (float)H;
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-    f32x4 v[NI], g[NI];
+    f32x4 v[NI], g[NI], dm[NI];
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       v[i] = ld4(x + (size_t)row * ldx + 4 * lane + 256 * i);
       g[i] = ld4(dy + (size_t)row * lddy + 4 * lane + 256 * i);
+      if constexpr (DROPAT != 0) {
+        float m4[4];
+        dropout_mul4_ctr(dr.state->seed, dr.state->step, dr.p, dr.tag, (uint32_t)(((size_t)row * H + 4 * lane + 256 * i) >> 2), m4);
+        dm[i] = f32x4{m4[0], m4[1], m4[2], m4[3]};
+        if constexpr (DROPAT == UFND_LN_BWD_DROP_DY) g[i] *= dm[i];
+      }
       s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
     const float mean = wave_sum(s) * inv_h;
@@ -72,6 +82,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       if (add) o += ld4(add + (size_t)row * ldadd + col);
       if (dx) *reinterpret_cast<f32x4*>(dx + (size_t)row * lddx + col) = o;
       if (dxb) {
+        if constexpr (DROPAT == UFND_LN_BWD_DROP_DXB) o *= dm[i];      // (after the fp32 store)
         bf16x4 ob = {(__bf16)o[0], (__bf16)o[1], (__bf16)o[2], (__bf16)o[3]};
         *reinterpret_cast<bf16x4*>(dxb + (size_t)row * lddx + col) = ob;
       }
@@ -329,6 +340,15 @@ __global__ __launch_bounds__(256) void act_bf16_kernel(const __bf16* __restrict_
     else hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                    \
   } while (0)
 
+// the same over a kernel with a second template argument T
+#define NI_LAUNCH_T(H, KERNEL, T, GRID, STREAM, ...)                                                       \
+  do {                                                                                                     \
+    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);           \
+    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
+    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
+    else hipLaunchKernelGGL((KERNEL<4, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                      \
+  } while (0)
+
 inline bool h_ok(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
 inline int ln_bwd_blocks(int M) { const int b = ufnd_cdiv(M, 8); return b < 1 ? 1 : (b > 256 ? 256 : b); }
 
@@ -360,7 +380,40 @@ extern "C" int ufnd_layernorm_bwd(const float* x, int ldx, const float* gamma, c
   const bool defer = accumulate == UFND_PARTIALS_DEFER;
   UFND_REQUIRE(!defer || workspace, "layernorm_bwd: deferred parameter gradients need the workspace");
   float* part = (dgamma || dbeta || defer) ? workspace : nullptr;
-  NI_LAUNCH(H, layernorm_bwd_kernel, dim3(nblk), stream, x, ldx, gamma, dy, lddy, add, ldadd, dx_f32, (__bf16*)dx_bf16, lddx, part, M, H, eps);
+  NI_LAUNCH(H, layernorm_bwd_kernel, dim3(nblk), stream, x, ldx, gamma, dy, lddy, add, ldadd, dx_f32, (__bf16*)dx_bf16, lddx, part, M, H, eps,
+            ufnd_dropout{});
+  UFND_CHECK_LAUNCH();
+  if (part && !defer) {
+    hipLaunchKernelGGL(row_partials_finish_kernel, dim3(ufnd_cdiv(H, 16), 2), dim3(256), 0, stream, part, nblk, H, dgamma, dbeta, accumulate);
+    UFND_CHECK_LAUNCH();
+  }
+  return UFND_OK;
+}
+
+extern "C" int ufnd_layernorm_bwd_dropout(const float* x, int ldx, const float* gamma, const float* dy, int lddy, const float* add, int ldadd,
+                                          float* dx_f32, void* dx_bf16, int lddx, float* dgamma, float* dbeta, float* workspace, int accumulate,
+                                          int M, int H, float eps, const ufnd_dropout* drop, int where, void* stream_) {
+  UFND_REQUIRE(x && gamma && dy && (dx_f32 || dx_bf16) && M >= 1 && drop && drop->state, "layernorm_bwd_dropout: null argument");
+  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "layernorm_bwd_dropout: p=%g (0 < p < 1; p = 0 is ufnd_layernorm_bwd)", (double)drop->p);
+  UFND_REQUIRE(where == UFND_LN_BWD_DROP_DXB || where == UFND_LN_BWD_DROP_DY, "layernorm_bwd_dropout: where=%d", where);
+  UFND_REQUIRE(where != UFND_LN_BWD_DROP_DXB || dx_bf16, "layernorm_bwd_dropout: the mask at the bf16 output needs dx_bf16");
+  UFND_REQUIRE(h_ok(H), "layernorm_bwd_dropout: H=%d (supported 256/512/768/1024)", H);
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && lddy % 4 == 0 && lddy >= H && lddx % 8 == 0 && lddx >= H && (!add || (ldadd % 4 == 0 && ldadd >= H)),
+               "layernorm_bwd_dropout: strides");
+  UFND_REQUIRE(ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(dy, 16) && (!add || ufnd_aligned(add, 16)) &&
+                   (!dx_f32 || ufnd_aligned(dx_f32, 16)) && (!dx_bf16 || ufnd_aligned(dx_bf16, 8)), "layernorm_bwd_dropout: alignment");
+  UFND_REQUIRE((long long)M * H / 4 <= (1ll << 32), "layernorm_bwd_dropout: M=%d H=%d overflows the 32-bit dropout counter", M, H);
+  const bool defer = accumulate == UFND_PARTIALS_DEFER;
+  UFND_REQUIRE(((!dgamma && !dbeta) && !defer) || workspace, "layernorm_bwd_dropout: parameter gradients need the workspace");
+  hipStream_t stream = (hipStream_t)stream_;
+  const int nblk = ln_bwd_blocks(M);
+  float* part = (dgamma || dbeta || defer) ? workspace : nullptr;
+  if (where == UFND_LN_BWD_DROP_DXB)
+    NI_LAUNCH_T(H, layernorm_bwd_kernel, UFND_LN_BWD_DROP_DXB, dim3(nblk), stream, x, ldx, gamma, dy, lddy, add, ldadd, dx_f32, (__bf16*)dx_bf16, lddx,
+                part, M, H, eps, *drop);
+  else
+    NI_LAUNCH_T(H, layernorm_bwd_kernel, UFND_LN_BWD_DROP_DY, dim3(nblk), stream, x, ldx, gamma, dy, lddy, add, ldadd, dx_f32, (__bf16*)dx_bf16, lddx,
+                part, M, H, eps, *drop);
   UFND_CHECK_LAUNCH();
   if (part && !defer) {
     hipLaunchKernelGGL(row_partials_finish_kernel, dim3(ufnd_cdiv(H, 16), 2), dim3(256), 0, stream, part, nblk, H, dgamma, dbeta, accumulate);

@@ -20,7 +20,14 @@ How it is built.
     dy and x (dy's column sums = the bias gradient fall out of the same pass), weight gradient as the forward's NT kernel over
     the token dimension with split-K slabs, data gradient as the NT kernel on W^T with the residual-branch gradient or the
     activation derivative fused into its epilogue -> flash-style attention backward.  No atomics anywhere: gradients are
-    run-to-run identical."""
+    run-to-run identical.
+  * Dropout (HF train mode; BertTextEncoder.hidden_dropout_prob / .attention_probs_dropout_prob, ClipVisualEncoder.attention_dropout).
+    Only here, never in the frozen paths.  At p = 0 a site runs exactly the launches it ran before dropout existed.  At p > 0:
+    attention probabilities -> ufnd_attention_bf16_lse_dropout / _bwd_dropout; a text hidden site -> the dense GEMM writes its output
+    without the residual and ufnd_dropout_residual_layernorm forms x + m o d and its LayerNorm (same launch count), the LayerNorm
+    backward masks its bf16 output; the embeddings -> ufnd_layernorm_dropout, and the LayerNorm backward masks its dy.  No mask is
+    stored: the kernels regenerate it from (seed, step) of `rng()` -- the trainer's step state (the head's), or the encoder's own,
+    advanced by every forward_train -- and the site's tag (`text_tag`, `vision_tag`; ranges in csrc/common.hpp)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
@@ -28,8 +35,25 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib as L
+from .encoders import dropout_prob
+from .state import StepStateBuffer
 
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_GELU_BWD, ACT_QUICK_GELU_BWD = 0, 1, 2, 3, 4
+
+# dropout stream tags (csrc/common.hpp: UFND_TAG_TEXT, UFND_TAG_VISION)
+TAG_TEXT, TAG_VISION = 256, 4096
+SITE_ATTN, SITE_ATTN_OUT, SITE_FFN_OUT = 0, 1, 2
+TAG_TEXT_EMB = TAG_TEXT
+
+
+def text_tag(layer: int, site: int) -> int:
+    """Text encoder layer `layer`, site SITE_ATTN (probabilities) / SITE_ATTN_OUT / SITE_FFN_OUT."""
+    return TAG_TEXT + 1 + 3 * layer + site
+
+
+def vision_tag(layer: int) -> int:
+    """Visual encoder layer `layer`: the attention probabilities."""
+    return TAG_VISION + layer
 
 
 def _pad64(n: int) -> int:
@@ -56,6 +80,33 @@ class _Backprop:
         # A/B/A/B on one box: 9.17 / 9.24 ms per step with it, 9.48 / 9.42 without -- once the host enqueue had come down to 4.6-5.2 ms per step
         # (memoised arena views); at 6.4 ms the events' extra 2-3 ms of host time made the step host-bound and the overlap invisible
         self.overlap_wgrad = True
+        self.drop_state: Optional[StepStateBuffer] = None      # the trainer sets its own (the head's); None: rng() makes one
+        self._owns_state = False
+        self._drops: Dict[Tuple[int, float, int], object] = {}
+
+    # ------------------------------------------------------------------ dropout
+    def rng(self) -> StepStateBuffer:
+        """The step state the dropout masks are drawn from (seed, step on the device): the trainer's, or this encoder's own (as
+        DeepTruthClassifier.rng()), which every forward_train with dropout advances first."""
+        if self.drop_state is None:
+            self.drop_state = StepStateBuffer(self.enc.device, seed=torch.initial_seed() + 0xE7C)
+            self._owns_state = True
+        return self.drop_state
+
+    def _begin_dropout(self) -> None:
+        """Start of a training forward with dropout: a state of our own moves to the next step (forward and backward share it)."""
+        st = self.rng()
+        if self._owns_state:
+            st.advance()
+
+    def _drop(self, p: float, tag: int):
+        """The ufnd_dropout descriptor of a site (memoised: one per site)."""
+        st = self.rng()
+        key = (st.ptr, p, tag)
+        d = self._drops.get(key)
+        if d is None:
+            d = self._drops[key] = L.Dropout(st.ptr, p, tag)
+        return d
 
     # ------------------------------------------------------------------ parameters
     def groups(self) -> List[List[Tuple[str, Tuple[int, ...]]]]:
@@ -244,7 +295,9 @@ class _Backprop:
             L.check(L.lib().ufnd_row_partials_finish(C.byref(job[0]), 0, L.stream_ptr(self.enc.device)), "ufnd_row_partials_finish")
             job[1]["ln_busy"][job[2]] = None            # (stream order protects the buffer)
 
-    def _ln_bwd(self, sc: dict, x, ldx, gamma, dy, dx_f32, dx_bf16, lddx, dgamma, dbeta, M, add=None):
+    def _ln_bwd(self, sc: dict, x, ldx, gamma, dy, dx_f32, dx_bf16, lddx, dgamma, dbeta, M, add=None, drop=None, where=0):
+        """drop (a ufnd_dropout) / where (L.LN_BWD_DROP_DXB or _DY): the mask of a dropout site at this LayerNorm."""
+        import ctypes as C
         H = self.enc.hidden
         self._flush_ln()                   # one pending job at a time: a LayerNorm backward right behind another one finishes the first here
         kk = sc["ln_flip"]
@@ -253,16 +306,39 @@ class _Backprop:
             torch.cuda.current_stream(x.device).wait_event(sc["ln_busy"][kk])
             sc["ln_busy"][kk] = None
         ws = sc["ln"][kk]
-        L.check(L.lib().ufnd_layernorm_bwd(x.data_ptr(), ldx, gamma.data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add), add.stride(0) if add is not None else 0,
-                                           L.ptr(dx_f32), L.ptr(dx_bf16), lddx, L.ptr(dgamma), L.ptr(dbeta), ws.data_ptr(), L.PARTIALS_DEFER, M, H,
-                                           self.enc.eps, L.stream_ptr(x.device)), "ufnd_layernorm_bwd")
+        args = (x.data_ptr(), ldx, gamma.data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add), add.stride(0) if add is not None else 0,
+                L.ptr(dx_f32), L.ptr(dx_bf16), lddx, L.ptr(dgamma), L.ptr(dbeta), ws.data_ptr(), L.PARTIALS_DEFER, M, H, self.enc.eps)
+        if drop is None:
+            L.check(L.lib().ufnd_layernorm_bwd(*args, L.stream_ptr(x.device)), "ufnd_layernorm_bwd")
+        else:
+            L.check(L.lib().ufnd_layernorm_bwd_dropout(*args, C.byref(drop), where, L.stream_ptr(x.device)), "ufnd_layernorm_bwd_dropout")
         job = L.PartialsJob()
         job.part, job.nblk, job.H, job.out0, job.out1 = ws.data_ptr(), L.lib().ufnd_layernorm_bwd_blocks(M), H, dgamma.data_ptr(), dbeta.data_ptr()
         self._pending_ln = (job, sc, kk)
 
-    def _attn_bwd(self, qkv, ctx, dctx, lse, mask, dqkv, ws, B, Lq):
-        L.check(L.lib().ufnd_attention_bf16_bwd(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), L.ptr(mask), dqkv.data_ptr(), ws.data_ptr(),
-                                                B, Lq, self.enc.heads, L.stream_ptr(qkv.device)), "ufnd_attention_bf16_bwd")
+    def _attn_fwd(self, qkv, mask, ctx, lse, B, Lq, drop=None):
+        import ctypes as C
+        args = (qkv.data_ptr(), L.ptr(mask), ctx.data_ptr(), lse.data_ptr(), B, Lq, self.enc.heads)
+        if drop is None:
+            L.check(L.lib().ufnd_attention_bf16_lse(*args, L.stream_ptr(qkv.device)), "ufnd_attention_bf16_lse")
+        else:
+            L.check(L.lib().ufnd_attention_bf16_lse_dropout(*args, C.byref(drop), L.stream_ptr(qkv.device)), "ufnd_attention_bf16_lse_dropout")
+
+    def _attn_bwd(self, qkv, ctx, dctx, lse, mask, dqkv, ws, B, Lq, drop=None):
+        import ctypes as C
+        args = (qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), L.ptr(mask), dqkv.data_ptr(), ws.data_ptr(), B, Lq, self.enc.heads)
+        if drop is None:
+            L.check(L.lib().ufnd_attention_bf16_bwd(*args, L.stream_ptr(qkv.device)), "ufnd_attention_bf16_bwd")
+        else:
+            L.check(L.lib().ufnd_attention_bf16_bwd_dropout(*args, C.byref(drop), L.stream_ptr(qkv.device)), "ufnd_attention_bf16_bwd_dropout")
+
+    def _drop_ln(self, x, d, gamma, beta, y, out_bf16, out_f32, M, drop) -> None:
+        """y = x + m o d, out = LayerNorm(y) (a post-LN residual site with dropout on the dense output d)."""
+        import ctypes as C
+        e = self.enc
+        L.check(L.lib().ufnd_dropout_residual_layernorm(x.data_ptr(), x.stride(0), d.data_ptr(), d.stride(0), gamma.data_ptr(), beta.data_ptr(),
+                                                        y.data_ptr(), L.ptr(out_bf16), L.ptr(out_f32), M, e.hidden, e.eps, C.byref(drop),
+                                                        L.stream_ptr(x.device)), "ufnd_dropout_residual_layernorm")
 
 
 def _act(x: torch.Tensor, out: torch.Tensor, act: int) -> None:
@@ -332,27 +408,48 @@ class TextBackprop(_Backprop):
         sv = self._save_bufs(B, Lq)
         M, H, w, s = B * Lq, e.hidden, e._w, L.stream_ptr(dev)
         lib = L.lib()
+        ph = dropout_prob("hidden_dropout_prob", e.hidden_dropout_prob)
+        pa = dropout_prob("attention_probs_dropout_prob", e.attention_probs_dropout_prob)
+        if ph > 0.0 or pa > 0.0:
+            self._begin_dropout()
+        if ph > 0.0 and "d" not in sv:
+            sv["d"] = torch.empty(M, H, dtype=torch.float32, device=dev)       # a hidden site's dense output (without its residual)
         # embeddings: the raw sums are kept (their LayerNorm's backward needs its input)
         L.check(lib.ufnd_bert_embed(ids.data_ptr(), w["embeddings.word_embeddings.weight"].data_ptr(), w["embeddings.position_embeddings.weight"].data_ptr(),
                                     w["embeddings.token_type_embeddings.weight"].data_ptr(), None, None, None, sv["s"].data_ptr(), B, Lq, H, e.vocab, e.eps, s),
                 "ufnd_bert_embed")
         x_f, x_b = sv["xf"], sv["layers"][0]["xb"]
-        e._ln(sv["s"], H, w["embeddings.LayerNorm.weight"], w["embeddings.LayerNorm.bias"], x_b, x_f, M, H, e.eps)
+        if ph > 0.0:
+            import ctypes as C
+            L.check(lib.ufnd_layernorm_dropout(sv["s"].data_ptr(), H, w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
+                                               x_b.data_ptr(), x_f.data_ptr(), M, H, e.eps, C.byref(self._drop(ph, TAG_TEXT_EMB)), s), "ufnd_layernorm_dropout")
+        else:
+            e._ln(sv["s"], H, w["embeddings.LayerNorm.weight"], w["embeddings.LayerNorm.bias"], x_b, x_f, M, H, e.eps)
         for i, a in enumerate(sv["layers"]):
             k = self._lk(i)
             wqkv, wo, w1, w2 = self._ops[f"{i}.qkv"][0], self._ops[f"{i}.o"][0], self._ops[f"{i}.w1"][0], self._ops[f"{i}.w2"][0]
             self._gemm(a["xb"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
-            L.check(lib.ufnd_attention_bf16_lse(a["qkv"].data_ptr(), mask.data_ptr(), a["ctx"].data_ptr(), a["lse"].data_ptr(), B, Lq, e.heads, s), "ufnd_attention_bf16_lse")
-            self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["y1"], residual=x_f)
-            e._ln(a["y1"], H, self.master(k["g1"]), self.master(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
+            self._attn_fwd(a["qkv"], mask, a["ctx"], a["lse"], B, Lq, self._drop(pa, text_tag(i, SITE_ATTN)) if pa > 0.0 else None)
+            if ph > 0.0:
+                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=sv["d"])
+                self._drop_ln(x_f, sv["d"], self.master(k["g1"]), self.master(k["b1n"]), a["y1"], a["x1b"], sv["x1f"], M,
+                              self._drop(ph, text_tag(i, SITE_ATTN_OUT)))
+            else:
+                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["y1"], residual=x_f)
+                e._ln(a["y1"], H, self.master(k["g1"]), self.master(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
             self._gemm(a["x1b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
             _act(a["pre"], a["h"], ACT_GELU)
-            self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
             nxt_b = sv["layers"][i + 1]["xb"] if i + 1 < e.layers else sv["xb_last"]
-            e._ln(a["y2"], H, self.master(k["g2"]), self.master(k["b2n"]), nxt_b, x_f, M, H, e.eps)
+            if ph > 0.0:
+                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=sv["d"])
+                self._drop_ln(sv["x1f"], sv["d"], self.master(k["g2"]), self.master(k["b2n"]), a["y2"], nxt_b, x_f, M,
+                              self._drop(ph, text_tag(i, SITE_FFN_OUT)))
+            else:
+                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
+                e._ln(a["y2"], H, self.master(k["g2"]), self.master(k["b2n"]), nxt_b, x_f, M, H, e.eps)
         sv["hid"].copy_(x_f)
         L.check(lib.ufnd_masked_meanpool_l2(sv["hid"].data_ptr(), mask.data_ptr(), sv["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
-        self.saved = {"B": B, "L": Lq, "ids": ids, "mask": mask, "sv": sv}
+        self.saved = {"B": B, "L": Lq, "ids": ids, "mask": mask, "sv": sv, "ph": ph, "pa": pa}
         return sv["feat"]
 
     @torch.no_grad()
@@ -362,7 +459,9 @@ class TextBackprop(_Backprop):
         if st is None:
             raise RuntimeError("backward() without forward_train()")
         B, Lq, ids, mask, sv = st["B"], st["L"], st["ids"], st["mask"], st["sv"]
+        ph, pa = st["ph"], st["pa"]
         M, H, I = B * Lq, e.hidden, e.inter
+        DXB = L.LN_BWD_DROP_DXB
         sc = self._bwd_scratch(M, (H, 3 * H, I))
         s = L.stream_ptr(e.device)
         dfeat = L.f32c(dfeat)
@@ -373,22 +472,25 @@ class TextBackprop(_Backprop):
             a, k = sv["layers"][i], self._lk(i)
             ops = {n: self._ops[f"{i}.{n}"] for n in ("qkv", "o", "w1", "w2")}
             # output.LayerNorm, output.dense, GELU, intermediate.dense
-            self._ln_bwd(sc, a["y2"], H, self.master(k["g2"]), dx, sv["dyf"], sv["dyb"], H, self.grad(k["g2"]), self.grad(k["b2n"]), M)
+            self._ln_bwd(sc, a["y2"], H, self.master(k["g2"]), dx, sv["dyf"], sv["dyb"], H, self.grad(k["g2"]), self.grad(k["b2n"]), M,
+                         drop=self._drop(ph, text_tag(i, SITE_FFN_OUT)) if ph > 0.0 else None, where=DXB)
             self._wgrad(sc, sv["dyb"], a["h"], self.grad(k["w2"]), self.grad(k["b2"]))
             self._dgrad(sv["dyb"], ops["w2"][1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_GELU_BWD)
             self._wgrad(sc, sv["dpre"], a["x1b"], self.grad(k["w1"]), self.grad(k["b1"]))
             self._dgrad(sv["dpre"], ops["w1"][1], out_f32=sv["dx1"], residual=sv["dyf"])
             # attention.output.LayerNorm, attention.output.dense, attention, q/k/v
-            self._ln_bwd(sc, a["y1"], H, self.master(k["g1"]), sv["dx1"], sv["dyf"], sv["dyb"], H, self.grad(k["g1"]), self.grad(k["b1n"]), M)
+            self._ln_bwd(sc, a["y1"], H, self.master(k["g1"]), sv["dx1"], sv["dyf"], sv["dyb"], H, self.grad(k["g1"]), self.grad(k["b1n"]), M,
+                         drop=self._drop(ph, text_tag(i, SITE_ATTN_OUT)) if ph > 0.0 else None, where=DXB)
             self._wgrad(sc, sv["dyb"], a["ctx"], self.grad(k["o_w"]), self.grad(k["o_b"]))
             self._dgrad(sv["dyb"], ops["o"][1], out_bf16=sv["dctx"])
-            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], mask, sv["dqkv"], sv["aws"], B, Lq)
+            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], mask, sv["dqkv"], sv["aws"], B, Lq,
+                           self._drop(pa, text_tag(i, SITE_ATTN)) if pa > 0.0 else None)
             self._wgrad(sc, sv["dqkv"], a["xb"], self.grad(k["qkv_w"]), self.grad(k["qkv_b"]))
             self._dgrad(sv["dqkv"], ops["qkv"][1], out_f32=dx, residual=sv["dyf"])
         # embeddings: LayerNorm backward to the raw sums, then the three tables
         ek = "embeddings."
         self._ln_bwd(sc, sv["s"], H, self.master([ek + "LayerNorm.weight"]), dx, sv["ds"], None, H, self.grad([ek + "LayerNorm.weight"]),
-                     self.grad([ek + "LayerNorm.bias"]), M)
+                     self.grad([ek + "LayerNorm.bias"]), M, drop=self._drop(ph, TAG_TEXT_EMB) if ph > 0.0 else None, where=L.LN_BWD_DROP_DY)
         L.check(L.lib().ufnd_bert_embed_bwd(ids.data_ptr(), sv["ds"].data_ptr(), self.grad([ek + "word_embeddings.weight"]).data_ptr(),
                                             self.grad([ek + "position_embeddings.weight"]).data_ptr(), self.grad([ek + "token_type_embeddings.weight"]).data_ptr(),
                                             B, Lq, H, e.vocab, e.max_position, self.master([ek + "token_type_embeddings.weight"]).shape[0], s), "ufnd_bert_embed_bwd")
@@ -467,6 +569,9 @@ class VisualBackprop(_Backprop):
             raise RuntimeError(f"frames: expected (B,F,3,{e.image},{e.image}), got {tuple(frames.shape)}")
         fr = L.f32c(frames.to(dev)).view(B * Fr, 3, e.image, e.image)
         sv = self._save_bufs(B, Fr)
+        pa = dropout_prob("attention_dropout", e.attention_dropout)
+        if pa > 0.0:
+            self._begin_dropout()
         N, T, H, w, V = B * Fr, e.n_patches + 1, e.hidden, e._w, self.V
         M, s, lib = N * T, L.stream_ptr(dev), L.lib()
         L.check(lib.ufnd_vit_patchify(fr.data_ptr(), sv["patches"].data_ptr(), N, e.image, e.patch, s), "ufnd_vit_patchify")
@@ -480,7 +585,7 @@ class VisualBackprop(_Backprop):
             wqkv, wo, w1, w2 = self._ops[f"{i}.qkv"][0], self._ops[f"{i}.o"][0], self._ops[f"{i}.w1"][0], self._ops[f"{i}.w2"][0]
             e._ln(a["xin"], H, self.master(k["g1"]), self.master(k["b1n"]), a["h1b"], None, M, H, e.eps)
             self._gemm(a["h1b"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
-            L.check(lib.ufnd_attention_bf16_lse(a["qkv"].data_ptr(), None, a["ctx"].data_ptr(), a["lse"].data_ptr(), N, T, e.heads, s), "ufnd_attention_bf16_lse")
+            self._attn_fwd(a["qkv"], None, a["ctx"], a["lse"], N, T, self._drop(pa, vision_tag(i)) if pa > 0.0 else None)
             self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["xmid"], residual=a["xin"])
             e._ln(a["xmid"], H, self.master(k["g2"]), self.master(k["b2n"]), a["h2b"], None, M, H, e.eps)
             self._gemm(a["h2b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
@@ -490,7 +595,7 @@ class VisualBackprop(_Backprop):
         e._ln(sv["xout"], T * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], sv["pooled_b"], sv["pooled_f"], N, H, e.eps)
         self._gemm(sv["pooled_b"][:N], self._ops["proj"][0], None, out_f32=sv["e"])
         L.check(lib.ufnd_l2norm_frames(sv["e"].data_ptr(), sv["feat"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames")
-        self.saved = {"B": B, "F": Fr, "sv": sv}
+        self.saved = {"B": B, "F": Fr, "sv": sv, "pa": pa}
         return sv["feat"]
 
     @torch.no_grad()
@@ -528,7 +633,8 @@ class VisualBackprop(_Backprop):
             # attention branch: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
             self._wgrad(sc, sv["dmidb"], a["ctx"], self.grad(k["o_w"]), self.grad(k["o_b"]))
             self._dgrad(sv["dmidb"], ops["o"][1], out_bf16=sv["dctx"])
-            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T)
+            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T,
+                           self._drop(st["pa"], vision_tag(i)) if st["pa"] > 0.0 else None)
             self._wgrad(sc, sv["dqkv"], a["h1b"], self.grad(k["qkv_w"]), self.grad(k["qkv_b"]))
             self._dgrad(sv["dqkv"], ops["qkv"][1], out_f32=sv["dh"])
             self._ln_bwd(sc, a["xin"], H, self.master(k["g1"]), sv["dh"], dx, sv["dxb"], H, self.grad(k["g1"]), self.grad(k["b1n"]), M, add=sv["dmid"])

@@ -54,6 +54,14 @@ def _bf16(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def dropout_prob(name: str, p) -> float:
+    """A dropout probability of the trainable encoders (HF config names), refused by name outside [0, 1)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}={p!r}: a dropout probability in [0, 1)")
+    return p
+
+
 class _EncoderBase(nn.Module):
     """Weight store with third-party key names + lazily packed bf16 operands + per-shape buffers."""
 
@@ -210,9 +218,14 @@ class _EncoderBase(nn.Module):
 class BertTextEncoder(_EncoderBase):
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
                  vocab_size: int = 30522, max_position: int = 512, type_vocab: int = 2, eps: float = 1e-12,
-                 fold_ln: bool = True, residual_dtype: str = "bf16"):
+                 fold_ln: bool = True, residual_dtype: str = "bf16", hidden_dropout_prob: float = 0.0,
+                 attention_probs_dropout_prob: float = 0.0):
         super().__init__()
         self.fold_ln = fold_ln
+        # train-mode dropout (HF BertConfig names): applied only by encoder_train.TextBackprop.forward_train and its backward, never
+        # by forward() / encode_fields, whatever the module's mode
+        self.hidden_dropout_prob = dropout_prob("hidden_dropout_prob", hidden_dropout_prob)
+        self.attention_probs_dropout_prob = dropout_prob("attention_probs_dropout_prob", attention_probs_dropout_prob)
         if residual_dtype not in ("fp32", "bf16"):
             raise ValueError(f"residual_dtype={residual_dtype!r}: 'fp32' or 'bf16'")
         self.residual_dtype = residual_dtype
@@ -470,9 +483,13 @@ class BertTextEncoder(_EncoderBase):
 # =============================================================================================
 class ClipVisualEncoder(_EncoderBase):
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, patch: int = 32,
-                 image: int = 224, projection_dim: int = 512, eps: float = 1e-5, fold_ln: bool = True, residual_dtype: str = "bf16"):
+                 image: int = 224, projection_dim: int = 512, eps: float = 1e-5, fold_ln: bool = True, residual_dtype: str = "bf16",
+                 attention_dropout: float = 0.0):
         super().__init__()
         self.fold_ln = fold_ln
+        # train-mode dropout on the attention probabilities (HF CLIPVisionConfig name; CLIP has no hidden-state dropout): applied only by
+        # encoder_train.VisualBackprop.forward_train and its backward
+        self.attention_dropout = dropout_prob("attention_dropout", attention_dropout)
         if residual_dtype not in ("fp32", "bf16"):
             raise ValueError(f"residual_dtype={residual_dtype!r}: 'fp32' or 'bf16'")
         self.residual_dtype = residual_dtype

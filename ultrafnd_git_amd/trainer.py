@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -40,6 +40,7 @@ from .arena import rehome
 from .classifier import DeepTruthClassifier
 from .data import CachedTensorDataset, DeviceBatchLoader, IndexedBatch, _batch_size, synthetic_cache  # noqa: F401  (re-exported)
 from .dp import FactorExchange, GradReducer, as_comm, broadcast_from_rank0, gather_epoch_outputs, save_checkpoint
+from .encoders import dropout_prob
 from .fusion import CrossModalTransformer
 from .head_step import HeadStep
 from .metrics import aggregate_epoch_metrics, pretty_print
@@ -94,8 +95,26 @@ class TrainConfig:
     # fine-tune the encoders with the head (encoder_train.py: forward with saved activations + hand-written backward; needs
     # encode_inline and both encoders).  The reference keeps them frozen (text_blocks.py:52,63): False reproduces it.
     train_encoders: bool = False
+    # train-mode dropout of the trainable encoders (HF's BertModel.train() / CLIPVisionModel.train() regularisers; 0.1 is BERT's
+    # default).  Set together with train_encoders, it overrides all three encoder probabilities: BertTextEncoder.hidden_dropout_prob,
+    # .attention_probs_dropout_prob and ClipVisualEncoder.attention_dropout.  None keeps the encoders' own values (0.0 unless
+    # constructed otherwise).  The masks are drawn from the head's step state (seed, step); validation, test and the frozen
+    # encoder paths never drop.  An init-only option (kept as the attribute cfg.encoder_dropout), not a dataclass field: the field
+    # list stays the reference's plus the additions tests/test_host_logic.py pins.
+    encoder_dropout: InitVar[Optional[float]] = None
     # the head's forward + CE and its backward as two C-ABI calls over both modules (21 launches, same bits); False: the five module-level calls (26)
     fused_head: bool = True
+
+    def __post_init__(self, encoder_dropout: Optional[float]):
+        self.encoder_dropout = None if encoder_dropout is None else dropout_prob("encoder_dropout", encoder_dropout)
+
+
+def apply_encoder_dropout(cfg: "TrainConfig", text_encoder, visual_encoder) -> None:
+    """TrainConfig.encoder_dropout (with train_encoders): the one probability of every encoder dropout site."""
+    if cfg.train_encoders and cfg.encoder_dropout is not None:
+        p = dropout_prob("encoder_dropout", cfg.encoder_dropout)
+        text_encoder.hidden_dropout_prob = text_encoder.attention_probs_dropout_prob = p
+        visual_encoder.attention_dropout = p
 
 
 class ForensicTrainer:
@@ -168,6 +187,7 @@ class ForensicTrainer:
                 raise ValueError("train_encoders=True needs encode_inline=True with text_encoder= and visual_encoder= (and not gnn_in_graph)")
             from .encoder_train import TextBackprop, VisualBackprop
             text_encoder._require_hip(); visual_encoder._require_hip()
+            apply_encoder_dropout(cfg, text_encoder, visual_encoder)
             self.text_bp, self.vis_bp = TextBackprop(text_encoder), VisualBackprop(visual_encoder)
             extra = [[("text." + k, s) for k, s in g] for g in self.text_bp.groups()] + [[("vis." + k, s) for k, s in g] for g in self.vis_bp.groups()]
         # one flat arena for both modules: clf first (its gradients are ready first in backward)
@@ -203,6 +223,8 @@ class ForensicTrainer:
         self.optim = FusedAdamW(self.arena, lr=cfg.lr, weight_decay=cfg.weight_decay,
                                 max_norm=cfg.grad_clip if cfg.grad_clip and cfg.grad_clip > 0 else 0.0,
                                 seed=cfg.seed + 1000 * self.rank, grad_scale=self.reducer.grad_scale)
+        if self.text_bp is not None:        # encoder dropout draws from the head's step state: one (seed, step) per rank and step
+            self.text_bp.drop_state = self.vis_bp.drop_state = self.optim.state
         if cfg.use_cosine:
             self.scheduler = CosineAnnealingLR(self.optim, T_max=cfg.epochs, eta_min=cfg.lr * cfg.min_lr_scale)
         else:
