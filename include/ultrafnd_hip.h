@@ -416,6 +416,39 @@ int ufnd_attention_bf16_varlen(const void* qkv, const int32_t* cu_seqlens, void*
 int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_seqlens, const int32_t* pos_ids, float* out, int B, int H,
                             void* stream);
 
+/* Packed rows with the row count on the device (no host synchronisation, fixed launch geometry: hipGraph-capturable; a replay
+ * follows whatever mask the captured buffers hold).  Sample b of a (B, L) batch keeps its positions 0 .. n_b - 1, n_b = 1 + its last
+ * kept position (0 for an all-masked sample): only TRAILING padding is dropped, holes stay as rows and stay masked as keys, so every
+ * kept token's value is bit-identical to the padded computation for every mask.  The buffers keep their padded capacity B L; the
+ * live row count T = cu_seqlens[B] is read by every kernel at entry, and rows T .. capacity are never read into a live row.
+ *   ufnd_text_pack                 (B, L) int32 mask -> cu_seqlens (B + 1) and row_src (capacity): row_src[cu[b] + l] = b L + l
+ *   ufnd_bert_embed_live           ufnd_bert_embed of the live rows (token row_src[r] of ids (B, L))
+ *   ufnd_gemm_bf16_live / _ln_live ufnd_gemm_bf16_ex / ufnd_gemm_bf16_ln over the first *m_live of M rows: M (the capacity) picks
+ *                                  the tile and bounds the grid, workgroups past the live tiles exit at entry, the live tiles are
+ *                                  spread over every XCD; per-row arithmetic is that of the M-row call (bit-identical rows)
+ *   ufnd_qkv_attention_bf16_packed ufnd_qkv_attention_bf16 with sample b's rows at cu_seqlens[b] .. cu_seqlens[b+1] (key_mask (B, 128))
+ *   ufnd_attention_bf16_varlen_masked  ufnd_attention_bf16_varlen with a (B, max_len) key mask (NULL: every key valid)
+ *   ufnd_layernorm_live            ufnd_layernorm over the first *m_live of `capacity` rows
+ *   ufnd_masked_meanpool_l2_live   ufnd_masked_meanpool_l2 over the packed rows: the same groups and summation order */
+int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream);
+int ufnd_bert_embed_live(const int64_t* ids, const int32_t* row_src, const int* m_live, const float* word, const float* pos,
+                         const float* type0, const float* gamma, const float* beta, void* x_bf16, float* x_f32, int capacity, int L,
+                         int H, int vocab, float eps, void* stream);
+int ufnd_gemm_bf16_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16, float* out_f32,
+                        int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act, int tile_cfg, const int* m_live,
+                        void* stream);
+int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16, float* out_f32,
+                           int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act, const ufnd_gemm_ln* ln,
+                           const int* m_live, void* stream);
+int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, const int32_t* cu_seqlens,
+                                   void* ctx, int B, int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream);
+int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
+                                      int heads, void* stream);
+int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32, int capacity,
+                        int H, float eps, const int* m_live, void* stream);
+int ufnd_masked_meanpool_l2_live(const float* hidden, const int32_t* mask, const int32_t* cu_seqlens, float* out, int B, int L, int H,
+                                 void* stream);
+
 /* BertEmbeddings: LayerNorm(word[ids] + position[0..L) + token_type[0]).  Tables fp32.
  *   ids (B,L) int64 in [0,vocab).  Outputs (B*L,H): bf16 and fp32. */
 int ufnd_bert_embed(const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,

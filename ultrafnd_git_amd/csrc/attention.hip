@@ -56,8 +56,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
   const int qb = lid % nqb, h = (lid / nqb) % heads, b = lid / (nqb * heads);
   const int H = heads * 64, ld = 3 * H;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, fr = lane & 15, g = lane >> 4;
-  size_t tok0 = (size_t)b * L;
-  if (cu) {              // packed (un-padded) sequences: rows cu[b] .. cu[b+1], every key valid
+  size_t tok0 = (size_t)b * L, mtok0 = tok0;      // (the key mask keeps the padded (B, L) layout)
+  if (cu) {              // packed (un-padded) sequences: rows cu[b] .. cu[b+1], keys masked by mask[b L + key] if a mask is given
     tok0 = (size_t)cu[b];
     L = cu[b + 1] - cu[b];
     if (qb * (NW * 32) >= L) return;      // (block-uniform, before any barrier)
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     if (tid < KB) {
       const int key = kb0 + tid;
       breg = -INFINITY;
-      if (key < L) breg = (!mask || mask[tok0 + key] != 0) ? 0.0f : NEG_MASK;
+      if (key < L) breg = (!mask || mask[mtok0 + key] != 0) ? 0.0f : NEG_MASK;
     }
   };
   if constexpr (PREFETCH) load_block(0);
@@ -245,15 +245,22 @@ extern "C" int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask,
   return UFND_OK;
 }
 
+extern "C" int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B,
+                                                 int max_len, int heads, void* stream_);
 extern "C" int ufnd_attention_bf16_varlen(const void* qkv, const int32_t* cu_seqlens, void* ctx, int B, int max_len, int heads,
                                           void* stream_) {
+  return ufnd_attention_bf16_varlen_masked(qkv, cu_seqlens, nullptr, ctx, B, max_len, heads, stream_);
+}
+
+extern "C" int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B,
+                                                 int max_len, int heads, void* stream_) {
   UFND_REQUIRE(qkv && ctx && cu_seqlens, "attention_varlen: null operand");
   UFND_REQUIRE(B >= 1 && B <= 65535 && max_len >= 1 && max_len <= 4096 && heads >= 1 && heads <= 64, "attention_varlen: B=%d max_len=%d heads=%d",
                B, max_len, heads);
   UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_varlen: 16-B alignment required");
   const float scale_log2e = 0.125f * 1.44269504088896340736f;
   hipLaunchKernelGGL((attention_kernel<64, 4>), dim3(ufnd_cdiv(max_len, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
-                     (const __bf16*)qkv, (const int32_t*)nullptr, (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr,
+                     (const __bf16*)qkv, key_mask, (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr,
                      ufnd_cdiv(max_len, QB), ufnd_dropout{});
   UFND_CHECK_LAUNCH();
   return UFND_OK;

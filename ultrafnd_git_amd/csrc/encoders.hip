@@ -61,10 +61,10 @@ __device__ __forceinline__ void row_stats(const f32x4 (&v)[NI], float* stats, si
 
 template <int NI>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, int ldx, const float* gamma, const float* beta,
-                                                        __bf16* ob, float* of, int M, int H, float eps) {
+                                                        __bf16* ob, float* of, int M, int H, float eps, const int* m_live) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
+  if (row >= M || (m_live && row >= *m_live)) return;      // (m_live: M is the capacity, the first *m_live rows are live)
   f32x4 v[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) v[i] = ld4(x + (size_t)row * ldx + 4 * lane + 256 * i);
@@ -111,13 +111,15 @@ template <int NI>
 __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* ids, const float* word, const float* pos,
                                                          const float* type0, const float* gamma, const float* beta,
                                                          __bf16* ob, float* of, int M, int L, int H, int vocab,
-                                                         float eps, const int32_t* pos_ids) {
+                                                         float eps, const int32_t* pos_ids, const int32_t* row_src,
+                                                         const int* m_live) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  long long id = ids[row];
+  if (row >= M || (m_live && row >= *m_live)) return;
+  const int src = row_src ? row_src[row] : row;     // packed rows of ufnd_text_pack: the (B, L) index of the token
+  long long id = ids[src];
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);  // never read outside the table
-  int l = pos_ids ? pos_ids[row] : row % L;         // packed (un-padded) rows carry their position
+  int l = pos_ids ? pos_ids[row] : src % L;         // packed (un-padded) rows carry their position
   l = l < 0 ? 0 : (l >= L ? L - 1 : l);
   f32x4 v[NI];
 #pragma unroll
@@ -131,26 +133,30 @@ __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* ids, con
 
 // masked mean over tokens (phase 1: grid (H/256, B), 256 threads = 4 token-groups x 64 lanes x 4 columns,
 // LDS-reduced), then L2 normalise (phase 2, one block per sample).  text_blocks.py:82-86,100.
-__global__ __launch_bounds__(256) void meanpool_kernel(const float* hidden, const int32_t* mask, float* out, int L, int H) {
+// PACKED (cu != NULL): sample b's positions 0 .. n_b - 1 are rows cu[b] .. cu[b+1] (ufnd_text_pack); the same groups, the same order.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void meanpool_kernel(const float* hidden, const int32_t* mask, float* out, int L, int H, const int32_t* cu) {
   __shared__ f32x4 part[4][64];
   __shared__ float cnts[4];
   const int b = blockIdx.y, col = blockIdx.x * 256 + 4 * (threadIdx.x & 63), grp = threadIdx.x >> 6, lane = threadIdx.x & 63;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   float cnt = 0.0f;
+  const size_t r0 = PACKED ? (size_t)cu[b] : (size_t)b * L;
+  const int n = PACKED ? cu[b + 1] - cu[b] : L;      // rows of the sample (positions past them are masked)
   // eight tokens of the group per pass: their mask words and rows are requested together (a mask load -> branch -> row
   // load chain per token made this kernel 27 us for 12.6 MB); rows are added in token order, only where the mask keeps them
-  for (int l0 = grp; l0 < L; l0 += 32) {
+  for (int l0 = grp; l0 < n; l0 += 32) {
     int mk[8];
     f32x4 x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int l = l0 + 4 * u;
-      mk[u] = l < L ? mask[(size_t)b * L + l] : 0;
+      mk[u] = l < n ? mask[(size_t)b * L + l] : 0;
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const int l = l0 + 4 * u < L ? l0 + 4 * u : L - 1;
-      x[u] = ld4(hidden + ((size_t)b * L + l) * H + col);
+      const int l = l0 + 4 * u < n ? l0 + 4 * u : n - 1;
+      x[u] = ld4(hidden + (r0 + l) * H + col);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -194,6 +200,54 @@ __global__ __launch_bounds__(256) void meanpool_packed_kernel(const float* hidde
     *reinterpret_cast<f32x4*>(out + (size_t)b * H + col) = s / denom;
   }
 }
+// ufnd_text_pack: one workgroup.  n_b = 1 + the last kept position of sample b (0 for an all-masked sample); cu = exclusive prefix sum
+// of n_b (cu[B] = the live row count); row_src[cu[b] + l] = b L + l for l < n_b.
+constexpr int PACK_THREADS = 1024, PACK_MAX_B = 16384;
+__global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src) {
+  __shared__ int lens[PACK_MAX_B];
+  __shared__ int wsum[PACK_THREADS / 64];
+  __shared__ int total;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int b = wave; b < B; b += PACK_THREADS / 64) {      // a wave per sample: the largest kept position + 1
+    int last = 0;
+    for (int l = lane; l < L; l += 64) last = mask[(size_t)b * L + l] != 0 ? l + 1 : last;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if (lane == 0) lens[b] = last;
+  }
+  __syncthreads();
+  // exclusive scan: thread t owns the contiguous samples [t per, (t + 1) per)
+  const int per = (B + PACK_THREADS - 1) / PACK_THREADS, b0 = tid * per, b1 = min(b0 + per, B);
+  int own = 0;
+  for (int b = b0; b < b1; ++b) own += lens[b];
+  int inc = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += wsum[w];
+  int run = base + inc - own;
+  for (int b = b0; b < b1; ++b) {
+    const int n = lens[b];
+    lens[b] = run;      // (only this thread touches its samples' slots)
+    cu[b] = run;
+    run += n;
+  }
+  if (tid == PACK_THREADS - 1) {
+    cu[B] = run;
+    total = run;
+  }
+  __syncthreads();
+  for (int b = wave; b < B; b += PACK_THREADS / 64) {
+    const int r0 = lens[b], n = (b + 1 < B ? lens[b + 1] : total) - r0;
+    for (int l = lane; l < n; l += 64) row_src[r0 + l] = b * L + l;
+  }
+}
+
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* x, int H) {
   __shared__ float sh[4];
   float* row = x + (size_t)blockIdx.x * H;
@@ -345,7 +399,7 @@ extern "C" int ufnd_layernorm(const float* x, int ldx, const float* gamma, const
   UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16),
                "layernorm: alignment");
   NI_LAUNCH(H, layernorm_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, x, ldx, gamma, beta, (__bf16*)out_bf16,
-            out_f32, M, H, eps);
+            out_f32, M, H, eps, (const int*)nullptr);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -387,7 +441,8 @@ extern "C" int ufnd_bert_embed(const int64_t* ids, const float* word, const floa
   UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed: alignment");
   const int M = B * L;
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
-            (__bf16*)x_bf16, x_f32, M, L, H, vocab, eps, (const int32_t*)nullptr);
+            (__bf16*)x_bf16, x_f32, M, L, H, vocab, eps, (const int32_t*)nullptr, (const int32_t*)nullptr,
+            (const int*)nullptr);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -399,7 +454,7 @@ extern "C" int ufnd_bert_embed_packed(const int64_t* ids, const int32_t* pos_ids
   UFND_REQUIRE(h_ok(H) && T >= 1 && max_pos >= 1 && vocab >= 1, "bert_embed_packed: T=%d H=%d vocab=%d", T, H, vocab);
   UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed_packed: alignment");
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(T, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
-            (__bf16*)x_bf16, x_f32, T, max_pos, H, vocab, eps, pos_ids);
+            (__bf16*)x_bf16, x_f32, T, max_pos, H, vocab, eps, pos_ids, (const int32_t*)nullptr, (const int*)nullptr);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -408,7 +463,8 @@ extern "C" int ufnd_masked_meanpool_l2(const float* hidden, const int32_t* mask,
                                        void* stream_) {
   UFND_REQUIRE(hidden && mask && out && B >= 1 && L >= 1, "meanpool: null argument");
   UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool: H=%d (multiple of 256)", H);
-  hipLaunchKernelGGL(meanpool_kernel, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H);
+  hipLaunchKernelGGL(meanpool_kernel<false>, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H,
+                     (const int32_t*)nullptr);
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
   UFND_CHECK_LAUNCH();
@@ -420,6 +476,49 @@ extern "C" int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_se
   UFND_REQUIRE(hidden && cu_seqlens && pos_ids && out && B >= 1, "meanpool_packed: null argument");
   UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool_packed: H=%d (multiple of 256)", H);
   hipLaunchKernelGGL(meanpool_packed_kernel, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, cu_seqlens, pos_ids, out, H);
+  UFND_CHECK_LAUNCH();
+  hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream_) {
+  UFND_REQUIRE(mask && cu_seqlens && row_src, "text_pack: null argument");
+  UFND_REQUIRE(B >= 1 && B <= PACK_MAX_B && L >= 1 && (long long)B * L < (1ll << 31), "text_pack: B=%d L=%d (B <= %d)", B, L, PACK_MAX_B);
+  hipLaunchKernelGGL(text_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_bert_embed_live(const int64_t* ids, const int32_t* row_src, const int* m_live, const float* word, const float* pos,
+                                    const float* type0, const float* gamma, const float* beta, void* x_bf16, float* x_f32, int capacity,
+                                    int L, int H, int vocab, float eps, void* stream_) {
+  UFND_REQUIRE(ids && row_src && m_live && word && pos && type0 && gamma && beta && (x_bf16 || x_f32), "bert_embed_live: null argument");
+  UFND_REQUIRE(h_ok(H) && capacity >= 1 && L >= 1 && vocab >= 1, "bert_embed_live: capacity=%d L=%d H=%d vocab=%d", capacity, L, H, vocab);
+  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed_live: alignment");
+  NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(capacity, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
+            (__bf16*)x_bf16, x_f32, capacity, L, H, vocab, eps, (const int32_t*)nullptr, row_src, m_live);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32,
+                                   int capacity, int H, float eps, const int* m_live, void* stream_) {
+  UFND_REQUIRE(x && gamma && beta && (out_bf16 || out_f32) && m_live && capacity >= 1, "layernorm_live: null argument");
+  UFND_REQUIRE(h_ok(H), "layernorm_live: H=%d (supported 256/512/768/1024)", H);
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16),
+               "layernorm_live: alignment");
+  NI_LAUNCH(H, layernorm_kernel, dim3(ufnd_cdiv(capacity, 4)), (hipStream_t)stream_, x, ldx, gamma, beta, (__bf16*)out_bf16,
+            out_f32, capacity, H, eps, m_live);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_masked_meanpool_l2_live(const float* hidden, const int32_t* mask, const int32_t* cu_seqlens, float* out, int B, int L,
+                                            int H, void* stream_) {
+  UFND_REQUIRE(hidden && mask && cu_seqlens && out && B >= 1 && L >= 1, "meanpool_live: null argument");
+  UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool_live: H=%d (multiple of 256)", H);
+  hipLaunchKernelGGL(meanpool_kernel<true>, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H, cu_seqlens);
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
   UFND_CHECK_LAUNCH();

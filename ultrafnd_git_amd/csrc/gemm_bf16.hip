@@ -23,9 +23,9 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* src, __bf16
 
 }  // namespace
 
-extern "C" int ufnd_gemm_bf16_ex(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
-                                 float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
-                                 int tile_cfg, void* stream_) {
+extern "C" int ufnd_gemm_bf16_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
+                                   float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
+                                   int tile_cfg, const int* m_live, void* stream_) {
   UFND_REQUIRE(A && W && (out_bf16 || out_f32), "gemm_bf16: null operand");
   UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "gemm_bf16: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
   UFND_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ufnd_aligned(A, 16) && ufnd_aligned(W, 16),
@@ -36,6 +36,7 @@ extern "C" int ufnd_gemm_bf16_ex(const void* A, const void* W, const float* bias
   UFND_REQUIRE(!bias || ufnd_aligned(bias, 4), "gemm_bf16: bias alignment");
   UFND_REQUIRE(act >= 0 && act <= 2, "gemm_bf16: act=%d", act);
   GemmArgs a{(const __bf16*)A, (const __bf16*)W, bias, residual, (__bf16*)out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, 0, 0, nullptr};
+  a.m_live = m_live;
   if (tile_cfg == UFND_GEMM_TILE_PP || (tile_cfg < 0 && ufnd_pp_pick(&a))) return ufnd_pp_launch(&a, stream_);      // the persistent, software-pipelined form
   const int cfg = tile_cfg < 0 ? auto_cfg(M, N, K) : tile_cfg;
   UFND_REQUIRE(cfg < kNumTiles && kTiles[cfg].built, "gemm_bf16: tile config %d is not part of this library (ufnd_gemm_bf16_tile_info)", cfg);
@@ -44,6 +45,12 @@ extern "C" int ufnd_gemm_bf16_ex(const void* A, const void* W, const float* bias
   if (rc != UFND_OK) return rc;
   UFND_CHECK_LAUNCH();
   return UFND_OK;
+}
+
+extern "C" int ufnd_gemm_bf16_ex(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
+                                 float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
+                                 int tile_cfg, void* stream_) {
+  return ufnd_gemm_bf16_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, tile_cfg, nullptr, stream_);
 }
 
 extern "C" int ufnd_gemm_bf16_tile_info(int tile_cfg, int* bm, int* bn, int* ln_aware) {
@@ -65,9 +72,18 @@ extern "C" int ufnd_gemm_bf16_stat_parts(int M, int N, int K) {
   return stat_parts_for(auto_cfg(M, N, K), N);      // (the persistent form is never the automatic choice of a call with out_stats)
 }
 
+extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
+                                      float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
+                                      const ufnd_gemm_ln* ln, const int* m_live, void* stream_);
 extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
                                  float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
                                  const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_gemm_bf16_ln_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln, nullptr, stream_);
+}
+
+extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
+                                      float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
+                                      const ufnd_gemm_ln* ln, const int* m_live, void* stream_) {
   UFND_REQUIRE(A && W && ln && (out_bf16 || out_f32), "gemm_bf16_ln: null operand");
   UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "gemm_bf16_ln: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
   UFND_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ufnd_aligned(A, 16) && ufnd_aligned(W, 16),
@@ -100,6 +116,7 @@ extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias
   a.residual_b = (const __bf16*)ln->residual_bf16;
   a.ldrb = ln->ldrb;
   a.guard = ln->a_stats ? ln->guard : nullptr;
+  a.m_live = m_live;
   if (ln->tile_cfg == UFND_GEMM_TILE_PP || (ln->tile_cfg < 0 && ufnd_pp_pick(&a))) return ufnd_pp_launch(&a, stream_);      // the persistent, software-pipelined form
   const int cfg = ln->tile_cfg < 0 ? auto_cfg(M, N, K) : ln->tile_cfg;
   UFND_REQUIRE(cfg < kNumTiles && kTiles[cfg].built && kTiles[cfg].lnx && N % kTiles[cfg].bn == 0,
@@ -114,8 +131,17 @@ extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias
 }
 
 // BertSelfAttention of one layer in ONE launch: fused Q/K/V projection (optionally of LayerNorm(X), folded) + attention.
+extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                              const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
+                                              const ufnd_gemm_ln* ln, void* stream_);
 extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, void* ctx,
                                        int B, int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_qkv_attention_bf16_packed(X, Wqkv, bqkv, key_mask, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
+}
+
+extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                              const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
+                                              const ufnd_gemm_ln* ln, void* stream_) {
   UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention: null operand");
   UFND_REQUIRE(L == 128 && heads >= 2 && heads % 2 == 0 && heads <= 64 && B >= 1 && B <= 16384,
                "qkv_attention: B=%d L=%d heads=%d (this kernel is built for 128-token samples and an even head count; "
@@ -133,6 +159,8 @@ extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const fl
     a.guard = ln->guard;
   }
   a.att_mask = key_mask;
+  a.att_cu = cu_seqlens;
+  a.m_live = cu_seqlens ? cu_seqlens + B : nullptr;      // (the live row count is cu_seqlens[B])
   a.att_ctx = (__bf16*)ctx;
   a.att_h = H;
   a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)

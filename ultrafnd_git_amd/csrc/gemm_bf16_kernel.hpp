@@ -80,6 +80,11 @@ struct GemmArgs {
   // normalises in slot blockIdx.x % 1024 (one atomicMax at its very end: non-negative floats order like ints)
   float* guard;
   int pp_rows;               // persistent form (gemm_bf16_pp.hpp): row panels per tile group of the walk order
+  // live rows (forward kernels): M is the capacity (grid, tile choice); the launch computes the first *m_live rows only.  Read
+  // on the device at entry, so a captured launch follows whatever row count the graph's earlier kernels left there.
+  const int* m_live;
+  // ATT kernels over packed rows: sample b's rows are att_cu[b] .. att_cu[b+1] (its first positions; the key mask stays (B, 128))
+  const int32_t* att_cu;
 };
 
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
@@ -182,8 +187,19 @@ void gemm_bf16_kernel(const GemmArgs a) {
     stamp[1] = __builtin_amdgcn_s_memrealtime();
   }
 
+  // live rows: tiles past them exit before any load, and the remap below spreads the LIVE tiles over all eight XCDs (the grid's
+  // first nblk workgroups are exactly the live ones: workgroup i runs on XCD i % 8)
+  int mlive = a.M, m_tiles = a.m_tiles;
+  if constexpr (!BWD && !ATT) {
+    if (a.m_live) {
+      const int v = __builtin_amdgcn_readfirstlane(*a.m_live);
+      mlive = v < a.M ? (v > 0 ? v : 0) : a.M;
+      m_tiles = (mlive + BM - 1) / BM;
+      if ((int)blockIdx.x >= m_tiles * a.n_tiles) return;
+    }
+  }
   // XCD-aware bijective remap of the block id
-  const int nblk = a.m_tiles * a.n_tiles;
+  const int nblk = m_tiles * a.n_tiles;
   int bid, kslice = 0;
   {
     const int ngrid = BWD ? nblk * (a.ksplit > 1 ? a.ksplit : 1) : nblk;
@@ -200,12 +216,25 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // of the columns and XCDs 4-7 the right half (reads = 2 A + 4 W).
   int tm = bid / a.n_tiles, tn = bid % a.n_tiles;
   if (a.xcd_cols == 2) {
-    const int nh = a.n_tiles >> 1, per_half = a.m_tiles * nh;
+    const int nh = a.n_tiles >> 1, per_half = m_tiles * nh;
     const int half = bid / per_half, rem = bid - half * per_half;
     tm = rem / nh;
     tn = half * nh + (rem - tm * nh);
   }
   const int m0 = tm * BM, n0 = tn * BN;
+  // rows of the A operand / statistics / ctx this tile works on: arow0 .. arow0 + alen (ATT over packed rows: sample tm's own rows,
+  // its key-mask row stays m0).  Row loads clamp to the live rows; rows of the tile past alen are computed, never stored.
+  int arow0 = m0, alen = BM;
+  if constexpr (ATT) {
+    if (a.att_cu) {
+      mlive = __builtin_amdgcn_readfirstlane(*a.m_live);
+      arow0 = __builtin_amdgcn_readfirstlane(a.att_cu[tm]);
+      alen = __builtin_amdgcn_readfirstlane(a.att_cu[tm + 1]) - arow0;
+      if (alen <= 0) return;      // (a sample without kept tokens has no rows; block-uniform, before any barrier)
+    }
+  } else {
+    alen = mlive - m0;
+  }
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int wm = wave / WN, wn = wave % WN, fr = lane & (MI - 1), g = lane / MI;   // fragment row, k-group
 
@@ -235,8 +264,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int p = wave + NW * ii;                  // piece id: rows 8p..8p+7 of the A tile
       const int r = 8 * p + prow;
       const int c = ppos ^ ((r >> 1) & 7);
-      int gr = m0 + r;
-      gr = gr < a.M ? gr : a.M - 1;
+      int gr = arow0 + r;
+      gr = gr < mlive ? gr : mlive - 1;
       dma16(a.A + (size_t)gr * a.lda + k0 + c * 8, buf + p * 1024);
     }
   };
@@ -272,8 +301,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
     sp = a.a_stats ? a.a_stats : a.r_stats;
     if (sp) {
       const int parts = a.a_stats ? a.a_parts : a.r_parts;
-      int row = m0 + (int)threadIdx.x / TPR;
-      row = row < a.M ? row : a.M - 1;
+      int row = arow0 + (int)threadIdx.x / TPR;
+      row = row < mlive ? row : mlive - 1;
       const f32x4* base = reinterpret_cast<const f32x4*>(sp + (size_t)row * parts * 2);
       const int nq = parts >> 1, sub = threadIdx.x % TPR;
 #pragma unroll
@@ -351,7 +380,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
       if (a.guard && a.a_stats) {      // fold guard: the largest |mean| / std among the rows this workgroup folds (reported at the kernel's end)
         float ratio = __fmul_rn(fabsf(mean), rstd);
         ratio = ratio == ratio ? ratio : INFINITY;      // (a NaN statistic must trip the guard: fmaxf would drop it)
-        const float worst = wave_max(threadIdx.x % TPR == 0 ? ratio : 0.0f);
+        const float worst = wave_max(threadIdx.x % TPR == 0 && (int)threadIdx.x / TPR < alen ? ratio : 0.0f);      // (live rows only)
         if (lane == 0) reinterpret_cast<float*>(smem + STAT_OFF + BM * 8)[wave] = worst;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -613,7 +642,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
         const int rr = id / CPR, cl = (id % CPR) * 8;
         const int row = m0 + wm * TM + i * MI + rr;
         const int col = n0 + wn * TN + cl;
-        const bool live = row < a.M;
+        const bool live = row < mlive;
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(cst + rr * CP + cl);
         const f32x4 v1 = *reinterpret_cast<const f32x4*>(cst + rr * CP + cl + 4);
         float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
@@ -726,6 +755,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
     constexpr int KB = 64, KT = KB / 16;
+    // (packed rows: a wave whose 32 queries all lie past the sample's length has nothing to compute or store)
+    if (wq * 32 < alen) {
 #pragma unroll
     for (int kb0 = 0; kb0 < BM; kb0 += KB) {
       const char* ks = kimg + kb0 * 128;
@@ -774,6 +805,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
         }
       }
     }
+    }
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       float l = l_run[qt];
@@ -781,7 +813,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       l += __shfl_xor(l, 32, 64);
       const float inv = 1.0f / l;
       const int q = wq * 32 + qt * 16 + f16;
-      __bf16* dst = a.att_ctx + (size_t)(m0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4;
+      if (q >= alen) continue;
+      __bf16* dst = a.att_ctx + (size_t)(arow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};

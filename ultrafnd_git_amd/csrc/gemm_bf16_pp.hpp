@@ -98,7 +98,16 @@ void gemm_pp_kernel(const GemmArgs a) {
   // [x T / 8, (x + 1) T / 8) of the tile order below and deals it round-robin to its workgroups, so the workgroups of an XCD
   // work on neighbouring tiles at any time: pp_rows row panels x (workgroups per XCD / pp_rows) column tiles, whose A panels
   // stay in that XCD's L2 while it walks the columns.
-  const int G = gridDim.x, T = a.m_tiles * a.n_tiles;
+  // live rows (a.m_live): M is the capacity; the walk covers the panels of the first *m_live rows only, dealt over all eight XCDs as
+  // below.  A ragged last live panel is computed whole (its loads stay inside the capacity) and its rows past *m_live are stored
+  // like the others -- rows nobody reads -- so that every vector-memory instruction stays unconditional; they join no fold guard.
+  int mlive = a.M, m_tiles = a.m_tiles;
+  if (a.m_live) {
+    const int v = __builtin_amdgcn_readfirstlane(*a.m_live);
+    mlive = v < a.M ? (v > 0 ? v : 0) : a.M;
+    m_tiles = (mlive + BM - 1) / BM;
+  }
+  const int G = gridDim.x, T = m_tiles * a.n_tiles;
   const int gpx = G >> 3;
   const int L = xcd_contiguous_id(blockIdx.x, G);
   const int xcd = L / gpx;
@@ -108,7 +117,7 @@ void gemm_pp_kernel(const GemmArgs a) {
   auto coords = [&](int uu, int& m0, int& n0) {      // tile order: groups of pp_rows row panels, column-major inside a group
     const int R = a.pp_rows, per = R * a.n_tiles;
     const int rg = uu / per, rem = uu - rg * per;
-    int rows = a.m_tiles - rg * R;
+    int rows = m_tiles - rg * R;
     rows = rows < R ? rows : R;
     const int tn = rem / rows;
     m0 = (rg * R + (rem - tn * rows)) * BM;
@@ -289,7 +298,7 @@ void gemm_pp_kernel(const GemmArgs a) {
       if constexpr (MODE == FOLD) {
         float ratio = __fmul_rn(fabsf(mean), rstd);
         ratio = ratio == ratio ? ratio : INFINITY;      // (a NaN statistic must trip the guard: fmaxf would drop it)
-        guard_max = fmaxf(guard_max, sub == 0 ? ratio : 0.0f);
+        guard_max = fmaxf(guard_max, sub == 0 && m0c + (tid >> 1) < mlive ? ratio : 0.0f);      // (live rows only)
       }
     }
     {

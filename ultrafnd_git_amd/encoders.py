@@ -119,15 +119,20 @@ class _EncoderBase(nn.Module):
     # trainer when the encoder runs on a compute-unit partition (a launch wants about one tile per CU it may use).
     tiles: Dict[str, int] = {}
 
+    # Live rows (BertTextEncoder's packed pass): a device int holding how many of the work buffers' rows are live.  While it is
+    # set, every Linear / LayerNorm below computes the first *_m_live rows of its capacity-sized operands only (include/ultrafnd_hip.h,
+    # ufnd_gemm_bf16_live): same launches, same shapes, same tiles.
+    _m_live: Optional[int] = None
+
     def _gemm(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, M=None, which=None):
         M = A.shape[0] if M is None else M
         N, K = W.shape
-        L.check(L.lib().ufnd_gemm_bf16_ex(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
-                                          L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
-                                          residual.stride(0) if residual is not None else 0,
-                                          out_bf16.stride(0) if out_bf16 is not None else 0,
-                                          out_f32.stride(0) if out_f32 is not None else 0, act, self.tiles.get(which, -1),
-                                          L.stream_ptr(A.device)), "ufnd_gemm_bf16_ex")
+        L.check(L.lib().ufnd_gemm_bf16_live(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
+                                            L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
+                                            residual.stride(0) if residual is not None else 0,
+                                            out_bf16.stride(0) if out_bf16 is not None else 0,
+                                            out_f32.stride(0) if out_f32 is not None else 0, act, self.tiles.get(which, -1),
+                                            self._m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_live")
 
     def _gemm_ln(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, a_stats=None, colsum=None,
                  r_stats=None, r_gamma=None, r_beta=None, out_stats=None, eps=1e-5, which=None, residual_bf16=None):
@@ -148,12 +153,12 @@ class _EncoderBase(nn.Module):
         if a_stats is not None:      # fold guard: the launch reports the largest |mean| / std among the rows it folds
             ln.guard = self._guard_buf(A.device).data_ptr()
         import ctypes
-        L.check(L.lib().ufnd_gemm_bf16_ln(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
-                                          L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
-                                          residual.stride(0) if residual is not None else 0,
-                                          out_bf16.stride(0) if out_bf16 is not None else 0,
-                                          out_f32.stride(0) if out_f32 is not None else 0, act, ctypes.byref(ln),
-                                          L.stream_ptr(A.device)), "ufnd_gemm_bf16_ln")
+        L.check(L.lib().ufnd_gemm_bf16_ln_live(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
+                                               L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
+                                               residual.stride(0) if residual is not None else 0,
+                                               out_bf16.stride(0) if out_bf16 is not None else 0,
+                                               out_f32.stride(0) if out_f32 is not None else 0, act, ctypes.byref(ln),
+                                               self._m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_ln_live")
 
     def _guard_buf(self, dev) -> torch.Tensor:
         """The fold guard's slots (UFND_FOLD_GUARD_SLOTS floats): every folded GEMM launch -- inside captured graphs too -- leaves
@@ -194,20 +199,25 @@ class _EncoderBase(nn.Module):
         return Wp, Wp.float().sum(1).contiguous(), (b + (W * beta[None, :]).sum(1)).contiguous()
 
     def _ln(self, x, ldx, gamma, beta, out_bf16, out_f32, M, H, eps):
+        if self._m_live is not None:
+            L.check(L.lib().ufnd_layernorm_live(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
+                                                L.ptr(out_f32), M, H, eps, self._m_live, L.stream_ptr(x.device)), "ufnd_layernorm_live")
+            return
         L.check(L.lib().ufnd_layernorm(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
                                        L.ptr(out_f32), M, H, eps, L.stream_ptr(x.device)), "ufnd_layernorm")
 
-    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5):
-        """ufnd_qkv_attention_bf16: fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer."""
+    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None):
+        """ufnd_qkv_attention_bf16: fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer
+        (cu: sample b's rows are cu[b] .. cu[b+1] of the packed pass)."""
         import ctypes
         ln = None
         if a_stats is not None:
             ln = L.GemmLn()
             ln.a_stats, ln.colsum, ln.a_parts, ln.a_eps, ln.r_eps, ln.width = a_stats.data_ptr(), colsum.data_ptr(), a_stats.shape[1], eps, eps, self.hidden
             ln.guard = self._guard_buf(A.device).data_ptr()
-        L.check(L.lib().ufnd_qkv_attention_bf16(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), ctx.data_ptr(), B, Lq, heads,
-                                                A.stride(0), W.stride(0), ctypes.byref(ln) if ln is not None else None,
-                                                L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16")
+        L.check(L.lib().ufnd_qkv_attention_bf16_packed(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), ctx.data_ptr(),
+                                                       B, Lq, heads, A.stride(0), W.stride(0), ctypes.byref(ln) if ln is not None else None,
+                                                       L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16_packed")
 
     def _attn(self, qkv, mask_i32, ctx, B, Lq, heads):
         L.check(L.lib().ufnd_attention_bf16(qkv.data_ptr(), L.ptr(mask_i32), ctx.data_ptr(), B, Lq, heads,
@@ -294,7 +304,9 @@ class BertTextEncoder(_EncoderBase):
             self._bufs[key] = {"xb": torch.empty(M, H, **bf), "xf": torch.empty(M, H, **f32), "y": torch.empty(M, H, **f32),
                                "x1b": torch.empty(M, H, **bf), "x1f": torch.empty(M, H, **f32),
                                "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
-                               "h": torch.empty(M, self.inter, **bf), "feat": torch.empty(B, H, **f32)}
+                               "h": torch.empty(M, self.inter, **bf), "feat": torch.empty(B, H, **f32),
+                               # packed pass (ufnd_text_pack): cu_seqlens (B + 1; cu[B] = the live row count) and row -> (b, pos)
+                               "cu": torch.zeros(B + 1, dtype=torch.int32, device=dev), "row_src": torch.zeros(M, dtype=torch.int32, device=dev)}
             p1 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, H)
             p2 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, self.inter)
             if self.fold_ln and p1 > 0 and p1 == p2 and p1 % 2 == 0:
@@ -337,11 +349,12 @@ class BertTextEncoder(_EncoderBase):
         batch or packed sequences).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
         H = self.hidden
         v = {k: (x[:M] if torch.is_tensor(x) and x.dim() >= 2 and x.shape[0] >= M and k not in ("feat", "st") else x) for k, x in b.items()}
+        cu = fused[3] if fused is not None and len(fused) > 3 else None
         if "st" in b:
             return self._layers_folded(p, v, M, attn, fused)
         for ly in p["layers"]:
             if fused is not None:
-                self._qkv_attn(v["xb"], ly["wqkv"], ly["bqkv"], fused[2], v["ctx"], fused[0], fused[1], self.heads)
+                self._qkv_attn(v["xb"], ly["wqkv"], ly["bqkv"], fused[2], v["ctx"], fused[0], fused[1], self.heads, cu=cu)
             else:
                 self._gemm(v["xb"], ly["wqkv"], ly["bqkv"], out_bf16=v["qkv"], which="qkv")
                 attn(v["qkv"], v["ctx"])
@@ -357,16 +370,17 @@ class BertTextEncoder(_EncoderBase):
         H, eps = self.hidden, self.eps
         y1, y2 = b["y"], b["y2"]
         st = b["st"]
+        cu = fused[3] if fused is not None and len(fused) > 3 else None
         prev = None
         for i, ly in enumerate(p["layers"]):
             st1, st2 = st[2 * i][:M], st[2 * i + 1][:M]
             stp = st[2 * i - 1][:M] if i > 0 else None           # the previous layer's feed-forward half
             if fused is not None:
                 if prev is None:
-                    self._qkv_attn(b["xb"], ly["wqkv"], ly["bqkv"], fused[2], b["ctx"], fused[0], fused[1], self.heads)
+                    self._qkv_attn(b["xb"], ly["wqkv"], ly["bqkv"], fused[2], b["ctx"], fused[0], fused[1], self.heads, cu=cu)
                 else:
                     self._qkv_attn(b["y2b"], ly["wqkvf"], ly["bqkvf"], fused[2], b["ctx"], fused[0], fused[1], self.heads,
-                                   a_stats=stp, colsum=ly["csqkv"], eps=eps)
+                                   a_stats=stp, colsum=ly["csqkv"], eps=eps, cu=cu)
             elif prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
                 self._gemm(b["xb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
             else:
@@ -390,13 +404,15 @@ class BertTextEncoder(_EncoderBase):
         self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps)           # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
 
     @torch.no_grad()
-    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, unpad: bool = False, strict: bool = False) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, unpad: bool = True, strict: bool = False) -> torch.Tensor:
         """Batched BERTContextEncoder.encode: (B,L) ids/mask -> (B,768) L2-normalised features.
         strict=True is the offline feature builder's mode: fp32 residual stream (whatever `residual_dtype` says), the fold guard checked
         after the pass (one host sync) and, if it tripped, the batch repeated with materialised LayerNorms; not for hipGraph capture.
-        unpad=True runs the encoder over the kept tokens only (packed rows, per-sequence attention): the padded
-        positions never reach the pooling (text_blocks.py:82-86), so no returned value changes -- bit-identical for
-        prefix masks -- while the work drops with the padding fraction.  Shapes vary per batch: not for hipGraph capture."""
+        unpad=True (default): the encoder runs over packed rows -- sample b keeps its positions 0 .. its last kept position, so only
+        trailing padding is dropped (holes stay rows, masked as keys).  Padded positions never reach the pooling (text_blocks.py:82-86)
+        and every kept row is computed exactly as in the padded batch: bit-identical features for every mask, while the work drops
+        with the padding fraction.  The row count stays on the device (ufnd_text_pack) and every launch keeps its padded geometry:
+        no host sync, hipGraph-capturable, a replay follows the ids / mask its buffers hold.  unpad=False: the padded computation."""
         if strict:
             # the offline feature builder (encode_fields; caches for the reference-style training mode): the more faithful fp32
             # residual stream whatever the in-step default is -- the bf16 stream's speed only matters inside the train step (ADVICE r3)
@@ -410,7 +426,7 @@ class BertTextEncoder(_EncoderBase):
             finally:
                 self.residual_dtype = rd
         if unpad:
-            return self._forward_packed(input_ids, attention_mask)
+            return self._forward_live(input_ids, attention_mask)
         hid = self.last_hidden_state(input_ids, attention_mask)
         B, Lq, H = hid.shape
         feat = self._workbufs(B, Lq)["feat"]
@@ -418,38 +434,37 @@ class BertTextEncoder(_EncoderBase):
                                                 L.stream_ptr(self.device)), "ufnd_masked_meanpool_l2")
         return feat
 
-    def _forward_packed(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    def _forward_live(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         self._require_hip()
         dev = self.device
         B, Lq = input_ids.shape
         if Lq > self.max_position:
             raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
-        ids = input_ids.to(dev, torch.int64).reshape(-1)
+        ids = input_ids.to(dev, torch.int64).contiguous()
         mask = attention_mask.to(dev, torch.int32).contiguous()
-        keep = torch.nonzero(mask.reshape(-1), as_tuple=False).flatten()          # (host sync: the packed row count)
-        T = int(keep.numel())
         p, b, w = self._pack(), self._workbufs(B, Lq), self._w
-        H, s = self.hidden, L.stream_ptr(dev)
-        feat = b["feat"]
-        if T == 0:
-            return feat.zero_()
-        ids_p = ids[keep].contiguous()
-        pos = (keep % Lq).to(torch.int32).contiguous()
-        cu = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        cu[1:] = torch.cumsum(mask.sum(1, dtype=torch.int32), 0)
-        L.check(L.lib().ufnd_bert_embed_packed(ids_p.data_ptr(), pos.data_ptr(), w["embeddings.word_embeddings.weight"].data_ptr(),
-                                               w["embeddings.position_embeddings.weight"].data_ptr(),
-                                               w["embeddings.token_type_embeddings.weight"].data_ptr(),
-                                               w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
-                                               b["xb"].data_ptr(), b["xf"].data_ptr(), T, self.max_position, H, self.vocab, self.eps, s),
-                "ufnd_bert_embed_packed")
+        M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
+        cu, feat = b["cu"], b["feat"]
+        live = cu.data_ptr() + 4 * B          # cu[B]: the live row count, written by the pack kernel
+        L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
+        L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, w["embeddings.word_embeddings.weight"].data_ptr(),
+                                             w["embeddings.position_embeddings.weight"].data_ptr(),
+                                             w["embeddings.token_type_embeddings.weight"].data_ptr(),
+                                             w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
+                                             b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr(),
+                                             M, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed_live")
+        fused = (B, Lq, mask, cu) if (self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0) else None
 
         def attn(qkv, ctx):
-            L.check(L.lib().ufnd_attention_bf16_varlen(qkv.data_ptr(), cu.data_ptr(), ctx.data_ptr(), B, Lq, self.heads, s),
-                    "ufnd_attention_bf16_varlen")
-        self._layers(p, b, T, attn)
-        L.check(L.lib().ufnd_meanpool_l2_packed(b["xf"].data_ptr(), cu.data_ptr(), pos.data_ptr(), feat.data_ptr(), B, H, s),
-                "ufnd_meanpool_l2_packed")
+            L.check(L.lib().ufnd_attention_bf16_varlen_masked(qkv.data_ptr(), cu.data_ptr(), mask.data_ptr(), ctx.data_ptr(), B, Lq,
+                                                              self.heads, s), "ufnd_attention_bf16_varlen_masked")
+        self._m_live = live
+        try:
+            self._layers(p, b, M, attn, fused)
+        finally:
+            self._m_live = None
+        L.check(L.lib().ufnd_masked_meanpool_l2_live(b["xf"].data_ptr(), mask.data_ptr(), cu.data_ptr(), feat.data_ptr(), B, Lq, H, s),
+                "ufnd_masked_meanpool_l2_live")
         return feat
 
     encode_batch = forward

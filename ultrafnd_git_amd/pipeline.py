@@ -14,7 +14,8 @@ buffers (bench.py: four) -- are read in place by a graph captured for exactly th
 alone would be a 19 MB device-to-device copy per step).  Everything else is staged into the encoder's static buffers and
 replayed from ONE graph per shape; `stats` counts both kinds, and a pinned cache that runs full is reported once.
 
-Fold guard.  Every folded GEMM of an encoder pass reports the largest |mean| / std among the rows it folds (ufnd_gemm_ln.guard:
+Fold guard.  Every folded GEMM of an encoder pass reports the largest |mean| / std among the LIVE rows it folds (the text encoder
+runs over packed rows, BertTextEncoder.forward: rows past the device-side live count are never looked at; ufnd_gemm_ln.guard:
 1,024 slots per encoder, encoders.py); after every pass the scheduler copies both encoders' slots to pinned host memory
 (asynchronously, 4 KB each) and looks at the copies that have
 landed before it enqueues the next pass: a trip switches that encoder to materialised LayerNorms from the next pass on and
