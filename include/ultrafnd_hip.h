@@ -357,8 +357,8 @@ typedef struct ufnd_gemm_ln {
 int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
                       float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
                       const ufnd_gemm_ln* ln, void* stream);
-/* Number of {sum, sumsq} partials per row that ufnd_gemm_bf16_ln writes to out_stats for this shape
- * (0 = the shape's tile has no statistics epilogue). */
+/* Number of {sum, sumsq} partials per row that an automatic (tile_cfg < 0) ufnd_gemm_bf16_ln call of this shape writes to
+ * out_stats, whichever kernel the dispatch picks for it -- the persistent form included (0 = no statistics epilogue). */
 int ufnd_gemm_bf16_stat_parts(int M, int N, int K);
 
 /* *guard = max(*guard, max over rows of |mean| * rstd) for the M rows of a statistics buffer (M, parts, 2) as

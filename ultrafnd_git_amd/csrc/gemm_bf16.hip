@@ -7,6 +7,7 @@
 #define UFND_GEMM_TILE_PP UFND_GEMM_TILE_PERSISTENT
 int ufnd_pp_pick(const void* gemm_args);
 int ufnd_pp_launch(void* gemm_args, void* stream);
+int ufnd_pp_stat_parts(int N);
 
 namespace {
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* src, __bf16* dst, size_t n) {
@@ -69,7 +70,17 @@ static int stat_parts_for(int cfg, int N) {
   return N / 32;
 }
 extern "C" int ufnd_gemm_bf16_stat_parts(int M, int N, int K) {
-  return stat_parts_for(auto_cfg(M, N, K), N);      // (the persistent form is never the automatic choice of a call with out_stats)
+  // the automatic choice of an out_stats call on the bf16 residual stream (ufnd_gemm_ln.residual_bf16, bf16 output only) can be the
+  // persistent form (pp_pick: the configs[3] geometry's out-projection, 65,536 rows): ask the same dispatch the call will take
+  static const __bf16 probe[8] = {};
+  GemmArgs a{};
+  a.A = a.W = probe;
+  a.out_bf16 = const_cast<__bf16*>(probe);
+  a.residual_b = probe;
+  a.out_stats = reinterpret_cast<float*>(const_cast<__bf16*>(probe));
+  a.M = M; a.N = N; a.K = K; a.lda = a.ldw = K; a.ldo = a.ldrb = N;
+  if (ufnd_pp_pick(&a)) return ufnd_pp_stat_parts(N);
+  return stat_parts_for(auto_cfg(M, N, K), N);
 }
 
 extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,

@@ -7,6 +7,7 @@
 
 // internal interface to gemm_bf16.hip (GemmArgs lives in an anonymous namespace of a shared header: same layout in both units)
 __attribute__((visibility("hidden"))) int ufnd_pp_pick(const void* gemm_args) { return pp_pick(*static_cast<const GemmArgs*>(gemm_args)) ? 1 : 0; }
+__attribute__((visibility("hidden"))) int ufnd_pp_stat_parts(int N) { return pp_stat_parts(N); }
 __attribute__((visibility("hidden"))) int ufnd_pp_launch(void* gemm_args, void* stream) {
   GemmArgs& a = *static_cast<GemmArgs*>(gemm_args);
   if (a.out_stats && (pp_stat_parts(a.N) == 0 || !ufnd_aligned(a.out_stats, 16))) {
