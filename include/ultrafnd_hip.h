@@ -426,11 +426,18 @@ int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_seqlens, cons
  *   ufnd_gemm_bf16_live / _ln_live ufnd_gemm_bf16_ex / ufnd_gemm_bf16_ln over the first *m_live of M rows: M (the capacity) picks
  *                                  the tile and bounds the grid, workgroups past the live tiles exit at entry, the live tiles are
  *                                  spread over every XCD; per-row arithmetic is that of the M-row call (bit-identical rows)
+ *   ufnd_text_pack_bins            ufnd_text_pack (L <= 128) + slot bins: sample b takes ceil(n_b / 32) contiguous 32-row slots of a
+ *                                  4-slot bin, full bins first; bins (B, 8): slot j of bin i is {cu[b] + 32 s, (b << 10) | (s << 8) | n_b}
+ *                                  ({0, -1}: empty), *nbins = the bin count
  *   ufnd_qkv_attention_bf16_packed ufnd_qkv_attention_bf16 with sample b's rows at cu_seqlens[b] .. cu_seqlens[b+1] (key_mask (B, 128))
+ *   ufnd_qkv_attention_bf16_bins   ..._packed with one workgroup per bin of ufnd_text_pack_bins (up to four samples) and head pair;
+ *                                  the grid keeps B x heads / 2, workgroups of bins past *nbins exit at entry; bit-identical ctx
  *   ufnd_attention_bf16_varlen_masked  ufnd_attention_bf16_varlen with a (B, max_len) key mask (NULL: every key valid)
  *   ufnd_layernorm_live            ufnd_layernorm over the first *m_live of `capacity` rows
  *   ufnd_masked_meanpool_l2_live   ufnd_masked_meanpool_l2 over the packed rows: the same groups and summation order */
 int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream);
+int ufnd_text_pack_bins(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, int32_t* bins, int32_t* nbins,
+                        void* stream);
 int ufnd_bert_embed_live(const int64_t* ids, const int32_t* row_src, const int* m_live, const float* word, const float* pos,
                          const float* type0, const float* gamma, const float* beta, void* x_bf16, float* x_f32, int capacity, int L,
                          int H, int vocab, float eps, void* stream);
@@ -442,6 +449,9 @@ int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, cons
                            const int* m_live, void* stream);
 int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, const int32_t* cu_seqlens,
                                    void* ctx, int B, int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream);
+int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, const int32_t* cu_seqlens,
+                                 const int32_t* bins, const int32_t* nbins, void* ctx, int B, int L, int heads, int ldx, int ldw,
+                                 const ufnd_gemm_ln* ln, void* stream);
 int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
                                       int heads, void* stream);
 int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32, int capacity,

@@ -202,10 +202,19 @@ __global__ __launch_bounds__(256) void meanpool_packed_kernel(const float* hidde
 }
 // ufnd_text_pack: one workgroup.  n_b = 1 + the last kept position of sample b (0 for an all-masked sample); cu = exclusive prefix sum
 // of n_b (cu[B] = the live row count); row_src[cu[b] + l] = b L + l for l < n_b.
+// Slot bins (bins != NULL, L <= 128): sample b takes c_b = ceil(n_b / 32) contiguous 32-row slots of one 4-slot bin
+// (ufnd_qkv_attention_bf16_bins: a bin is one workgroup's 128 tile rows).  Bins, in this order:
+//   full:    [4-slot sample], [3-slot + 1-slot] (pairs by rank), [2 + 2], [the odd 2-slot + two 1-slot] (if full), [1 x 4];
+//   partial: [3-slot alone] (3-slot samples beyond the 1-slot count), [the odd 2-slot (+ one 1-slot)], [the last 1-3 1-slot];
+// every bin fills its slots from slot 0 on, samples in ascending order within a class.  This is an optimal packing (no bin
+// count is lower) and a function of the n_b alone.  Bin i is 8 ints: slot j's {cu[b] + 32 s, (b << 10) | (s << 8) | n_b} for
+// slot s of sample b, {0, -1} if empty; *nbins = the bin count (0 when every sample is all-masked).
 constexpr int PACK_THREADS = 1024, PACK_MAX_B = 16384;
-__global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src) {
+__global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src,
+                                                                 int32_t* bins, int32_t* nbins) {
   __shared__ int lens[PACK_MAX_B];
   __shared__ int wsum[PACK_THREADS / 64];
+  __shared__ long long csum[PACK_THREADS / 64];
   __shared__ int total;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int b = wave; b < B; b += PACK_THREADS / 64) {      // a wave per sample: the largest kept position + 1
@@ -246,6 +255,70 @@ __global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* 
     const int r0 = lens[b], n = (b + 1 < B ? lens[b + 1] : total) - r0;
     for (int l = lane; l < n; l += 64) row_src[r0 + l] = b * L + l;
   }
+  if (!bins) return;
+  // ranks within the slot classes: four 16-bit counters in one 64-bit scan (counts <= PACK_MAX_B < 2^16)
+  auto nrows = [&](int b) { return (b + 1 < B ? lens[b + 1] : total) - lens[b]; };
+  long long cown = 0;
+  for (int b = b0; b < b1; ++b) {
+    const int c = (nrows(b) + 31) >> 5;
+    if (c > 0) cown += 1ll << (16 * (c - 1));
+  }
+  long long cinc = cown;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long y = __shfl_up(cinc, o, 64);
+    if (lane >= o) cinc += y;
+  }
+  if (lane == 63) csum[wave] = cinc;
+  __syncthreads();
+  long long cbase = 0, call = 0;
+  for (int w = 0; w < PACK_THREADS / 64; ++w) {
+    if (w < wave) cbase += csum[w];
+    call += csum[w];
+  }
+  auto field = [](long long v, int c) { return (int)((v >> (16 * (c - 1))) & 0xffff); };
+  const int n1 = field(call, 1), n2 = field(call, 2), n3 = field(call, 3), n4 = field(call, 4);
+  const int p = min(n1, n3), r1 = n1 - p, h = n2 >> 1, t = n2 & 1, u = t ? min(2, r1) : 0;
+  const bool odd_full = t && u == 2;
+  const int f1 = (r1 - u) >> 2, rem1 = (r1 - u) & 3;
+  const int b31 = n4, b22 = b31 + p, b211 = b22 + h, b1111 = b211 + (odd_full ? 1 : 0);
+  const int bp3 = b1111 + f1, bp2 = bp3 + (n3 - p), bp1 = bp2 + ((t && !odd_full) ? 1 : 0), nb = bp1 + (rem1 ? 1 : 0);
+  const int bodd = odd_full ? b211 : bp2;
+  long long rank = cbase + cinc - cown;      // ranks of my first sample in each class
+  for (int b = b0; b < b1; ++b) {
+    const int n = nrows(b), c = (n + 31) >> 5;
+    if (c == 0) continue;
+    const int k = field(rank, c);
+    rank += 1ll << (16 * (c - 1));
+    int bin, s0;
+    if (c == 4) {
+      bin = k, s0 = 0;
+    } else if (c == 3) {
+      bin = k < p ? b31 + k : bp3 + (k - p), s0 = 0;
+    } else if (c == 2) {
+      bin = k < 2 * h ? b22 + (k >> 1) : bodd, s0 = k < 2 * h ? 2 * (k & 1) : 0;
+    } else if (k < p) {
+      bin = b31 + k, s0 = 3;
+    } else if (k - p < u) {
+      bin = bodd, s0 = 2 + (k - p);
+    } else {
+      const int k1 = k - p - u;
+      bin = (k1 >> 2) < f1 ? b1111 + (k1 >> 2) : bp1, s0 = k1 & 3;
+    }
+    for (int s = 0; s < c; ++s) {
+      bins[(size_t)bin * 8 + 2 * (s0 + s)] = lens[b] + 32 * s;
+      bins[(size_t)bin * 8 + 2 * (s0 + s) + 1] = (b << 10) | (s << 8) | n;
+    }
+  }
+  // the empty slots of the partial bins (no sample writes them)
+  for (int i = bp3 + tid; i < nb; i += PACK_THREADS) {
+    const int used = i < bp2 ? 3 : (i < bp1 ? 2 + u : rem1);
+    for (int j = used; j < 4; ++j) {
+      bins[(size_t)i * 8 + 2 * j] = 0;
+      bins[(size_t)i * 8 + 2 * j + 1] = -1;
+    }
+  }
+  if (tid == 0) *nbins = nb;
 }
 
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* x, int H) {
@@ -485,7 +558,17 @@ extern "C" int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_se
 extern "C" int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream_) {
   UFND_REQUIRE(mask && cu_seqlens && row_src, "text_pack: null argument");
   UFND_REQUIRE(B >= 1 && B <= PACK_MAX_B && L >= 1 && (long long)B * L < (1ll << 31), "text_pack: B=%d L=%d (B <= %d)", B, L, PACK_MAX_B);
-  hipLaunchKernelGGL(text_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src);
+  hipLaunchKernelGGL(text_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src,
+                     (int32_t*)nullptr, (int32_t*)nullptr);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_text_pack_bins(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, int32_t* bins,
+                                   int32_t* nbins, void* stream_) {
+  UFND_REQUIRE(mask && cu_seqlens && row_src && bins && nbins, "text_pack_bins: null argument");
+  UFND_REQUIRE(B >= 1 && B <= PACK_MAX_B && L >= 1 && L <= 128, "text_pack_bins: B=%d L=%d (B <= %d, L <= 128)", B, L, PACK_MAX_B);
+  hipLaunchKernelGGL(text_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src, bins, nbins);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

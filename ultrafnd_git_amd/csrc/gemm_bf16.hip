@@ -150,10 +150,21 @@ extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const fl
   return ufnd_qkv_attention_bf16_packed(X, Wqkv, bqkv, key_mask, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
 }
 
+extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                            const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B,
+                                            int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_);
 extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
                                               const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
                                               const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_qkv_attention_bf16_bins(X, Wqkv, bqkv, key_mask, cu_seqlens, nullptr, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
+}
+
+// bins / nbins (with cu_seqlens; ufnd_text_pack_bins): workgroup row tm runs bin tm's four 32-row slots, tm < *nbins
+extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                            const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B,
+                                            int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
   UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention: null operand");
+  UFND_REQUIRE(!bins == !nbins && (!bins || cu_seqlens), "qkv_attention: slot bins need cu_seqlens, bins and nbins");
   UFND_REQUIRE(L == 128 && heads >= 2 && heads % 2 == 0 && heads <= 64 && B >= 1 && B <= 16384,
                "qkv_attention: B=%d L=%d heads=%d (this kernel is built for 128-token samples and an even head count; "
                "use ufnd_gemm_bf16[_ln] + ufnd_attention_bf16 otherwise)", B, L, heads);
@@ -171,6 +182,8 @@ extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, c
   }
   a.att_mask = key_mask;
   a.att_cu = cu_seqlens;
+  a.att_bins = bins;
+  a.att_nbins = nbins;
   a.m_live = cu_seqlens ? cu_seqlens + B : nullptr;      // (the live row count is cu_seqlens[B])
   a.att_ctx = (__bf16*)ctx;
   a.att_h = H;

@@ -85,6 +85,10 @@ struct GemmArgs {
   const int* m_live;
   // ATT kernels over packed rows: sample b's rows are att_cu[b] .. att_cu[b+1] (its first positions; the key mask stays (B, 128))
   const int32_t* att_cu;
+  // ATT kernels over slot bins (with att_cu): tile tm is bin tm of ufnd_text_pack_bins, four 32-row slots of up to four samples;
+  // tiles past *att_nbins exit at entry (see the ATT notes at the kernel)
+  const int32_t* att_bins;
+  const int* att_nbins;
 };
 
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
@@ -138,6 +142,17 @@ template <int V> struct IntC { static constexpr int value = V; };
 //          S^T = K Q^T, online softmax over two 64-key blocks, O^T = V^T P^T.  Same operations in the same order as
 //          ufnd_gemm_bf16[_ln] + ufnd_attention_bf16: bit-identical ctx, without the (tokens, 3H) round trip through
 //          HBM, the second launch and its three dependent memory round trips.
+//          Slot bins (att_bins, packed rows): the tile's 128 rows are four 32-row slots; a sample of n rows takes ceil(n / 32)
+//          contiguous slots of one bin, and a bin may hold several samples (ufnd_text_pack_bins: 768 -> ~540 workgroups per
+//          128 bench samples).  Slot j's tile rows read the sample's rows 32 s + (r & 31) (clamped inside the sample); attention
+//          wave wq serves exactly its slot's sample: its key block kb of the sample is tile rows (off + kb + k) & 127, off = the
+//          tile row of the sample's row 0, and every key past the sample's length or masked in its key-mask row (another
+//          sample's rows, wrapped rows) gets NEG_MASK -- what a padding key gets in the one-sample tile.  The same blocks, the same
+//          short paths, masked scores set to the same -3e38 and P = 0 against finite V rows: every live ctx row is bit-identical.
+//          The projection is the K-ordered per-row product either way.  Empty slots compute clamped rows and store nothing.
+//          Measured (bench group of 128 samples, MI355X): 768 -> ~544 live workgroups, but one 149-KiB workgroup per CU keeps
+//          both at 3 rounds (89 -> 86 us per launch); the step gains 3 % (profiles/slot_bins_summary.md), presumably because the
+//          concurrent visual stream fills the CUs the emptier last round leaves (inferred, not traced).
 // waves per SIMD the register allocation must leave room for: tiles whose LDS footprint lets two workgroups share a CU
 // (<= 80 KiB) only do so if two workgroups' waves also fit the register file (8-wave blocks: 128 registers per lane)
 constexpr int gemm_waves_per_simd(int BM, int BN, int WM, int WN, int STA, int STB, int MI, int LNX, int ATT) {
@@ -168,10 +183,10 @@ void gemm_bf16_kernel(const GemmArgs a) {
   constexpr int CP = TN + 4;                     // fp32 C-staging pitch (floats), MI rows per wave
   constexpr int CBYTES = NW * MI * CP * 4;
   constexpr int RING = STA * ASLOT + STB * BSLOT;
-  // ATT: six 16-KiB images (Q, K, V of two heads; 128 tokens x 128 B) + 128 key biases, behind the C staging patches
-  // (they overlay the operand ring, which is dead by then)
+  // ATT: six 16-KiB images (Q, K, V of two heads; 128 tokens x 128 B) + 4 x 128 key biases (one row per 32-row slot), behind
+  // the C staging patches (they overlay the operand ring, which is dead by then)
   constexpr int ATT_OFF = (CBYTES + 1023) & ~1023;
-  constexpr int ATT_END = ATT ? ATT_OFF + 6 * 16384 + 512 : 0;
+  constexpr int ATT_END = ATT ? ATT_OFF + 6 * 16384 + 2048 : 0;
   constexpr int STAT_OFF0 = (RING > CBYTES) ? RING : CBYTES;
   constexpr int STAT_OFF = STAT_OFF0 > ATT_END ? STAT_OFF0 : ATT_END;  // LNX: {mean, rstd} per tile row, behind the ring (and the images)
   constexpr int SMEM = STAT_OFF + (LNX ? BM * 8 + 64 : 0);      // (+ 16 floats: the waves' guard maxima)
@@ -195,6 +210,13 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int v = __builtin_amdgcn_readfirstlane(*a.m_live);
       mlive = v < a.M ? (v > 0 ? v : 0) : a.M;
       m_tiles = (mlive + BM - 1) / BM;
+      if ((int)blockIdx.x >= m_tiles * a.n_tiles) return;
+    }
+  }
+  if constexpr (ATT) {
+    if (a.att_bins) {      // slot bins: the first *att_nbins row tiles are live (a bin count never exceeds the capacity B)
+      const int v = __builtin_amdgcn_readfirstlane(*a.att_nbins);
+      m_tiles = v < a.m_tiles ? (v > 0 ? v : 0) : a.m_tiles;
       if ((int)blockIdx.x >= m_tiles * a.n_tiles) return;
     }
   }
@@ -225,8 +247,26 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // rows of the A operand / statistics / ctx this tile works on: arow0 .. arow0 + alen (ATT over packed rows: sample tm's own rows,
   // its key-mask row stays m0).  Row loads clamp to the live rows; rows of the tile past alen are computed, never stored.
   int arow0 = m0, alen = BM;
+  // (slot bins: arow0, alen and mlive keep placeholder values that decide nothing -- every row, liveness, key and store
+  //  decision goes through tile_row / tile_row_live, the slot descriptors and the per-wave wrow0 / wcnt / koff below)
+  // ATT over slot bins: slot j (tile rows 32 j ..) holds rows 32 s_j .. of sample b_j, i.e. global rows srow_j + (r & 31) for
+  // (r & 31) < scnt_j (clamped to the slot's last live row); an empty slot (scnt_j = 0) re-reads slot 0's first row.  Descriptor
+  // of slot j (ufnd_text_pack_bins): {cu[b] + 32 s, (b << 10) | (s << 8) | n_b}, meta -1 = empty.
+  int srow[4] = {0, 0, 0, 0}, scnt[4] = {0, 0, 0, 0}, smeta[4] = {-1, -1, -1, -1};
+  const bool slots = ATT && a.att_bins != nullptr;
   if constexpr (ATT) {
-    if (a.att_cu) {
+    if (slots) {
+      const int32_t* bd = a.att_bins + (size_t)tm * 8;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        srow[j] = __builtin_amdgcn_readfirstlane(bd[2 * j]);
+        smeta[j] = __builtin_amdgcn_readfirstlane(bd[2 * j + 1]);
+        const int n = smeta[j] & 255, rest = n - 32 * ((smeta[j] >> 8) & 3);
+        scnt[j] = smeta[j] < 0 ? 0 : (rest < 32 ? rest : 32);
+      }
+#pragma unroll
+      for (int j = 1; j < 4; ++j) srow[j] = scnt[j] > 0 ? srow[j] : srow[0];
+    } else if (a.att_cu) {
       mlive = __builtin_amdgcn_readfirstlane(*a.m_live);
       arow0 = __builtin_amdgcn_readfirstlane(a.att_cu[tm]);
       alen = __builtin_amdgcn_readfirstlane(a.att_cu[tm + 1]) - arow0;
@@ -235,6 +275,24 @@ void gemm_bf16_kernel(const GemmArgs a) {
   } else {
     alen = mlive - m0;
   }
+  // global row of tile row tr (the A operand and its statistics), and whether that row is stored (and joins the fold guard)
+  auto tile_row = [&](int tr) {
+    if (slots) {
+      const int j = tr >> 5, q = tr & 31;
+      const int r0 = j == 0 ? srow[0] : j == 1 ? srow[1] : j == 2 ? srow[2] : srow[3];
+      const int c = j == 0 ? scnt[0] : j == 1 ? scnt[1] : j == 2 ? scnt[2] : scnt[3];
+      return r0 + (q < c ? q : (c > 0 ? c - 1 : 0));
+    }
+    const int gr = arow0 + tr;
+    return gr < mlive ? gr : mlive - 1;
+  };
+  auto tile_row_live = [&](int tr) {
+    if (slots) {
+      const int j = tr >> 5;
+      return (tr & 31) < (j == 0 ? scnt[0] : j == 1 ? scnt[1] : j == 2 ? scnt[2] : scnt[3]);
+    }
+    return tr < alen;
+  };
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int wm = wave / WN, wn = wave % WN, fr = lane & (MI - 1), g = lane / MI;   // fragment row, k-group
 
@@ -256,9 +314,15 @@ void gemm_bf16_kernel(const GemmArgs a) {
   }
   // per-lane source rows of my pieces (fixed over the K loop): only the column offset moves
   const int prow = lane >> 3, ppos = lane & 7;
-  auto issueA = [&](int t) {
+  int arow_att[ATT ? PWA : 1];      // ATT: the rows of my A pieces, mapped once
+  if constexpr (ATT) {
+#pragma unroll
+    for (int ii = 0; ii < PWA; ++ii) arow_att[ii] = tile_row(8 * (wave + NW * ii) + prow);
+  }
+  // issueA / issueB (t, kt): K-step kt's pieces into step t's ring slot (kt = t but in the LNX prologue's fillers, below)
+  auto issueA = [&](int t, int kt) {
     char* buf = smem + (t % STA) * ASLOT;
-    const int k0 = kbase + t * BK;
+    const int k0 = kbase + kt * BK;
 #pragma unroll
     for (int ii = 0; ii < PWA; ++ii) {
       const int p = wave + NW * ii;                  // piece id: rows 8p..8p+7 of the A tile
@@ -266,12 +330,13 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int c = ppos ^ ((r >> 1) & 7);
       int gr = arow0 + r;
       gr = gr < mlive ? gr : mlive - 1;
+      if constexpr (ATT) gr = arow_att[ii];
       dma16(a.A + (size_t)gr * a.lda + k0 + c * 8, buf + p * 1024);
     }
   };
-  auto issueB = [&](int t) {
+  auto issueB = [&](int t, int kt) {
     char* buf = smem + STA * ASLOT + (t % STB) * BSLOT;
-    const int k0 = kbase + t * BK;
+    const int k0 = kbase + kt * BK;
 #pragma unroll
     for (int ii = 0; ii < PWB; ++ii) {
       int p = wave + NW * ii;
@@ -303,6 +368,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int parts = a.a_stats ? a.a_parts : a.r_parts;
       int row = arow0 + (int)threadIdx.x / TPR;
       row = row < mlive ? row : mlive - 1;
+      if constexpr (ATT) row = tile_row((int)threadIdx.x / TPR);
       const f32x4* base = reinterpret_cast<const f32x4*>(sp + (size_t)row * parts * 2);
       const int nq = parts >> 1, sub = threadIdx.x % TPR;
 #pragma unroll
@@ -319,35 +385,40 @@ void gemm_bf16_kernel(const GemmArgs a) {
   }
   int att_mk = 1;
   if constexpr (ATT) {      // this sample's key mask: requested now, used after the K loop (older than every DMA piece)
-    if (a.att_mask && threadIdx.x < BM) att_mk = a.att_mask[m0 + threadIdx.x];
+    if (slots) {            // slot bins: thread t holds key t % 128 of slot t / 128's sample (wave-uniform slot)
+      const int j = (int)threadIdx.x >> 7, k = threadIdx.x & 127;
+      const int mt = j == 0 ? smeta[0] : j == 1 ? smeta[1] : j == 2 ? smeta[2] : smeta[3];
+      att_mk = mt >= 0 && k < (mt & 255);
+      if (att_mk && a.att_mask) att_mk = a.att_mask[(size_t)(mt >> 10) * BM + k];
+    } else if (a.att_mask && threadIdx.x < BM) {
+      att_mk = a.att_mask[m0 + threadIdx.x];
+    }
   }
   // prologue: every ring slot is filled (W(s) before A(s), step by step, so that a counted vmcnt
   // separates "steps <= t+1" from the later ones)
 #pragma unroll
   for (int s = 0; s < STA; ++s) {
-    if (s < STB && s < nk) issueB(s);
-    if (s < nk) issueA(s);
+    // LNX (nk >= 1, host-checked): a slot whose step does not exist (nk < STA) still gets one, a re-load of the last step that
+    // nothing reads, so that exactly NPRO pieces follow the statistics loads whatever K is and ONE wait retires them (below)
+    const int ks = s < nk ? s : nk - 1;
+    if (s < STB && (LNX || s < nk)) issueB(s, ks);
+    if (LNX || s < nk) issueA(s, ks);
   }
 
   if constexpr (LNX) {
     if (sp) {
-      // the statistics loads are older than every prologue DMA piece: wait until at most those pieces are
-      // outstanding (the loaded registers are operands, so nothing that reads them can move above the wait)
+      // the statistics loads are older than every prologue DMA piece, and exactly NPRO pieces follow them: wait until at most
+      // those are outstanding.  ONE wait statement, never one per arm of a branch: the compiler does not know the destinations
+      // are in flight, and where two waits merged it copied the registers in front of the branch, i.e. read them before they
+      // had landed (K < STA * 64: garbage statistics for a whole tile, on some launches only).  STATRETIRE names the retired
+      // registers for the ISA audit (tests/test_gemm_stats_audit.py).
       constexpr int NPRO = STA * PWA + STB * PWB;
       static_assert(NPRO <= 63, "vmcnt range");
-      if (STA <= nk) {
-        if constexpr (GPT == 1)
-          asm volatile("s_waitcnt vmcnt(%3)" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]) : "n"(NPRO) : "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(%6)" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]), "+v"(sv[GPT - 1][0]), "+v"(sv[GPT - 1][1]),
-                       "+v"(sv[GPT - 1][2]) : "n"(NPRO) : "memory");
-      } else {
-        if constexpr (GPT == 1)
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]) : : "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]), "+v"(sv[GPT - 1][0]), "+v"(sv[GPT - 1][1]),
-                       "+v"(sv[GPT - 1][2]) : : "memory");
-      }
+      if constexpr (GPT == 1)
+        asm volatile("s_waitcnt vmcnt(%3) ; STATRETIRE %0 %1 %2" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]) : "n"(NPRO) : "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(%6) ; STATRETIRE %0 %1 %2 %3 %4 %5" : "+v"(sv[0][0]), "+v"(sv[0][1]), "+v"(sv[0][2]), "+v"(sv[GPT - 1][0]),
+                     "+v"(sv[GPT - 1][1]), "+v"(sv[GPT - 1][2]) : "n"(NPRO) : "memory");
       const int nq_ = (a.a_stats ? a.a_parts : a.r_parts) >> 1, sub_ = threadIdx.x % TPR;
       float gs[GPT], gq[GPT];
 #pragma unroll
@@ -380,7 +451,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
       if (a.guard && a.a_stats) {      // fold guard: the largest |mean| / std among the rows this workgroup folds (reported at the kernel's end)
         float ratio = __fmul_rn(fabsf(mean), rstd);
         ratio = ratio == ratio ? ratio : INFINITY;      // (a NaN statistic must trip the guard: fmaxf would drop it)
-        const float worst = wave_max(threadIdx.x % TPR == 0 && (int)threadIdx.x / TPR < alen ? ratio : 0.0f);      // (live rows only)
+        const float worst = wave_max(threadIdx.x % TPR == 0 && tile_row_live((int)threadIdx.x / TPR) ? ratio : 0.0f);      // (live rows only)
         if (lane == 0) reinterpret_cast<float*>(smem + STAT_OFF + BM * 8)[wave] = worst;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -452,8 +523,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       //  would keep every LDS read behind the last DMA)
       if constexpr (ABL != 1) read_half(t + 1, IntC<0>{}, af0, bf0);
       if constexpr (ABL != 2) {
-        if constexpr (IB) issueB(t + STB);
-        if constexpr (IA) issueA(t + STA);
+        if constexpr (IB) issueB(t + STB, t + STB);
+        if constexpr (IA) issueA(t + STA, t + STA);
       }
     }
     if constexpr (ABL != 1) {
@@ -735,9 +806,19 @@ void gemm_bf16_kernel(const GemmArgs a) {
     // ---- attention of the tile's two heads on the LDS images (attention.hip's per-wave schedule, L = 128 = two key blocks)
     constexpr float NEG_MASK = -3.0e38f;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 6 * 16384);
-    if (threadIdx.x < BM) kbias[threadIdx.x] = att_mk != 0 ? 0.0f : NEG_MASK;
+    if (slots || threadIdx.x < BM) kbias[threadIdx.x] = att_mk != 0 ? 0.0f : NEG_MASK;
     __syncthreads();
     const int hh = wave >> 2, wq = wave & 3, g4 = lane >> 4, f16 = lane & 15;
+    // my 32 queries are rows wrow0 .. wrow0 + wcnt of the sample whose row 0 is tile row koff (its keys: tile rows koff + k, mod 128)
+    int wrow0 = arow0 + 32 * wq, wcnt = alen - 32 * wq, koff = 0;
+    const float* wbias = kbias;
+    if (slots) {
+      const int mt = wq == 0 ? smeta[0] : wq == 1 ? smeta[1] : wq == 2 ? smeta[2] : smeta[3];
+      wrow0 = wq == 0 ? srow[0] : wq == 1 ? srow[1] : wq == 2 ? srow[2] : srow[3];
+      wcnt = wq == 0 ? scnt[0] : wq == 1 ? scnt[1] : wq == 2 ? scnt[2] : scnt[3];
+      koff = 32 * (wq - ((mt >> 8) & 3));
+      wbias = kbias + wq * BM;
+    }
     const char* qimg = smem + ATT_OFF + hh * 16384;
     const char* kimg = smem + ATT_OFF + (2 + hh) * 16384;
     const char* vimg = smem + ATT_OFF + (4 + hh) * 16384;
@@ -755,13 +836,12 @@ void gemm_bf16_kernel(const GemmArgs a) {
       for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
     constexpr int KB = 64, KT = KB / 16;
-    // (packed rows: a wave whose 32 queries all lie past the sample's length has nothing to compute or store)
-    if (wq * 32 < alen) {
+    // (packed rows: a wave whose 32 queries all lie past the sample's length, or whose slot is empty, has nothing to do)
+    if (wcnt > 0) {
 #pragma unroll
     for (int kb0 = 0; kb0 < BM; kb0 += KB) {
-      const char* ks = kimg + kb0 * 128;
-      const char* vs = vimg + kb0 * 128;
-      if (masked_block_is_noop(kbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
+      const int kr0 = koff + kb0;      // tile row of the block's first key (mod 128; koff and kb0 are multiples of 32)
+      if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
       f32x4 sc[KT][2];
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt)
@@ -771,15 +851,15 @@ void gemm_bf16_kernel(const GemmArgs a) {
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
-          const bf16x8 kf = lds_frag(ks, kt * 16 + f16, g4 + 4 * kk);
+          const bf16x8 kf = lds_frag(kimg, (kr0 + kt * 16 + f16) & (BM - 1), g4 + 4 * kk);
 #pragma unroll
           for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
         }
-      const bool any_masked = __any(kbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
+      const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
       bf16x8 pf[KT / 2][2];
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        const float alpha = online_softmax_block<KT>(sc, qt, kbias + kb0, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
+        const float alpha = online_softmax_block<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
         if (!__all(alpha == 1.0f)) {
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
@@ -790,13 +870,13 @@ void gemm_bf16_kernel(const GemmArgs a) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           const int qq = f16 >> 2, pp = f16 & 3;
-          const int key0 = 32 * ksd + 4 * g4 + qq;
+          const int key0 = (kr0 + 32 * ksd + 4 * g4 + qq) & (BM - 1);      // (tile rows; the swizzle only sees key bits 1-2)
           const int ch = 2 * dt + (pp >> 1);
           const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
           const int key1 = key0 + 16;
           const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-          const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vs + off0));
-          const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vs + off1));
+          const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
+          const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
           union { s16x4 s2[2]; bf16x8 v; } u;
           u.s2[0] = t0;
           u.s2[1] = t1;
@@ -812,9 +892,9 @@ void gemm_bf16_kernel(const GemmArgs a) {
       l += __shfl_xor(l, 16, 64);
       l += __shfl_xor(l, 32, 64);
       const float inv = 1.0f / l;
-      const int q = wq * 32 + qt * 16 + f16;
-      if (q >= alen) continue;
-      __bf16* dst = a.att_ctx + (size_t)(arow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4;
+      const int q = qt * 16 + f16;
+      if (q >= wcnt) continue;
+      __bf16* dst = a.att_ctx + (size_t)(wrow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};

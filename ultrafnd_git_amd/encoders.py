@@ -62,6 +62,37 @@ def dropout_prob(name: str, p) -> float:
     return p
 
 
+def text_slot_bins(n_rows) -> list:
+    """The slot bins ufnd_text_pack_bins computes on the device, from the per-sample row counts n_b (1 + the last kept position,
+    0 for an all-masked sample; n_b <= 128): a list of bins, each four slots (b, s) -- slot s of sample b -- or None (empty).
+    Sample b takes ceil(n_b / 32) contiguous slots.  Full bins first: [4], [3 + 1], [2 + 2], [the odd 2 + 1 + 1], [1 x 4]; then
+    the partial ones: [3 alone], [the odd 2 (+ 1)], [the last 1-3 1-slot samples]; samples in ascending order within a class."""
+    cls = {c: [b for b, n in enumerate(n_rows) if (int(n) + 31) // 32 == c] for c in (1, 2, 3, 4)}
+    one, two, three = cls[1], cls[2], cls[3]
+    p = min(len(one), len(three))
+    ones = one[p:]
+    u = min(2, len(ones)) if len(two) % 2 else 0
+    slots = lambda *bs: [(b, s) for b in bs for s in range((int(n_rows[b]) + 31) // 32)]
+    full = [slots(b) for b in cls[4]] + [slots(three[k], one[k]) for k in range(p)]
+    full += [slots(two[k], two[k + 1]) for k in range(0, len(two) - 1, 2)]
+    odd = slots(two[-1], *ones[:u]) if len(two) % 2 else None
+    rest = ones[u:]
+    if odd is not None and u == 2:
+        full.append(odd)
+    full += [slots(*rest[k:k + 4]) for k in range(0, len(rest) - len(rest) % 4, 4)]
+    part = [slots(b) for b in three[p:]]
+    if odd is not None and u < 2:
+        part.append(odd)
+    if len(rest) % 4:
+        part.append(slots(*rest[len(rest) - len(rest) % 4:]))
+    return [x + [None] * (4 - len(x)) for x in full + part]
+
+
+def text_slot_bin_count(n_rows) -> int:
+    """len(text_slot_bins(n_rows)): the workgroup rows the fused Q/K/V + attention runs over slot bins."""
+    return len(text_slot_bins(n_rows))
+
+
 class _EncoderBase(nn.Module):
     """Weight store with third-party key names + lazily packed bf16 operands + per-shape buffers."""
 
@@ -206,15 +237,22 @@ class _EncoderBase(nn.Module):
         L.check(L.lib().ufnd_layernorm(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
                                        L.ptr(out_f32), M, H, eps, L.stream_ptr(x.device)), "ufnd_layernorm")
 
-    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None):
+    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None):
         """ufnd_qkv_attention_bf16: fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer
-        (cu: sample b's rows are cu[b] .. cu[b+1] of the packed pass)."""
+        (cu: sample b's rows are cu[b] .. cu[b+1] of the packed pass; bins = (bins, nbins) of ufnd_text_pack_bins: one workgroup
+        per bin of up to four samples and head pair)."""
         import ctypes
         ln = None
         if a_stats is not None:
             ln = L.GemmLn()
             ln.a_stats, ln.colsum, ln.a_parts, ln.a_eps, ln.r_eps, ln.width = a_stats.data_ptr(), colsum.data_ptr(), a_stats.shape[1], eps, eps, self.hidden
             ln.guard = self._guard_buf(A.device).data_ptr()
+        if bins is not None:
+            L.check(L.lib().ufnd_qkv_attention_bf16_bins(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), cu.data_ptr(),
+                                                         bins[0].data_ptr(), bins[1].data_ptr(), ctx.data_ptr(), B, Lq, heads, A.stride(0),
+                                                         W.stride(0), ctypes.byref(ln) if ln is not None else None,
+                                                         L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16_bins")
+            return
         L.check(L.lib().ufnd_qkv_attention_bf16_packed(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), ctx.data_ptr(),
                                                        B, Lq, heads, A.stride(0), W.stride(0), ctypes.byref(ln) if ln is not None else None,
                                                        L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16_packed")
@@ -306,7 +344,9 @@ class BertTextEncoder(_EncoderBase):
                                "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
                                "h": torch.empty(M, self.inter, **bf), "feat": torch.empty(B, H, **f32),
                                # packed pass (ufnd_text_pack): cu_seqlens (B + 1; cu[B] = the live row count) and row -> (b, pos)
-                               "cu": torch.zeros(B + 1, dtype=torch.int32, device=dev), "row_src": torch.zeros(M, dtype=torch.int32, device=dev)}
+                               "cu": torch.zeros(B + 1, dtype=torch.int32, device=dev), "row_src": torch.zeros(M, dtype=torch.int32, device=dev),
+                               # (L <= 128: ufnd_text_pack_bins) the fused Q/K/V + attention's slot bins and their count
+                               "bins": torch.zeros(B, 8, dtype=torch.int32, device=dev), "nbins": torch.zeros(1, dtype=torch.int32, device=dev)}
             p1 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, H)
             p2 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, self.inter)
             if self.fold_ln and p1 > 0 and p1 == p2 and p1 % 2 == 0:
@@ -350,11 +390,12 @@ class BertTextEncoder(_EncoderBase):
         H = self.hidden
         v = {k: (x[:M] if torch.is_tensor(x) and x.dim() >= 2 and x.shape[0] >= M and k not in ("feat", "st") else x) for k, x in b.items()}
         cu = fused[3] if fused is not None and len(fused) > 3 else None
+        bins = fused[4] if fused is not None and len(fused) > 4 else None
         if "st" in b:
             return self._layers_folded(p, v, M, attn, fused)
         for ly in p["layers"]:
             if fused is not None:
-                self._qkv_attn(v["xb"], ly["wqkv"], ly["bqkv"], fused[2], v["ctx"], fused[0], fused[1], self.heads, cu=cu)
+                self._qkv_attn(v["xb"], ly["wqkv"], ly["bqkv"], fused[2], v["ctx"], fused[0], fused[1], self.heads, cu=cu, bins=bins)
             else:
                 self._gemm(v["xb"], ly["wqkv"], ly["bqkv"], out_bf16=v["qkv"], which="qkv")
                 attn(v["qkv"], v["ctx"])
@@ -371,16 +412,17 @@ class BertTextEncoder(_EncoderBase):
         y1, y2 = b["y"], b["y2"]
         st = b["st"]
         cu = fused[3] if fused is not None and len(fused) > 3 else None
+        bins = fused[4] if fused is not None and len(fused) > 4 else None
         prev = None
         for i, ly in enumerate(p["layers"]):
             st1, st2 = st[2 * i][:M], st[2 * i + 1][:M]
             stp = st[2 * i - 1][:M] if i > 0 else None           # the previous layer's feed-forward half
             if fused is not None:
                 if prev is None:
-                    self._qkv_attn(b["xb"], ly["wqkv"], ly["bqkv"], fused[2], b["ctx"], fused[0], fused[1], self.heads, cu=cu)
+                    self._qkv_attn(b["xb"], ly["wqkv"], ly["bqkv"], fused[2], b["ctx"], fused[0], fused[1], self.heads, cu=cu, bins=bins)
                 else:
                     self._qkv_attn(b["y2b"], ly["wqkvf"], ly["bqkvf"], fused[2], b["ctx"], fused[0], fused[1], self.heads,
-                                   a_stats=stp, colsum=ly["csqkv"], eps=eps, cu=cu)
+                                   a_stats=stp, colsum=ly["csqkv"], eps=eps, cu=cu, bins=bins)
             elif prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
                 self._gemm(b["xb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
             else:
@@ -446,14 +488,19 @@ class BertTextEncoder(_EncoderBase):
         M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
         cu, feat = b["cu"], b["feat"]
         live = cu.data_ptr() + 4 * B          # cu[B]: the live row count, written by the pack kernel
-        L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
+        fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0
+        if fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
+            L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
+                                                b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
+        else:
+            L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
         L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, w["embeddings.word_embeddings.weight"].data_ptr(),
                                              w["embeddings.position_embeddings.weight"].data_ptr(),
                                              w["embeddings.token_type_embeddings.weight"].data_ptr(),
                                              w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
                                              b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr(),
                                              M, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed_live")
-        fused = (B, Lq, mask, cu) if (self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0) else None
+        fused = (B, Lq, mask, cu, (b["bins"], b["nbins"])) if fuse else None
 
         def attn(qkv, ctx):
             L.check(L.lib().ufnd_attention_bf16_varlen_masked(qkv.data_ptr(), cu.data_ptr(), mask.data_ptr(), ctx.data_ptr(), B, Lq,
