@@ -652,7 +652,9 @@ int ufnd_gemm_bf16_dgrad(const void* dY, const void* Wt, const float* residual, 
 
 /* dW (n_out, k_in) fp32 [+]= dYt (n_out, tokens) x Xt (k_in, tokens)^T: the weight gradient of y = x W^T from the transposed
  * activations (ufnd_transpose_bf16; `tokens` padded to a multiple of 64 with zero columns).  The token range is cut into
- * slices (grid = tiles x slices, fp32 partial slabs in `workspace`), a reduce pass adds the slabs in slice order. */
+ * slices (grid = tiles x slices, fp32 partial slabs in `workspace`), a reduce pass adds the slabs in slice order.
+ * The workspace query sizes every shape either entry accepts (any n_out >= 1, ufnd_linear_wgrad's 8 <= N < 64 included); it returns 0
+ * only for k_in or tokens that are not positive multiples of 64. */
 size_t ufnd_gemm_bf16_wgrad_workspace_floats(int n_out, int k_in, int tokens);
 int ufnd_gemm_bf16_wgrad(const void* dYt, const void* Xt, float* dW, int n_out, int k_in, int tokens, int lda, int ldb, int ldw,
                          float* workspace, int accumulate, void* stream);

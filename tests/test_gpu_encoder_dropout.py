@@ -47,7 +47,7 @@ def _state(bp):
     return int(st.seed), int(st.step)
 
 
-@pytest.mark.parametrize("B,Lq,one_token_row", [(4, 64, False), (4, 128, False), (3, 77, True)])
+@pytest.mark.parametrize("B,Lq,one_token_row", [(4, 64, False), (4, 128, False), (3, 77, True), (8, 256, False)])
 def test_text_encoder_dropout_vs_float64_restatement(B, Lq, one_token_row):
     w, ids, mask, bp, arena = _text(2, B, Lq, one_token_row)
     feat = bp.forward_train(ids, mask).clone()

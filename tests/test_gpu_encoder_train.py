@@ -158,6 +158,81 @@ def test_visual_encoder_gradients_three_frames():
     assert torch.equal(torch.nan_to_num(arena.grad, nan=-7.0), torch.nan_to_num(first, nan=-7.0))
 
 
+def test_text_encoder_gradients_at_the_real_step_size():
+    """2 layers at the bench's text step: B = 32, L = 128 (4,096 tokens, varied lengths) -- the weight gradients split their tokens
+    into 2 (Q/K/V) and 4 (out-projection) slices and the LayerNorm backward runs at its 256-block cap, paths the smaller cases
+    above never reach.  The bound of the 2-layer cases."""
+    from oracle import encoders_ref as E
+    from ultrafnd_git_amd.encoder_train import TextBackprop
+    from ultrafnd_git_amd.encoders import BertTextEncoder
+    w = E.seeded_weights(E.bert_shapes(layers=2, vocab=1000), 27)
+    ids, mask = E.synthetic_tokens(327, 32, 128, vocab=1000)
+    assert len(set(mask.sum(1).tolist())) > 8                              # varied lengths
+    enc = BertTextEncoder(layers=2, vocab_size=1000)
+    enc.load_state_dict(w)
+    bp, arena = _standalone(TextBackprop, enc.to(DEV))
+    feat = bp.forward_train(ids, mask).clone()
+    ref_feat, ref = E.text_feature_grads(w, ids, mask, 80)
+    assert (feat.cpu() - ref_feat).abs().max().item() <= 1.2e-3
+    bp.backward(torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(80)).to(DEV))
+    torch.cuda.synchronize()
+    _compare(arena, ref, 1.6e-2, "BERT B=32 L=128 (4,096 tokens, 2 layers)")
+
+
+def test_visual_encoder_gradients_at_the_real_step_size():
+    """2 layers at the bench's ViT step: B = 32, one frame (1,600 tokens) -- the weight gradients in two slices of 13 and 12 K-steps
+    (a ragged last slice).  The bound of the 2-layer cases."""
+    from oracle import encoders_ref as E
+    from ultrafnd_git_amd.encoder_train import VisualBackprop
+    from ultrafnd_git_amd.encoders import ClipVisualEncoder
+    w = E.seeded_weights(E.vit_shapes(layers=2), 28)
+    frames = E.synthetic_frames(328, 32, 1)
+    enc = ClipVisualEncoder(layers=2)
+    enc.load_state_dict(w)
+    bp, arena = _standalone(VisualBackprop, enc.to(DEV))
+    feat = bp.forward_train(frames).clone()
+    ref_feat, ref = E.visual_feature_grads(w, frames, 81)
+    assert (feat.cpu() - ref_feat).abs().max().item() <= 1.5e-3
+    bp.backward(torch.randn(ref_feat.shape, generator=torch.Generator().manual_seed(81)).to(DEV))
+    torch.cuda.synchronize()
+    _compare(arena, ref, 1.6e-2, "ViT B=32 F=1 (1,600 tokens, 2 layers)")
+
+
+@pytest.mark.parametrize("which", ["text", "vision"])
+def test_overlapped_weight_gradients_identical_at_the_real_step_size(which):
+    """12 layers at the bench's sizes (text B = 32, L = 128; ViT B = 32, one frame): the weight-gradient products on the second
+    stream (overlap_wgrad, the default) and on the backward's own stream give identical arenas, and a rerun the same bits again."""
+    from oracle import encoders_ref as E
+    if which == "text":
+        from ultrafnd_git_amd.encoder_train import TextBackprop as BP
+        from ultrafnd_git_amd.encoders import BertTextEncoder
+        w = E.seeded_weights(E.bert_shapes(layers=12, vocab=1000), 29)
+        enc = BertTextEncoder(layers=12, vocab_size=1000)
+        ids, mask = E.synthetic_tokens(329, 32, 128, vocab=1000)
+        inputs = (ids, mask)
+    else:
+        from ultrafnd_git_amd.encoder_train import VisualBackprop as BP
+        from ultrafnd_git_amd.encoders import ClipVisualEncoder
+        w = E.seeded_weights(E.vit_shapes(layers=12), 30)
+        enc = ClipVisualEncoder(layers=12)
+        inputs = (E.synthetic_frames(330, 32, 1),)
+    enc.load_state_dict(w)
+    bp, arena = _standalone(BP, enc.to(DEV))
+    dfeat = None
+    runs = []
+    for overlap in (True, True, False):
+        bp.overlap_wgrad = overlap
+        arena.grad.fill_(float("nan"))
+        feat = bp.forward_train(*inputs)
+        if dfeat is None:
+            dfeat = torch.randn(feat.shape, generator=torch.Generator().manual_seed(82)).to(DEV)
+        bp.backward(dfeat)
+        torch.cuda.synchronize()
+        runs.append(torch.nan_to_num(arena.grad, nan=-7.0).clone())
+    assert torch.equal(runs[0], runs[1]), "overlap_wgrad rerun"
+    assert torch.equal(runs[0], runs[2]), "overlap_wgrad True vs False"
+
+
 def test_full_depth_text_encoder_gradients_sampled_tensors():
     """12 layers (BERT-base geometry, small vocabulary so that the CPU autograd stays quick): first, middle and last layer's
     tensors and the embeddings."""

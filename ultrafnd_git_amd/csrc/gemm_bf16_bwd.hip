@@ -275,8 +275,10 @@ extern "C" int ufnd_gemm_bf16_dgrad(const void* dY, const void* Wt, const float*
   return UFND_OK;
 }
 
+// Every n_out the two weight-gradient entries accept (ufnd_gemm_bf16_wgrad: >= 1, ufnd_linear_wgrad: >= 8): the slab set is S x n_out x k_in
+// floats whatever the tile, so a narrow output (n_out < 64, one partial row tile) is sized like any other.
 extern "C" size_t ufnd_gemm_bf16_wgrad_workspace_floats(int n_out, int k_in, int m_tokens) {
-  if (n_out < 64 || k_in < 64 || m_tokens < 64 || k_in % 64 || m_tokens % 64) return 0;
+  if (n_out < 1 || k_in < 64 || m_tokens < 64 || k_in % 64 || m_tokens % 64) return 0;
   const int cfg = wgrad_cfg(n_out, k_in, m_tokens);
   return (size_t)wgrad_slices(n_out, k_in, m_tokens, cfg) * (size_t)n_out * (size_t)k_in;
 }
