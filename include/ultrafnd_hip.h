@@ -28,7 +28,7 @@ extern "C" {
 #define UFND_ERR_INVALID 1 /* bad argument: shape, alignment, null pointer */
 #define UFND_ERR_LAUNCH 2  /* HIP launch error */
 
-#define UFND_ABI_VERSION 5
+#define UFND_ABI_VERSION 6
 
 const char* ufnd_last_error(void);
 int ufnd_abi_version(void);
@@ -349,7 +349,7 @@ typedef struct ufnd_gemm_ln {
   /* fold guard inside the GEMM (ABI v4; optional, used with a_stats): UFND_FOLD_GUARD_SLOTS floats.  Every workgroup of the
    * launch leaves max(slot, largest |mean| * rstd among the rows it folds) in slot (workgroup id % UFND_FOLD_GUARD_SLOTS) -- the
    * statistics are in its registers at that point anyway, so the guard costs one atomicMax per workgroup at its very end instead
-   * of a kernel that re-reads every statistics buffer of the pass (ufnd_ln_fold_guard_multi: 55-75 MB per pass).  The largest
+   * of a kernel that re-reads every statistics buffer of the pass (55-75 MB per pass).  The largest
    * ratio any folded row has had since the slots were last zeroed = the maximum over the slots (the caller reduces 4 KB). */
   float* guard;
 } ufnd_gemm_ln;
@@ -364,12 +364,6 @@ int ufnd_gemm_bf16_stat_parts(int M, int N, int K);
 /* *guard = max(*guard, max over rows of |mean| * rstd) for the M rows of a statistics buffer (M, parts, 2) as
  * ufnd_gemm_bf16_ln writes and reads them (partial {sum, sumsq}; statistics over `width` elements). */
 int ufnd_ln_fold_guard(const float* stats, int M, int parts, int width, float eps, float* guard, void* stream);
-/* The same over `nbuf` statistics buffers of M rows each, `buf_stride` floats apart, in ONE launch: an encoder keeps one
- * statistics buffer per folded LayerNorm of a pass (2 x layers of them, back to back) and looks at all of them with a single
- * kernel at the end of the pass -- every row of every batch is guarded, at the price of re-reading the statistics once
- * (75 MB per 16,384-row text pass). */
-int ufnd_ln_fold_guard_multi(const float* stats, int M, int parts, int nbuf, size_t buf_stride, int width, float eps, float* guard,
-                             void* stream);
 
 /* The tile table of this library: ids 0 .. ufnd_gemm_bf16_tile_count()-1; ufnd_gemm_bf16_tile_info returns 1 and the
  * block tile (rows x columns) of a tile that is built into the library (ln_aware: usable by ufnd_gemm_bf16_ln), 0 for
@@ -402,27 +396,15 @@ int ufnd_attention_bf16(const void* qkv, const int32_t* key_mask, void* ctx, int
 int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, void* ctx, int B, int L,
                             int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream);
 
-/* Packed (un-padded) forms: the tokens a padding mask keeps, concatenated over the batch (T rows; sequence b owns
- * rows cu_seqlens[b] .. cu_seqlens[b+1]; pos_ids (T) = each token's position in its sequence).  HF BertModel computes
- * the padded positions too (text_blocks.py:71-79 pads every string to max_length) and the pooling then ignores them
- * (:82-86); skipping them changes no kept value -- with prefix masks the features are bit-identical.
- *   ufnd_bert_embed_packed     LayerNorm(word[ids] + position[pos_ids] + token_type[0]) for T packed tokens
- *   ufnd_attention_bf16_varlen per-sequence attention over the packed fused-QKV rows (every key valid)
- *   ufnd_meanpool_l2_packed    mean over each sequence's rows, then v / (||v|| + 1e-9) */
-int ufnd_bert_embed_packed(const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0,
-                           const float* gamma, const float* beta, void* x_bf16, float* x_f32, int T, int max_pos, int H,
-                           int vocab, float eps, void* stream);
-int ufnd_attention_bf16_varlen(const void* qkv, const int32_t* cu_seqlens, void* ctx, int B, int max_len, int heads, void* stream);
-int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_seqlens, const int32_t* pos_ids, float* out, int B, int H,
-                            void* stream);
-
 /* Packed rows with the row count on the device (no host synchronisation, fixed launch geometry: hipGraph-capturable; a replay
- * follows whatever mask the captured buffers hold).  Sample b of a (B, L) batch keeps its positions 0 .. n_b - 1, n_b = 1 + its last
+ * follows whatever mask the captured buffers hold).  HF BertModel computes the padded positions too (text_blocks.py:71-79 pads every
+ * string to max_length) and the pooling then ignores them (:82-86).  Sample b of a (B, L) batch keeps its positions 0 .. n_b - 1, n_b = 1 + its last
  * kept position (0 for an all-masked sample): only TRAILING padding is dropped, holes stay as rows and stay masked as keys, so every
  * kept token's value is bit-identical to the padded computation for every mask.  The buffers keep their padded capacity B L; the
  * live row count T = cu_seqlens[B] is read by every kernel at entry, and rows T .. capacity are never read into a live row.
  *   ufnd_text_pack                 (B, L) int32 mask -> cu_seqlens (B + 1) and row_src (capacity): row_src[cu[b] + l] = b L + l
- *   ufnd_bert_embed_live           ufnd_bert_embed of the live rows (token row_src[r] of ids (B, L))
+ *   ufnd_bert_embed_live           ufnd_bert_embed of the first *m_live of `capacity` rows: row r is token row_src[r] of ids (B, L), at
+ *                                  position row_src[r] % L
  *   ufnd_gemm_bf16_live / _ln_live ufnd_gemm_bf16_ex / ufnd_gemm_bf16_ln over the first *m_live of M rows: M (the capacity) picks
  *                                  the tile and bounds the grid, workgroups past the live tiles exit at entry, the live tiles are
  *                                  spread over every XCD; per-row arithmetic is that of the M-row call (bit-identical rows)
@@ -432,7 +414,9 @@ int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_seqlens, cons
  *   ufnd_qkv_attention_bf16_packed ufnd_qkv_attention_bf16 with sample b's rows at cu_seqlens[b] .. cu_seqlens[b+1] (key_mask (B, 128))
  *   ufnd_qkv_attention_bf16_bins   ..._packed with one workgroup per bin of ufnd_text_pack_bins (up to four samples) and head pair;
  *                                  the grid keeps B x heads / 2, workgroups of bins past *nbins exit at entry; bit-identical ctx
- *   ufnd_attention_bf16_varlen_masked  ufnd_attention_bf16_varlen with a (B, max_len) key mask (NULL: every key valid)
+ *   ufnd_attention_bf16_varlen_masked  ufnd_attention_bf16 per sample over the packed fused-QKV rows: sample b's rows are
+ *                                  cu_seqlens[b] .. cu_seqlens[b+1] (at most max_len of them), key_mask (B, max_len) indexed by position
+ *                                  (NULL: every key valid); ctx rows are packed like qkv's
  *   ufnd_layernorm_live            ufnd_layernorm over the first *m_live of `capacity` rows
  *   ufnd_masked_meanpool_l2_live   ufnd_masked_meanpool_l2 over the packed rows: the same groups and summation order */
 int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream);

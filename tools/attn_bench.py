@@ -30,11 +30,11 @@ def main():
         # the same work through the packed-sequence entry (always the 4-wave form)
         cu = (torch.arange(B + 1, device=dev, dtype=torch.int32) * Lq).contiguous()
         for _ in range(5):
-            L.check(L.lib().ufnd_attention_bf16_varlen(qkv.data_ptr(), cu.data_ptr(), ctx.data_ptr(), B, Lq, heads, s), "varlen")
+            L.check(L.lib().ufnd_attention_bf16_varlen_masked(qkv.data_ptr(), cu.data_ptr(), None, ctx.data_ptr(), B, Lq, heads, s), "varlen")
         torch.cuda.synchronize()
         e0.record()
         for _ in range(20):
-            L.check(L.lib().ufnd_attention_bf16_varlen(qkv.data_ptr(), cu.data_ptr(), ctx.data_ptr(), B, Lq, heads, s), "varlen")
+            L.check(L.lib().ufnd_attention_bf16_varlen_masked(qkv.data_ptr(), cu.data_ptr(), None, ctx.data_ptr(), B, Lq, heads, s), "varlen")
         e1.record()
         torch.cuda.synchronize()
         us4 = e0.elapsed_time(e1) / 20 * 1e3

@@ -105,7 +105,7 @@ class GemmLn(C.Structure):
 STEP_STATE_BYTES = C.sizeof(StepState)
 BWD_ALL, BWD_FUSE_MLP, BWD_REST = 0, 1, 2
 BWD_NO_LINEAR_GRADS = 16          # OR-ed into the phase / flags: the factor form of the gradient exchange (dp.FactorExchange)
-ABI_VERSION = 5
+ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 
 _lib: Optional[C.CDLL] = None
@@ -170,9 +170,6 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_qkv_attention_bf16": [P, P, P, P, P, I, I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_bert_embed": [P] * 8 + [I, I, I, I, F, P],
         "ufnd_masked_meanpool_l2": [P, P, P, I, I, I, P],
-        "ufnd_bert_embed_packed": [P] * 9 + [I, I, I, I, F, P],
-        "ufnd_attention_bf16_varlen": [P, P, P, I, I, I, P],
-        "ufnd_meanpool_l2_packed": [P, P, P, P, I, I, P],
         "ufnd_text_pack": [P, I, I, P, P, P],
         "ufnd_text_pack_bins": [P, I, I, P, P, P, P, P],
         "ufnd_bert_embed_live": [P] * 10 + [I, I, I, I, F, P],
@@ -188,7 +185,6 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_gemm_bf16_ln": [P] * 6 + [I] * 9 + [C.POINTER(GemmLn), P],
         "ufnd_gemm_bf16_stat_parts": [I, I, I],
         "ufnd_ln_fold_guard": [P, I, I, I, F, P, P],
-        "ufnd_ln_fold_guard_multi": [P, I, I, I, S, I, F, P, P],
         "ufnd_gemm_bf16_tile_count": [],
         "ufnd_gemm_bf16_tile_info": [I, C.POINTER(I), C.POINTER(I), C.POINTER(I)],
         "ufnd_stream_create_cu_mask": [C.POINTER(C.c_uint32), I, C.POINTER(P)],

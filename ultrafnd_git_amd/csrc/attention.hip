@@ -246,13 +246,6 @@ extern "C" int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask,
 }
 
 extern "C" int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B,
-                                                 int max_len, int heads, void* stream_);
-extern "C" int ufnd_attention_bf16_varlen(const void* qkv, const int32_t* cu_seqlens, void* ctx, int B, int max_len, int heads,
-                                          void* stream_) {
-  return ufnd_attention_bf16_varlen_masked(qkv, cu_seqlens, nullptr, ctx, B, max_len, heads, stream_);
-}
-
-extern "C" int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B,
                                                  int max_len, int heads, void* stream_) {
   UFND_REQUIRE(qkv && ctx && cu_seqlens, "attention_varlen: null operand");
   UFND_REQUIRE(B >= 1 && B <= 65535 && max_len >= 1 && max_len <= 4096 && heads >= 1 && heads <= 64, "attention_varlen: B=%d max_len=%d heads=%d",

@@ -111,15 +111,14 @@ template <int NI>
 __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* ids, const float* word, const float* pos,
                                                          const float* type0, const float* gamma, const float* beta,
                                                          __bf16* ob, float* of, int M, int L, int H, int vocab,
-                                                         float eps, const int32_t* pos_ids, const int32_t* row_src,
-                                                         const int* m_live) {
+                                                         float eps, const int32_t* row_src, const int* m_live) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M || (m_live && row >= *m_live)) return;
   const int src = row_src ? row_src[row] : row;     // packed rows of ufnd_text_pack: the (B, L) index of the token
   long long id = ids[src];
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);  // never read outside the table
-  int l = pos_ids ? pos_ids[row] : src % L;         // packed (un-padded) rows carry their position
+  int l = src % L;
   l = l < 0 ? 0 : (l >= L ? L - 1 : l);
   f32x4 v[NI];
 #pragma unroll
@@ -164,31 +163,6 @@ __global__ __launch_bounds__(256) void meanpool_kernel(const float* hidden, cons
         acc += x[u];
         cnt += 1.0f;
       }
-    }
-  }
-  part[grp][lane] = acc;
-  if (lane == 0) cnts[grp] = cnt;
-  __syncthreads();
-  if (grp == 0) {
-    const f32x4 s = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-    const float denom = fmaxf((cnts[0] + cnts[1]) + (cnts[2] + cnts[3]), 1e-6f);
-    *reinterpret_cast<f32x4*>(out + (size_t)b * H + col) = s / denom;
-  }
-}
-// the same reduction over a PACKED sequence (rows cu[b] .. cu[b+1]): a token joins the group its original position
-// selects and groups add in token order, so the sum is bit-identical to the padded kernel's
-__global__ __launch_bounds__(256) void meanpool_packed_kernel(const float* hidden, const int32_t* cu, const int32_t* pos_ids, float* out,
-                                                              int H) {
-  __shared__ f32x4 part[4][64];
-  __shared__ float cnts[4];
-  const int b = blockIdx.y, col = blockIdx.x * 256 + 4 * (threadIdx.x & 63), grp = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r0 = cu[b], r1 = cu[b + 1];
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float cnt = 0.0f;
-  for (int r = r0; r < r1; ++r) {
-    if ((pos_ids[r] & 3) == grp) {
-      acc += ld4(hidden + (size_t)r * H + col);
-      cnt += 1.0f;
     }
   }
   part[grp][lane] = acc;
@@ -514,20 +488,7 @@ extern "C" int ufnd_bert_embed(const int64_t* ids, const float* word, const floa
   UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed: alignment");
   const int M = B * L;
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
-            (__bf16*)x_bf16, x_f32, M, L, H, vocab, eps, (const int32_t*)nullptr, (const int32_t*)nullptr,
-            (const int*)nullptr);
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
-}
-
-extern "C" int ufnd_bert_embed_packed(const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos,
-                                      const float* type0, const float* gamma, const float* beta, void* x_bf16, float* x_f32,
-                                      int T, int max_pos, int H, int vocab, float eps, void* stream_) {
-  UFND_REQUIRE(ids && pos_ids && word && pos && type0 && gamma && beta && (x_bf16 || x_f32), "bert_embed_packed: null argument");
-  UFND_REQUIRE(h_ok(H) && T >= 1 && max_pos >= 1 && vocab >= 1, "bert_embed_packed: T=%d H=%d vocab=%d", T, H, vocab);
-  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed_packed: alignment");
-  NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(T, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
-            (__bf16*)x_bf16, x_f32, T, max_pos, H, vocab, eps, pos_ids, (const int32_t*)nullptr, (const int*)nullptr);
+            (__bf16*)x_bf16, x_f32, M, L, H, vocab, eps, (const int32_t*)nullptr, (const int*)nullptr);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -538,17 +499,6 @@ extern "C" int ufnd_masked_meanpool_l2(const float* hidden, const int32_t* mask,
   UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool: H=%d (multiple of 256)", H);
   hipLaunchKernelGGL(meanpool_kernel<false>, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H,
                      (const int32_t*)nullptr);
-  UFND_CHECK_LAUNCH();
-  hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
-}
-
-extern "C" int ufnd_meanpool_l2_packed(const float* hidden, const int32_t* cu_seqlens, const int32_t* pos_ids, float* out, int B, int H,
-                                       void* stream_) {
-  UFND_REQUIRE(hidden && cu_seqlens && pos_ids && out && B >= 1, "meanpool_packed: null argument");
-  UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool_packed: H=%d (multiple of 256)", H);
-  hipLaunchKernelGGL(meanpool_packed_kernel, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, cu_seqlens, pos_ids, out, H);
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
   UFND_CHECK_LAUNCH();
@@ -580,7 +530,7 @@ extern "C" int ufnd_bert_embed_live(const int64_t* ids, const int32_t* row_src, 
   UFND_REQUIRE(h_ok(H) && capacity >= 1 && L >= 1 && vocab >= 1, "bert_embed_live: capacity=%d L=%d H=%d vocab=%d", capacity, L, H, vocab);
   UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed_live: alignment");
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(capacity, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
-            (__bf16*)x_bf16, x_f32, capacity, L, H, vocab, eps, (const int32_t*)nullptr, row_src, m_live);
+            (__bf16*)x_bf16, x_f32, capacity, L, H, vocab, eps, row_src, m_live);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -651,14 +601,12 @@ extern "C" int ufnd_field_mean_l2(const float* parts, const int32_t* valid, floa
 // ------------------------------------------------------------------------------------------------
 namespace {
 // Four lanes per row: lane j of a quad adds 16-B chunks j, j + 4, ... of the row's `parts` {sum, sumsq} pairs (parts is even),
-// the quad combines by DPP.  Rows are `nbuf` buffers of M rows each, `buf_stride` floats apart (one launch looks at every
-// statistics buffer of an encoder pass).
-__global__ __launch_bounds__(256) void ln_fold_guard_kernel(const float* stats, int M, int parts, int nbuf, size_t buf_stride, float inv_h,
-                                                            float eps, float* guard) {
+// the quad combines by DPP.
+__global__ __launch_bounds__(256) void ln_fold_guard_kernel(const float* stats, int M, int parts, float inv_h, float eps, float* guard) {
   __shared__ float sh[4];
   float worst = 0.0f;
   const int nq = parts >> 1, sub = threadIdx.x & 3;
-  const long long total = (long long)M * nbuf;
+  const long long total = M;
   // two rows per quad and pass, their (at most 3 + 3: parts <= 24) chunk loads issued together (clamped, masked at use): the
   // kernel is a stream of 192-B rows and was latency-bound with one load in flight per lane (36 us for 55 MB)
   const long long step = (long long)gridDim.x * 64;
@@ -670,8 +618,7 @@ __global__ __launch_bounds__(256) void ln_fold_guard_kernel(const float* stats, 
       const long long rk = r + k * step;
       live[k] = rk < total;
       const long long rc = live[k] ? rk : r;
-      const int bi = (int)(rc / M), row = (int)(rc - (long long)bi * M);
-      const f32x4* p = reinterpret_cast<const f32x4*>(stats + bi * buf_stride + (size_t)row * parts * 2);
+      const f32x4* p = reinterpret_cast<const f32x4*>(stats + (size_t)rc * parts * 2);
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const int c = sub + 4 * u;
@@ -707,20 +654,12 @@ __global__ __launch_bounds__(256) void ln_fold_guard_kernel(const float* stats, 
 }
 }  // namespace
 
-extern "C" int ufnd_ln_fold_guard_multi(const float* stats, int M, int parts, int nbuf, size_t buf_stride, int width, float eps, float* guard,
-                                        void* stream_) {
-  UFND_REQUIRE(stats && guard && M >= 1 && parts >= 2 && parts <= 24 && parts % 2 == 0 && nbuf >= 1 && width >= 1 && ufnd_aligned(stats, 16) &&
-               (nbuf == 1 || (buf_stride % 4 == 0 && buf_stride >= (size_t)M * parts * 2)),
-               "ln_fold_guard: M=%d parts=%d (even) nbuf=%d stride=%zu", M, parts, nbuf, buf_stride);
-  const long long rows = (long long)M * nbuf;
-  const long long want = (rows + 63) / 64;
-  const int blocks = (int)(want < 2048 ? want : 2048);
-  hipLaunchKernelGGL(ln_fold_guard_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, stats, M, parts, nbuf, buf_stride,
+extern "C" int ufnd_ln_fold_guard(const float* stats, int M, int parts, int width, float eps, float* guard, void* stream_) {
+  UFND_REQUIRE(stats && guard && M >= 1 && parts >= 2 && parts <= 24 && parts % 2 == 0 && width >= 1 && ufnd_aligned(stats, 16),
+               "ln_fold_guard: M=%d parts=%d (even)", M, parts);
+  const int want = (int)((M + 63ll) / 64);
+  hipLaunchKernelGGL(ln_fold_guard_kernel, dim3(want < 2048 ? want : 2048), dim3(256), 0, (hipStream_t)stream_, stats, M, parts,
                      1.0f / (float)width, eps, guard);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
-}
-
-extern "C" int ufnd_ln_fold_guard(const float* stats, int M, int parts, int width, float eps, float* guard, void* stream_) {
-  return ufnd_ln_fold_guard_multi(stats, M, parts, 1, 0, width, eps, guard, stream_);
 }

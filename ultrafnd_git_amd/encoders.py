@@ -35,8 +35,10 @@ out-projection launches 49 -> 31 us and FFN2 100 -> 83 us at 16,384 rows, the st
 """
 from __future__ import annotations
 
+import ctypes
+import warnings
 from collections import OrderedDict
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -101,14 +103,30 @@ class _EncoderBase(nn.Module):
     # below the bf16 floor of the materialised path; beyond, the encoder falls back to one LayerNorm kernel per LayerNorm.
     FOLD_GUARD_MAX = 4.0
 
-    def __init__(self):
+    def __init__(self, hidden: int, heads: int, fold_ln: bool, residual_dtype: str):
         super().__init__()
-        self.tiles = {}
+        if residual_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"residual_dtype={residual_dtype!r}: 'fp32' or 'bf16'")
+        if hidden != heads * 64:
+            raise ValueError("head_dim must be 64 (hidden == heads * 64)")
+        self.hidden, self.heads, self.fold_ln, self.residual_dtype = hidden, heads, fold_ln, residual_dtype
+        # GEMM tile per Linear ("qkv", "out", "ffn1", "ffn2"): -1 = the library's own choice for the shape.  Set by the
+        # trainer when the encoder runs on a compute-unit partition (a launch wants about one tile per CU it may use).
+        self.tiles: Dict[str, int] = {}
         self._guard: Optional[torch.Tensor] = None      # device float: largest |mean| / std any folded LayerNorm has seen
         self._w: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         self._packed: Optional[dict] = None
         self._bufs: Dict[Tuple, dict] = {}
         self.weights_version = 0      # bumped whenever the packed operands are invalidated (captured graphs name them)
+
+    @staticmethod
+    def _seeded_init():
+        """init(shape, std=0.02): the constructors' placeholder weights, drawn in call order from one generator seeded with 0."""
+        g = torch.Generator().manual_seed(0)
+
+        def init(shape, std=0.02):
+            return torch.randn(shape, generator=g) * std
+        return init
 
     # ---- state_dict with the third-party names
     def state_dict(self, *args, **kwargs):
@@ -145,28 +163,44 @@ class _EncoderBase(nn.Module):
         if self.device.type != "cuda":
             raise L.UltrafndHipError(f"{type(self).__name__} runs on a HIP device only: call .to('cuda') (no CPU fallback)")
 
+    def _strict(self, run):
+        """forward(strict=True), the offline feature builder's mode (encode_fields; caches for the reference-style training mode): run()
+        with the more faithful fp32 residual stream whatever the in-step default is -- the bf16 stream's speed only matters inside the
+        train step -- then the fold guard is read (one host sync) and, if it tripped, run() repeated with materialised
+        LayerNorms."""
+        rd, self.residual_dtype = self.residual_dtype, "fp32"
+        try:
+            if self.fold_ln:
+                out = run()
+                if not self.check_fold():
+                    return out
+            return run()
+        finally:
+            self.residual_dtype = rd
+
+    def _fold_parts(self, M: int) -> int:
+        """The {sum, sumsq} partials per row (an even count) that the GEMMs of an M-row pass write for its folded LayerNorms, or 0 when
+        the pass cannot fold: fold_ln is off, or the two GEMM widths that produce a residual-stream row disagree on the count."""
+        p1 = L.lib().ufnd_gemm_bf16_stat_parts(M, self.hidden, self.hidden)
+        p2 = L.lib().ufnd_gemm_bf16_stat_parts(M, self.hidden, self.inter)
+        return p1 if (self.fold_ln and p1 > 0 and p1 == p2 and p1 % 2 == 0) else 0
+
     # ---- thin wrappers over the C ABI
-    # GEMM tile per Linear ("qkv", "out", "ffn1", "ffn2"): -1 = the library's own choice for the shape.  Set by the
-    # trainer when the encoder runs on a compute-unit partition (a launch wants about one tile per CU it may use).
-    tiles: Dict[str, int] = {}
-
-    # Live rows (BertTextEncoder's packed pass): a device int holding how many of the work buffers' rows are live.  While it is
-    # set, every Linear / LayerNorm below computes the first *_m_live rows of its capacity-sized operands only (include/ultrafnd_hip.h,
-    # ufnd_gemm_bf16_live): same launches, same shapes, same tiles.
-    _m_live: Optional[int] = None
-
-    def _gemm(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, M=None, which=None):
-        M = A.shape[0] if M is None else M
+    # m_live (BertTextEncoder's packed pass): the device address of an int holding how many of the operands' rows are live.  With it a
+    # Linear / LayerNorm computes the first *m_live rows of its capacity-sized operands only (include/ultrafnd_hip.h,
+    # ufnd_gemm_bf16_live): same launches, same shapes, same tiles.  None: every row.
+    def _gemm(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, which=None, m_live=None):
+        M = A.shape[0]
         N, K = W.shape
         L.check(L.lib().ufnd_gemm_bf16_live(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
                                             L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
                                             residual.stride(0) if residual is not None else 0,
                                             out_bf16.stride(0) if out_bf16 is not None else 0,
                                             out_f32.stride(0) if out_f32 is not None else 0, act, self.tiles.get(which, -1),
-                                            self._m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_live")
+                                            m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_live")
 
     def _gemm_ln(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, a_stats=None, colsum=None,
-                 r_stats=None, r_gamma=None, r_beta=None, out_stats=None, eps=1e-5, which=None, residual_bf16=None):
+                 r_stats=None, r_gamma=None, r_beta=None, out_stats=None, eps=1e-5, which=None, residual_bf16=None, m_live=None):
         """ufnd_gemm_bf16_ln: a_stats / r_stats / out_stats are (M, parts, 2) fp32 tensors."""
         M = A.shape[0]
         N, K = W.shape
@@ -183,13 +217,12 @@ class _EncoderBase(nn.Module):
             ln.residual_bf16, ln.ldrb = residual_bf16.data_ptr(), residual_bf16.stride(0)
         if a_stats is not None:      # fold guard: the launch reports the largest |mean| / std among the rows it folds
             ln.guard = self._guard_buf(A.device).data_ptr()
-        import ctypes
         L.check(L.lib().ufnd_gemm_bf16_ln_live(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(residual), L.ptr(out_bf16),
                                                L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
                                                residual.stride(0) if residual is not None else 0,
                                                out_bf16.stride(0) if out_bf16 is not None else 0,
                                                out_f32.stride(0) if out_f32 is not None else 0, act, ctypes.byref(ln),
-                                               self._m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_ln_live")
+                                               m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_ln_live")
 
     def _guard_buf(self, dev) -> torch.Tensor:
         """The fold guard's slots (UFND_FOLD_GUARD_SLOTS floats): every folded GEMM launch -- inside captured graphs too -- leaves
@@ -213,7 +246,6 @@ class _EncoderBase(nn.Module):
         if reset and self._guard is not None:
             self._guard.zero_()
         if self.fold_ln and r > self.FOLD_GUARD_MAX:
-            import warnings
             warnings.warn(f"{type(self).__name__}: a residual-stream row with |mean|/std = {r:.1f} (> {self.FOLD_GUARD_MAX}) went through a "
                           "folded LayerNorm; switching to materialised LayerNorms (fold_ln=False)")
             self.fold_ln = False
@@ -229,37 +261,43 @@ class _EncoderBase(nn.Module):
         # (W * beta).sum(1), not W @ beta: packing is one-off setup, but it was the only vendor-BLAS call (rocblas gemv) of the tree
         return Wp, Wp.float().sum(1).contiguous(), (b + (W * beta[None, :]).sum(1)).contiguous()
 
-    def _ln(self, x, ldx, gamma, beta, out_bf16, out_f32, M, H, eps):
-        if self._m_live is not None:
+    def _ln(self, x, ldx, gamma, beta, out_bf16, out_f32, M, H, eps, m_live=None):
+        if m_live is not None:      # (its own entry: ufnd_layernorm_live refuses a NULL count)
             L.check(L.lib().ufnd_layernorm_live(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
-                                                L.ptr(out_f32), M, H, eps, self._m_live, L.stream_ptr(x.device)), "ufnd_layernorm_live")
+                                                L.ptr(out_f32), M, H, eps, m_live, L.stream_ptr(x.device)), "ufnd_layernorm_live")
             return
         L.check(L.lib().ufnd_layernorm(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
                                        L.ptr(out_f32), M, H, eps, L.stream_ptr(x.device)), "ufnd_layernorm")
 
-    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None):
-        """ufnd_qkv_attention_bf16: fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer
-        (cu: sample b's rows are cu[b] .. cu[b+1] of the packed pass; bins = (bins, nbins) of ufnd_text_pack_bins: one workgroup
-        per bin of up to four samples and head pair)."""
-        import ctypes
+    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None, nbins=None):
+        """Fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer.  cu: sample b's rows are
+        cu[b] .. cu[b+1] of the packed pass (None: the padded batch); bins, nbins (ufnd_text_pack_bins, with cu): one workgroup per
+        bin of up to four samples and head pair (None: one per sample and head pair)."""
         ln = None
         if a_stats is not None:
             ln = L.GemmLn()
             ln.a_stats, ln.colsum, ln.a_parts, ln.a_eps, ln.r_eps, ln.width = a_stats.data_ptr(), colsum.data_ptr(), a_stats.shape[1], eps, eps, self.hidden
             ln.guard = self._guard_buf(A.device).data_ptr()
-        if bins is not None:
-            L.check(L.lib().ufnd_qkv_attention_bf16_bins(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), cu.data_ptr(),
-                                                         bins[0].data_ptr(), bins[1].data_ptr(), ctx.data_ptr(), B, Lq, heads, A.stride(0),
-                                                         W.stride(0), ctypes.byref(ln) if ln is not None else None,
-                                                         L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16_bins")
-            return
-        L.check(L.lib().ufnd_qkv_attention_bf16_packed(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), ctx.data_ptr(),
-                                                       B, Lq, heads, A.stride(0), W.stride(0), ctypes.byref(ln) if ln is not None else None,
-                                                       L.stream_ptr(A.device)), "ufnd_qkv_attention_bf16_packed")
+        L.check(L.lib().ufnd_qkv_attention_bf16_bins(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), L.ptr(bins),
+                                                     L.ptr(nbins), ctx.data_ptr(), B, Lq, heads, A.stride(0), W.stride(0),
+                                                     ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
+                "ufnd_qkv_attention_bf16_bins")
 
     def _attn(self, qkv, mask_i32, ctx, B, Lq, heads):
         L.check(L.lib().ufnd_attention_bf16(qkv.data_ptr(), L.ptr(mask_i32), ctx.data_ptr(), B, Lq, heads,
                                             L.stream_ptr(qkv.device)), "ufnd_attention_bf16")
+
+
+class _TextPass(NamedTuple):
+    """What the layer loops need to know about one BertTextEncoder pass.  A padded pass has no live / cu / bins / nbins."""
+    B: int
+    Lq: int
+    mask: torch.Tensor                      # (B, L) int32, 1 = a key to attend to
+    fuse: bool                              # a layer's Q/K/V projection + attention as one launch (_qkv_attn)
+    live: Optional[int] = None              # packed rows: the device address of the live row count, cu[B] (m_live of the wrappers)
+    cu: Optional[torch.Tensor] = None       # packed rows: sample b's rows are cu[b] .. cu[b+1]
+    bins: Optional[torch.Tensor] = None     # packed rows, fused: the slot bins of ufnd_text_pack_bins ...
+    nbins: Optional[torch.Tensor] = None    # ... and their count
 
 
 # =============================================================================================
@@ -268,28 +306,17 @@ class BertTextEncoder(_EncoderBase):
                  vocab_size: int = 30522, max_position: int = 512, type_vocab: int = 2, eps: float = 1e-12,
                  fold_ln: bool = True, residual_dtype: str = "bf16", hidden_dropout_prob: float = 0.0,
                  attention_probs_dropout_prob: float = 0.0):
-        super().__init__()
-        self.fold_ln = fold_ln
+        super().__init__(hidden, heads, fold_ln, residual_dtype)
         # train-mode dropout (HF BertConfig names): applied only by encoder_train.TextBackprop.forward_train and its backward, never
         # by forward() / encode_fields, whatever the module's mode
         self.hidden_dropout_prob = dropout_prob("hidden_dropout_prob", hidden_dropout_prob)
         self.attention_probs_dropout_prob = dropout_prob("attention_probs_dropout_prob", attention_probs_dropout_prob)
-        if residual_dtype not in ("fp32", "bf16"):
-            raise ValueError(f"residual_dtype={residual_dtype!r}: 'fp32' or 'bf16'")
-        self.residual_dtype = residual_dtype
         # 128-token samples: Q/K/V projection + attention of a layer as ONE launch (ufnd_qkv_attention_bf16); bit-identical
         # to the two-launch form, which every other length uses
         self.fuse_qkv_attention = True
-        if hidden != heads * 64:
-            raise ValueError("head_dim must be 64 (hidden == heads * 64)")
-        self.layers, self.hidden, self.heads, self.inter, self.vocab, self.eps = layers, hidden, heads, intermediate, vocab_size, eps
+        self.layers, self.inter, self.vocab, self.eps = layers, intermediate, vocab_size, eps
         self.max_position = max_position
-        # output.dense as a 2-way split-K GEMM when the token count gives a full wave of 128x192 tiles
-        w = self._w
-        g = torch.Generator().manual_seed(0)
-
-        def init(shape, std=0.02):
-            return torch.randn(shape, generator=g) * std
+        w, init = self._w, self._seeded_init()
         w["embeddings.word_embeddings.weight"] = init((vocab_size, hidden))
         w["embeddings.position_embeddings.weight"] = init((max_position, hidden))
         w["embeddings.token_type_embeddings.weight"] = init((type_vocab, hidden))
@@ -347,9 +374,8 @@ class BertTextEncoder(_EncoderBase):
                                "cu": torch.zeros(B + 1, dtype=torch.int32, device=dev), "row_src": torch.zeros(M, dtype=torch.int32, device=dev),
                                # (L <= 128: ufnd_text_pack_bins) the fused Q/K/V + attention's slot bins and their count
                                "bins": torch.zeros(B, 8, dtype=torch.int32, device=dev), "nbins": torch.zeros(1, dtype=torch.int32, device=dev)}
-            p1 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, H)
-            p2 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, self.inter)
-            if self.fold_ln and p1 > 0 and p1 == p2 and p1 % 2 == 0:
+            p1 = self._fold_parts(M)
+            if p1:
                 # one statistics buffer per folded LayerNorm of the pass (st[2i]: layer i's attention half, st[2i+1]: its
                 # feed-forward half); every buffer is read by a folded GEMM, which reports its rows' |mean| / std (fold guard)
                 self._bufs[key].update({"y2": torch.empty(M, H, **f32), "y1b": torch.empty(M, H, **bf), "y2b": torch.empty(M, H, **bf),
@@ -357,11 +383,10 @@ class BertTextEncoder(_EncoderBase):
                 self._guard_buf(dev)
         return self._bufs[key]
 
-    @torch.no_grad()
-    def last_hidden_state(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, n_layers: Optional[int] = None) -> torch.Tensor:
-        """BertModel(input_ids, attention_mask).last_hidden_state -> (B, L, H) fp32 (a view of an
-        internal buffer, valid until the next call with the same shape).  n_layers: stop after that many layers (the
-        hidden state BertModel reports as hidden_states[n_layers]; per-layer localisation in the parity tests)."""
+    def _pass(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True) -> dict:
+        """One pass over a (B, L) batch: embeddings, the first n_layers layers (all by default) and, with pool, the pooled features.
+        packed: over the rows ufnd_text_pack keeps, their count on the device (forward's unpad paragraph); otherwise over all B L rows.
+        Returns the work buffers: last_hidden_state in "xf" (packed: its live rows), the features in "feat"."""
         self._require_hip()
         dev = self.device
         B, Lq = input_ids.shape
@@ -369,81 +394,98 @@ class BertTextEncoder(_EncoderBase):
             raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
         ids = input_ids.to(dev, torch.int64).contiguous()
         mask = attention_mask.to(dev, torch.int32).contiguous()
-        self._mask_i32 = mask
         p, b, w = self._pack(), self._workbufs(B, Lq), self._w
-        M, H = B * Lq, self.hidden
-        L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), w["embeddings.word_embeddings.weight"].data_ptr(),
-                                        w["embeddings.position_embeddings.weight"].data_ptr(),
-                                        w["embeddings.token_type_embeddings.weight"].data_ptr(),
-                                        w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
-                                        b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr(),
-                                        B, Lq, H, self.vocab, self.eps, L.stream_ptr(dev)), "ufnd_bert_embed")      # (bf16 stream, folded: nothing reads the fp32 copy)
-        fused = (B, Lq, mask) if (self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0) else None
-        if n_layers is not None:
-            p = {"layers": p["layers"][:max(1, int(n_layers))]}
-        self._layers(p, b, M, lambda qkv, ctx: self._attn(qkv, mask, ctx, B, Lq, self.heads), fused)
-        return b["xf"].view(B, Lq, H)
-
-    def _layers(self, p, b, M, attn, fused=None) -> None:
-        """The encoder layers over the first M rows of the work buffers; attn(qkv, ctx) runs the attention (padded
-        batch or packed sequences).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
-        H = self.hidden
-        v = {k: (x[:M] if torch.is_tensor(x) and x.dim() >= 2 and x.shape[0] >= M and k not in ("feat", "st") else x) for k, x in b.items()}
-        cu = fused[3] if fused is not None and len(fused) > 3 else None
-        bins = fused[4] if fused is not None and len(fused) > 4 else None
-        if "st" in b:
-            return self._layers_folded(p, v, M, attn, fused)
-        for ly in p["layers"]:
-            if fused is not None:
-                self._qkv_attn(v["xb"], ly["wqkv"], ly["bqkv"], fused[2], v["ctx"], fused[0], fused[1], self.heads, cu=cu, bins=bins)
+        M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
+        t = _TextPass(B, Lq, mask, fuse=self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0)
+        if packed:
+            t = t._replace(cu=b["cu"], live=b["cu"].data_ptr() + 4 * B)          # cu[B]: the live row count, written by the pack kernel
+            if t.fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
+                t = t._replace(bins=b["bins"], nbins=b["nbins"])
+                L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, b["cu"].data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
+                                                    b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
             else:
-                self._gemm(v["xb"], ly["wqkv"], ly["bqkv"], out_bf16=v["qkv"], which="qkv")
-                attn(v["qkv"], v["ctx"])
-            self._gemm(v["ctx"], ly["wo"], ly["bo"], out_f32=v["y"], residual=v["xf"], which="out")
-            self._ln(v["y"], H, ly["g1"], ly["b1"], v["x1b"], v["x1f"], M, H, self.eps)
-            self._gemm(v["x1b"], ly["w1"], ly["bi"], out_bf16=v["h"], act=ACT_GELU, which="ffn1")
-            self._gemm(v["h"], ly["w2"], ly["b2"], out_f32=v["y"], residual=v["x1f"], which="ffn2")
-            self._ln(v["y"], H, ly["g2"], ly["b2n"], v["xb"], v["xf"], M, H, self.eps)
+                L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, b["cu"].data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
+        tables = [w["embeddings." + n].data_ptr() for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight",
+                                                            "LayerNorm.weight", "LayerNorm.bias")]
+        outs = (b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr())      # (bf16 stream, folded: nothing reads the fp32 copy)
+        if packed:
+            L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), t.live, *tables, *outs, M, Lq, H, self.vocab, self.eps, s),
+                    "ufnd_bert_embed_live")
+        else:
+            L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
+        layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
+        (self._layers_folded if "st" in b else self._layers)(layers, b, t)
+        if pool and packed:
+            L.check(L.lib().ufnd_masked_meanpool_l2_live(b["xf"].data_ptr(), mask.data_ptr(), b["cu"].data_ptr(), b["feat"].data_ptr(), B, Lq, H, s),
+                    "ufnd_masked_meanpool_l2_live")
+        elif pool:
+            L.check(L.lib().ufnd_masked_meanpool_l2(b["xf"].data_ptr(), mask.data_ptr(), b["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
+        return b
 
-    def _layers_folded(self, p, b, M, attn, fused=None) -> None:
+    def _self_attention(self, t: _TextPass, b, A, W, bias, a_stats=None, colsum=None) -> None:
+        """A layer's Q/K/V projection of A (of LayerNorm(A), folded, with a_stats / colsum) and its attention into b["ctx"]: one fused
+        launch, or the GEMM into b["qkv"] followed by the attention over the padded batch or over the packed rows."""
+        if t.fuse:
+            self._qkv_attn(A, W, bias, t.mask, b["ctx"], t.B, t.Lq, self.heads, a_stats=a_stats, colsum=colsum, eps=self.eps,
+                           cu=t.cu, bins=t.bins, nbins=t.nbins)
+            return
+        if a_stats is None:
+            self._gemm(A, W, bias, out_bf16=b["qkv"], which="qkv", m_live=t.live)
+        else:
+            self._gemm_ln(A, W, bias, out_bf16=b["qkv"], a_stats=a_stats, colsum=colsum, eps=self.eps, which="qkv", m_live=t.live)
+        if t.cu is None:
+            self._attn(b["qkv"], t.mask, b["ctx"], t.B, t.Lq, self.heads)
+        else:
+            L.check(L.lib().ufnd_attention_bf16_varlen_masked(b["qkv"].data_ptr(), t.cu.data_ptr(), t.mask.data_ptr(), b["ctx"].data_ptr(), t.B, t.Lq,
+                                                              self.heads, L.stream_ptr(self.device)), "ufnd_attention_bf16_varlen_masked")
+
+    def _layers(self, layers, b, t: _TextPass) -> None:
+        """The encoder layers with one LayerNorm kernel per LayerNorm, over the work buffers' rows (pass t: all of them, or the live
+        ones).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
+        M, H, eps, live = t.B * t.Lq, self.hidden, self.eps, t.live
+        for ly in layers:
+            self._self_attention(t, b, b["xb"], ly["wqkv"], ly["bqkv"])
+            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["y"], residual=b["xf"], which="out", m_live=live)
+            self._ln(b["y"], H, ly["g1"], ly["b1"], b["x1b"], b["x1f"], M, H, eps, m_live=live)
+            self._gemm(b["x1b"], ly["w1"], ly["bi"], out_bf16=b["h"], act=ACT_GELU, which="ffn1", m_live=live)
+            self._gemm(b["h"], ly["w2"], ly["b2"], out_f32=b["y"], residual=b["x1f"], which="ffn2", m_live=live)
+            self._ln(b["y"], H, ly["g2"], ly["b2n"], b["xb"], b["xf"], M, H, eps, m_live=live)
+
+    def _layers_folded(self, layers, b, t: _TextPass) -> None:
         """The layers without a LayerNorm kernel between Linears (module docstring).  y1 / y2 are the
         PRE-LayerNorm sums of the attention and the feed-forward halves (fp32 + bf16 + row statistics)."""
-        H, eps = self.hidden, self.eps
-        y1, y2 = b["y"], b["y2"]
-        st = b["st"]
-        cu = fused[3] if fused is not None and len(fused) > 3 else None
-        bins = fused[4] if fused is not None and len(fused) > 4 else None
+        M, H, eps, live = t.B * t.Lq, self.hidden, self.eps, t.live
+        y1, y2, st = b["y"], b["y2"], b["st"]
+        rb = self.residual_dtype == "bf16"
         prev = None
-        for i, ly in enumerate(p["layers"]):
-            st1, st2 = st[2 * i][:M], st[2 * i + 1][:M]
-            stp = st[2 * i - 1][:M] if i > 0 else None           # the previous layer's feed-forward half
-            if fused is not None:
-                if prev is None:
-                    self._qkv_attn(b["xb"], ly["wqkv"], ly["bqkv"], fused[2], b["ctx"], fused[0], fused[1], self.heads, cu=cu, bins=bins)
-                else:
-                    self._qkv_attn(b["y2b"], ly["wqkvf"], ly["bqkvf"], fused[2], b["ctx"], fused[0], fused[1], self.heads,
-                                   a_stats=stp, colsum=ly["csqkv"], eps=eps, cu=cu, bins=bins)
-            elif prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
-                self._gemm(b["xb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
-            else:
-                self._gemm_ln(b["y2b"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stp, colsum=ly["csqkv"], eps=eps, which="qkv")
-            if fused is None:
-                attn(b["qkv"], b["ctx"])
-            rb = self.residual_dtype == "bf16"
-            last = i == len(p["layers"]) - 1
-            if prev is None:
+        for i, ly in enumerate(layers):
+            st1, st2 = st[2 * i], st[2 * i + 1]
+            last = i == len(layers) - 1
+            if prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
+                self._self_attention(t, b, b["xb"], ly["wqkv"], ly["bqkv"])
                 self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else b["xf"],
-                              residual_bf16=b["xb"] if rb else None, out_stats=st1, eps=eps, which="out")
+                              residual_bf16=b["xb"] if rb else None, out_stats=st1, eps=eps, which="out", m_live=live)
             else:
+                stp = st[2 * i - 1]           # the previous layer's feed-forward half
+                self._self_attention(t, b, b["y2b"], ly["wqkvf"], ly["bqkvf"], a_stats=stp, colsum=ly["csqkv"])
                 self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else y2,
                               residual_bf16=b["y2b"] if rb else None, r_stats=stp, r_gamma=prev["g2"], r_beta=prev["b2n"], out_stats=st1,
-                              eps=eps, which="out")
-            self._gemm_ln(b["y1b"], ly["w1f"], ly["bif"], out_bf16=b["h"], act=ACT_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
+                              eps=eps, which="out", m_live=live)
+            self._gemm_ln(b["y1b"], ly["w1f"], ly["bif"], out_bf16=b["h"], act=ACT_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1",
+                          m_live=live)
             self._gemm_ln(b["h"], ly["w2"], ly["b2"], out_f32=y2 if (last or not rb) else None, out_bf16=b["y2b"], residual=None if rb else y1,
                           residual_bf16=b["y1b"] if rb else None, r_stats=st1, r_gamma=ly["g1"], r_beta=ly["b1"], out_stats=st2, eps=eps,
-                          which="ffn2")      # (the last layer's fp32 sums feed the final, materialised LayerNorm)
+                          which="ffn2", m_live=live)      # (the last layer's fp32 sums feed the final, materialised LayerNorm)
             prev = ly
-        self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps)           # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
+        self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps, m_live=live)           # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
+
+    @torch.no_grad()
+    def last_hidden_state(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, n_layers: Optional[int] = None) -> torch.Tensor:
+        """BertModel(input_ids, attention_mask).last_hidden_state -> (B, L, H) fp32 (a view of an
+        internal buffer, valid until the next call with the same shape).  n_layers: stop after that many layers (the
+        hidden state BertModel reports as hidden_states[n_layers]; per-layer localisation in the parity tests)."""
+        b = self._pass(input_ids, attention_mask, packed=False, n_layers=n_layers, pool=False)
+        return b["xf"].view(*input_ids.shape, self.hidden)
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, unpad: bool = True, strict: bool = False) -> torch.Tensor:
@@ -456,63 +498,8 @@ class BertTextEncoder(_EncoderBase):
         with the padding fraction.  The row count stays on the device (ufnd_text_pack) and every launch keeps its padded geometry:
         no host sync, hipGraph-capturable, a replay follows the ids / mask its buffers hold.  unpad=False: the padded computation."""
         if strict:
-            # the offline feature builder (encode_fields; caches for the reference-style training mode): the more faithful fp32
-            # residual stream whatever the in-step default is -- the bf16 stream's speed only matters inside the train step (ADVICE r3)
-            rd, self.residual_dtype = self.residual_dtype, "fp32"
-            try:
-                if self.fold_ln:
-                    out = self.forward(input_ids, attention_mask, unpad=unpad)
-                    if not self.check_fold():
-                        return out
-                return self.forward(input_ids, attention_mask, unpad=unpad)
-            finally:
-                self.residual_dtype = rd
-        if unpad:
-            return self._forward_live(input_ids, attention_mask)
-        hid = self.last_hidden_state(input_ids, attention_mask)
-        B, Lq, H = hid.shape
-        feat = self._workbufs(B, Lq)["feat"]
-        L.check(L.lib().ufnd_masked_meanpool_l2(hid.data_ptr(), self._mask_i32.data_ptr(), feat.data_ptr(), B, Lq, H,
-                                                L.stream_ptr(self.device)), "ufnd_masked_meanpool_l2")
-        return feat
-
-    def _forward_live(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
-        self._require_hip()
-        dev = self.device
-        B, Lq = input_ids.shape
-        if Lq > self.max_position:
-            raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        mask = attention_mask.to(dev, torch.int32).contiguous()
-        p, b, w = self._pack(), self._workbufs(B, Lq), self._w
-        M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
-        cu, feat = b["cu"], b["feat"]
-        live = cu.data_ptr() + 4 * B          # cu[B]: the live row count, written by the pack kernel
-        fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0
-        if fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
-            L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
-                                                b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
-        else:
-            L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
-        L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, w["embeddings.word_embeddings.weight"].data_ptr(),
-                                             w["embeddings.position_embeddings.weight"].data_ptr(),
-                                             w["embeddings.token_type_embeddings.weight"].data_ptr(),
-                                             w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
-                                             b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr(),
-                                             M, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed_live")
-        fused = (B, Lq, mask, cu, (b["bins"], b["nbins"])) if fuse else None
-
-        def attn(qkv, ctx):
-            L.check(L.lib().ufnd_attention_bf16_varlen_masked(qkv.data_ptr(), cu.data_ptr(), mask.data_ptr(), ctx.data_ptr(), B, Lq,
-                                                              self.heads, s), "ufnd_attention_bf16_varlen_masked")
-        self._m_live = live
-        try:
-            self._layers(p, b, M, attn, fused)
-        finally:
-            self._m_live = None
-        L.check(L.lib().ufnd_masked_meanpool_l2_live(b["xf"].data_ptr(), mask.data_ptr(), cu.data_ptr(), feat.data_ptr(), B, Lq, H, s),
-                "ufnd_masked_meanpool_l2_live")
-        return feat
+            return self._strict(lambda: self.forward(input_ids, attention_mask, unpad=unpad))
+        return self._pass(input_ids, attention_mask, packed=unpad)["feat"]
 
     encode_batch = forward
 
@@ -547,24 +534,14 @@ class ClipVisualEncoder(_EncoderBase):
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, patch: int = 32,
                  image: int = 224, projection_dim: int = 512, eps: float = 1e-5, fold_ln: bool = True, residual_dtype: str = "bf16",
                  attention_dropout: float = 0.0):
-        super().__init__()
-        self.fold_ln = fold_ln
+        super().__init__(hidden, heads, fold_ln, residual_dtype)
         # train-mode dropout on the attention probabilities (HF CLIPVisionConfig name; CLIP has no hidden-state dropout): applied only by
         # encoder_train.VisualBackprop.forward_train and its backward
         self.attention_dropout = dropout_prob("attention_dropout", attention_dropout)
-        if residual_dtype not in ("fp32", "bf16"):
-            raise ValueError(f"residual_dtype={residual_dtype!r}: 'fp32' or 'bf16'")
-        self.residual_dtype = residual_dtype
-        if hidden != heads * 64:
-            raise ValueError("head_dim must be 64 (hidden == heads * 64)")
-        self.layers, self.hidden, self.heads, self.inter = layers, hidden, heads, intermediate
+        self.layers, self.inter = layers, intermediate
         self.patch, self.image, self.proj, self.eps = patch, image, projection_dim, eps
         self.n_patches = (image // patch) ** 2
-        w, V = self._w, "vision_model."
-        g = torch.Generator().manual_seed(0)
-
-        def init(shape, std=0.02):
-            return torch.randn(shape, generator=g) * std
+        w, V, init = self._w, "vision_model.", self._seeded_init()
         w[V + "embeddings.class_embedding"] = init((hidden,))
         w[V + "embeddings.patch_embedding.weight"] = init((hidden, 3, patch, patch))
         w[V + "embeddings.position_embedding.weight"] = init((self.n_patches + 1, hidden))
@@ -616,9 +593,8 @@ class ClipVisualEncoder(_EncoderBase):
                                "ctx": torch.empty(M, H, **bf), "m": torch.empty(M, self.inter, **bf),
                                "pooled": torch.empty(N, H, **bf), "e": torch.empty(N, self.proj, **f32),
                                "feat": torch.empty(B, self.proj, **f32)}
-            p1 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, H)
-            p2 = L.lib().ufnd_gemm_bf16_stat_parts(M, H, self.inter)
-            if self.fold_ln and p1 > 0 and p1 == p2 and p1 % 2 == 0:
+            p1 = self._fold_parts(M)
+            if p1:
                 # st0: the assembled embeddings' statistics; st[2i] / st[2i+1]: layer i's attention / feed-forward half
                 self._bufs[key].update({"st0": torch.zeros(M, 2, 2, **f32), "st": torch.zeros(2 * self.layers, M, p1, 2, **f32)})
                 self._guard_buf(dev)
@@ -640,19 +616,9 @@ class ClipVisualEncoder(_EncoderBase):
         N = frames.shape[0] * frames.shape[1]
         return b["xf"].view(N, self.n_patches + 1, self.hidden)
 
-    def _run(self, frames5: torch.Tensor, n_layers: Optional[int] = None):
-        self._require_hip()
-        dev = self.device
-        B, Fr = frames5.shape[:2]
-        if tuple(frames5.shape[2:]) != (3, self.image, self.image):
-            raise RuntimeError(f"frames: expected (B,F,3,{self.image},{self.image}), got {tuple(frames5.shape)}")
-        fr = L.f32c(frames5.to(dev)).view(B * Fr, 3, self.image, self.image)
-        p, b, w, V = self._pack(), self._workbufs(B, Fr), self._w, "vision_model."
-        if n_layers is not None:
-            p = dict(p, layers=p["layers"][:max(1, int(n_layers))])
-        N, H, T = B * Fr, self.hidden, self.n_patches + 1
-        M = N * T
-        s = L.stream_ptr(dev)
+    def _embed(self, fr, p, b, N) -> None:
+        """Patchify, patch GEMM, then class token + positions + pre-LayerNorm into the residual stream (folded: hb and its statistics st0)."""
+        w, V, s = self._w, "vision_model.", L.stream_ptr(self.device)
         L.check(L.lib().ufnd_vit_patchify(fr.data_ptr(), b["patches"].data_ptr(), N, self.image, self.patch, s), "ufnd_vit_patchify")
         self._gemm(b["patches"], p["wpatch"], None, out_f32=b["pe"])
         L.check(L.lib().ufnd_vit_assemble(b["pe"].data_ptr(), w[V + "embeddings.class_embedding"].data_ptr(),
@@ -660,37 +626,56 @@ class ClipVisualEncoder(_EncoderBase):
                                           w[V + "pre_layrnorm.weight"].data_ptr(), w[V + "pre_layrnorm.bias"].data_ptr(),
                                           None if ("st0" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr(),      # (bf16 stream: hb is the stream)
                                           L.ptr(b["hb"]) if "st0" in b else None, L.ptr(b.get("st0")),
-                                          N, self.n_patches, H, self.eps, s), "ufnd_vit_assemble")
-        if "st0" in b:
-            # pre-LN blocks without LayerNorm kernels: hb is the bf16 rounding of the residual stream xf,
-            # st* the row statistics its LayerNorms need (module docstring)
-            eps, stA, st = self.eps, b["st0"], b["st"]
-            for i, ly in enumerate(p["layers"]):
-                st1, st2 = st[2 * i], st[2 * i + 1]
-                self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
-                self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
-                rb = self.residual_dtype == "bf16"       # the stream is hb itself, updated in place (a tile reads exactly what it rewrites)
-                last = i == len(p["layers"]) - 1
-                self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else b["xf"], out_bf16=b["hb"], residual=None if rb else b["xf"],
-                              residual_bf16=b["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
-                self._gemm_ln(b["hb"], ly["w1f"], ly["bif"], out_bf16=b["m"], act=ACT_QUICK_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
-                self._gemm_ln(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"] if (last or not rb) else None, out_bf16=b["hb"],
-                              residual=None if rb else b["xf"], residual_bf16=b["hb"] if rb else None, out_stats=st2, eps=eps, which="ffn2")
-                stA = st2
-            self._ln(b["xf"], T * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], b["pooled"], None, N, H, self.eps)
-            self._gemm(b["pooled"], p["wproj"], None, out_f32=b["e"])
-            return b["e"], b
-        for ly in p["layers"]:
-            self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, self.eps)
+                                          N, self.n_patches, self.hidden, self.eps, s), "ufnd_vit_assemble")
+
+    def _blocks_folded(self, layers, b, N) -> None:
+        """Pre-LN blocks without LayerNorm kernels: hb is the bf16 rounding of the residual stream xf, st* the row statistics its
+        LayerNorms need (module docstring)."""
+        eps, stA, st, T = self.eps, b["st0"], b["st"], self.n_patches + 1
+        rb = self.residual_dtype == "bf16"       # the stream is hb itself, updated in place (a tile reads exactly what it rewrites)
+        for i, ly in enumerate(layers):
+            st1, st2 = st[2 * i], st[2 * i + 1]
+            last = i == len(layers) - 1
+            self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
+            self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
+            self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else b["xf"], out_bf16=b["hb"], residual=None if rb else b["xf"],
+                          residual_bf16=b["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
+            self._gemm_ln(b["hb"], ly["w1f"], ly["bif"], out_bf16=b["m"], act=ACT_QUICK_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
+            self._gemm_ln(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"] if (last or not rb) else None, out_bf16=b["hb"],
+                          residual=None if rb else b["xf"], residual_bf16=b["hb"] if rb else None, out_stats=st2, eps=eps, which="ffn2")
+            stA = st2
+
+    def _blocks(self, layers, b, N) -> None:
+        """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf."""
+        H, T, eps = self.hidden, self.n_patches + 1, self.eps
+        M = N * T
+        for ly in layers:
+            self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps)
             self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
             self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
             self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["xf"], residual=b["xf"], which="out")
-            self._ln(b["xf"], H, ly["g2"], ly["b2n"], b["hb"], None, M, H, self.eps)
+            self._ln(b["xf"], H, ly["g2"], ly["b2n"], b["hb"], None, M, H, eps)
             self._gemm(b["hb"], ly["w1"], ly["bi"], out_bf16=b["m"], act=ACT_QUICK_GELU, which="ffn1")
             self._gemm(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"], residual=b["xf"], which="ffn2")
-        # post-LN on the CLS rows (row stride T*H), bias-free projection
-        self._ln(b["xf"], T * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], b["pooled"], None, N, H, self.eps)
+
+    def _pooled_projection(self, p, b, N) -> None:
+        """post-LN on the CLS rows (row stride T*H), bias-free projection into b["e"]."""
+        w, V, H = self._w, "vision_model.", self.hidden
+        self._ln(b["xf"], (self.n_patches + 1) * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], b["pooled"], None, N, H, self.eps)
         self._gemm(b["pooled"], p["wproj"], None, out_f32=b["e"])
+
+    def _run(self, frames5: torch.Tensor, n_layers: Optional[int] = None):
+        """One pass over (B, F) frames: (the (B F, projection_dim) embeddings, the work buffers)."""
+        self._require_hip()
+        B, Fr = frames5.shape[:2]
+        if tuple(frames5.shape[2:]) != (3, self.image, self.image):
+            raise RuntimeError(f"frames: expected (B,F,3,{self.image},{self.image}), got {tuple(frames5.shape)}")
+        fr = L.f32c(frames5.to(self.device)).view(B * Fr, 3, self.image, self.image)
+        p, b = self._pack(), self._workbufs(B, Fr)
+        layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
+        self._embed(fr, p, b, B * Fr)
+        (self._blocks_folded if "st0" in b else self._blocks)(layers, b, B * Fr)
+        self._pooled_projection(p, b, B * Fr)
         return b["e"], b
 
     @torch.no_grad()
@@ -698,16 +683,8 @@ class ClipVisualEncoder(_EncoderBase):
         """frames (B,F,3,224,224) or (B,3,224,224) -> (B,512) features.  strict: as BertTextEncoder.forward."""
         if frames.dim() == 4:
             frames = frames[:, None]
-        if strict:      # (fp32 residual stream for offline feature building: see BertTextEncoder.forward)
-            rd, self.residual_dtype = self.residual_dtype, "fp32"
-            try:
-                if self.fold_ln:
-                    out = self.forward(frames)
-                    if not self.check_fold():
-                        return out
-                return self.forward(frames)
-            finally:
-                self.residual_dtype = rd
+        if strict:
+            return self._strict(lambda: self.forward(frames))
         B, Fr = frames.shape[:2]
         e, b = self._run(frames)
         L.check(L.lib().ufnd_l2norm_frames(e.data_ptr(), b["feat"].data_ptr(), B, Fr, self.proj, L.stream_ptr(self.device)),
