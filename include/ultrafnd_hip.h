@@ -605,6 +605,55 @@ int ufnd_fusion_feature_grads(const ufnd_dims* d, const ufnd_fusion_params* p, f
 int ufnd_fusion_gnn_input_grad(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* d_gnn,
                                const ufnd_step_state* state, void* stream);
 
+/* The gradients at ALL five fusion inputs out of the workspace a fusion backward has just filled, any subset non-NULL
+ * (contiguous rows, 16-byte aligned; d_gnn must be NULL when dims.gnn_dim == 0), as ONE grouped launch.  The two entries above
+ * are this call with their own subset: the same kernel, the same bits. */
+int ufnd_fusion_input_grads(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* d_text, float* d_audio,
+                            float* d_visual, float* d_temporal, float* d_gnn, const ufnd_step_state* state, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Explanations: gradients with respect to the classifier's INPUTS         src/models/fusion/deep_truth_classifier.py:189-272
+ * (feature_importance: gradient x input at the logits; explain_shap's smooth-grad branch: mean |gradient| of probs[:, 1] over
+ * a 16-point random walk).  None of these entries takes a gradient table: parameters and the gradient arena are untouched.
+ *
+ * ufnd_classifier_input_grad: ufnd_classifier_forward (same arguments, same logits / probs), then the gradient of
+ *     UFND_TARGET_LOGIT  sum_b logits[b, class_idx]
+ *     UFND_TARGET_PROB   sum_b probs[b, class_idx]     (through softmax(logits / clamp(temperature, 0.5, 5)))
+ *   with respect to the WHOLE input row [fused | aux]: d_x (B, hidden + aux_dim), row stride ld_dx >= hidden + aux_dim.
+ *   The backward is the training backward's dX chain (node_bwd, pre.3, pre.0 over all hidden + aux_dim weight columns)
+ *   without a single parameter-gradient launch; train != 0 regenerates the forward's dropout masks from `state`.
+ *   If `fused` points at the workspace's input panel (ufnd_clf_input_panel) the panel is used as it stands -- fused AND
+ *   aux columns, `aux` is not read -- which is how the walk below feeds it.
+ * ---------------------------------------------------------------------------------- */
+#define UFND_TARGET_LOGIT 0
+#define UFND_TARGET_PROB 1
+int ufnd_classifier_input_grad(const ufnd_dims* d, const ufnd_clf_params* p, const float* fused, int ld_fused, const float* aux,
+                               int B, int train, int target, int class_idx, float* workspace, float* d_x, int ld_dx,
+                               float* logits, float* probs, const ufnd_step_state* state, void* stream);
+
+/* The smooth-grad evaluation points (deep_truth_classifier.py:258-270): a random WALK X_i = X_{i-1} + noise_{i-1} * sigma
+ * (that order of operations, no fused multiply-add), X_0 = x0; the N-th draw is never used.  Rows of steps
+ * [step0, step0 + steps) are written step-major (row (i - step0) * B + b) straight into the input panel
+ * [fused | aux | zero pad] (row stride hidden + 4) of `workspace`, a classifier workspace of steps * B rows, so that
+ * ufnd_classifier_input_grad on that panel skips its input copy.
+ *   x0 (B, W) stride ld_x0; sigma (W rounded up to 4); noise (N, B, W) with row stride ld_noise, step stride B * ld_noise;
+ *   W = hidden + aux_dim; ld_x0 and ld_noise multiples of 4, all pointers 16-byte aligned (16-byte loads and stores). */
+int ufnd_smoothgrad_points(const ufnd_dims* d, const float* x0, int ld_x0, const float* sigma, const float* noise, int ld_noise,
+                           int B, int N, int step0, int steps, float* workspace, void* stream);
+
+/* Attribution reductions over a gradient panel G (row stride ldg), W columns.  No atomics: a rerun gives the same bits.
+ *   UFND_ATTR_SMOOTHGRAD    out[b, j] = (acc + sum_{i < steps} |G[i * B + b, j]|) / divisor, added in step order;
+ *                           acc = 0, or out's previous content when `accumulate` != 0 (a walk evaluated in several chunks of
+ *                           whole steps); divisor <= 0: no division yet (every chunk but the last).  X, agg, partials unused.
+ *   UFND_ATTR_GRAD_X_INPUT  out[b, j] = |G[b, j] * X[b, j]| (steps == 1) and, when agg != NULL, agg[j] = mean_b out[b, j]
+ *                           as a fixed-order column reduction: slices of 32 rows -> partials -> one finishing pass in
+ *                           ascending slice order.  partials: ((B + 31) / 32) * W floats.
+ * Rows of 16-byte aligned panels whose strides are multiples of 4 move as 16-byte words; any other layout by element. */
+#define UFND_ATTR_SMOOTHGRAD 0
+#define UFND_ATTR_GRAD_X_INPUT 1
+int ufnd_attribution_reduce(int mode, const float* G, int ldg, const float* X, int ldx, int B, int W, int steps, int accumulate,
+                            int divisor, float* out, int ldo, float* agg, float* partials, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Compute-unit partitions.  The reference runs its step in program order on one queue
  * (src/training/forensic_trainer.py:285-298); here the text encoder, the visual encoder and the

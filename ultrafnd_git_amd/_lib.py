@@ -104,6 +104,10 @@ class GemmLn(C.Structure):
 
 STEP_STATE_BYTES = C.sizeof(StepState)
 BWD_ALL, BWD_FUSE_MLP, BWD_REST = 0, 1, 2
+TARGET_LOGIT, TARGET_PROB = 0, 1           # ufnd_classifier_input_grad
+ATTR_SMOOTHGRAD, ATTR_GRAD_X_INPUT = 0, 1   # ufnd_attribution_reduce
+ATTR_SLICE_ROWS = 32                        # its partials: ceil(B / 32) * W floats
+MAX_ROWS = 65536                            # check_dims: rows of one call
 BWD_NO_LINEAR_GRADS = 16          # OR-ed into the phase / flags: the factor form of the gradient exchange (dp.FactorExchange)
 ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
@@ -248,6 +252,14 @@ def _declare_encoders(lib: C.CDLL) -> None:
     lib.ufnd_fusion_gnn_input_grad.restype = I
     lib.ufnd_fusion_feature_grads.argtypes = [C.POINTER(Dims), C.POINTER(FusionParams), P, I, P, P, P, P]
     lib.ufnd_fusion_feature_grads.restype = I
+    lib.ufnd_fusion_input_grads.argtypes = [C.POINTER(Dims), C.POINTER(FusionParams), P, I, P, P, P, P, P, P, P]
+    lib.ufnd_fusion_input_grads.restype = I
+    lib.ufnd_classifier_input_grad.argtypes = [C.POINTER(Dims), C.POINTER(ClfParams), P, I, P, I, I, I, I, P, P, I, P, P, P, P]
+    lib.ufnd_classifier_input_grad.restype = I
+    lib.ufnd_smoothgrad_points.argtypes = [C.POINTER(Dims), P, I, P, P, I, I, I, I, I, P, P]
+    lib.ufnd_smoothgrad_points.restype = I
+    lib.ufnd_attribution_reduce.argtypes = [I, P, I, P, I, I, I, I, I, I, P, I, P, P, P]
+    lib.ufnd_attribution_reduce.restype = I
     lib.ufnd_gather_rows.argtypes = [P, I, C.POINTER(GatherItem), I, P]
     lib.ufnd_gather_rows.restype = I
     lib.ufnd_tcn_weight_ld.argtypes = [I, I]

@@ -172,6 +172,8 @@ __device__ __forceinline__ void clf_prep_block(const ClfPrep& a, int B, int H, i
   for (int c = threadIdx.x; c < H; c += 256) a.alpha[(size_t)tk * H + c] = __expf(gp[c] - mx) / sm;
 }
 __global__ __launch_bounds__(256) void clf_prep_kernel(ClfPrep a, int B, int H) { clf_prep_block(a, B, H, blockIdx.x); }
+// the gate blocks alone (grid = trees * depth): alpha for a caller whose input panel is already complete
+__global__ __launch_bounds__(256) void clf_alpha_kernel(ClfPrep a, int B, int H) { clf_prep_block(a, B, H, B + blockIdx.x); }
 
 // ---------------------------------------------------------------- co-attention + pairwise -> CAT
 // cross_modal_transformer.py:153-164 (evidence scalars), :48 (evidence gates), :44-54 and :172-178 (co-attention combine, pairwise features).
@@ -979,6 +981,132 @@ __global__ __launch_bounds__(256) void softmax_ce_ws_kernel(const float* logits,
   if (threadIdx.x == 0) st->loss = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / W;
 }
 
+// ---------------------------------------------------------------- explanations
+// deep_truth_classifier.py:189-272 (feature_importance, the smooth-grad branch of explain_shap)
+// The seed of the input-gradient backward, d target / d logits (two floats per row): onehot(c) for sum_b logits[b, c], or
+// p_c (delta_cj - p_j) / T for sum_b probs[b, c] -- the probabilities by node_head's own softmax expressions.
+__global__ __launch_bounds__(256) void attr_seed_kernel(const float* logits, const float* temperature, int B, int target, int c, float* dlog) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= B) return;
+  float d0 = c == 0 ? 1.0f : 0.0f, d1 = c == 1 ? 1.0f : 0.0f;
+  if (target == UFND_TARGET_PROB) {
+    const float T = fminf(fmaxf(temperature[0], 0.5f), 5.0f);
+    const float a0 = logits[r * 2] / T, a1 = logits[r * 2 + 1] / T, mx = fmaxf(a0, a1);
+    const float e0 = __expf(a0 - mx), e1 = __expf(a1 - mx);
+    const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1), pc = c ? p1 : p0;
+    d0 = pc * (d0 - p0) / T;
+    d1 = pc * (d1 - p1) / T;
+  }
+  dlog[r * 2] = d0;
+  dlog[r * 2 + 1] = d1;
+}
+
+__device__ __forceinline__ f32x4 keep_cols(f32x4 v, int col, int W) {      // zero beyond the W live columns (the panel's pad)
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = col + q < W ? v[q] : 0.0f;
+  return v;
+}
+// The smooth-grad walk, X_{i+1} = X_i + n_i * sigma (one product, one sum, in that order: deep_truth_classifier.py:264,270), written
+// straight into the classifier's input panel.  One thread owns one (row, 4 columns) strip and walks the steps in order.
+__global__ __launch_bounds__(256) void smoothgrad_points_kernel(const float* x0, int ld_x0, const float* sigma, const float* noise, int ld_noise,
+                                                                int B, int W, int step0, int steps, float* xin, int ldx) {
+#pragma clang fp contract(off)
+  const int strips = ldx >> 2;
+  const size_t t = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (t >= (size_t)B * strips) return;
+  const int b = (int)(t / strips), col = (int)(t % strips) * 4;
+  const bool live = col < W;
+  f32x4 x = {0.f, 0.f, 0.f, 0.f}, s = x;
+  if (live) {
+    x = keep_cols(ld4(x0 + (size_t)b * ld_x0 + col), col, W);
+    s = ld4(sigma + col);
+  }
+  const int last = step0 + steps;
+  for (int i = 0; i < last; ++i) {
+    if (i >= step0) st4(xin + ((size_t)(i - step0) * B + b) * ldx + col, x);
+    if (live && i + 1 < last) {
+      const f32x4 n = ld4(noise + ((size_t)i * B + b) * ld_noise + col);
+      x = keep_cols(x + n * s, col, W);
+    }
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void ld_strip(const float* p, float (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    const f32x4 t = ld4(p);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void st_strip(float* p, const float (&v)[VEC]) {
+  if constexpr (VEC == 4) st4(p, f32x4{v[0], v[1], v[2], v[3]});
+  else p[0] = v[0];
+}
+// smooth-grad: out[b, j] = (acc + sum_i |G[i B + b, j]|) / divisor, the steps added in order.  One thread per (row, VEC columns).
+template <int VEC>
+__global__ __launch_bounds__(256) void attr_smooth_kernel(const float* G, int ldg, int B, int W, int steps, int accumulate, int divisor,
+                                                          float* out, int ldo) {
+  const int per = (W + VEC - 1) / VEC;
+  const size_t t = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (t >= (size_t)B * per) return;
+  const int b = (int)(t / per), col = (int)(t % per) * VEC;
+  float acc[VEC];
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
+  if (accumulate) ld_strip<VEC>(out + (size_t)b * ldo + col, acc);
+  for (int i = 0; i < steps; ++i) {
+    float g[VEC];
+    ld_strip<VEC>(G + ((size_t)i * B + b) * ldg + col, g);
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) acc[q] += fabsf(g[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) {
+    if (divisor > 0) acc[q] /= (float)divisor;
+    if (col + q >= W) acc[q] = 0.0f;
+  }
+  st_strip<VEC>(out + (size_t)b * ldo + col, acc);
+}
+// grad x input: out = |G * X|; block (x, s) also sums its slice of ATTR_SLICE_ROWS rows into part[s][W] (when asked), which
+// attr_mean_finish_kernel adds in ascending slice order -- the row-slice form of node_param_kernel / node_param_finish_kernel.
+constexpr int ATTR_SLICE_ROWS = 32;
+template <int VEC>
+__global__ __launch_bounds__(64) void attr_gxi_kernel(const float* G, int ldg, const float* X, int ldx, int B, int W, float* out, int ldo,
+                                                      float* part) {
+  const int per = (W + VEC - 1) / VEC, strip = blockIdx.x * 64 + threadIdx.x;
+  if (strip >= per) return;
+  const int col = strip * VEC, r0 = blockIdx.y * ATTR_SLICE_ROWS, r1 = r0 + ATTR_SLICE_ROWS < B ? r0 + ATTR_SLICE_ROWS : B;
+  float sum[VEC];
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) sum[q] = 0.0f;
+  for (int r = r0; r < r1; ++r) {
+    float g[VEC], x[VEC], v[VEC];
+    ld_strip<VEC>(G + (size_t)r * ldg + col, g);
+    ld_strip<VEC>(X + (size_t)r * ldx + col, x);
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) {
+      v[q] = col + q < W ? fabsf(g[q] * x[q]) : 0.0f;
+      sum[q] += v[q];
+    }
+    st_strip<VEC>(out + (size_t)r * ldo + col, v);
+  }
+  if (part) {
+#pragma unroll
+    for (int q = 0; q < VEC; ++q)
+      if (col + q < W) part[(size_t)blockIdx.y * W + col + q] = sum[q];
+  }
+}
+__global__ __launch_bounds__(256) void attr_mean_finish_kernel(const float* part, int S, int W, int B, float* agg) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= W) return;
+  float s = 0.0f;
+  for (int k = 0; k < S; ++k) s += part[(size_t)k * W + j];      // ascending slice order
+  agg[j] = s / (float)B;
+}
+
 int check_dims(const ufnd_dims* d, int B) {
   UFND_REQUIRE(d, "dims is null");
   UFND_REQUIRE(d->hidden == 256 || d->hidden == 512 || d->hidden == 1024, "hidden=%d: supported 256/512/1024", d->hidden);
@@ -1342,35 +1470,47 @@ extern "C" int ufnd_fusion_backward(const ufnd_dims* d, const ufnd_fusion_params
                                     state, stream_, side_stream_, join, UFND_BWD_ALL);
 }
 
-// d loss / d gnn_feat = dg . gnn_proj.weight, from the workspace a fusion backward has just filled (the gradient at the
-// gnn_proj output lives there).  The main trainer's gnn_feat is data (a detached table, forensic_trainer.py:209-211); the
-// integrated variant's comes from a GNN inside the graph (forensic_trainer_integrated.py:203-224) and needs this.
+// The gradients at the fusion's INPUTS, d loss / d x = (gradient at the projection's output) . proj.weight, from the workspace a
+// fusion backward has just filled: the one place that knows where those gradients live (dtavu = [text audio visual temporal], dg).
+// Any subset, one grouped launch.  The main trainer's inputs are cached data (forensic_trainer.py:60-83,209-211) and get none;
+// the integrated variant's gnn_feat comes from a GNN inside the graph (forensic_trainer_integrated.py:203-224), trainable encoders
+// produce text / visual (TrainConfig.train_encoders), and an explanation wants all of them.
+namespace {
+int fusion_input_grads_impl(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* const (&dx)[5],
+                            const ufnd_step_state* state, void* stream_, const char* who) {
+  TRY(check_dims(d, B));
+  UFND_REQUIRE(p && workspace && (dx[0] || dx[1] || dx[2] || dx[3] || dx[4]), "%s: null argument", who);
+  UFND_REQUIRE(!dx[4] || d->gnn_dim > 0, "%s: d_gnn with dims.gnn_dim == 0 (use_gnn: false has no gnn_proj)", who);
+  const int H = d->hidden;
+  const FusionWs w = carve_fusion(*d, B, workspace);
+  const FusionFactors f = fusion_factors(w, B, H, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const float* pw[5] = {p->text_w, p->audio_w, p->visual_w, p->temporal_w, p->gnn_w};
+  const int ks[5] = {d->text_dim, d->audio_dim, d->visual_dim, d->temporal_dim, d->gnn_dim};
+  NnProb n[5];
+  int k = 0;
+  for (int i = 0; i < 5; ++i) {
+    if (!dx[i]) continue;
+    UFND_REQUIRE(ufnd_aligned(dx[i], 16), "%s: output %d is not 16-byte aligned", who, i);
+    n[k++] = NnProb{f.dproj[i], pw[i], dx[i], nullptr, nullptr, B, H, ks[i], H, ks[i], ks[i], 0, 0, 0.0f, 0, 0, 1};
+  }
+  return launch_nn(n, k, state, (hipStream_t)stream_);
+}
+}  // namespace
+
+extern "C" int ufnd_fusion_input_grads(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* d_text, float* d_audio,
+                                       float* d_visual, float* d_temporal, float* d_gnn, const ufnd_step_state* state, void* stream_) {
+  float* const dx[5] = {d_text, d_audio, d_visual, d_temporal, d_gnn};
+  return fusion_input_grads_impl(d, p, workspace, B, dx, state, stream_, "fusion_input_grads");
+}
 extern "C" int ufnd_fusion_gnn_input_grad(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* d_gnn,
                                           const ufnd_step_state* state, void* stream_) {
-  TRY(check_dims(d, B));
-  UFND_REQUIRE(p && workspace && d_gnn && ufnd_aligned(d_gnn, 16), "fusion_gnn_input_grad: null argument");
-  FusionWs w = carve_fusion(*d, B, workspace);
-  const int H = d->hidden;
-  NnProb n{w.dg, p->gnn_w, d_gnn, nullptr, nullptr, B, H, d->gnn_dim, H, d->gnn_dim, d->gnn_dim, 0, 0, 0.0f, 0, 0, 1};
-  return launch_nn(&n, 1, state, (hipStream_t)stream_);
+  float* const dx[5] = {nullptr, nullptr, nullptr, nullptr, d_gnn};
+  return fusion_input_grads_impl(d, p, workspace, B, dx, state, stream_, "fusion_gnn_input_grad");
 }
-
-// d loss / d text_features = dt . text_proj.weight and d loss / d visual_features = dv . visual_proj.weight, from the workspace a
-// fusion backward has just filled.  In the reference trainer these inputs are cached data (forensic_trainer.py:60-83); with
-// trainable encoders (TrainConfig.train_encoders) they are the encoders' outputs and this is where their backward starts.
 extern "C" int ufnd_fusion_feature_grads(const ufnd_dims* d, const ufnd_fusion_params* p, float* workspace, int B, float* d_text,
                                          float* d_visual, const ufnd_step_state* state, void* stream_) {
-  TRY(check_dims(d, B));
-  UFND_REQUIRE(p && workspace && (d_text || d_visual), "fusion_feature_grads: null argument");
-  UFND_REQUIRE((!d_text || ufnd_aligned(d_text, 16)) && (!d_visual || ufnd_aligned(d_visual, 16)), "fusion_feature_grads: alignment");
-  FusionWs w = carve_fusion(*d, B, workspace);
-  const int H = d->hidden;
-  NnProb n[2];
-  int k = 0;
-  if (d_text) n[k++] = NnProb{w.dtavu, p->text_w, d_text, nullptr, nullptr, B, H, d->text_dim, H, d->text_dim, d->text_dim, 0, 0, 0.0f, 0, 0, 1};
-  if (d_visual)
-    n[k++] = NnProb{w.dtavu + (size_t)2 * B * H, p->visual_w, d_visual, nullptr, nullptr, B, H, d->visual_dim, H, d->visual_dim, d->visual_dim, 0, 0, 0.0f, 0, 0, 1};
-  return launch_nn(n, k, state, (hipStream_t)stream_);
+  float* const dx[5] = {d_text, nullptr, d_visual, nullptr, nullptr};
+  return fusion_input_grads_impl(d, p, workspace, B, dx, state, stream_, "fusion_feature_grads");
 }
 
 namespace {
@@ -1378,13 +1518,14 @@ struct FusedClfFwd {
   bool prep_done;             // the input panel's aux columns and alpha were written by the co-attention launch
   const int64_t* labels;      // non-null: node_head also writes this row's CE term (workspace) and d_logits
   float* d_logits;
+  bool alpha_only;            // the input panel is complete as it stands, aux columns included (`aux` is not read): only alpha is prepared
 };
 int classifier_forward_impl(const ufnd_dims* d, const ufnd_clf_params* p, const float* fused, int ld_fused,
                             const float* aux, int B, int train, float* workspace, float* logits,
                             float* probs, const ufnd_step_state* state, void* stream_, const FusedClfFwd* fo) {
   TRY(check_dims(d, B));
   UFND_REQUIRE(p && fused && workspace && logits && probs && state, "classifier_forward: null argument");
-  UFND_REQUIRE((d->aux_dim == 0) == (aux == nullptr), "classifier_forward: aux must be given iff aux_dim > 0 (pre.0 is %d wide)",
+  UFND_REQUIRE((fo && fo->alpha_only) || (d->aux_dim == 0) == (aux == nullptr), "classifier_forward: aux must be given iff aux_dim > 0 (pre.0 is %d wide)",
                d->hidden + d->aux_dim);
   UFND_REQUIRE(ufnd_aligned(workspace, 256), "classifier_forward: workspace alignment");
   hipStream_t stream = (hipStream_t)stream_;
@@ -1393,7 +1534,11 @@ int classifier_forward_impl(const ufnd_dims* d, const ufnd_clf_params* p, const 
   const float drop = train ? d->clf_dropout : 0.0f;
   const dim3 rows(ufnd_cdiv(B, 4)), blk(256);
 
-  if (!(fo && fo->prep_done)) {
+  if (fo && fo->alpha_only) {
+    const ClfPrep prep{nullptr, nullptr, (const float*)p->gates, w.xin, w.alpha, 0, 0, w.ldx, 0, d->trees * d->depth};
+    hipLaunchKernelGGL(clf_alpha_kernel, dim3(prep.blocks), blk, 0, stream, prep, B, H);
+    UFND_CHECK_LAUNCH();
+  } else if (!(fo && fo->prep_done)) {
     const ClfPrep prep{fused, aux, (const float*)p->gates, w.xin, w.alpha, ld_fused, d->aux_dim, w.ldx, fused != w.xin ? 1 : 0, B + d->trees * d->depth};
     hipLaunchKernelGGL(clf_prep_kernel, dim3(prep.blocks), blk, 0, stream, prep, B, H);
     UFND_CHECK_LAUNCH();
@@ -1499,6 +1644,99 @@ extern "C" int ufnd_classifier_backward(const ufnd_dims* d, const ufnd_clf_param
                                         int ld_dfused, const ufnd_step_state* state, void* stream_, void* side_stream_,
                                         int join) {
   return ufnd_classifier_backward_ex(d, p, g, B, train, workspace, d_logits, d_fused, ld_dfused, state, stream_, side_stream_, join, 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Explanations (deep_truth_classifier.py:189-272): the forward, a two-float seed per row, then the training backward's dX chain
+// -- node_bwd, pre.3, pre.0 over ALL hidden + aux_dim weight columns -- and nothing else: no node_param, no dW problem, no
+// gradient table.  8 launches: input preparation (alpha only, on a panel the walk has written in place), pre.0, pre.3, node_head, the
+// seed, node_bwd, pre.3's dX, pre.0's dX.
+// ------------------------------------------------------------------------------------------------
+extern "C" int ufnd_classifier_input_grad(const ufnd_dims* d, const ufnd_clf_params* p, const float* fused, int ld_fused, const float* aux,
+                                          int B, int train, int target, int class_idx, float* workspace, float* d_x, int ld_dx,
+                                          float* logits, float* probs, const ufnd_step_state* state, void* stream_) {
+  TRY(check_dims(d, B));
+  UFND_REQUIRE(p && fused && workspace && d_x && logits && probs && state, "classifier_input_grad: null argument");
+  UFND_REQUIRE(target == UFND_TARGET_LOGIT || target == UFND_TARGET_PROB, "classifier_input_grad: target=%d", target);
+  UFND_REQUIRE(class_idx == 0 || class_idx == 1, "classifier_input_grad: class_idx=%d (classes = 2)", class_idx);
+  UFND_REQUIRE(ld_dx >= d->hidden + d->aux_dim, "classifier_input_grad: ld_dx=%d < hidden + aux_dim = %d", ld_dx, d->hidden + d->aux_dim);
+  UFND_REQUIRE(ufnd_aligned(workspace, 256), "classifier_input_grad: workspace alignment");
+  hipStream_t stream = (hipStream_t)stream_;
+  const int H = d->hidden;
+  const ClfWs w = carve_clf(*d, B, workspace);
+  const float drop = train ? d->clf_dropout : 0.0f, ndrop = train ? d->node_dropout : 0.0f;
+  if (fused == w.xin) {
+    // the panel stands as written (fused and aux columns: ufnd_smoothgrad_points): only alpha = softmax(gates) is prepared
+    UFND_REQUIRE(ld_fused == w.ldx, "classifier_input_grad: the input panel's row stride is %d", w.ldx);
+    const FusedClfFwd fo{true, nullptr, nullptr, true};
+    TRY(classifier_forward_impl(d, p, w.xin, w.ldx, nullptr, B, train, workspace, logits, probs, state, stream_, &fo));
+  } else {
+    TRY(classifier_forward_impl(d, p, fused, ld_fused, aux, B, train, workspace, logits, probs, state, stream_, nullptr));
+  }
+  hipLaunchKernelGGL(attr_seed_kernel, dim3(ufnd_cdiv(B, 256)), dim3(256), 0, stream, (const float*)logits, (const float*)p->temperature, B,
+                     target, class_idx, w.dl);
+  UFND_CHECK_LAUNCH();
+  NI_DISPATCH(H, node_bwd_kernel, dim3(B), dim3(256), stream, (const float*)w.dl, (const float*)w.fs, (const float*)w.alpha,
+              (const float*)p->leaf, (const float*)p->tau, (const float*)p->bypass_w, (const float*)w.z4, B, H, d->trees,
+              d->depth, ndrop, drop, state, w.df, w.dz4, (const float*)nullptr, (ufnd_step_state*)nullptr);
+  UFND_CHECK_LAUNCH();
+  {  // pre.3: dX -> dz3 (epilogue applies gelu'(z3) * mask)
+    NnProb n{w.dz4, p->pre3_w, w.dz3, w.z3, nullptr, B, H, H, H, H, H, H, 0, drop, LAYER_PRE0, H, 1};
+    TRY(launch_nn(&n, 1, state, stream));
+  }
+  {  // pre.0: dX over the whole input row, aux columns included (the training backward stops at the fused columns)
+    NnProb n{w.dz3, p->pre0_w, d_x, nullptr, nullptr, B, H, H + d->aux_dim, H, H + d->aux_dim, ld_dx, 0, 0, 0.0f, 0, 0, 1};
+    TRY(launch_nn(&n, 1, state, stream));
+  }
+  return UFND_OK;
+}
+
+extern "C" int ufnd_smoothgrad_points(const ufnd_dims* d, const float* x0, int ld_x0, const float* sigma, const float* noise, int ld_noise,
+                                      int B, int N, int step0, int steps, float* workspace, void* stream_) {
+  UFND_REQUIRE(N >= 1 && step0 >= 0 && steps >= 1 && step0 + steps <= N, "smoothgrad_points: steps [%d, %d) of %d", step0, step0 + steps, N);
+  UFND_REQUIRE(B >= 1 && (long long)B * steps <= 65536, "smoothgrad_points: %d rows x %d steps exceed one call's 65536 rows", B, steps);
+  TRY(check_dims(d, B * steps));
+  UFND_REQUIRE(x0 && sigma && workspace && (noise || N == 1), "smoothgrad_points: null argument");
+  const int W = d->hidden + d->aux_dim, W4 = (W + 3) & ~3;
+  UFND_REQUIRE(ld_x0 % 4 == 0 && ld_x0 >= W4 && (N == 1 || (ld_noise % 4 == 0 && ld_noise >= W4)), "smoothgrad_points: ld_x0=%d ld_noise=%d (multiples of 4, >= %d)",
+               ld_x0, ld_noise, W4);
+  UFND_REQUIRE(ufnd_aligned(x0, 16) && ufnd_aligned(sigma, 16) && ufnd_aligned(noise, 16) && ufnd_aligned(workspace, 256), "smoothgrad_points: alignment");
+  const ClfWs w = carve_clf(*d, B * steps, workspace);
+  const long long threads = (long long)B * (w.ldx / 4);
+  hipLaunchKernelGGL(smoothgrad_points_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x0, ld_x0, sigma, noise,
+                     ld_noise, B, W, step0, steps, w.xin, w.ldx);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_attribution_reduce(int mode, const float* G, int ldg, const float* X, int ldx, int B, int W, int steps, int accumulate,
+                                       int divisor, float* out, int ldo, float* agg, float* partials, void* stream_) {
+  UFND_REQUIRE(mode == UFND_ATTR_SMOOTHGRAD || mode == UFND_ATTR_GRAD_X_INPUT, "attribution_reduce: mode=%d", mode);
+  UFND_REQUIRE(G && out && B >= 1 && W >= 1 && steps >= 1 && (long long)B * steps <= 65536, "attribution_reduce: B=%d W=%d steps=%d", B, W, steps);
+  UFND_REQUIRE(ldg >= W && ldo >= W, "attribution_reduce: ldg=%d ldo=%d < W=%d", ldg, ldo, W);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int W4 = (W + 3) & ~3;
+  bool vec4 = ldg % 4 == 0 && ldo % 4 == 0 && ldg >= W4 && ldo >= W4 && ufnd_aligned(G, 16) && ufnd_aligned(out, 16);
+  if (mode == UFND_ATTR_SMOOTHGRAD) {
+    const long long threads = (long long)B * (vec4 ? W4 / 4 : W);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (vec4) hipLaunchKernelGGL((attr_smooth_kernel<4>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
+    else hipLaunchKernelGGL((attr_smooth_kernel<1>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
+    UFND_CHECK_LAUNCH();
+    return UFND_OK;
+  }
+  UFND_REQUIRE(X && ldx >= W && steps == 1 && (!agg || partials), "attribution_reduce: grad x input needs X (ldx >= W), steps == 1, and partials with agg");
+  vec4 = vec4 && ldx % 4 == 0 && ldx >= W4 && ufnd_aligned(X, 16);
+  const int S = ufnd_cdiv(B, ATTR_SLICE_ROWS);
+  float* part = agg ? partials : nullptr;
+  if (vec4) hipLaunchKernelGGL((attr_gxi_kernel<4>), dim3(ufnd_cdiv(W4 / 4, 64), S), dim3(64), 0, stream, G, ldg, X, ldx, B, W, out, ldo, part);
+  else hipLaunchKernelGGL((attr_gxi_kernel<1>), dim3(ufnd_cdiv(W, 64), S), dim3(64), 0, stream, G, ldg, X, ldx, B, W, out, ldo, part);
+  UFND_CHECK_LAUNCH();
+  if (agg) {
+    hipLaunchKernelGGL(attr_mean_finish_kernel, dim3(ufnd_cdiv(W, 256)), dim3(256), 0, stream, (const float*)partials, S, W, B, agg);
+    UFND_CHECK_LAUNCH();
+  }
+  return UFND_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -434,6 +434,34 @@ class ForensicTrainer:
         return {"loss": self.optim.state.float_view("loss"), "probs": b["probs"], "y": b["label"],
                 "forensic": b["forensic"], "logits": b["logits"]}
 
+    def explain(self, split: str = "test", max_samples: int = 256, class_idx: int = 1) -> dict:
+        """Per-modality attribution (explain.modality_attribution) of the first min(len(split), max_samples) rows of a split's
+        device-resident cache: {"inputs", "modality", "order", "index" (the rows, as indices into the split)}.  The rows are
+        gathered (one ufnd_gather_rows launch: the cached tensors and gnn_Z[index]) into buffers of this call's own, not the
+        captured step's static ones; the modules keep the mode they are in.  Like any fusion backward it overwrites the
+        evidence gates' gradients, which every train step rewrites before the optimizer reads them."""
+        if self.cfg.gnn_in_graph:
+            raise NotImplementedError("explain: gnn_in_graph=True computes gnn_feat from each mini-batch's own graph "
+                                      "(forensic_trainer_integrated.py:203-224): a row has no gnn_feat outside its batch to attribute to")
+        if self.cfg.encode_inline or self.text_bp is not None:
+            raise NotImplementedError("explain: encoder-fed batches (encode_inline / train_encoders) take their text and visual features "
+                                      "from the encoders at step time; explanations cover cached-feature trainers only")
+        from .explain import modality_attribution
+        ds = self._dataset(split)
+        n = min(len(ds), int(max_samples))
+        if n < 1:
+            raise ValueError(f"explain: split {split!r} has no rows (max_samples={max_samples})")
+        index = torch.arange(n, dtype=torch.int64, device=self.device)
+        srcs = {"text_features": ds.T, "audio_features": ds.A, "visual_features": ds.V, "temporal_features": ds.U, "gnn_feat": ds.G}
+        if self.head.aux_dim:
+            srcs["aux"] = ds.AUX
+        bufs = {k: torch.empty(n, *src.shape[1:], dtype=src.dtype, device=self.device) for k, src in srcs.items()}
+        self.head._gather(index.data_ptr(), n, [(src.data_ptr(), bufs[k], src[0].numel() * src.element_size(), src.shape[0])
+                                                for k, src in srcs.items()], "ufnd_gather_rows")
+        out = modality_attribution(self.fusion, self.clf, bufs, bufs.get("aux"), class_idx)
+        out["index"] = index
+        return out
+
     # ---- encode_inline: the scheduler's entry points under the trainer's name (bench.py, tests, tools call them here)
     def prefetch_features(self, batch, slot: Optional[int] = None, inputs_ready=None, group: bool = False) -> None:
         self.pipe.prefetch_features(batch, slot, inputs_ready, group)
