@@ -648,9 +648,12 @@ int ufnd_smoothgrad_points(const ufnd_dims* d, const float* x0, int ld_x0, const
  *   UFND_ATTR_GRAD_X_INPUT  out[b, j] = |G[b, j] * X[b, j]| (steps == 1) and, when agg != NULL, agg[j] = mean_b out[b, j]
  *                           as a fixed-order column reduction: slices of 32 rows -> partials -> one finishing pass in
  *                           ascending slice order.  partials: ((B + 31) / 32) * W floats.
+ *   UFND_ATTR_PATH_MEAN     out[b, j] = (acc + sum_{i < steps} G[i * B + b, j]) / divisor: UFND_ATTR_SMOOTHGRAD without the absolute
+ *                           value (the SIGNED mean gradient along an integration path), the same accumulate / divisor protocol.
  * Rows of 16-byte aligned panels whose strides are multiples of 4 move as 16-byte words; any other layout by element. */
 #define UFND_ATTR_SMOOTHGRAD 0
 #define UFND_ATTR_GRAD_X_INPUT 1
+#define UFND_ATTR_PATH_MEAN 3 /* (2 is not a mode: it stays refused) */
 int ufnd_attribution_reduce(int mode, const float* G, int ldg, const float* X, int ldx, int B, int W, int steps, int accumulate,
                             int divisor, float* out, int ldo, float* agg, float* partials, void* stream);
 
@@ -772,7 +775,8 @@ int ufnd_l2norm_frames_bwd(const float* e, const float* dfeat, float* de, int B,
 int ufnd_bert_embed_bwd(const int64_t* ids, const float* ds, float* dword, float* dpos, float* dtype, int B, int L, int H, int vocab,
                         int max_pos, int type_vocab, void* stream);
 /* ViT token assembly backward from ds (N (P + 1), H): dcls (H), dpos (P + 1, H) overwritten; dpe (N P, H) bf16 = the patch rows
- * (the `patch_embed_bwd` of SURVEY 8b is ufnd_gemm_bf16_wgrad on dpe and the patch matrix). */
+ * (the `patch_embed_bwd` of SURVEY 8b is ufnd_gemm_bf16_wgrad on dpe and the patch matrix).  dcls = dpos = NULL: the patch rows
+ * only (a data-gradient pass: one launch). */
 int ufnd_vit_assemble_bwd(const float* ds, float* dcls, float* dpos, void* dpe_bf16, int N, int P, int H, void* stream);
 
 /* ------------------------------------------------------------------------------------
@@ -810,6 +814,33 @@ int ufnd_layernorm_dropout(const float* x, int ldx, const float* gamma, const fl
 int ufnd_layernorm_bwd_dropout(const float* x, int ldx, const float* gamma, const float* dy, int lddy, const float* add, int ldadd,
                                float* dx_f32, void* dx_bf16, int lddx, float* dgamma, float* dbeta, float* workspace, int accumulate,
                                int M, int H, float eps, const ufnd_dropout* drop, int where, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Attributions at the encoders' INPUTS (explain.input_attribution): which tokens, which image patches.  The gradient reaches
+ * them through the data-gradient chain of the entries above (ufnd_gemm_bf16_dgrad, ufnd_attention_bf16_bwd, ufnd_layernorm_bwd
+ * with dgamma = dbeta = NULL, ufnd_vit_assemble_bwd with dcls = dpos = NULL): no parameter gradient is formed anywhere.
+ * No atomics: every sum below runs in a fixed order.
+ * ---------------------------------------------------------------------------------- */
+
+/* Points of a straight path: out[k, r, :] = base[r, :] + alphas[k] (x[r, :] - base[r, :]), k < n_points (out: n_points panels of
+ * rows x width, point-major).  alphas is a HOST array, read at enqueue time; base = NULL is the zero baseline.  width a multiple of 4,
+ * dense 16-byte aligned panels.  Serves the text encoder's embedding sums (B L x H) and the frames (B F x 3 S S). */
+#define UFND_PATH_MAX_POINTS 64
+int ufnd_path_points(const float* x, const float* base, const float* alphas, int n_points, size_t rows, int width, float* out,
+                     void* stream);
+
+/* Per token row r < R: score[r] = sum_h g[r, h] (s[r, h] - base[r, h]) and grad_norm[r] = ||g[r, :]||_2, one wave per row.
+ * mask (R) int32 or NULL: rows with mask 0 are written as exactly 0.  H and the strides multiples of 4, 16-byte aligned panels. */
+int ufnd_token_attribution(const float* g, int ldg, const float* s, int lds, const float* base, int ldb, const int32_t* mask, int R, int H,
+                           float* score, float* grad_norm, void* stream);
+
+/* The inverse of ufnd_vit_patchify's layout for a gradient panel dpatches (N (S/P)^2, 3 P P) fp32, columns in (c, ky, kx) order:
+ *   grad (N, 3, S, S)        the gradient at the pixels,
+ *   pixels (N, 3, S, S)      grad * (x - base)  (base = NULL: zero baseline),
+ *   patch_sums (N, (S/P)^2)  each patch's sum of `pixels`,
+ * any subset (NULL = not written); pixels and patch_sums need x (N, 3, S, S).  patch a multiple of 4. */
+int ufnd_vit_unpatchify_attribution(const float* dpatches, const float* x, const float* base, float* grad, float* pixels, float* patch_sums,
+                                    int N, int image, int patch, void* stream);
 
 #ifdef __cplusplus
 }

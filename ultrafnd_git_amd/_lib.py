@@ -105,7 +105,8 @@ class GemmLn(C.Structure):
 STEP_STATE_BYTES = C.sizeof(StepState)
 BWD_ALL, BWD_FUSE_MLP, BWD_REST = 0, 1, 2
 TARGET_LOGIT, TARGET_PROB = 0, 1           # ufnd_classifier_input_grad
-ATTR_SMOOTHGRAD, ATTR_GRAD_X_INPUT = 0, 1   # ufnd_attribution_reduce
+ATTR_SMOOTHGRAD, ATTR_GRAD_X_INPUT, ATTR_PATH_MEAN = 0, 1, 3   # ufnd_attribution_reduce (2 is not a mode)
+PATH_MAX_POINTS = 64                        # ufnd_path_points: points per call
 ATTR_SLICE_ROWS = 32                        # its partials: ceil(B / 32) * W floats
 MAX_ROWS = 65536                            # check_dims: rows of one call
 BWD_NO_LINEAR_GRADS = 16          # OR-ed into the phase / flags: the factor form of the gradient exchange (dp.FactorExchange)
@@ -260,6 +261,12 @@ def _declare_encoders(lib: C.CDLL) -> None:
     lib.ufnd_smoothgrad_points.restype = I
     lib.ufnd_attribution_reduce.argtypes = [I, P, I, P, I, I, I, I, I, I, P, I, P, P, P]
     lib.ufnd_attribution_reduce.restype = I
+    lib.ufnd_path_points.argtypes = [P, P, C.POINTER(C.c_float), I, S, I, P, P]
+    lib.ufnd_path_points.restype = I
+    lib.ufnd_token_attribution.argtypes = [P, I, P, I, P, I, P, I, I, P, P, P]
+    lib.ufnd_token_attribution.restype = I
+    lib.ufnd_vit_unpatchify_attribution.argtypes = [P, P, P, P, P, P, I, I, I, P]
+    lib.ufnd_vit_unpatchify_attribution.restype = I
     lib.ufnd_gather_rows.argtypes = [P, I, C.POINTER(GatherItem), I, P]
     lib.ufnd_gather_rows.restype = I
     lib.ufnd_tcn_weight_ld.argtypes = [I, I]

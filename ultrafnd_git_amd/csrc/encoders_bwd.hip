@@ -475,14 +475,17 @@ extern "C" int ufnd_bert_embed_bwd(const int64_t* ids, const float* ds, float* d
 
 // ViT token assembly backward, given ds = the gradient of the assembled tokens before the pre-LayerNorm (N (P + 1) rows):
 // dpos (P + 1, H) and dcls (H) overwritten, dpe (N P, H) bf16 = the patch rows (operand of the patch-embedding weight gradient).
+// dcls = dpos = NULL (a data-gradient pass): the patch rows only.
 extern "C" int ufnd_vit_assemble_bwd(const float* ds, float* dcls, float* dpos, void* dpe_bf16, int N, int P, int H, void* stream_) {
-  UFND_REQUIRE(ds && dcls && dpos && dpe_bf16 && N >= 1 && P >= 1 && H % 4 == 0, "vit_assemble_bwd: null argument");
+  UFND_REQUIRE(ds && ((dcls && dpos) || (!dcls && !dpos)) && dpe_bf16 && N >= 1 && P >= 1 && H % 4 == 0, "vit_assemble_bwd: null argument");
   UFND_REQUIRE(ufnd_aligned(ds, 16) && ufnd_aligned(dpos, 16) && ufnd_aligned(dpe_bf16, 8), "vit_assemble_bwd: alignment");
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(position_sum_kernel, dim3(P + 1), dim3(256), 0, stream, ds, dpos, N, P + 1, H);
-  UFND_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rows_sum_kernel, dim3(ufnd_cdiv(H, 256)), dim3(256), 0, stream, (const float*)dpos, dcls, 1, H);       // x[n][0] = cls + pos[0]
-  UFND_CHECK_LAUNCH();
+  if (dpos) {
+    hipLaunchKernelGGL(position_sum_kernel, dim3(P + 1), dim3(256), 0, stream, ds, dpos, N, P + 1, H);
+    UFND_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rows_sum_kernel, dim3(ufnd_cdiv(H, 256)), dim3(256), 0, stream, (const float*)dpos, dcls, 1, H);       // x[n][0] = cls + pos[0]
+    UFND_CHECK_LAUNCH();
+  }
   size_t want = ((size_t)N * P * H / 4 + 255) / 256;
   hipLaunchKernelGGL(patch_rows_kernel, dim3((unsigned)(want > 4096 ? 4096 : want)), dim3(256), 0, stream, ds, (__bf16*)dpe_bf16, N, P, H);
   UFND_CHECK_LAUNCH();

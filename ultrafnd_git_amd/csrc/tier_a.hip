@@ -1046,7 +1046,8 @@ __device__ __forceinline__ void st_strip(float* p, const float (&v)[VEC]) {
   else p[0] = v[0];
 }
 // smooth-grad: out[b, j] = (acc + sum_i |G[i B + b, j]|) / divisor, the steps added in order.  One thread per (row, VEC columns).
-template <int VEC>
+// SIGNED: the same without the absolute value (the mean gradient along an integration path).
+template <int VEC, bool SIGNED = false>
 __global__ __launch_bounds__(256) void attr_smooth_kernel(const float* G, int ldg, int B, int W, int steps, int accumulate, int divisor,
                                                           float* out, int ldo) {
   const int per = (W + VEC - 1) / VEC;
@@ -1061,7 +1062,7 @@ __global__ __launch_bounds__(256) void attr_smooth_kernel(const float* G, int ld
     float g[VEC];
     ld_strip<VEC>(G + ((size_t)i * B + b) * ldg + col, g);
 #pragma unroll
-    for (int q = 0; q < VEC; ++q) acc[q] += fabsf(g[q]);
+    for (int q = 0; q < VEC; ++q) acc[q] += SIGNED ? g[q] : fabsf(g[q]);
   }
 #pragma unroll
   for (int q = 0; q < VEC; ++q) {
@@ -1711,7 +1712,7 @@ extern "C" int ufnd_smoothgrad_points(const ufnd_dims* d, const float* x0, int l
 
 extern "C" int ufnd_attribution_reduce(int mode, const float* G, int ldg, const float* X, int ldx, int B, int W, int steps, int accumulate,
                                        int divisor, float* out, int ldo, float* agg, float* partials, void* stream_) {
-  UFND_REQUIRE(mode == UFND_ATTR_SMOOTHGRAD || mode == UFND_ATTR_GRAD_X_INPUT, "attribution_reduce: mode=%d", mode);
+  UFND_REQUIRE(mode == UFND_ATTR_SMOOTHGRAD || mode == UFND_ATTR_GRAD_X_INPUT || mode == UFND_ATTR_PATH_MEAN, "attribution_reduce: mode=%d", mode);
   UFND_REQUIRE(G && out && B >= 1 && W >= 1 && steps >= 1 && (long long)B * steps <= 65536, "attribution_reduce: B=%d W=%d steps=%d", B, W, steps);
   UFND_REQUIRE(ldg >= W && ldo >= W, "attribution_reduce: ldg=%d ldo=%d < W=%d", ldg, ldo, W);
   hipStream_t stream = (hipStream_t)stream_;
@@ -1722,6 +1723,14 @@ extern "C" int ufnd_attribution_reduce(int mode, const float* G, int ldg, const 
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (vec4) hipLaunchKernelGGL((attr_smooth_kernel<4>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
     else hipLaunchKernelGGL((attr_smooth_kernel<1>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
+    UFND_CHECK_LAUNCH();
+    return UFND_OK;
+  }
+  if (mode == UFND_ATTR_PATH_MEAN) {
+    const long long threads = (long long)B * (vec4 ? W4 / 4 : W);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (vec4) hipLaunchKernelGGL((attr_smooth_kernel<4, true>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
+    else hipLaunchKernelGGL((attr_smooth_kernel<1, true>), grid, dim3(256), 0, stream, G, ldg, B, W, steps, accumulate, divisor, out, ldo);
     UFND_CHECK_LAUNCH();
     return UFND_OK;
   }

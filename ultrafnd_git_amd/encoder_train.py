@@ -27,7 +27,14 @@ How it is built.
     without the residual and ufnd_dropout_residual_layernorm forms x + m o d and its LayerNorm (same launch count), the LayerNorm
     backward masks its bf16 output; the embeddings -> ufnd_layernorm_dropout, and the LayerNorm backward masks its dy.  No mask is
     stored: the kernels regenerate it from (seed, step) of `rng()` -- the trainer's step state (the head's), or the encoder's own,
-    advanced by every forward_train -- and the site's tag (`text_tag`, `vision_tag`; ranges in csrc/common.hpp)."""
+    advanced by every forward_train -- and the site's tag (`text_tag`, `vision_tag`; ranges in csrc/common.hpp).
+  * Input gradients (`forward_saved` / `input_grad`; explain.input_attribution).  The same layer chain as `backward` with every
+    parameter gradient left out: no transposes, no weight-gradient product, no second stream, LayerNorm backwards without dgamma /
+    dbeta, and it goes one hop further -- to the raw embedding sums (text) and, through the patch embedding's data gradient and
+    ufnd_vit_unpatchify_attribution, to the pixels (vision).  Dropout is off.  Its activations live in buffers of its own, so a
+    forward_train waiting for its backward() is untouched.  It also runs on a FROZEN encoder (no arena bound): the bf16 W / W^T
+    copies and the stacked q|k|v biases are then built from `enc._w` on first use and again when `weights_version` moves; nothing
+    of the encoder is written either way."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
@@ -83,6 +90,9 @@ class _Backprop:
         self.drop_state: Optional[StepStateBuffer] = None      # the trainer sets its own (the head's); None: rng() makes one
         self._owns_state = False
         self._drops: Dict[Tuple[int, float, int], object] = {}
+        self.xsaved: Optional[dict] = None     # forward_saved's state (input_grad reads it; `saved` belongs to forward_train / backward)
+        self._xbufs: Optional[Tuple[Tuple, dict]] = None       # its buffers: the latest shape only (a path chunk's are gigabytes)
+        self._fz: Optional[dict] = None        # frozen encoder: operand copies and stacked biases of `weights_version`
 
     # ------------------------------------------------------------------ dropout
     def rng(self) -> StepStateBuffer:
@@ -164,6 +174,55 @@ class _Backprop:
 
     def master(self, keys: List[str]) -> torch.Tensor:
         return self._stacked(self.arena.data, keys)
+
+    def _frozen(self) -> dict:
+        """No arena bound (a frozen encoder): {"ops": linear name -> (W bf16, W^T bf16), "stacked": first key -> the q|k|v biases as
+        one vector}, cast from `enc._w` once per `weights_version`.  Reads the encoder only."""
+        e = self.enc
+        if self._fz is None or self._fz["version"] != e.weights_version:
+            w, s, lib = e._w, L.stream_ptr(e.device), L.lib()
+            ops, stacked = {}, {}
+            for name, (wk, bk) in self.linears().items():
+                m = w[wk[0]] if len(wk) == 1 else torch.cat([w[k] for k in wk], 0)
+                m2 = m.reshape(m.shape[0], -1).contiguous()
+                wb = torch.empty(m2.shape, dtype=torch.bfloat16, device=m2.device)
+                wt = torch.empty((m2.shape[1], m2.shape[0]), dtype=torch.bfloat16, device=m2.device)
+                L.check(lib.ufnd_cast_bf16(m2.data_ptr(), wb.data_ptr(), m2.numel(), s), "ufnd_cast_bf16")
+                L.check(lib.ufnd_transpose_bf16(m2.data_ptr(), 1, m2.shape[0], m2.shape[1], m2.stride(0), wt.data_ptr(), wt.stride(0), m2.shape[0],
+                                                None, None, 0, s), "ufnd_transpose_bf16")
+                ops[name] = (wb, wt)
+                if bk is not None and len(bk) > 1:
+                    stacked[bk[0]] = torch.cat([w[k] for k in bk], 0).contiguous()
+            self._fz = {"version": e.weights_version, "ops": ops, "stacked": stacked}
+        return self._fz
+
+    def _m(self, keys: List[str]) -> torch.Tensor:
+        """A master tensor (or adjacent ones stacked): the arena's view, or -- frozen -- the encoder's own."""
+        if self.arena is not None:
+            return self._stacked(self.arena.data, keys)
+        return self.enc._w[keys[0]] if len(keys) == 1 else self._frozen()["stacked"][keys[0]]
+
+    def _op(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(W bf16, W^T bf16) of a Linear: the trained copies, or the frozen ones."""
+        return self._ops[name] if self.arena is not None else self._frozen()["ops"][name]
+
+    def _explain_bufs(self, key: Tuple, make) -> dict:
+        key = key + (self.enc.device,)
+        if self._xbufs is None or self._xbufs[0] != key:
+            self._xbufs = None                 # (released before the next set is allocated)
+            self._xbufs = (key, make())
+        return self._xbufs[1]
+
+    def _begin_saved(self) -> None:
+        self.enc._require_hip()
+        if self.arena is not None and not self._ops:
+            self.refresh_operands()
+
+    def _ln_bwd_data(self, x, ldx, gamma, dy, dx_f32, dx_bf16, lddx, M, add=None) -> None:
+        """A LayerNorm backward's data gradient alone: no dgamma / dbeta, no workspace, nothing deferred."""
+        L.check(L.lib().ufnd_layernorm_bwd(x.data_ptr(), ldx, gamma.data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add),
+                                           add.stride(0) if add is not None else 0, L.ptr(dx_f32), L.ptr(dx_bf16), lddx, None, None, None, 0,
+                                           M, self.enc.hidden, self.enc.eps, L.stream_ptr(x.device)), "ufnd_layernorm_bwd")
 
     def grad(self, keys: List[str]) -> torch.Tensor:
         return self._stacked(self.arena.ensure_grad(), keys)
@@ -378,21 +437,24 @@ class TextBackprop(_Backprop):
             d[f"{i}.qkv"], d[f"{i}.o"], d[f"{i}.w1"], d[f"{i}.w2"] = (k["qkv_w"], k["qkv_b"]), (k["o_w"], k["o_b"]), (k["w1"], k["b1"]), (k["w2"], k["b2"])
         return d
 
+    def _make_bufs(self, B: int, Lq: int) -> dict:
+        e, dev = self.enc, self.enc.device
+        M, H, I = B * Lq, e.hidden, e.inter
+        bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
+        layers = [{"xb": torch.empty(M, H, **bf), "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
+                   "lse": torch.empty(M, e.heads, **f32), "y1": torch.empty(M, H, **f32), "x1b": torch.empty(M, H, **bf),
+                   "pre": torch.empty(M, I, **bf), "h": torch.empty(M, I, **bf), "y2": torch.empty(M, H, **f32)} for _ in range(e.layers)]
+        return {"layers": layers, "s": torch.empty(M, H, **f32), "xf": torch.empty(M, H, **f32), "x1f": torch.empty(M, H, **f32),
+                "xb_last": torch.empty(M, H, **bf), "hid": torch.empty(M, H, **f32), "feat": torch.empty(B, H, **f32),
+                # backward
+                "dx": torch.empty(M, H, **f32), "dyf": torch.empty(M, H, **f32), "dyb": torch.empty(M, H, **bf), "dx1": torch.empty(M, H, **f32),
+                "dpre": torch.empty(M, I, **bf), "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf),
+                "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(B, Lq, e.heads), **f32), "ds": torch.empty(M, H, **f32)}
+
     def _save_bufs(self, B: int, Lq: int) -> dict:
         key = ("save", B, Lq)
         if key not in self._scratch:
-            e, dev = self.enc, self.enc.device
-            M, H, I = B * Lq, e.hidden, e.inter
-            bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
-            layers = [{"xb": torch.empty(M, H, **bf), "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
-                       "lse": torch.empty(M, e.heads, **f32), "y1": torch.empty(M, H, **f32), "x1b": torch.empty(M, H, **bf),
-                       "pre": torch.empty(M, I, **bf), "h": torch.empty(M, I, **bf), "y2": torch.empty(M, H, **f32)} for _ in range(e.layers)]
-            self._scratch[key] = {"layers": layers, "s": torch.empty(M, H, **f32), "xf": torch.empty(M, H, **f32), "x1f": torch.empty(M, H, **f32),
-                                  "xb_last": torch.empty(M, H, **bf), "hid": torch.empty(M, H, **f32), "feat": torch.empty(B, H, **f32),
-                                  # backward
-                                  "dx": torch.empty(M, H, **f32), "dyf": torch.empty(M, H, **f32), "dyb": torch.empty(M, H, **bf), "dx1": torch.empty(M, H, **f32),
-                                  "dpre": torch.empty(M, I, **bf), "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf),
-                                  "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(B, Lq, e.heads), **f32), "ds": torch.empty(M, H, **f32)}
+            self._scratch[key] = self._make_bufs(B, Lq)
         return self._scratch[key]
 
     @torch.no_grad()
@@ -401,56 +463,102 @@ class TextBackprop(_Backprop):
         e._require_hip()
         if not self._ops:
             self.refresh_operands()
-        dev = e.device
-        B, Lq = input_ids.shape
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        mask = attention_mask.to(dev, torch.int32).contiguous()
-        sv = self._save_bufs(B, Lq)
-        M, H, w, s = B * Lq, e.hidden, e._w, L.stream_ptr(dev)
-        lib = L.lib()
         ph = dropout_prob("hidden_dropout_prob", e.hidden_dropout_prob)
         pa = dropout_prob("attention_probs_dropout_prob", e.attention_probs_dropout_prob)
         if ph > 0.0 or pa > 0.0:
             self._begin_dropout()
+        B, Lq = input_ids.shape
+        self.saved = self._forward(self._save_bufs(B, Lq), input_ids, attention_mask, ph, pa)
+        return self.saved["sv"]["feat"]
+
+    @torch.no_grad()
+    def forward_saved(self, input_ids: Optional[torch.Tensor], attention_mask: torch.Tensor, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """forward_train without dropout, on a bound or a frozen encoder, keeping its activations for input_grad() in buffers of its
+        own.  `sums` (B L, H) fp32: start from these raw embedding sums instead of embedding input_ids (a point of an integration
+        path); they are read where they lie, also by input_grad()."""
+        self._begin_saved()
+        B, Lq = attention_mask.shape
+        sv = self._explain_bufs(("text", B, Lq), lambda: self._make_bufs(B, Lq))
+        self.xsaved = self._forward(sv, input_ids, attention_mask, 0.0, 0.0, sums)
+        return sv["feat"]
+
+    def _forward(self, sv: dict, input_ids, attention_mask: torch.Tensor, ph: float, pa: float, sums: Optional[torch.Tensor] = None) -> dict:
+        e = self.enc
+        dev = e.device
+        B, Lq = attention_mask.shape
+        mask = attention_mask.to(dev, torch.int32).contiguous()
+        M, H, w, s = B * Lq, e.hidden, e._w, L.stream_ptr(dev)
+        lib = L.lib()
         if ph > 0.0 and "d" not in sv:
             sv["d"] = torch.empty(M, H, dtype=torch.float32, device=dev)       # a hidden site's dense output (without its residual)
-        # embeddings: the raw sums are kept (their LayerNorm's backward needs its input)
-        L.check(lib.ufnd_bert_embed(ids.data_ptr(), w["embeddings.word_embeddings.weight"].data_ptr(), w["embeddings.position_embeddings.weight"].data_ptr(),
-                                    w["embeddings.token_type_embeddings.weight"].data_ptr(), None, None, None, sv["s"].data_ptr(), B, Lq, H, e.vocab, e.eps, s),
-                "ufnd_bert_embed")
+        if sums is None:
+            # embeddings: the raw sums are kept (their LayerNorm's backward needs its input)
+            ids, sm = input_ids.to(dev, torch.int64).contiguous(), sv["s"]
+            L.check(lib.ufnd_bert_embed(ids.data_ptr(), w["embeddings.word_embeddings.weight"].data_ptr(), w["embeddings.position_embeddings.weight"].data_ptr(),
+                                        w["embeddings.token_type_embeddings.weight"].data_ptr(), None, None, None, sm.data_ptr(), B, Lq, H, e.vocab, e.eps, s),
+                    "ufnd_bert_embed")
+        else:
+            ids, sm = None, sums
+            if tuple(sm.shape) != (M, H) or sm.dtype != torch.float32 or not sm.is_contiguous() or sm.device != dev or sm.data_ptr() % 16:
+                raise RuntimeError(f"sums: expected a contiguous 16-byte aligned fp32 ({M},{H}) tensor on {dev}")
         x_f, x_b = sv["xf"], sv["layers"][0]["xb"]
         if ph > 0.0:
             import ctypes as C
-            L.check(lib.ufnd_layernorm_dropout(sv["s"].data_ptr(), H, w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
+            L.check(lib.ufnd_layernorm_dropout(sm.data_ptr(), H, w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
                                                x_b.data_ptr(), x_f.data_ptr(), M, H, e.eps, C.byref(self._drop(ph, TAG_TEXT_EMB)), s), "ufnd_layernorm_dropout")
         else:
-            e._ln(sv["s"], H, w["embeddings.LayerNorm.weight"], w["embeddings.LayerNorm.bias"], x_b, x_f, M, H, e.eps)
+            e._ln(sm, H, w["embeddings.LayerNorm.weight"], w["embeddings.LayerNorm.bias"], x_b, x_f, M, H, e.eps)
         for i, a in enumerate(sv["layers"]):
             k = self._lk(i)
-            wqkv, wo, w1, w2 = self._ops[f"{i}.qkv"][0], self._ops[f"{i}.o"][0], self._ops[f"{i}.w1"][0], self._ops[f"{i}.w2"][0]
-            self._gemm(a["xb"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
+            wqkv, wo, w1, w2 = self._op(f"{i}.qkv")[0], self._op(f"{i}.o")[0], self._op(f"{i}.w1")[0], self._op(f"{i}.w2")[0]
+            self._gemm(a["xb"], wqkv, self._m(k["qkv_b"]), out_bf16=a["qkv"])
             self._attn_fwd(a["qkv"], mask, a["ctx"], a["lse"], B, Lq, self._drop(pa, text_tag(i, SITE_ATTN)) if pa > 0.0 else None)
             if ph > 0.0:
-                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=sv["d"])
-                self._drop_ln(x_f, sv["d"], self.master(k["g1"]), self.master(k["b1n"]), a["y1"], a["x1b"], sv["x1f"], M,
+                self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=sv["d"])
+                self._drop_ln(x_f, sv["d"], self._m(k["g1"]), self._m(k["b1n"]), a["y1"], a["x1b"], sv["x1f"], M,
                               self._drop(ph, text_tag(i, SITE_ATTN_OUT)))
             else:
-                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["y1"], residual=x_f)
-                e._ln(a["y1"], H, self.master(k["g1"]), self.master(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
-            self._gemm(a["x1b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
+                self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=a["y1"], residual=x_f)
+                e._ln(a["y1"], H, self._m(k["g1"]), self._m(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
+            self._gemm(a["x1b"], w1, self._m(k["b1"]), out_bf16=a["pre"])
             _act(a["pre"], a["h"], ACT_GELU)
             nxt_b = sv["layers"][i + 1]["xb"] if i + 1 < e.layers else sv["xb_last"]
             if ph > 0.0:
-                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=sv["d"])
-                self._drop_ln(sv["x1f"], sv["d"], self.master(k["g2"]), self.master(k["b2n"]), a["y2"], nxt_b, x_f, M,
+                self._gemm(a["h"], w2, self._m(k["b2"]), out_f32=sv["d"])
+                self._drop_ln(sv["x1f"], sv["d"], self._m(k["g2"]), self._m(k["b2n"]), a["y2"], nxt_b, x_f, M,
                               self._drop(ph, text_tag(i, SITE_FFN_OUT)))
             else:
-                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
-                e._ln(a["y2"], H, self.master(k["g2"]), self.master(k["b2n"]), nxt_b, x_f, M, H, e.eps)
+                self._gemm(a["h"], w2, self._m(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
+                e._ln(a["y2"], H, self._m(k["g2"]), self._m(k["b2n"]), nxt_b, x_f, M, H, e.eps)
         sv["hid"].copy_(x_f)
         L.check(lib.ufnd_masked_meanpool_l2(sv["hid"].data_ptr(), mask.data_ptr(), sv["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
-        self.saved = {"B": B, "L": Lq, "ids": ids, "mask": mask, "sv": sv, "ph": ph, "pa": pa}
-        return sv["feat"]
+        return {"B": B, "L": Lq, "ids": ids, "mask": mask, "sv": sv, "ph": ph, "pa": pa, "s": sm}
+
+    @torch.no_grad()
+    def input_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
+        """ds (B L, H): the gradient of the raw embedding sums (`xsaved["s"]`, before the embedding LayerNorm) from d / d features
+        (B, H), for the batch of the last forward_saved().  The layer chain of backward() without a single parameter gradient;
+        rows of masked tokens come out as zero.  The returned buffer is rewritten by the next call of the same shape."""
+        e, st = self.enc, self.xsaved
+        if st is None:
+            raise RuntimeError("input_grad() without forward_saved()")
+        B, Lq, mask, sv = st["B"], st["L"], st["mask"], st["sv"]
+        M, H = B * Lq, e.hidden
+        dfeat = L.f32c(dfeat.to(e.device))
+        L.check(L.lib().ufnd_masked_meanpool_l2_bwd(sv["hid"].data_ptr(), mask.data_ptr(), dfeat.data_ptr(), sv["dx"].data_ptr(), B, Lq, H,
+                                                    L.stream_ptr(e.device)), "ufnd_masked_meanpool_l2_bwd")
+        dx = sv["dx"]
+        for i in reversed(range(e.layers)):
+            a, k = sv["layers"][i], self._lk(i)
+            self._ln_bwd_data(a["y2"], H, self._m(k["g2"]), dx, sv["dyf"], sv["dyb"], H, M)
+            self._dgrad(sv["dyb"], self._op(f"{i}.w2")[1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_GELU_BWD)
+            self._dgrad(sv["dpre"], self._op(f"{i}.w1")[1], out_f32=sv["dx1"], residual=sv["dyf"])
+            self._ln_bwd_data(a["y1"], H, self._m(k["g1"]), sv["dx1"], sv["dyf"], sv["dyb"], H, M)
+            self._dgrad(sv["dyb"], self._op(f"{i}.o")[1], out_bf16=sv["dctx"])
+            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], mask, sv["dqkv"], sv["aws"], B, Lq)
+            self._dgrad(sv["dqkv"], self._op(f"{i}.qkv")[1], out_f32=dx, residual=sv["dyf"])
+        self._ln_bwd_data(st["s"], H, self._m(["embeddings.LayerNorm.weight"]), dx, sv["ds"], None, H, M)
+        return sv["ds"]
 
     @torch.no_grad()
     def backward(self, dfeat: torch.Tensor) -> None:
@@ -533,27 +641,38 @@ class VisualBackprop(_Backprop):
             d[f"{i}.qkv"], d[f"{i}.o"], d[f"{i}.w1"], d[f"{i}.w2"] = (k["qkv_w"], k["qkv_b"]), (k["o_w"], k["o_b"]), (k["w1"], k["b1"]), (k["w2"], k["b2"])
         return d
 
+    def _make_bufs(self, B: int, Fr: int) -> dict:
+        e, dev = self.enc, self.enc.device
+        N, T, H, I = B * Fr, e.n_patches + 1, e.hidden, e.inter
+        M, NP = N * T, N * e.n_patches
+        bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
+        layers = [{"xin": torch.empty(M, H, **f32), "h1b": torch.empty(M, H, **bf), "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
+                   "lse": torch.empty(M, e.heads, **f32), "xmid": torch.empty(M, H, **f32), "h2b": torch.empty(M, H, **bf),
+                   "pre": torch.empty(M, I, **bf), "m": torch.empty(M, I, **bf)} for _ in range(e.layers)]
+        Np = _pad64(N)
+        return {"layers": layers, "patches": torch.empty(NP, 3 * e.patch ** 2, **bf), "pe": torch.empty(NP, H, **f32),
+                "s": torch.empty(M, H, **f32), "xout": torch.empty(M, H, **f32), "pooled_b": torch.zeros(Np, H, **bf),
+                "pooled_f": torch.empty(N, H, **f32), "e": torch.empty(N, e.proj, **f32), "feat": torch.empty(B, e.proj, **f32),
+                # backward
+                "de": torch.empty(N, e.proj, **f32), "de_b": torch.zeros(Np, e.proj, **bf), "dpool": torch.empty(Np, H, **f32),
+                "dx": torch.empty(M, H, **f32), "dxb": torch.empty(M, H, **bf), "dh": torch.empty(M, H, **f32),
+                "dmid": torch.empty(M, H, **f32), "dmidb": torch.empty(M, H, **bf), "dpre": torch.empty(M, I, **bf),
+                "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf), "ds": torch.empty(M, H, **f32),
+                "dpe": torch.empty(NP, H, **bf), "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(N, T, e.heads), **f32)}
+
     def _save_bufs(self, B: int, Fr: int) -> dict:
         key = ("save", B, Fr)
         if key not in self._scratch:
-            e, dev = self.enc, self.enc.device
-            N, T, H, I = B * Fr, e.n_patches + 1, e.hidden, e.inter
-            M, NP = N * T, N * e.n_patches
-            bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
-            layers = [{"xin": torch.empty(M, H, **f32), "h1b": torch.empty(M, H, **bf), "qkv": torch.empty(M, 3 * H, **bf), "ctx": torch.empty(M, H, **bf),
-                       "lse": torch.empty(M, e.heads, **f32), "xmid": torch.empty(M, H, **f32), "h2b": torch.empty(M, H, **bf),
-                       "pre": torch.empty(M, I, **bf), "m": torch.empty(M, I, **bf)} for _ in range(e.layers)]
-            Np = _pad64(N)
-            self._scratch[key] = {"layers": layers, "patches": torch.empty(NP, 3 * e.patch ** 2, **bf), "pe": torch.empty(NP, H, **f32),
-                                  "s": torch.empty(M, H, **f32), "xout": torch.empty(M, H, **f32), "pooled_b": torch.zeros(Np, H, **bf),
-                                  "pooled_f": torch.empty(N, H, **f32), "e": torch.empty(N, e.proj, **f32), "feat": torch.empty(B, e.proj, **f32),
-                                  # backward
-                                  "de": torch.empty(N, e.proj, **f32), "de_b": torch.zeros(Np, e.proj, **bf), "dpool": torch.empty(Np, H, **f32),
-                                  "dx": torch.empty(M, H, **f32), "dxb": torch.empty(M, H, **bf), "dh": torch.empty(M, H, **f32),
-                                  "dmid": torch.empty(M, H, **f32), "dmidb": torch.empty(M, H, **bf), "dpre": torch.empty(M, I, **bf),
-                                  "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf), "ds": torch.empty(M, H, **f32),
-                                  "dpe": torch.empty(NP, H, **bf), "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(N, T, e.heads), **f32)}
+            self._scratch[key] = self._make_bufs(B, Fr)
         return self._scratch[key]
+
+    def _frames5(self, frames: torch.Tensor) -> torch.Tensor:
+        if frames.dim() == 4:
+            frames = frames[:, None]
+        e = self.enc
+        if frames.dim() != 5 or tuple(frames.shape[2:]) != (3, e.image, e.image):
+            raise RuntimeError(f"frames: expected (B,F,3,{e.image},{e.image}), got {tuple(frames.shape)}")
+        return frames
 
     @torch.no_grad()
     def forward_train(self, frames: torch.Tensor) -> torch.Tensor:
@@ -561,42 +680,101 @@ class VisualBackprop(_Backprop):
         e._require_hip()
         if not self._ops:
             self.refresh_operands()
-        if frames.dim() == 4:
-            frames = frames[:, None]
-        dev = e.device
-        B, Fr = frames.shape[:2]
-        if tuple(frames.shape[2:]) != (3, e.image, e.image):
-            raise RuntimeError(f"frames: expected (B,F,3,{e.image},{e.image}), got {tuple(frames.shape)}")
-        fr = L.f32c(frames.to(dev)).view(B * Fr, 3, e.image, e.image)
-        sv = self._save_bufs(B, Fr)
+        frames = self._frames5(frames)
         pa = dropout_prob("attention_dropout", e.attention_dropout)
         if pa > 0.0:
             self._begin_dropout()
+        self.saved = self._forward(self._save_bufs(*frames.shape[:2]), frames, pa)
+        return self.saved["sv"]["feat"]
+
+    @torch.no_grad()
+    def forward_saved(self, frames: torch.Tensor) -> torch.Tensor:
+        """forward_train without dropout, on a bound or a frozen encoder, keeping its activations for input_grad() in buffers of its
+        own."""
+        self._begin_saved()
+        frames = self._frames5(frames)
+        B, Fr = frames.shape[:2]
+
+        def make():
+            sv = self._make_bufs(B, Fr)
+            sv["dpatch"] = torch.empty(B * Fr * self.enc.n_patches, 3 * self.enc.patch ** 2, dtype=torch.float32, device=self.enc.device)
+            return sv
+        self.xsaved = self._forward(self._explain_bufs(("vision", B, Fr), make), frames, 0.0)
+        return self.xsaved["sv"]["feat"]
+
+    def _forward(self, sv: dict, frames: torch.Tensor, pa: float) -> dict:
+        e = self.enc
+        dev = e.device
+        B, Fr = frames.shape[:2]
+        fr = L.f32c(frames.to(dev)).view(B * Fr, 3, e.image, e.image)
         N, T, H, w, V = B * Fr, e.n_patches + 1, e.hidden, e._w, self.V
         M, s, lib = N * T, L.stream_ptr(dev), L.lib()
         L.check(lib.ufnd_vit_patchify(fr.data_ptr(), sv["patches"].data_ptr(), N, e.image, e.patch, s), "ufnd_vit_patchify")
-        self._gemm(sv["patches"], self._ops["patch"][0], None, out_f32=sv["pe"])
+        self._gemm(sv["patches"], self._op("patch")[0], None, out_f32=sv["pe"])
         L.check(lib.ufnd_vit_assemble(sv["pe"].data_ptr(), w[V + "embeddings.class_embedding"].data_ptr(), w[V + "embeddings.position_embedding.weight"].data_ptr(),
                                       None, None, sv["s"].data_ptr(), None, None, N, e.n_patches, H, e.eps, s), "ufnd_vit_assemble")
         x = sv["layers"][0]["xin"]
         e._ln(sv["s"], H, w[V + "pre_layrnorm.weight"], w[V + "pre_layrnorm.bias"], None, x, M, H, e.eps)
         for i, a in enumerate(sv["layers"]):
             k = self._lk(i)
-            wqkv, wo, w1, w2 = self._ops[f"{i}.qkv"][0], self._ops[f"{i}.o"][0], self._ops[f"{i}.w1"][0], self._ops[f"{i}.w2"][0]
-            e._ln(a["xin"], H, self.master(k["g1"]), self.master(k["b1n"]), a["h1b"], None, M, H, e.eps)
-            self._gemm(a["h1b"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
+            wqkv, wo, w1, w2 = self._op(f"{i}.qkv")[0], self._op(f"{i}.o")[0], self._op(f"{i}.w1")[0], self._op(f"{i}.w2")[0]
+            e._ln(a["xin"], H, self._m(k["g1"]), self._m(k["b1n"]), a["h1b"], None, M, H, e.eps)
+            self._gemm(a["h1b"], wqkv, self._m(k["qkv_b"]), out_bf16=a["qkv"])
             self._attn_fwd(a["qkv"], None, a["ctx"], a["lse"], N, T, self._drop(pa, vision_tag(i)) if pa > 0.0 else None)
-            self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["xmid"], residual=a["xin"])
-            e._ln(a["xmid"], H, self.master(k["g2"]), self.master(k["b2n"]), a["h2b"], None, M, H, e.eps)
-            self._gemm(a["h2b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
+            self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=a["xmid"], residual=a["xin"])
+            e._ln(a["xmid"], H, self._m(k["g2"]), self._m(k["b2n"]), a["h2b"], None, M, H, e.eps)
+            self._gemm(a["h2b"], w1, self._m(k["b1"]), out_bf16=a["pre"])
             _act(a["pre"], a["m"], ACT_QUICK_GELU)
             nxt = sv["layers"][i + 1]["xin"] if i + 1 < e.layers else sv["xout"]
-            self._gemm(a["m"], w2, self.master(k["b2"]), out_f32=nxt, residual=a["xmid"])
+            self._gemm(a["m"], w2, self._m(k["b2"]), out_f32=nxt, residual=a["xmid"])
         e._ln(sv["xout"], T * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], sv["pooled_b"], sv["pooled_f"], N, H, e.eps)
-        self._gemm(sv["pooled_b"][:N], self._ops["proj"][0], None, out_f32=sv["e"])
+        self._gemm(sv["pooled_b"][:N], self._op("proj")[0], None, out_f32=sv["e"])
         L.check(lib.ufnd_l2norm_frames(sv["e"].data_ptr(), sv["feat"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames")
-        self.saved = {"B": B, "F": Fr, "sv": sv, "pa": pa}
-        return sv["feat"]
+        return {"B": B, "F": Fr, "sv": sv, "pa": pa}
+
+    @torch.no_grad()
+    def patch_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
+        """(B F P, 3 p^2) fp32: the gradient of the patch matrix (ufnd_vit_patchify's layout) from d / d features (B, proj), for the
+        batch of the last forward_saved().  The layer chain of backward() without a single parameter gradient, then the patch
+        rows of the token-assembly backward through the patch embedding's data gradient.  Rewritten by the next call of the shape."""
+        e, st = self.enc, self.xsaved
+        if st is None:
+            raise RuntimeError("input_grad() without forward_saved()")
+        B, Fr, sv, V = st["B"], st["F"], st["sv"], self.V
+        N, T, H = B * Fr, e.n_patches + 1, e.hidden
+        M = N * T
+        s, lib = L.stream_ptr(e.device), L.lib()
+        dfeat = L.f32c(dfeat.to(e.device))
+        L.check(lib.ufnd_l2norm_frames_bwd(sv["e"].data_ptr(), dfeat.data_ptr(), sv["de"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames_bwd")
+        sv["de_b"][:N].copy_(sv["de"])
+        self._dgrad(sv["de_b"][:N], self._op("proj")[1], out_f32=sv["dpool"][:N])
+        dx = sv["dx"]
+        dx.zero_()                       # only the CLS rows of the last layer's output carry a gradient
+        sv["dxb"].zero_()
+        self._ln_bwd_data(sv["xout"], T * H, self._m([V + "post_layernorm.weight"]), sv["dpool"][:N], dx, sv["dxb"], T * H, N)
+        for i in reversed(range(e.layers)):
+            a, k = sv["layers"][i], self._lk(i)
+            self._dgrad(sv["dxb"], self._op(f"{i}.w2")[1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_QUICK_GELU_BWD)
+            self._dgrad(sv["dpre"], self._op(f"{i}.w1")[1], out_f32=sv["dh"])
+            self._ln_bwd_data(a["xmid"], H, self._m(k["g2"]), sv["dh"], sv["dmid"], sv["dmidb"], H, M, add=dx)
+            self._dgrad(sv["dmidb"], self._op(f"{i}.o")[1], out_bf16=sv["dctx"])
+            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T)
+            self._dgrad(sv["dqkv"], self._op(f"{i}.qkv")[1], out_f32=sv["dh"])
+            self._ln_bwd_data(a["xin"], H, self._m(k["g1"]), sv["dh"], dx, sv["dxb"], H, M, add=sv["dmid"])
+        self._ln_bwd_data(sv["s"], H, self._m([V + "pre_layrnorm.weight"]), dx, sv["ds"], None, H, M)
+        L.check(lib.ufnd_vit_assemble_bwd(sv["ds"].data_ptr(), None, None, sv["dpe"].data_ptr(), N, e.n_patches, H, s), "ufnd_vit_assemble_bwd")
+        self._dgrad(sv["dpe"], self._op("patch")[1], out_f32=sv["dpatch"])
+        return sv["dpatch"]
+
+    @torch.no_grad()
+    def input_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
+        """dframes (B, F, 3, S, S): patch_grad() laid back into frame layout (ufnd_vit_unpatchify_attribution)."""
+        dp = self.patch_grad(dfeat)
+        e, st = self.enc, self.xsaved
+        out = torch.empty(st["B"], st["F"], 3, e.image, e.image, dtype=torch.float32, device=e.device)
+        L.check(L.lib().ufnd_vit_unpatchify_attribution(dp.data_ptr(), None, None, out.data_ptr(), None, None, st["B"] * st["F"], e.image, e.patch,
+                                                        L.stream_ptr(e.device)), "ufnd_vit_unpatchify_attribution")
+        return out
 
     @torch.no_grad()
     def backward(self, dfeat: torch.Tensor) -> None:

@@ -462,6 +462,30 @@ class ForensicTrainer:
         out["index"] = index
         return out
 
+    def explain_inputs(self, batch: Dict[str, torch.Tensor], class_idx: int = 1, method: str = "grad_x_input", steps: int = 16) -> dict:
+        """Token and image-patch attribution (explain.input_attribution) of one encoder-fed batch -- input_ids, attention_mask,
+        frames and the cached modalities, as train_step takes it -- for `encode_inline` trainers, frozen or `train_encoders` (then
+        through the bound masters and their current operand copies).  temporal comes from the trainer's TemporalSyncNet
+        (deterministic align) when it has one, else from the batch; gnn_feat from the batch or gnn_Z[index].  Between train steps it
+        changes nothing a step reads before rewriting it: parameters, optimizer and step RNG state, the frozen path's packed
+        operands and the captured step's buffers are untouched; like any fusion backward it overwrites the evidence gates'
+        gradients, which every train step rewrites."""
+        if not self.cfg.encode_inline or self.cfg.gnn_in_graph or "input_ids" not in batch:
+            raise ValueError("explain_inputs: needs an encode_inline trainer (not gnn_in_graph) and a batch with input_ids / attention_mask / "
+                             "frames; cached-feature trainers have explain()")
+        from .explain import input_attribution
+        b = {k: batch[k] for k in ("input_ids", "attention_mask", "frames", "audio_features", "aux") if k in batch}
+        if self.temporal_net is None:
+            b["temporal_features"] = batch["temporal_features"]
+        if "gnn_feat" in batch and batch["gnn_feat"] is not None:
+            b["gnn_feat"] = batch["gnn_feat"]
+        else:
+            idx = batch["index"]
+            idx = idx.to(self.device) if isinstance(idx, torch.Tensor) else torch.as_tensor(idx, device=self.device)
+            b["gnn_feat"] = torch.index_select(self._dataset("train").G, 0, idx)
+        return input_attribution(self.fusion, self.clf, self.text_bp or self.text_encoder, self.vis_bp or self.visual_encoder, b,
+                                 class_idx=class_idx, method=method, steps=steps, temporal_net=self.temporal_net)
+
     # ---- encode_inline: the scheduler's entry points under the trainer's name (bench.py, tests, tools call them here)
     def prefetch_features(self, batch, slot: Optional[int] = None, inputs_ready=None, group: bool = False) -> None:
         self.pipe.prefetch_features(batch, slot, inputs_ready, group)
