@@ -346,6 +346,38 @@ def test_bound_encoders_keep_their_gradients_and_a_pending_backward():
         assert torch.equal(fz.input_grad(2 * d), g1), bp_cls.__name__
 
 
+@pytest.mark.parametrize("overlap", [True, False])
+def test_backward_and_input_grad_are_one_chain_bit_for_bit(overlap):
+    """backward() and input_grad() walk the same chain, so at dropout 0 its two modes give the same data gradients to the bit: text
+    the raw embedding sums' (`ds`), vision the patch embedding's output's (`dpe`) -- and the mode without parameter gradients leaves
+    the arena's gradient buffer as backward() wrote it.  Text 3 x 77 (231 rows, not a multiple of 64; sample 1 has a single real
+    token), vision 2 x 2 frames (200 token rows, 4 CLS rows): row padding, masked rows and the CLS-only gradient all occur."""
+    from oracle import encoders_ref as E
+    from tests.test_gpu_encoder_train import _standalone
+    from ultrafnd_git_amd.encoder_train import TextBackprop, VisualBackprop
+    tenc, _ = _text_encoder(2, 37)
+    venc, _ = _visual_encoder(2, 38)
+    ids, mask = _tokens(3, 77, 710)
+    frames = E.synthetic_frames(711, 2, 2)
+    gen = torch.Generator().manual_seed(712)
+    dt, dv = torch.randn(3, 768, generator=gen).to(DEV), torch.randn(2, 512, generator=gen).to(DEV)
+    for bp_cls, enc, fwd, d, key in ((TextBackprop, tenc, (ids, mask), dt, "ds"), (VisualBackprop, venc, (frames,), dv, "dpe")):
+        bp, arena = _standalone(bp_cls, enc)
+        bp.overlap_wgrad = overlap
+        bp.forward_train(*fwd)
+        bp.backward(d)
+        torch.cuda.synchronize()
+        full, grads = bp.saved["sv"][key].clone(), arena.grad.clone()
+        assert torch.isfinite(full).all() and full.abs().max().item() > 0
+        bp.forward_saved(*fwd)
+        got = bp.input_grad(d)
+        torch.cuda.synchronize()
+        data = got if key == "ds" else bp.xsaved["sv"][key]
+        assert data.data_ptr() != bp.saved["sv"][key].data_ptr()
+        assert torch.equal(data, full), (bp_cls.__name__, key, overlap)
+        assert torch.equal(arena.grad.view(torch.int32), grads.view(torch.int32)), bp_cls.__name__       # (as bits: the padding is NaN)
+
+
 # ------------------------------------------------------------------------------------------------ 5. the trainer
 def _inline_trainer(tmp_path, train_encoders, use_graph):
     from oracle import tier_a as O

@@ -16,8 +16,9 @@ How it is built.
   * Forward (`forward_train`).  The un-folded layer sequence (one LayerNorm kernel per LayerNorm), with what the backward needs
     kept per layer: the bf16 GEMM inputs, fused q|k|v rows, attention output and per-query log-sum-exp, the pre-LayerNorm sums
     (fp32), FFN1's pre-activations.
-  * Backward (`backward`).  Per layer: LayerNorm backward (row kernel, two-stage parameter sums) -> for each Linear: transpose
-    dy and x (dy's column sums = the bias gradient fall out of the same pass), weight gradient as the forward's NT kernel over
+  * Backward (`backward`).  ONE chain per encoder (`_chain`) walks from d features down to the input; the parameter gradients
+    are an option of that walk (`params`), which `backward` takes.  Per layer: LayerNorm backward (row kernel, two-stage
+    parameter sums) -> for each Linear: transpose dy and x (dy's column sums = the bias gradient fall out of the same pass), weight gradient as the forward's NT kernel over
     the token dimension with split-K slabs, data gradient as the NT kernel on W^T with the residual-branch gradient or the
     activation derivative fused into its epilogue -> flash-style attention backward.  No atomics anywhere: gradients are
     run-to-run identical.
@@ -28,24 +29,26 @@ How it is built.
     backward masks its bf16 output; the embeddings -> ufnd_layernorm_dropout, and the LayerNorm backward masks its dy.  No mask is
     stored: the kernels regenerate it from (seed, step) of `rng()` -- the trainer's step state (the head's), or the encoder's own,
     advanced by every forward_train -- and the site's tag (`text_tag`, `vision_tag`; ranges in csrc/common.hpp).
-  * Input gradients (`forward_saved` / `input_grad`; explain.input_attribution).  The same layer chain as `backward` with every
-    parameter gradient left out: no transposes, no weight-gradient product, no second stream, LayerNorm backwards without dgamma /
-    dbeta, and it goes one hop further -- to the raw embedding sums (text) and, through the patch embedding's data gradient and
-    ufnd_vit_unpatchify_attribution, to the pixels (vision).  Dropout is off.  Its activations live in buffers of its own, so a
-    forward_train waiting for its backward() is untouched.  It also runs on a FROZEN encoder (no arena bound): the bf16 W / W^T
+  * Input gradients (`forward_saved` / `input_grad`; explain.input_attribution).  The same `_chain` without the parameter gradients:
+    `_wgrad` returns at once and `_ln_bwd` gets no scratch, so there are no transposes, no weight-gradient product, no second
+    stream, LayerNorm backwards without dgamma / dbeta or a workspace, and nothing of the arena is looked up (the building blocks
+    take parameter keys, not gradient tensors).  It goes one hop further -- to the raw embedding sums (text) and, through the patch
+    embedding's data gradient and ufnd_vit_unpatchify_attribution, to the pixels (vision).  Dropout is off.  Its activations live in
+    buffers of its own, so a forward_train waiting for its backward() is untouched.  It also runs on a FROZEN encoder (no arena bound): the bf16 W / W^T
     copies and the stacked q|k|v biases are then built from `enc._w` on first use and again when `weights_version` moves; nothing
     of the encoder is written either way."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib as L
-from .encoders import dropout_prob
+from .encoders import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, dropout_prob
 from .state import StepStateBuffer
 
-ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_GELU_BWD, ACT_QUICK_GELU_BWD = 0, 1, 2, 3, 4
+ACT_GELU_BWD, ACT_QUICK_GELU_BWD = 3, 4            # (ufnd_gemm_bf16_dgrad's epilogues; the forward's three are encoders.py's)
 
 # dropout stream tags (csrc/common.hpp: UFND_TAG_TEXT, UFND_TAG_VISION)
 TAG_TEXT, TAG_VISION = 256, 4096
@@ -65,6 +68,13 @@ def vision_tag(layer: int) -> int:
 
 def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+def _cast_operands(m2: torch.Tensor, wb: torch.Tensor, wt: torch.Tensor, s) -> None:
+    """bf16 W (wb) and W^T (wt) of one Linear from its fp32 master as a matrix (m2)."""
+    L.check(L.lib().ufnd_cast_bf16(m2.data_ptr(), wb.data_ptr(), m2.numel(), s), "ufnd_cast_bf16")
+    L.check(L.lib().ufnd_transpose_bf16(m2.data_ptr(), 1, m2.shape[0], m2.shape[1], m2.stride(0), wt.data_ptr(), wt.stride(0), m2.shape[0],
+                                        None, None, 0, s), "ufnd_transpose_bf16")
 
 
 class _Backprop:
@@ -173,34 +183,32 @@ class _Backprop:
         return k
 
     def master(self, keys: List[str]) -> torch.Tensor:
-        return self._stacked(self.arena.data, keys)
+        """A master tensor (or adjacent ones stacked): the arena's view, or -- frozen -- the encoder's own."""
+        if self.arena is not None:
+            return self._stacked(self.arena.data, keys)
+        return self.enc._w[keys[0]] if len(keys) == 1 else self._frozen()["stacked"][keys[0]]
+
+    def grad(self, keys: List[str]) -> torch.Tensor:
+        return self._stacked(self.arena.ensure_grad(), keys)
 
     def _frozen(self) -> dict:
         """No arena bound (a frozen encoder): {"ops": linear name -> (W bf16, W^T bf16), "stacked": first key -> the q|k|v biases as
         one vector}, cast from `enc._w` once per `weights_version`.  Reads the encoder only."""
         e = self.enc
         if self._fz is None or self._fz["version"] != e.weights_version:
-            w, s, lib = e._w, L.stream_ptr(e.device), L.lib()
+            w, s = e._w, L.stream_ptr(e.device)
             ops, stacked = {}, {}
             for name, (wk, bk) in self.linears().items():
                 m = w[wk[0]] if len(wk) == 1 else torch.cat([w[k] for k in wk], 0)
                 m2 = m.reshape(m.shape[0], -1).contiguous()
                 wb = torch.empty(m2.shape, dtype=torch.bfloat16, device=m2.device)
                 wt = torch.empty((m2.shape[1], m2.shape[0]), dtype=torch.bfloat16, device=m2.device)
-                L.check(lib.ufnd_cast_bf16(m2.data_ptr(), wb.data_ptr(), m2.numel(), s), "ufnd_cast_bf16")
-                L.check(lib.ufnd_transpose_bf16(m2.data_ptr(), 1, m2.shape[0], m2.shape[1], m2.stride(0), wt.data_ptr(), wt.stride(0), m2.shape[0],
-                                                None, None, 0, s), "ufnd_transpose_bf16")
+                _cast_operands(m2, wb, wt, s)
                 ops[name] = (wb, wt)
                 if bk is not None and len(bk) > 1:
                     stacked[bk[0]] = torch.cat([w[k] for k in bk], 0).contiguous()
             self._fz = {"version": e.weights_version, "ops": ops, "stacked": stacked}
         return self._fz
-
-    def _m(self, keys: List[str]) -> torch.Tensor:
-        """A master tensor (or adjacent ones stacked): the arena's view, or -- frozen -- the encoder's own."""
-        if self.arena is not None:
-            return self._stacked(self.arena.data, keys)
-        return self.enc._w[keys[0]] if len(keys) == 1 else self._frozen()["stacked"][keys[0]]
 
     def _op(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """(W bf16, W^T bf16) of a Linear: the trained copies, or the frozen ones."""
@@ -213,19 +221,20 @@ class _Backprop:
             self._xbufs = (key, make())
         return self._xbufs[1]
 
-    def _begin_saved(self) -> None:
+    def _save_bufs(self, *shape: int) -> dict:
+        """forward_train's buffers of a batch shape (kept: one set per shape seen)."""
+        key = ("save",) + shape
+        if key not in self._scratch:
+            self._scratch[key] = self._make_bufs(*shape)
+        return self._scratch[key]
+
+    def _begin(self, train: bool) -> None:
+        """Start of a forward: a bound encoder has its operand copies; only forward_saved may run without an arena (_frozen())."""
         self.enc._require_hip()
+        if train and self.arena is None:
+            raise RuntimeError("forward_train() before bind(): the parameter gradients go to an arena")
         if self.arena is not None and not self._ops:
             self.refresh_operands()
-
-    def _ln_bwd_data(self, x, ldx, gamma, dy, dx_f32, dx_bf16, lddx, M, add=None) -> None:
-        """A LayerNorm backward's data gradient alone: no dgamma / dbeta, no workspace, nothing deferred."""
-        L.check(L.lib().ufnd_layernorm_bwd(x.data_ptr(), ldx, gamma.data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add),
-                                           add.stride(0) if add is not None else 0, L.ptr(dx_f32), L.ptr(dx_bf16), lddx, None, None, None, 0,
-                                           M, self.enc.hidden, self.enc.eps, L.stream_ptr(x.device)), "ufnd_layernorm_bwd")
-
-    def grad(self, keys: List[str]) -> torch.Tensor:
-        return self._stacked(self.arena.ensure_grad(), keys)
 
     def refresh_operands(self) -> None:
         """bf16 W and W^T of every Linear from the fp32 masters (after an optimizer step; captured-graph safe: fixed buffers): ONE
@@ -233,7 +242,6 @@ class _Backprop:
         the rest."""
         s = L.stream_ptr(self.enc.device)
         if self._refresh is None:
-            import ctypes as C
             items, rest, tile0 = [], [], 0
             for name, (wk, _) in self.linears().items():
                 m = self.master(wk)
@@ -263,11 +271,7 @@ class _Backprop:
             L.check(L.lib().ufnd_refresh_operands(table.data_ptr(), n_items, tiles, s), "ufnd_refresh_operands")
         for name in rest:
             m = self.master(self.linears()[name][0])
-            m2 = m.reshape(m.shape[0], -1)
-            wb, wt = self._ops[name]
-            L.check(L.lib().ufnd_cast_bf16(m2.data_ptr(), wb.data_ptr(), m2.numel(), s), "ufnd_cast_bf16")
-            L.check(L.lib().ufnd_transpose_bf16(m2.data_ptr(), 1, m2.shape[0], m2.shape[1], m2.stride(0), wt.data_ptr(), wt.stride(0), m2.shape[0],
-                                                None, None, 0, s), "ufnd_transpose_bf16")
+            _cast_operands(m.reshape(m.shape[0], -1), *self._ops[name], s)
 
     # ------------------------------------------------------------------ scratch
     def _bwd_scratch(self, M: int, widths: Tuple[int, ...]) -> dict:
@@ -300,12 +304,15 @@ class _Backprop:
                                              aux.stride(0) if aux is not None else 0, out_bf16.stride(0) if out_bf16 is not None else 0,
                                              out_f32.stride(0) if out_f32 is not None else 0, act, L.stream_ptr(dy.device)), "ufnd_gemm_bf16_dgrad")
 
-    def _wgrad(self, sc: dict, dy, x, dW: torch.Tensor, db: Optional[torch.Tensor]) -> None:
-        """dW (N, K) = dy (M, N)^T x (M, K); db (N) = column sums of dy.  (Overwrites: every step writes every gradient.)  Three
+    def _wgrad(self, sc: Optional[dict], dy, x, wk: List[str], bk: Optional[List[str]]) -> None:
+        """The gradients of a Linear's weight (keys wk) and bias (keys bk, or None): dW (N, K) = dy (M, N)^T x (M, K); db (N) = column
+        sums of dy.  (Overwrites: every step writes every gradient.)  sc None -- a pass without parameter gradients -- does nothing.  Three
         launches (ufnd_linear_wgrad): both transposes on the caller's stream -- dy may be overwritten behind them -- then the sliced NT
         product and one finish pass (which also carries a pending LayerNorm's dgamma / dbeta finish) on a SECOND stream, beside the
         data-gradient chain that continues on the caller's: the weight gradients are not on backward's critical path.  join_wgrad() ends it."""
-        import ctypes as C
+        if sc is None:
+            return
+        dW, db = self.grad(wk), self.grad(bk) if bk is not None else None
         M, N = dy.shape
         K = x.shape[1]
         lib, dev = L.lib(), dy.device
@@ -348,35 +355,39 @@ class _Backprop:
 
     def _flush_ln(self) -> None:
         """A deferred LayerNorm finish that no Linear picked up (the next kernel is another LayerNorm backward, or the backward ends)."""
-        import ctypes as C
         if self._pending_ln is not None:
             job, self._pending_ln = self._pending_ln, None
             L.check(L.lib().ufnd_row_partials_finish(C.byref(job[0]), 0, L.stream_ptr(self.enc.device)), "ufnd_row_partials_finish")
             job[1]["ln_busy"][job[2]] = None            # (stream order protects the buffer)
 
-    def _ln_bwd(self, sc: dict, x, ldx, gamma, dy, dx_f32, dx_bf16, lddx, dgamma, dbeta, M, add=None, drop=None, where=0):
-        """drop (a ufnd_dropout) / where (L.LN_BWD_DROP_DXB or _DY): the mask of a dropout site at this LayerNorm."""
-        import ctypes as C
+    def _ln_bwd(self, sc: Optional[dict], x, ldx, gk: List[str], bk: List[str], dy, dx_f32, dx_bf16, lddx, M, add=None, drop=None, where=0):
+        """Backward of the LayerNorm with gain gk / bias bk (keys).  With a scratch its dgamma / dbeta go to the arena's gradients, their
+        finish deferred (_pending_ln); sc None: the data gradient alone -- no dgamma / dbeta, no workspace, nothing deferred.
+        drop (a ufnd_dropout) / where (L.LN_BWD_DROP_DXB or _DY): the mask of a dropout site at this LayerNorm."""
         H = self.enc.hidden
-        self._flush_ln()                   # one pending job at a time: a LayerNorm backward right behind another one finishes the first here
-        kk = sc["ln_flip"]
-        sc["ln_flip"] ^= 1
-        if sc["ln_busy"][kk] is not None:  # the finish (on the weight-gradient stream) that read this workspace last
-            torch.cuda.current_stream(x.device).wait_event(sc["ln_busy"][kk])
-            sc["ln_busy"][kk] = None
-        ws = sc["ln"][kk]
-        args = (x.data_ptr(), ldx, gamma.data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add), add.stride(0) if add is not None else 0,
-                L.ptr(dx_f32), L.ptr(dx_bf16), lddx, L.ptr(dgamma), L.ptr(dbeta), ws.data_ptr(), L.PARTIALS_DEFER, M, H, self.enc.eps)
+        dgamma = dbeta = ws = None
+        if sc is not None:
+            self._flush_ln()               # one pending job at a time: a LayerNorm backward right behind another one finishes the first here
+            kk = sc["ln_flip"]
+            sc["ln_flip"] ^= 1
+            if sc["ln_busy"][kk] is not None:  # the finish (on the weight-gradient stream) that read this workspace last
+                torch.cuda.current_stream(x.device).wait_event(sc["ln_busy"][kk])
+                sc["ln_busy"][kk] = None
+            dgamma, dbeta, ws = self.grad(gk), self.grad(bk), sc["ln"][kk]
+        args = (x.data_ptr(), ldx, self.master(gk).data_ptr(), dy.data_ptr(), dy.stride(0), L.ptr(add), add.stride(0) if add is not None else 0,
+                L.ptr(dx_f32), L.ptr(dx_bf16), lddx, L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), L.PARTIALS_DEFER if sc is not None else 0, M, H,
+                self.enc.eps)
         if drop is None:
             L.check(L.lib().ufnd_layernorm_bwd(*args, L.stream_ptr(x.device)), "ufnd_layernorm_bwd")
         else:
             L.check(L.lib().ufnd_layernorm_bwd_dropout(*args, C.byref(drop), where, L.stream_ptr(x.device)), "ufnd_layernorm_bwd_dropout")
+        if sc is None:
+            return
         job = L.PartialsJob()
         job.part, job.nblk, job.H, job.out0, job.out1 = ws.data_ptr(), L.lib().ufnd_layernorm_bwd_blocks(M), H, dgamma.data_ptr(), dbeta.data_ptr()
         self._pending_ln = (job, sc, kk)
 
     def _attn_fwd(self, qkv, mask, ctx, lse, B, Lq, drop=None):
-        import ctypes as C
         args = (qkv.data_ptr(), L.ptr(mask), ctx.data_ptr(), lse.data_ptr(), B, Lq, self.enc.heads)
         if drop is None:
             L.check(L.lib().ufnd_attention_bf16_lse(*args, L.stream_ptr(qkv.device)), "ufnd_attention_bf16_lse")
@@ -384,7 +395,6 @@ class _Backprop:
             L.check(L.lib().ufnd_attention_bf16_lse_dropout(*args, C.byref(drop), L.stream_ptr(qkv.device)), "ufnd_attention_bf16_lse_dropout")
 
     def _attn_bwd(self, qkv, ctx, dctx, lse, mask, dqkv, ws, B, Lq, drop=None):
-        import ctypes as C
         args = (qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), L.ptr(mask), dqkv.data_ptr(), ws.data_ptr(), B, Lq, self.enc.heads)
         if drop is None:
             L.check(L.lib().ufnd_attention_bf16_bwd(*args, L.stream_ptr(qkv.device)), "ufnd_attention_bf16_bwd")
@@ -393,7 +403,6 @@ class _Backprop:
 
     def _drop_ln(self, x, d, gamma, beta, y, out_bf16, out_f32, M, drop) -> None:
         """y = x + m o d, out = LayerNorm(y) (a post-LN residual site with dropout on the dense output d)."""
-        import ctypes as C
         e = self.enc
         L.check(L.lib().ufnd_dropout_residual_layernorm(x.data_ptr(), x.stride(0), d.data_ptr(), d.stride(0), gamma.data_ptr(), beta.data_ptr(),
                                                         y.data_ptr(), L.ptr(out_bf16), L.ptr(out_f32), M, e.hidden, e.eps, C.byref(drop),
@@ -451,18 +460,10 @@ class TextBackprop(_Backprop):
                 "dpre": torch.empty(M, I, **bf), "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf),
                 "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(B, Lq, e.heads), **f32), "ds": torch.empty(M, H, **f32)}
 
-    def _save_bufs(self, B: int, Lq: int) -> dict:
-        key = ("save", B, Lq)
-        if key not in self._scratch:
-            self._scratch[key] = self._make_bufs(B, Lq)
-        return self._scratch[key]
-
     @torch.no_grad()
     def forward_train(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         e = self.enc
-        e._require_hip()
-        if not self._ops:
-            self.refresh_operands()
+        self._begin(True)
         ph = dropout_prob("hidden_dropout_prob", e.hidden_dropout_prob)
         pa = dropout_prob("attention_probs_dropout_prob", e.attention_probs_dropout_prob)
         if ph > 0.0 or pa > 0.0:
@@ -476,7 +477,7 @@ class TextBackprop(_Backprop):
         """forward_train without dropout, on a bound or a frozen encoder, keeping its activations for input_grad() in buffers of its
         own.  `sums` (B L, H) fp32: start from these raw embedding sums instead of embedding input_ids (a point of an integration
         path); they are read where they lie, also by input_grad()."""
-        self._begin_saved()
+        self._begin(False)
         B, Lq = attention_mask.shape
         sv = self._explain_bufs(("text", B, Lq), lambda: self._make_bufs(B, Lq))
         self.xsaved = self._forward(sv, input_ids, attention_mask, 0.0, 0.0, sums)
@@ -503,7 +504,6 @@ class TextBackprop(_Backprop):
                 raise RuntimeError(f"sums: expected a contiguous 16-byte aligned fp32 ({M},{H}) tensor on {dev}")
         x_f, x_b = sv["xf"], sv["layers"][0]["xb"]
         if ph > 0.0:
-            import ctypes as C
             L.check(lib.ufnd_layernorm_dropout(sm.data_ptr(), H, w["embeddings.LayerNorm.weight"].data_ptr(), w["embeddings.LayerNorm.bias"].data_ptr(),
                                                x_b.data_ptr(), x_f.data_ptr(), M, H, e.eps, C.byref(self._drop(ph, TAG_TEXT_EMB)), s), "ufnd_layernorm_dropout")
         else:
@@ -511,99 +511,88 @@ class TextBackprop(_Backprop):
         for i, a in enumerate(sv["layers"]):
             k = self._lk(i)
             wqkv, wo, w1, w2 = self._op(f"{i}.qkv")[0], self._op(f"{i}.o")[0], self._op(f"{i}.w1")[0], self._op(f"{i}.w2")[0]
-            self._gemm(a["xb"], wqkv, self._m(k["qkv_b"]), out_bf16=a["qkv"])
+            self._gemm(a["xb"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
             self._attn_fwd(a["qkv"], mask, a["ctx"], a["lse"], B, Lq, self._drop(pa, text_tag(i, SITE_ATTN)) if pa > 0.0 else None)
             if ph > 0.0:
-                self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=sv["d"])
-                self._drop_ln(x_f, sv["d"], self._m(k["g1"]), self._m(k["b1n"]), a["y1"], a["x1b"], sv["x1f"], M,
+                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=sv["d"])
+                self._drop_ln(x_f, sv["d"], self.master(k["g1"]), self.master(k["b1n"]), a["y1"], a["x1b"], sv["x1f"], M,
                               self._drop(ph, text_tag(i, SITE_ATTN_OUT)))
             else:
-                self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=a["y1"], residual=x_f)
-                e._ln(a["y1"], H, self._m(k["g1"]), self._m(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
-            self._gemm(a["x1b"], w1, self._m(k["b1"]), out_bf16=a["pre"])
+                self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["y1"], residual=x_f)
+                e._ln(a["y1"], H, self.master(k["g1"]), self.master(k["b1n"]), a["x1b"], sv["x1f"], M, H, e.eps)
+            self._gemm(a["x1b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
             _act(a["pre"], a["h"], ACT_GELU)
             nxt_b = sv["layers"][i + 1]["xb"] if i + 1 < e.layers else sv["xb_last"]
             if ph > 0.0:
-                self._gemm(a["h"], w2, self._m(k["b2"]), out_f32=sv["d"])
-                self._drop_ln(sv["x1f"], sv["d"], self._m(k["g2"]), self._m(k["b2n"]), a["y2"], nxt_b, x_f, M,
+                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=sv["d"])
+                self._drop_ln(sv["x1f"], sv["d"], self.master(k["g2"]), self.master(k["b2n"]), a["y2"], nxt_b, x_f, M,
                               self._drop(ph, text_tag(i, SITE_FFN_OUT)))
             else:
-                self._gemm(a["h"], w2, self._m(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
-                e._ln(a["y2"], H, self._m(k["g2"]), self._m(k["b2n"]), nxt_b, x_f, M, H, e.eps)
+                self._gemm(a["h"], w2, self.master(k["b2"]), out_f32=a["y2"], residual=sv["x1f"])
+                e._ln(a["y2"], H, self.master(k["g2"]), self.master(k["b2n"]), nxt_b, x_f, M, H, e.eps)
         sv["hid"].copy_(x_f)
         L.check(lib.ufnd_masked_meanpool_l2(sv["hid"].data_ptr(), mask.data_ptr(), sv["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
         return {"B": B, "L": Lq, "ids": ids, "mask": mask, "sv": sv, "ph": ph, "pa": pa, "s": sm}
 
-    @torch.no_grad()
-    def input_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
-        """ds (B L, H): the gradient of the raw embedding sums (`xsaved["s"]`, before the embedding LayerNorm) from d / d features
-        (B, H), for the batch of the last forward_saved().  The layer chain of backward() without a single parameter gradient;
-        rows of masked tokens come out as zero.  The returned buffer is rewritten by the next call of the same shape."""
-        e, st = self.enc, self.xsaved
-        if st is None:
-            raise RuntimeError("input_grad() without forward_saved()")
-        B, Lq, mask, sv = st["B"], st["L"], st["mask"], st["sv"]
+    def _chain(self, st: dict, dfeat: torch.Tensor, params: bool) -> None:
+        """The backward of the batch kept in `st`, from d / d features (B, H) down to the raw embedding sums (sv["ds"]).  params: also
+        every parameter gradient (weight gradients beside the chain, deferred LayerNorm sums, the embedding tables), into the arena's
+        gradient buffer; without them no launch but the data gradients', and nothing of the arena is touched."""
+        e = self.enc
+        B, Lq, ids, mask, sv, ph, pa = st["B"], st["L"], st["ids"], st["mask"], st["sv"], st["ph"], st["pa"]
         M, H = B * Lq, e.hidden
-        dfeat = L.f32c(dfeat.to(e.device))
-        L.check(L.lib().ufnd_masked_meanpool_l2_bwd(sv["hid"].data_ptr(), mask.data_ptr(), dfeat.data_ptr(), sv["dx"].data_ptr(), B, Lq, H,
-                                                    L.stream_ptr(e.device)), "ufnd_masked_meanpool_l2_bwd")
-        dx = sv["dx"]
-        for i in reversed(range(e.layers)):
-            a, k = sv["layers"][i], self._lk(i)
-            self._ln_bwd_data(a["y2"], H, self._m(k["g2"]), dx, sv["dyf"], sv["dyb"], H, M)
-            self._dgrad(sv["dyb"], self._op(f"{i}.w2")[1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_GELU_BWD)
-            self._dgrad(sv["dpre"], self._op(f"{i}.w1")[1], out_f32=sv["dx1"], residual=sv["dyf"])
-            self._ln_bwd_data(a["y1"], H, self._m(k["g1"]), sv["dx1"], sv["dyf"], sv["dyb"], H, M)
-            self._dgrad(sv["dyb"], self._op(f"{i}.o")[1], out_bf16=sv["dctx"])
-            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], mask, sv["dqkv"], sv["aws"], B, Lq)
-            self._dgrad(sv["dqkv"], self._op(f"{i}.qkv")[1], out_f32=dx, residual=sv["dyf"])
-        self._ln_bwd_data(st["s"], H, self._m(["embeddings.LayerNorm.weight"]), dx, sv["ds"], None, H, M)
-        return sv["ds"]
-
-    @torch.no_grad()
-    def backward(self, dfeat: torch.Tensor) -> None:
-        """Gradients of every encoder parameter (into the arena's gradient buffer) from d loss / d features (B, H)."""
-        e, st = self.enc, self.saved
-        if st is None:
-            raise RuntimeError("backward() without forward_train()")
-        B, Lq, ids, mask, sv = st["B"], st["L"], st["ids"], st["mask"], st["sv"]
-        ph, pa = st["ph"], st["pa"]
-        M, H, I = B * Lq, e.hidden, e.inter
         DXB = L.LN_BWD_DROP_DXB
-        sc = self._bwd_scratch(M, (H, 3 * H, I))
+        sc = self._bwd_scratch(M, (H, 3 * H, e.inter)) if params else None
         s = L.stream_ptr(e.device)
-        dfeat = L.f32c(dfeat)
+        dfeat = L.f32c(dfeat.to(e.device))
         L.check(L.lib().ufnd_masked_meanpool_l2_bwd(sv["hid"].data_ptr(), mask.data_ptr(), dfeat.data_ptr(), sv["dx"].data_ptr(), B, Lq, H, s),
                 "ufnd_masked_meanpool_l2_bwd")
         dx = sv["dx"]
         for i in reversed(range(e.layers)):
             a, k = sv["layers"][i], self._lk(i)
-            ops = {n: self._ops[f"{i}.{n}"] for n in ("qkv", "o", "w1", "w2")}
             # output.LayerNorm, output.dense, GELU, intermediate.dense
-            self._ln_bwd(sc, a["y2"], H, self.master(k["g2"]), dx, sv["dyf"], sv["dyb"], H, self.grad(k["g2"]), self.grad(k["b2n"]), M,
+            self._ln_bwd(sc, a["y2"], H, k["g2"], k["b2n"], dx, sv["dyf"], sv["dyb"], H, M,
                          drop=self._drop(ph, text_tag(i, SITE_FFN_OUT)) if ph > 0.0 else None, where=DXB)
-            self._wgrad(sc, sv["dyb"], a["h"], self.grad(k["w2"]), self.grad(k["b2"]))
-            self._dgrad(sv["dyb"], ops["w2"][1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_GELU_BWD)
-            self._wgrad(sc, sv["dpre"], a["x1b"], self.grad(k["w1"]), self.grad(k["b1"]))
-            self._dgrad(sv["dpre"], ops["w1"][1], out_f32=sv["dx1"], residual=sv["dyf"])
+            self._wgrad(sc, sv["dyb"], a["h"], k["w2"], k["b2"])
+            self._dgrad(sv["dyb"], self._op(f"{i}.w2")[1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_GELU_BWD)
+            self._wgrad(sc, sv["dpre"], a["x1b"], k["w1"], k["b1"])
+            self._dgrad(sv["dpre"], self._op(f"{i}.w1")[1], out_f32=sv["dx1"], residual=sv["dyf"])
             # attention.output.LayerNorm, attention.output.dense, attention, q/k/v
-            self._ln_bwd(sc, a["y1"], H, self.master(k["g1"]), sv["dx1"], sv["dyf"], sv["dyb"], H, self.grad(k["g1"]), self.grad(k["b1n"]), M,
+            self._ln_bwd(sc, a["y1"], H, k["g1"], k["b1n"], sv["dx1"], sv["dyf"], sv["dyb"], H, M,
                          drop=self._drop(ph, text_tag(i, SITE_ATTN_OUT)) if ph > 0.0 else None, where=DXB)
-            self._wgrad(sc, sv["dyb"], a["ctx"], self.grad(k["o_w"]), self.grad(k["o_b"]))
-            self._dgrad(sv["dyb"], ops["o"][1], out_bf16=sv["dctx"])
+            self._wgrad(sc, sv["dyb"], a["ctx"], k["o_w"], k["o_b"])
+            self._dgrad(sv["dyb"], self._op(f"{i}.o")[1], out_bf16=sv["dctx"])
             self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], mask, sv["dqkv"], sv["aws"], B, Lq,
                            self._drop(pa, text_tag(i, SITE_ATTN)) if pa > 0.0 else None)
-            self._wgrad(sc, sv["dqkv"], a["xb"], self.grad(k["qkv_w"]), self.grad(k["qkv_b"]))
-            self._dgrad(sv["dqkv"], ops["qkv"][1], out_f32=dx, residual=sv["dyf"])
-        # embeddings: LayerNorm backward to the raw sums, then the three tables
+            self._wgrad(sc, sv["dqkv"], a["xb"], k["qkv_w"], k["qkv_b"])
+            self._dgrad(sv["dqkv"], self._op(f"{i}.qkv")[1], out_f32=dx, residual=sv["dyf"])
+        # embeddings: LayerNorm backward to the raw sums (forward_saved's may be the caller's), then the three tables
         ek = "embeddings."
-        self._ln_bwd(sc, sv["s"], H, self.master([ek + "LayerNorm.weight"]), dx, sv["ds"], None, H, self.grad([ek + "LayerNorm.weight"]),
-                     self.grad([ek + "LayerNorm.bias"]), M, drop=self._drop(ph, TAG_TEXT_EMB) if ph > 0.0 else None, where=L.LN_BWD_DROP_DY)
-        L.check(L.lib().ufnd_bert_embed_bwd(ids.data_ptr(), sv["ds"].data_ptr(), self.grad([ek + "word_embeddings.weight"]).data_ptr(),
-                                            self.grad([ek + "position_embeddings.weight"]).data_ptr(), self.grad([ek + "token_type_embeddings.weight"]).data_ptr(),
-                                            B, Lq, H, e.vocab, e.max_position, self.master([ek + "token_type_embeddings.weight"]).shape[0], s), "ufnd_bert_embed_bwd")
-        self._flush_ln()                   # (the embedding LayerNorm's dgamma / dbeta: no Linear follows it)
-        self.join_wgrad()
+        self._ln_bwd(sc, st["s"], H, [ek + "LayerNorm.weight"], [ek + "LayerNorm.bias"], dx, sv["ds"], None, H, M,
+                     drop=self._drop(ph, TAG_TEXT_EMB) if ph > 0.0 else None, where=L.LN_BWD_DROP_DY)
+        if params:
+            L.check(L.lib().ufnd_bert_embed_bwd(ids.data_ptr(), sv["ds"].data_ptr(), self.grad([ek + "word_embeddings.weight"]).data_ptr(),
+                                                self.grad([ek + "position_embeddings.weight"]).data_ptr(), self.grad([ek + "token_type_embeddings.weight"]).data_ptr(),
+                                                B, Lq, H, e.vocab, e.max_position, self.master([ek + "token_type_embeddings.weight"]).shape[0], s), "ufnd_bert_embed_bwd")
+            self._flush_ln()               # (the embedding LayerNorm's dgamma / dbeta: no Linear follows it)
+            self.join_wgrad()
+
+    @torch.no_grad()
+    def input_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
+        """ds (B L, H): the gradient of the raw embedding sums (`xsaved["s"]`, before the embedding LayerNorm) from d / d features
+        (B, H), for the batch of the last forward_saved(): the chain without a single parameter gradient; rows of masked tokens
+        come out as zero.  The returned buffer is rewritten by the next call of the same shape."""
+        if self.xsaved is None:
+            raise RuntimeError("input_grad() without forward_saved()")
+        self._chain(self.xsaved, dfeat, False)
+        return self.xsaved["sv"]["ds"]
+
+    @torch.no_grad()
+    def backward(self, dfeat: torch.Tensor) -> None:
+        """Gradients of every encoder parameter (into the arena's gradient buffer) from d loss / d features (B, H)."""
+        if self.saved is None:
+            raise RuntimeError("backward() without forward_train()")
+        self._chain(self.saved, dfeat, True)
 
 
 # =============================================================================================
@@ -660,12 +649,6 @@ class VisualBackprop(_Backprop):
                 "dctx": torch.empty(M, H, **bf), "dqkv": torch.empty(M, 3 * H, **bf), "ds": torch.empty(M, H, **f32),
                 "dpe": torch.empty(NP, H, **bf), "aws": torch.empty(L.lib().ufnd_attention_bwd_workspace_floats(N, T, e.heads), **f32)}
 
-    def _save_bufs(self, B: int, Fr: int) -> dict:
-        key = ("save", B, Fr)
-        if key not in self._scratch:
-            self._scratch[key] = self._make_bufs(B, Fr)
-        return self._scratch[key]
-
     def _frames5(self, frames: torch.Tensor) -> torch.Tensor:
         if frames.dim() == 4:
             frames = frames[:, None]
@@ -677,9 +660,7 @@ class VisualBackprop(_Backprop):
     @torch.no_grad()
     def forward_train(self, frames: torch.Tensor) -> torch.Tensor:
         e = self.enc
-        e._require_hip()
-        if not self._ops:
-            self.refresh_operands()
+        self._begin(True)
         frames = self._frames5(frames)
         pa = dropout_prob("attention_dropout", e.attention_dropout)
         if pa > 0.0:
@@ -691,7 +672,7 @@ class VisualBackprop(_Backprop):
     def forward_saved(self, frames: torch.Tensor) -> torch.Tensor:
         """forward_train without dropout, on a bound or a frozen encoder, keeping its activations for input_grad() in buffers of its
         own."""
-        self._begin_saved()
+        self._begin(False)
         frames = self._frames5(frames)
         B, Fr = frames.shape[:2]
 
@@ -718,53 +699,82 @@ class VisualBackprop(_Backprop):
         for i, a in enumerate(sv["layers"]):
             k = self._lk(i)
             wqkv, wo, w1, w2 = self._op(f"{i}.qkv")[0], self._op(f"{i}.o")[0], self._op(f"{i}.w1")[0], self._op(f"{i}.w2")[0]
-            e._ln(a["xin"], H, self._m(k["g1"]), self._m(k["b1n"]), a["h1b"], None, M, H, e.eps)
-            self._gemm(a["h1b"], wqkv, self._m(k["qkv_b"]), out_bf16=a["qkv"])
+            e._ln(a["xin"], H, self.master(k["g1"]), self.master(k["b1n"]), a["h1b"], None, M, H, e.eps)
+            self._gemm(a["h1b"], wqkv, self.master(k["qkv_b"]), out_bf16=a["qkv"])
             self._attn_fwd(a["qkv"], None, a["ctx"], a["lse"], N, T, self._drop(pa, vision_tag(i)) if pa > 0.0 else None)
-            self._gemm(a["ctx"], wo, self._m(k["o_b"]), out_f32=a["xmid"], residual=a["xin"])
-            e._ln(a["xmid"], H, self._m(k["g2"]), self._m(k["b2n"]), a["h2b"], None, M, H, e.eps)
-            self._gemm(a["h2b"], w1, self._m(k["b1"]), out_bf16=a["pre"])
+            self._gemm(a["ctx"], wo, self.master(k["o_b"]), out_f32=a["xmid"], residual=a["xin"])
+            e._ln(a["xmid"], H, self.master(k["g2"]), self.master(k["b2n"]), a["h2b"], None, M, H, e.eps)
+            self._gemm(a["h2b"], w1, self.master(k["b1"]), out_bf16=a["pre"])
             _act(a["pre"], a["m"], ACT_QUICK_GELU)
             nxt = sv["layers"][i + 1]["xin"] if i + 1 < e.layers else sv["xout"]
-            self._gemm(a["m"], w2, self._m(k["b2"]), out_f32=nxt, residual=a["xmid"])
+            self._gemm(a["m"], w2, self.master(k["b2"]), out_f32=nxt, residual=a["xmid"])
         e._ln(sv["xout"], T * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], sv["pooled_b"], sv["pooled_f"], N, H, e.eps)
         self._gemm(sv["pooled_b"][:N], self._op("proj")[0], None, out_f32=sv["e"])
         L.check(lib.ufnd_l2norm_frames(sv["e"].data_ptr(), sv["feat"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames")
         return {"B": B, "F": Fr, "sv": sv, "pa": pa}
 
-    @torch.no_grad()
-    def patch_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
-        """(B F P, 3 p^2) fp32: the gradient of the patch matrix (ufnd_vit_patchify's layout) from d / d features (B, proj), for the
-        batch of the last forward_saved().  The layer chain of backward() without a single parameter gradient, then the patch
-        rows of the token-assembly backward through the patch embedding's data gradient.  Rewritten by the next call of the shape."""
-        e, st = self.enc, self.xsaved
-        if st is None:
-            raise RuntimeError("input_grad() without forward_saved()")
-        B, Fr, sv, V = st["B"], st["F"], st["sv"], self.V
+    def _chain(self, st: dict, dfeat: torch.Tensor, params: bool) -> None:
+        """The backward of the batch kept in `st`, from d / d features (B, proj) down to the patch embedding's output (sv["dpe"]).
+        params: also every parameter gradient, the patch embedding's weight included, into the arena's gradient buffer; without them
+        no launch but the data gradients', nothing of the arena is touched, and the walk goes one Linear further, to the patch
+        matrix (sv["dpatch"])."""
+        e = self.enc
+        B, Fr, sv, pa, V = st["B"], st["F"], st["sv"], st["pa"], self.V
         N, T, H = B * Fr, e.n_patches + 1, e.hidden
         M = N * T
+        sc = scp = sch = None
+        if params:
+            sc = self._bwd_scratch(M, (H, 3 * H, e.inter))
+            scp = self._bwd_scratch(N * e.n_patches, (H, 3 * e.patch ** 2))
+            sch = self._bwd_scratch(N, (e.proj, H))
         s, lib = L.stream_ptr(e.device), L.lib()
         dfeat = L.f32c(dfeat.to(e.device))
+        # frame pooling, projection (bias-free), post-LayerNorm on the CLS rows
         L.check(lib.ufnd_l2norm_frames_bwd(sv["e"].data_ptr(), dfeat.data_ptr(), sv["de"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames_bwd")
-        sv["de_b"][:N].copy_(sv["de"])
-        self._dgrad(sv["de_b"][:N], self._op("proj")[1], out_f32=sv["dpool"][:N])
+        de_b = sv["de_b"][:N]
+        de_b.copy_(sv["de"])
+        self._wgrad(sch, de_b, sv["pooled_b"][:N], ["visual_projection.weight"], None)
+        self._dgrad(de_b, self._op("proj")[1], out_f32=sv["dpool"][:N])
         dx = sv["dx"]
         dx.zero_()                       # only the CLS rows of the last layer's output carry a gradient
         sv["dxb"].zero_()
-        self._ln_bwd_data(sv["xout"], T * H, self._m([V + "post_layernorm.weight"]), sv["dpool"][:N], dx, sv["dxb"], T * H, N)
+        self._ln_bwd(sch, sv["xout"], T * H, [V + "post_layernorm.weight"], [V + "post_layernorm.bias"], sv["dpool"][:N], dx, sv["dxb"], T * H, N)
         for i in reversed(range(e.layers)):
             a, k = sv["layers"][i], self._lk(i)
+            # MLP branch: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
+            self._wgrad(sc, sv["dxb"], a["m"], k["w2"], k["b2"])
             self._dgrad(sv["dxb"], self._op(f"{i}.w2")[1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_QUICK_GELU_BWD)
+            self._wgrad(sc, sv["dpre"], a["h2b"], k["w1"], k["b1"])
             self._dgrad(sv["dpre"], self._op(f"{i}.w1")[1], out_f32=sv["dh"])
-            self._ln_bwd_data(a["xmid"], H, self._m(k["g2"]), sv["dh"], sv["dmid"], sv["dmidb"], H, M, add=dx)
+            self._ln_bwd(sc, a["xmid"], H, k["g2"], k["b2n"], sv["dh"], sv["dmid"], sv["dmidb"], H, M, add=dx)
+            # attention branch: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
+            self._wgrad(sc, sv["dmidb"], a["ctx"], k["o_w"], k["o_b"])
             self._dgrad(sv["dmidb"], self._op(f"{i}.o")[1], out_bf16=sv["dctx"])
-            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T)
+            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T,
+                           self._drop(pa, vision_tag(i)) if pa > 0.0 else None)
+            self._wgrad(sc, sv["dqkv"], a["h1b"], k["qkv_w"], k["qkv_b"])
             self._dgrad(sv["dqkv"], self._op(f"{i}.qkv")[1], out_f32=sv["dh"])
-            self._ln_bwd_data(a["xin"], H, self._m(k["g1"]), sv["dh"], dx, sv["dxb"], H, M, add=sv["dmid"])
-        self._ln_bwd_data(sv["s"], H, self._m([V + "pre_layrnorm.weight"]), dx, sv["ds"], None, H, M)
-        L.check(lib.ufnd_vit_assemble_bwd(sv["ds"].data_ptr(), None, None, sv["dpe"].data_ptr(), N, e.n_patches, H, s), "ufnd_vit_assemble_bwd")
-        self._dgrad(sv["dpe"], self._op("patch")[1], out_f32=sv["dpatch"])
-        return sv["dpatch"]
+            self._ln_bwd(sc, a["xin"], H, k["g1"], k["b1n"], sv["dh"], dx, sv["dxb"], H, M, add=sv["dmid"])
+        # pre-LayerNorm, token assembly, patch embedding
+        self._ln_bwd(sc, sv["s"], H, [V + "pre_layrnorm.weight"], [V + "pre_layrnorm.bias"], dx, sv["ds"], None, H, M)
+        dcls, dpos = (self.grad([V + "embeddings.class_embedding"]), self.grad([V + "embeddings.position_embedding.weight"])) if params else (None, None)
+        L.check(lib.ufnd_vit_assemble_bwd(sv["ds"].data_ptr(), L.ptr(dcls), L.ptr(dpos), sv["dpe"].data_ptr(), N, e.n_patches, H, s), "ufnd_vit_assemble_bwd")
+        if params:
+            self._wgrad(scp, sv["dpe"], sv["patches"], [V + "embeddings.patch_embedding.weight"], None)
+            self._flush_ln()
+            self.join_wgrad()
+        else:
+            self._dgrad(sv["dpe"], self._op("patch")[1], out_f32=sv["dpatch"])
+
+    @torch.no_grad()
+    def patch_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
+        """(B F P, 3 p^2) fp32: the gradient of the patch matrix (ufnd_vit_patchify's layout) from d / d features (B, proj), for the
+        batch of the last forward_saved(): the chain without a single parameter gradient, on through the patch rows of the
+        token-assembly backward and the patch embedding's data gradient.  Rewritten by the next call of the shape."""
+        if self.xsaved is None:
+            raise RuntimeError("patch_grad() without forward_saved()")
+        self._chain(self.xsaved, dfeat, False)
+        return self.xsaved["sv"]["dpatch"]
 
     @torch.no_grad()
     def input_grad(self, dfeat: torch.Tensor) -> torch.Tensor:
@@ -778,50 +788,7 @@ class VisualBackprop(_Backprop):
 
     @torch.no_grad()
     def backward(self, dfeat: torch.Tensor) -> None:
-        e, st = self.enc, self.saved
-        if st is None:
+        """Gradients of every encoder parameter (into the arena's gradient buffer) from d loss / d features (B, proj)."""
+        if self.saved is None:
             raise RuntimeError("backward() without forward_train()")
-        B, Fr, sv, V = st["B"], st["F"], st["sv"], self.V
-        N, T, H, I = B * Fr, e.n_patches + 1, e.hidden, e.inter
-        M, NP = N * T, N * e.n_patches
-        sc = self._bwd_scratch(M, (H, 3 * H, I))
-        scp = self._bwd_scratch(NP, (H, 3 * e.patch ** 2))
-        sch = self._bwd_scratch(N, (e.proj, H))
-        s, lib = L.stream_ptr(e.device), L.lib()
-        dfeat = L.f32c(dfeat)
-        # frame pooling, projection (bias-free), post-LayerNorm on the CLS rows
-        L.check(lib.ufnd_l2norm_frames_bwd(sv["e"].data_ptr(), dfeat.data_ptr(), sv["de"].data_ptr(), B, Fr, e.proj, s), "ufnd_l2norm_frames_bwd")
-        sv["de_b"][:N].copy_(sv["de"])
-        self._wgrad(sch, sv["de_b"][:N], sv["pooled_b"][:N], self.grad(["visual_projection.weight"]), None)
-        self._dgrad(sv["de_b"][:N], self._ops["proj"][1], out_f32=sv["dpool"][:N])
-        dx = sv["dx"]
-        dx.zero_()                       # only the CLS rows of the last layer's output carry a gradient
-        sv["dxb"].zero_()
-        self._ln_bwd(sch, sv["xout"], T * H, self.master([V + "post_layernorm.weight"]), sv["dpool"][:N], dx, sv["dxb"], T * H,
-                     self.grad([V + "post_layernorm.weight"]), self.grad([V + "post_layernorm.bias"]), N)
-        for i in reversed(range(e.layers)):
-            a, k = sv["layers"][i], self._lk(i)
-            ops = {n: self._ops[f"{i}.{n}"] for n in ("qkv", "o", "w1", "w2")}
-            # MLP branch: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
-            self._wgrad(sc, sv["dxb"], a["m"], self.grad(k["w2"]), self.grad(k["b2"]))
-            self._dgrad(sv["dxb"], ops["w2"][1], out_bf16=sv["dpre"], aux=a["pre"], act=ACT_QUICK_GELU_BWD)
-            self._wgrad(sc, sv["dpre"], a["h2b"], self.grad(k["w1"]), self.grad(k["b1"]))
-            self._dgrad(sv["dpre"], ops["w1"][1], out_f32=sv["dh"])
-            self._ln_bwd(sc, a["xmid"], H, self.master(k["g2"]), sv["dh"], sv["dmid"], sv["dmidb"], H, self.grad(k["g2"]), self.grad(k["b2n"]), M, add=dx)
-            # attention branch: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
-            self._wgrad(sc, sv["dmidb"], a["ctx"], self.grad(k["o_w"]), self.grad(k["o_b"]))
-            self._dgrad(sv["dmidb"], ops["o"][1], out_bf16=sv["dctx"])
-            self._attn_bwd(a["qkv"], a["ctx"], sv["dctx"], a["lse"], None, sv["dqkv"], sv["aws"], N, T,
-                           self._drop(st["pa"], vision_tag(i)) if st["pa"] > 0.0 else None)
-            self._wgrad(sc, sv["dqkv"], a["h1b"], self.grad(k["qkv_w"]), self.grad(k["qkv_b"]))
-            self._dgrad(sv["dqkv"], ops["qkv"][1], out_f32=sv["dh"])
-            self._ln_bwd(sc, a["xin"], H, self.master(k["g1"]), sv["dh"], dx, sv["dxb"], H, self.grad(k["g1"]), self.grad(k["b1n"]), M, add=sv["dmid"])
-        # pre-LayerNorm, token assembly, patch embedding
-        self._ln_bwd(sc, sv["s"], H, self.master([V + "pre_layrnorm.weight"]), dx, sv["ds"], None, H, self.grad([V + "pre_layrnorm.weight"]),
-                     self.grad([V + "pre_layrnorm.bias"]), M)
-        L.check(lib.ufnd_vit_assemble_bwd(sv["ds"].data_ptr(), self.grad([V + "embeddings.class_embedding"]).data_ptr(),
-                                          self.grad([V + "embeddings.position_embedding.weight"]).data_ptr(), sv["dpe"].data_ptr(), N, e.n_patches, H, s),
-                "ufnd_vit_assemble_bwd")
-        self._wgrad(scp, sv["dpe"], sv["patches"], self.grad([V + "embeddings.patch_embedding.weight"]), None)
-        self._flush_ln()
-        self.join_wgrad()
+        self._chain(self.saved, dfeat, True)
