@@ -38,8 +38,8 @@ int ufnd_abi_version(void);
  * from memory, never baked into launches).  Host initialises it with hipMemcpy.
  * ---------------------------------------------------------------------------------- */
 typedef struct ufnd_step_state {
-  uint64_t step;       /* optimizer steps taken so far (AdamW's t-1); ++ by ufnd_adamw_step */
-  uint64_t seed;       /* dropout key */
+  uint64_t step;       /* optimizer steps taken so far (AdamW's t-1); ++ by ufnd_step_advance / ufnd_clip_adamw_step */
+  uint64_t seed;       /* dropout key: every mask is drawn from (seed, step + ((uint64_t)micro << 40), layer tag, element) */
   float lr;            /* current learning rate (StepLR writes it between epochs) */
   float weight_decay;
   float beta1, beta2, eps;
@@ -49,7 +49,11 @@ typedef struct ufnd_step_state {
   float grad_norm;     /* out: global L2 norm (after grad_scale, before clipping) */
   float clip_coef;     /* out: min(1, max_norm / (grad_norm + 1e-6)) */
   float bc1, bc2_sqrt; /* out: 1-beta1^t, sqrt(1-beta2^t) for the step being applied */
-  float reserved[3];
+  uint32_t micro;      /* micro-batches already folded into the gradient accumulator since the last optimizer step: ++ by
+                        * ufnd_grad_accumulate (given the state), 0 again by whatever advances `step`.  Forward and backward of
+                        * micro-batch j of a group both run at micro == j, so its masks differ from every other micro-batch's
+                        * and from every other step's; 0 (always, without accumulation) leaves the key at `step` */
+  float reserved[2];
 } ufnd_step_state;
 
 /* ------------------------------------------------------------------------------------
@@ -249,7 +253,7 @@ int ufnd_softmax_ce_weighted(const float* logits, const int64_t* labels, int B, 
  *   ufnd_grad_norm : state->grad_norm = ||grad * grad_scale||_2, clip_coef, bias corrections
  *                    for step t = state->step + 1.  partials: >= 1024 floats scratch.
  *   ufnd_adamw_step: p *= 1 - lr*wd; m,v update with g = grad*grad_scale*clip_coef; p -= ...
- *   ufnd_step_advance: state->step += 1 (once per optimizer step, after every arena is done).
+ *   ufnd_step_advance: state->step += 1, state->micro = 0 (once per optimizer step, after every arena is done).
  * ---------------------------------------------------------------------------------- */
 int ufnd_grad_norm(const float* grad, size_t n, float* partials, ufnd_step_state* state, void* stream);
 int ufnd_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
@@ -261,6 +265,12 @@ int ufnd_step_advance(ufnd_step_state* state, void* stream);
  * are bit-identical to the three-call form. */
 int ufnd_clip_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float* partials,
                          ufnd_step_state* state, void* stream);
+/* Gradient accumulation over micro-batches: dst[i] = overwrite ? src[i] : dst[i] + src[i] over n floats (n % 4 == 0, both
+ * 16-byte aligned, not overlapping), one streaming launch.  With a state (may be NULL) the launch also does
+ * state->micro += 1: one more micro-batch is in the accumulator, and the next one draws other dropout masks.  Enqueue it
+ * behind everything that reads the masks of the micro-batch just finished (every side stream joined). */
+int ufnd_grad_accumulate(float* dst, const float* src, size_t n, int overwrite, ufnd_step_state* state /* may be NULL */,
+                         void* stream);
 
 /* ====================================================================================
  * Tier B -- the frozen, forward-only encoders that produce `text` and `visual`
@@ -789,7 +799,7 @@ int ufnd_vit_assemble_bwd(const float* ds, float* dcls, float* dpos, void* dpe_b
  * Every _dropout entry requires 0 < p < 1 (p = 0 is the entry without the suffix).
  * ---------------------------------------------------------------------------------- */
 typedef struct ufnd_dropout {
-  const ufnd_step_state* state; /* device: seed and step */
+  const ufnd_step_state* state; /* device: seed, step and micro (the key's step word is step + (micro << 40)) */
   float p;                      /* drop probability, 0 < p < 1 */
   uint32_t tag;                 /* the site's stream tag (ranges: csrc/common.hpp) */
 } ufnd_dropout;

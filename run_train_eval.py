@@ -36,6 +36,8 @@ def parse_args():
     p.add_argument("--eval_only", action="store_true")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic FakeSV-shaped samples")
     p.add_argument("--no_graph", action="store_true", help="launch kernels eagerly instead of replaying a hipGraph")
+    p.add_argument("--grad_accum_steps", type=int, default=1,
+                   help="micro-batches of --batch_size rows per optimizer step (gradient accumulation); 1 = off")
     return p.parse_args()
 
 
@@ -67,7 +69,7 @@ def main():
                       out_dir=str(out_dir), batch_size=args.batch_size, epochs=args.epochs, lr=args.lr,
                       weight_decay=args.weight_decay, gnn_dim=args.gnn_dim, gnn_overlap_thresh=args.gnn_overlap_thresh,
                       seed=args.seed, use_mps=False, use_gnn=(not args.no_gnn), save_best=True, device=f"cuda:{local}",
-                      use_graph=not args.no_graph)
+                      use_graph=not args.no_graph, grad_accum_steps=args.grad_accum_steps)
     cache = synthetic_cache(args.synthetic, seed=args.seed, gnn_dim=args.gnn_dim) if args.synthetic else None
     trainer = ForensicTrainer(cfg, cache=cache)
     if not args.eval_only:

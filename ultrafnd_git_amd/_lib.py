@@ -24,7 +24,7 @@ class StepState(C.Structure):
     _fields_ = [("step", C.c_uint64), ("seed", C.c_uint64), ("lr", C.c_float), ("weight_decay", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float),
                 ("grad_scale", C.c_float), ("loss", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
-                ("bc1", C.c_float), ("bc2_sqrt", C.c_float), ("reserved", C.c_float * 3)]
+                ("bc1", C.c_float), ("bc2_sqrt", C.c_float), ("micro", C.c_uint32), ("reserved", C.c_float * 2)]
 
 
 class Dims(C.Structure):
@@ -157,6 +157,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.ufnd_step_advance.argtypes = [P, P]
     lib.ufnd_clip_adamw_step.argtypes = [P, P, P, P, S, P, P, P]
     lib.ufnd_clip_adamw_step.restype = I
+    lib.ufnd_grad_accumulate.argtypes = [P, P, S, I, P, P]
+    lib.ufnd_grad_accumulate.restype = I
     for name in ("ufnd_fusion_forward", "ufnd_fusion_backward", "ufnd_classifier_forward", "ufnd_classifier_backward",
                  "ufnd_softmax_ce", "ufnd_grad_norm", "ufnd_adamw_step", "ufnd_step_advance"):
         getattr(lib, name).restype = I

@@ -50,6 +50,7 @@ class FlatArena:
         self.grad: torch.Tensor | None = None
         self.exp_avg: torch.Tensor | None = None
         self.exp_avg_sq: torch.Tensor | None = None
+        self.grad_acc: torch.Tensor | None = None      # gradient accumulator over micro-batches (FusedAdamW(accum_steps > 1) only)
 
     # views
     def _v(self, buf: torch.Tensor, key: str) -> torch.Tensor:
@@ -63,6 +64,12 @@ class FlatArena:
         if self.grad is None:
             self.grad = torch.zeros(self.n_grad, dtype=torch.float32, device=self.device)
         return self.grad
+
+    def ensure_grad_acc(self) -> torch.Tensor:
+        """The accumulator of the micro-batch gradients: the with-grad range once more (4 B per trainable parameter)."""
+        if self.grad_acc is None:
+            self.grad_acc = torch.zeros(self.n_grad, dtype=torch.float32, device=self.device)
+        return self.grad_acc
 
     def grad_view(self, key: str) -> torch.Tensor:
         o, shape = self.offsets[key]

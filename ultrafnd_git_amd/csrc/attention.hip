@@ -80,7 +80,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
   uint32_t drow[2] = {0u, 0u};      // DROP: the Philox counter of (query, key group 0) per query tile
   if constexpr (DROP) {
     dseed = dr.state->seed;
-    dstep = dr.state->step;
+    dstep = dropout_step_key(dr.state);
     const uint32_t lp4 = (uint32_t)(L + 3) >> 2;
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) drow[qt] = ((uint32_t)(b * heads + h) * (uint32_t)L + (uint32_t)qrow[qt]) * lp4 + (uint32_t)g;

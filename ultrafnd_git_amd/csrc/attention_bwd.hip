@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
   float kscale = 0.0f;
   if constexpr (DROP) {
     dseed = dr.state->seed;
-    dstep = dr.state->step;
+    dstep = dropout_step_key(dr.state);
     lp4 = (uint32_t)(L + 3) >> 2;
     bh0 = (uint32_t)(b * heads + h) * (uint32_t)L;
     kscale = 1.0f / (1.0f - dr.p);

@@ -181,11 +181,15 @@ __device__ __forceinline__ float dropout_keep(uint32_t r, float p) {
   const float u = (float)(r >> 8) * (1.0f / 16777216.0f);
   return (u >= p) ? 1.0f / (1.0f - p) : 0.0f;
 }
+// The step word of every mask draw.  Micro-batch j of a gradient-accumulation group runs at (step, micro = j): the optimizer
+// step moves only once per group, so `micro` goes into bits 40.. of the key (2^40 optimizer steps are out of reach).  At
+// micro == 0 -- always, without accumulation -- the key is `step` itself.
+__device__ __forceinline__ uint64_t dropout_step_key(const ufnd_step_state* st) { return st->step + ((uint64_t)st->micro << 40); }
 // multiplier applied to an activation: 0 (dropped) or 1/(1-p) (kept).  p == 0 -> 1.
 __device__ __forceinline__ float dropout_mul(const ufnd_step_state* st, float p, uint32_t layer, uint32_t elem) {
   if (p <= 0.0f) return 1.0f;
   uint32_t w[4];
-  philox_4x32(st->seed, st->step, layer, elem >> 2, w);
+  philox_4x32(st->seed, dropout_step_key(st), layer, elem >> 2, w);
   const uint32_t k = elem & 3u;
   return dropout_keep(k == 0 ? w[0] : (k == 1 ? w[1] : (k == 2 ? w[2] : w[3])), p);
 }
@@ -193,7 +197,7 @@ __device__ __forceinline__ float dropout_mul(const ufnd_step_state* st, float p,
 __device__ __forceinline__ void dropout_mul4(const ufnd_step_state* st, float p, uint32_t layer, uint32_t elem4, float (&m)[4]) {
   if (p <= 0.0f) { m[0] = m[1] = m[2] = m[3] = 1.0f; return; }
   uint32_t w[4];
-  philox_4x32(st->seed, st->step, layer, elem4 >> 2, w);
+  philox_4x32(st->seed, dropout_step_key(st), layer, elem4 >> 2, w);
 #pragma unroll
   for (int q = 0; q < 4; ++q) m[q] = dropout_keep(w[q], p);
 }

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void dropout_layernorm_kernel(const float* x, 
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
-  const uint64_t seed = dr.state->seed, step = dr.state->step;
+  const uint64_t seed = dr.state->seed, step = dropout_step_key(dr.state);
   f32x4 v[NI], m[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) {

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       g[i] = ld4(dy + (size_t)row * lddy + 4 * lane + 256 * i);
       if constexpr (DROPAT != 0) {
         float m4[4];
-        dropout_mul4_ctr(dr.state->seed, dr.state->step, dr.p, dr.tag, (uint32_t)(((size_t)row * H + 4 * lane + 256 * i) >> 2), m4);
+        dropout_mul4_ctr(dr.state->seed, dropout_step_key(dr.state), dr.p, dr.tag, (uint32_t)(((size_t)row * H + 4 * lane + 256 * i) >> 2), m4);
         dm[i] = f32x4{m4[0], m4[1], m4[2], m4[3]};
         if constexpr (DROPAT == UFND_LN_BWD_DROP_DY) g[i] *= dm[i];
       }

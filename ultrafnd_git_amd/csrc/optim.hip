@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
   }
 }
 
-__global__ void step_advance_kernel(ufnd_step_state* st) { st->step += 1; }
+__global__ void step_advance_kernel(ufnd_step_state* st) { st->step += 1; st->micro = 0; }      // a new step starts at micro-batch 0
 
 // ---- the whole optimizer step as TWO launches (ufnd_clip_adamw_step)
 // launch 1: the sum-of-squares partials, as above; its block 0 also advances the step counter, so that launch 2 reads
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void sumsq_advance_kernel(const float* g, size
   __syncthreads();
   if (threadIdx.x == 0) {
     partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    if (blockIdx.x == 0) st->step += 1;
+    if (blockIdx.x == 0) { st->step += 1; st->micro = 0; }
   }
 }
 // launch 2: every block repeats norm_finalize_kernel's fixed-order reduction of the partials (<= 1024 floats from L2: the
@@ -160,7 +160,48 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(float* p, const float* 
   }
 }
 
+// ---- gradient accumulation over micro-batches (ufnd_grad_accumulate): dst = src (the group's first micro-batch: 8 B per
+// element) or dst += src (12 B per element), streamed like the AdamW pass -- two elements' loads in flight before the first
+// store.  dst and src never alias (checked on the host).  Block 0 counts the micro-batch when it is given the state: the
+// next forward then draws its masks at another key (dropout_step_key).
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4, ufnd_step_state* st) {
+  f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
+  const size_t stride = (size_t)gridDim.x * 256;
+  size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    const size_t j = i + stride;
+    if constexpr (OVERWRITE) {
+      const f32x4 sa = s4[i], sb = s4[j];
+      d4[i] = sa; d4[j] = sb;
+    } else {
+      const f32x4 sa = s4[i], sb = s4[j], da = d4[i], db = d4[j];
+      d4[i] = da + sa; d4[j] = db + sb;
+    }
+  }
+  for (; i < n4; i += stride) {
+    if constexpr (OVERWRITE) d4[i] = s4[i];
+    else d4[i] = d4[i] + s4[i];
+  }
+  if (st != nullptr && blockIdx.x == 0 && threadIdx.x == 0) st->micro += 1;
+}
+
 }  // namespace
+
+extern "C" int ufnd_grad_accumulate(float* dst, const float* src, size_t n, int overwrite, ufnd_step_state* state, void* stream_) {
+  UFND_REQUIRE(dst && src && n > 0, "grad_accumulate: null argument");
+  UFND_REQUIRE(n % 4 == 0 && ufnd_aligned(dst, 16) && ufnd_aligned(src, 16), "grad_accumulate: n %% 4 == 0 and 16-B alignment required");
+  UFND_REQUIRE(dst + n <= src || src + n <= dst, "grad_accumulate: dst and src overlap");
+  size_t want = (n / 4 + 511) / 512;      // two float4 per thread and sweep, as the AdamW pass
+  const int blocks = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
+  if (overwrite)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, dst, src, n / 4, state);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, dst, src, n / 4, state);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
 
 extern "C" int ufnd_grad_norm(const float* grad, size_t n, float* partials, ufnd_step_state* state, void* stream_) {
   UFND_REQUIRE(grad && partials && state && n > 0, "grad_norm: null argument");

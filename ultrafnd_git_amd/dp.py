@@ -132,7 +132,12 @@ class GradReducer:
     [0, bounds[0]), [bounds[0], bounds[1]), ..., [bounds[-1], n).  `start(k)` begins reducing bucket k -- its
     gradients must be complete on the current stream; `finish()` makes the current stream wait for every started
     bucket.  Nothing happens at world size 1 unless force=True (runs the collectives anyway: the RCCL path on one GPU).
-    payload / algorithm: module docstring."""
+    payload / algorithm: module docstring.
+
+    Gradient accumulation: while `hold` is set the exchange is not `active` -- a micro-batch that is not its group's last runs
+    the single-rank form of the step and exchanges nothing.  For the last one the owner clears `hold` and sets
+    `before_bucket(lo, hi)`, which `start(k)` calls on the current stream in front of each bucket's reduction (the accumulator is
+    added into the bucket there): one exchange per optimizer step carries the group's sum."""
 
     def __init__(self, grad: torch.Tensor, group=None, bounds: Sequence[int] = (), force: bool = False,
                  payload: str = "fp32", algorithm: str = "all_reduce"):
@@ -151,10 +156,12 @@ class GradReducer:
         self._pending: list = []
         self._wire: Optional[torch.Tensor] = None        # bf16 payload: the rounded buckets (one buffer, bucket layout)
         self._shard: dict = {}                           # rs_ag: the reduced shard of each bucket
+        self.hold = False
+        self.before_bucket = None
 
     @property
     def active(self) -> bool:
-        return self.world > 1 or self.force
+        return (self.world > 1 or self.force) and not self.hold
 
     @property
     def grad_scale(self) -> float:
@@ -198,6 +205,8 @@ class GradReducer:
         if not self.active:
             return
         for lo, hi in (self.buckets if k is None else [self.buckets[k]]):
+            if self.before_bucket is not None:
+                self.before_bucket(lo, hi)
             w = self._reduce(lo, hi)
             if w is not None:
                 self._pending.append(w)

@@ -4,8 +4,11 @@
 Gradients are written by the kernels straight into the flat gradient arena; each parameter's
 `.grad` is bound to its arena view (the Functions return None for parameters, so autograd's
 accumulate step is skipped).  Consequence: a backward OVERWRITES the gradients, which equals
-the reference's `zero_grad(set_to_none=True)` + `backward()` sequence; accumulating several
-backward passes into one `.grad` is not supported on this path.
+the reference's `zero_grad(set_to_none=True)` + `backward()` sequence.  That holds for the bare
+modules' autograd path with accumulation too: several `backward()` calls do not add up in `.grad`.
+Gradient accumulation over micro-batches belongs to the optimizer and the trainer
+(`FusedAdamW(accum_steps=)` keeps a second arena and sums into it between backwards;
+`TrainConfig.grad_accum_steps`), after which `.grad` shows the group's sum, as torch's would.
 """
 from __future__ import annotations
 

@@ -297,12 +297,19 @@ class EncoderPipeline:
             b["temporal"].copy_(fallback)
 
     # ------------------------------------------------------------------ pipelined steps
+    def _no_accumulation(self, what: str) -> None:
+        k = getattr(self.optim, "accum_steps", 1)
+        if k > 1:
+            raise ValueError(f"{what}: the pipelined steps run the optimizer after every batch and do not accumulate gradients "
+                             f"(grad_accum_steps={k}); use train_step")
+
     def train_step_pipelined(self, batch: Dict[str, torch.Tensor], next_batch: Optional[Dict[str, torch.Tensor]]) -> dict:
         """train_step for raw batches whose features were started by prefetch_features():
           compute stream : wait features(i) -> head fwd/bwd(i) -> [all-reduce(i)] -> clip + AdamW(i)
           encoder streams: text(i+1) || visual(i+1), launched right after the head of i is enqueued
         so the head, the exchange and the optimizer of step i all hide behind the (frozen) encoders of
         step i+1.  Same arithmetic and order of parameter updates as train_step (bit-identical)."""
+        self._no_accumulation("train_step_pipelined")
         caller = torch.cuda.current_stream(self.device)
         hp = self._hp()
         hp.wait_stream(caller)
@@ -360,6 +367,7 @@ class EncoderPipeline:
         train_step does: G optimizer steps.  The next group's encoders are enqueued behind the first head.
         `on_step(b)` (optional) is called after every optimizer step with the step's static buffers (the epoch loop clones
         what its metrics need)."""
+        self._no_accumulation("train_group_pipelined")
         caller = torch.cuda.current_stream(self.device)
         hp = self._hp()
         hp.wait_stream(caller)

@@ -15,6 +15,8 @@ What is different, on purpose (SURVEY.md 3 "hot loops today", 8e):
   * loss / probabilities / forensic scalars stay on the device until the epoch ends (the
     reference syncs 5x per step, :301-313);
   * data parallel: batches are sharded over ranks, gradients all-reduced (dp.py);
+  * optional gradient accumulation (`TrainConfig.grad_accum_steps = k`): one optimizer step -- and one gradient exchange -- per k
+    micro-batches of batch_size rows, summed in a second arena between the backwards (optim.py);
   * optional `encode_inline`: raw token ids / frames go through the native BERT / ViT encoders
     inside the step (the north-star's "text+vision" step) instead of precomputed features.
 Where things live: data.py (device-resident split + loader), head_step.py (the head's forward / loss / backward on static
@@ -104,9 +106,17 @@ class TrainConfig:
     encoder_dropout: InitVar[Optional[float]] = None
     # the head's forward + CE and its backward as two C-ABI calls over both modules (21 launches, same bits); False: the five module-level calls (26)
     fused_head: bool = True
+    # gradient accumulation: one optimizer step per this many micro-batches of batch_size rows (effective batch = k x batch_size x
+    # world; the gradient applied is the mean of the micro-batches' mean-CE gradients).  1 = off: every path as before, bit for
+    # bit.  An init-only option kept as the attribute cfg.grad_accum_steps, like encoder_dropout.
+    grad_accum_steps: InitVar[int] = 1
 
-    def __post_init__(self, encoder_dropout: Optional[float]):
+    def __post_init__(self, encoder_dropout: Optional[float], grad_accum_steps: int = 1):
         self.encoder_dropout = None if encoder_dropout is None else dropout_prob("encoder_dropout", encoder_dropout)
+        k = grad_accum_steps
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+            raise ValueError(f"grad_accum_steps={k!r}: an integer >= 1 (micro-batches per optimizer step)")
+        self.grad_accum_steps = int(k)
 
 
 def apply_encoder_dropout(cfg: "TrainConfig", text_encoder, visual_encoder) -> None:
@@ -123,6 +133,10 @@ class ForensicTrainer:
         """`group`: a torch.distributed process group (None = the default one) or a dp.Collectives.  `force_exchange` runs the
         gradient exchange at world size 1 too (the RCCL path on one GPU: tests, bench --gpus 1 under torchrun)."""
         self.cfg = cfg
+        k_acc = int(cfg.grad_accum_steps)
+        if cfg.grad_exchange == "factors" and k_acc > 1:
+            raise ValueError('grad_exchange="factors" forms the Linear gradients from ONE micro-batch\'s factor panels and cannot '
+                             f'accumulate: grad_accum_steps={k_acc} needs grad_exchange "all_reduce" or "rs_ag"')
         os.makedirs(cfg.out_dir, exist_ok=True)
         self.device = torch.device(cfg.device)
         if self.device.type != "cuda":
@@ -180,6 +194,7 @@ class ForensicTrainer:
                              "gnn_feat to a head without the GNN slot (the reference silently ignores it; set use_gnn in both places alike)")
         # trainable encoders: their masters join the arena behind the head's, in gradient-ready order (text, then visual)
         self.text_bp = self.vis_bp = None
+        self._step_encoders = False      # the current group's micro-batches ran through the trainable encoders (_finish_micro_batch)
         self._enc_side = None      # second stream of the trainable-encoder step (visual encoder beside the text encoder)
         extra = []
         if cfg.train_encoders:
@@ -222,7 +237,7 @@ class ForensicTrainer:
             self._sync_encoder_operands()
         self.optim = FusedAdamW(self.arena, lr=cfg.lr, weight_decay=cfg.weight_decay,
                                 max_norm=cfg.grad_clip if cfg.grad_clip and cfg.grad_clip > 0 else 0.0,
-                                seed=cfg.seed + 1000 * self.rank, grad_scale=self.reducer.grad_scale)
+                                seed=cfg.seed + 1000 * self.rank, grad_scale=self.reducer.grad_scale, accum_steps=k_acc)
         if self.text_bp is not None:        # encoder dropout draws from the head's step state: one (seed, step) per rank and step
             self.text_bp.drop_state = self.vis_bp.drop_state = self.optim.state
         if cfg.use_cosine:
@@ -407,20 +422,72 @@ class ForensicTrainer:
             if self.reducer.active:
                 self.reducer.start(3)
         self.head.fwd_bwd(b, B, tail=tail)
-        self.reducer.finish()
-        self.optim.clip_and_step()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            self.vis_bp.refresh_operands()
-        self.text_bp.refresh_operands()
-        main.wait_stream(side)
-        self._enc_dirty = True
+        self._finish_micro_batch(encoders=True)      # (tail() joined the side stream: every mask of this micro-batch has been drawn)
         return {"loss": self.optim.state.float_view("loss"), "probs": b["probs"], "y": b["label"],
                 "forensic": b["forensic"], "logits": b["logits"]}
+
+    # ---- gradient accumulation (optim.py): what frames the backward of every train step
+    def _begin_micro_batch(self) -> None:
+        """In front of a micro-batch's forward.  A micro-batch that is not its group's last holds the exchange back (the step takes
+        its single-rank form); the last one releases it, with the accumulator folded into each bucket right before it leaves."""
+        o, r = self.optim, self.reducer
+        if o.accum_steps == 1:
+            return
+        r.hold = o.pending + 1 < o.accum_steps
+        r.before_bucket = None if r.hold else o.fold
+
+    def _finish_micro_batch(self, encoders: bool = False) -> None:
+        """Behind a micro-batch's backward, on the main stream with every side stream joined (the accumulate launch moves the
+        dropout key: it must follow the last mask draw of this micro-batch).  Either the gradients go into the accumulator, or --
+        last micro-batch of the group -- the group's sum is completed, exchanged and applied.  `encoders`: the micro-batch went
+        through the trainable encoders (their operand copies follow the optimizer step)."""
+        o, r = self.optim, self.reducer
+        self._step_encoders = encoders
+        if o.pending + 1 < o.accum_steps:
+            o.accumulate()
+            return
+        if o.accum_steps > 1 and not r.active:      # (with an active exchange start(k) folded bucket by bucket)
+            o.fold(0, self.arena.n_grad)
+        r.finish()
+        self._optimizer_step(o.pending + 1)
+
+    def _optimizer_step(self, micro_batches: int) -> None:
+        """clip + AdamW on arena.grad = the sum over `micro_batches` micro-batches [and ranks]; with trainable encoders, their
+        bf16 operands follow the masters (on optimizer steps only: between them the masters do not move)."""
+        o = self.optim
+        o.set_group(micro_batches)
+        o.clip_and_step()
+        o.pending = 0
+        if self._step_encoders:
+            main, side = torch.cuda.current_stream(self.device), self._enc_side
+            if side is None:
+                side = self._enc_side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                self.vis_bp.refresh_operands()
+            self.text_bp.refresh_operands()
+            main.wait_stream(side)
+            self._enc_dirty = True
+
+    def flush_accumulated(self) -> bool:
+        """The optimizer step on the micro-batches accumulated so far (a group cut short: end of an epoch), with the mean taken over
+        those k' < k; nothing when nothing is pending.  Every rank must call it after the same number of micro-batches: it runs
+        the gradient exchange.  Returns whether a step was taken."""
+        o, r = self.optim, self.reducer
+        if o.pending == 0:
+            return False
+        kp = o.pending
+        o.load_acc()
+        r.hold, r.before_bucket = False, None
+        r.start()
+        r.finish()
+        self._optimizer_step(kp)
+        return True
 
     def train_step(self, batch: Dict[str, torch.Tensor], split: str = "train") -> dict:
         """One iteration of the reference's train loop body (forensic_trainer.py:285-298):
         forward, CE, backward, [all-reduce], clip_grad_norm_, AdamW.step.  Returns device tensors."""
+        self._begin_micro_batch()
         if self.text_bp is not None and "input_ids" in batch:
             return self._train_step_encoders(batch)
         B = _batch_size(batch)
@@ -429,8 +496,7 @@ class ForensicTrainer:
         if self.gnn_model is not None:
             self._gnn_forward(b, batch, B, split, True)
         self.head.fwd_bwd(b, B, post=(lambda: self._gnn_backward(b, B)) if self.gnn_model is not None else None)
-        self.reducer.finish()
-        self.optim.clip_and_step()
+        self._finish_micro_batch()
         return {"loss": self.optim.state.float_view("loss"), "probs": b["probs"], "y": b["label"],
                 "forensic": b["forensic"], "logits": b["logits"]}
 
@@ -523,7 +589,7 @@ class ForensicTrainer:
         ys: List[torch.Tensor] = []
         p1s: List[torch.Tensor] = []
         fors: List[torch.Tensor] = []
-        lookahead = (is_train and self.cfg.encode_inline and int(self.cfg.encoder_lookahead) > 1 and self.cfg.use_graph and self.text_bp is None and
+        lookahead = (is_train and self.optim.accum_steps == 1 and self.cfg.encode_inline and int(self.cfg.encoder_lookahead) > 1 and self.cfg.use_graph and self.text_bp is None and
                      self.gnn_model is None and isinstance(loader, DeviceBatchLoader) and loader.dataset.ids_tok is not None and
                      loader.dataset.frames is not None and loader.dataset.G is not None)
         if lookahead:
@@ -548,6 +614,8 @@ class ForensicTrainer:
             ys.append(out["y"].clone())
             p1s.append(out["probs"][:, 1].clone())
             fors.append(f.clone())
+        if is_train:
+            self.flush_accumulated()     # (every rank saw the same number of batches: the collectives line up)
         if self.cfg.encode_inline:
             self.pipe.guard_flush()      # every pass evaluated the fold guard on the device; act on what has not been looked at yet
         if not losses and self.world == 1:
