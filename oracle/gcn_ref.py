@@ -103,7 +103,8 @@ def norm_adj(adj: torch.Tensor) -> torch.Tensor:
 
 
 def gcn_forward(w: Dict[str, torch.Tensor], x: torch.Tensor, adj: torch.Tensor, drop_mul: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """drop_mul: the dropout multiplier applied to gelu(lin1(.)) ((N,hid): 0 or 1/(1-p)); None = eval mode."""
+    """drop_mul: the explicit dropout mask of train mode, as the multiplier applied to gelu(lin1(.)) ((N,hid): 0 or 1/(1-p);
+    tests/dropout_mirror.multipliers with the GCN's tag 9, element row * hid + col and the module's step key); None = eval mode."""
     an = norm_adj(adj.float())
     h = F.gelu(F.linear(an @ x.float(), w["lin1.weight"], w["lin1.bias"]))
     if drop_mul is not None:
@@ -114,7 +115,7 @@ def gcn_forward(w: Dict[str, torch.Tensor], x: torch.Tensor, adj: torch.Tensor, 
 def pretrain(w: Dict[str, torch.Tensor], x: torch.Tensor, adj: torch.Tensor, head_w: torch.Tensor, head_b: torch.Tensor,
              epochs: int = 2, lr: float = 1e-3, weight_decay: float = 1e-4,
              drop_muls: Optional[Sequence[torch.Tensor]] = None) -> Tuple["OrderedDict[str, torch.Tensor]", List[float]]:
-    """forensic_trainer.py:214-224 with the dropout multipliers given explicitly (None = p 0).
+    """forensic_trainer.py:214-224 with the dropout multipliers given explicitly, one (N,hid) mask per epoch (None = p 0).
     Returns (updated weights, loss of every epoch)."""
     p = OrderedDict((k, v.clone().requires_grad_(True)) for k, v in w.items())
     opt = torch.optim.Adam(list(p.values()), lr=lr, weight_decay=weight_decay)

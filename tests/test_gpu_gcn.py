@@ -123,3 +123,55 @@ def test_trainer_builds_gnn_embeddings_from_ocr_sets():
     assert np.abs(tr.X.cpu().numpy() - G.node_features(cache["text"], cache["audio"], cache["visual"], cache["temporal"])).max() <= 1e-7
     loss, metrics = tr._epoch_loop(tr.train_loader, "train")
     assert np.isfinite(loss) and "auc" in metrics
+
+
+@pytest.mark.parametrize("n_nodes", [None, 33])
+def test_train_mode_steps_and_forward_match_the_oracle_run_with_the_mirrors_masks(n_nodes):
+    """SimpleGCN's real setting (p = 0.2): two pre-training steps, then a train-mode forward, against the oracle given the masks
+    the kernels should have drawn -- tag 9 (gcn.hip: LAYER_GCN), element row * hid + col, key (module seed, call counter).  The
+    forward draws the mask in the Linear's epilogue, the backward regenerates it in the aggregation product's epilogue: if the
+    two disagreed the loss and Z of step 1 would still match, the Adam update and everything after it would not."""
+    from tests import dropout_mirror as DM
+    from ultrafnd_git_amd.gcn import pretrain_gnn
+    import torch.nn as nn
+    z, n, sets, adj = _fixture()
+    X = torch.from_numpy(z["X"])
+    if n_nodes is not None:
+        n, adj, X = n_nodes, np.ascontiguousarray(adj[:n_nodes, :n_nodes]), X[:n_nodes].contiguous()
+    A = torch.from_numpy(adj)
+    hid, p = 256, 0.2
+    net = _gcn(z)
+    head = nn.Linear(128, 1)
+    with torch.no_grad():
+        head.weight.copy_(torch.from_numpy(z["head_w"])); head.bias.copy_(torch.from_numpy(z["head_b"]))
+    assert net.dropout == p and net._calls == 0
+    losses = pretrain_gnn(net, X.to(DEV), A.to(DEV), 128, epochs=2, head=head)
+    sd = {k: v.cpu() for k, v in net.state_dict().items()}
+    assert net.training
+    Z = net(X.to(DEV), A.to(DEV)).cpu()
+    assert net._calls == 3
+
+    w0 = G.seeded_weights(int(z["weight_seed"]))
+
+    def oracle(steps, ld=hid):
+        m = [torch.from_numpy(DM.multipliers(net._seed, s, 9, p, n, hid, ld)) for s in steps]
+        w2, ref_losses = G.pretrain(w0, X, A, torch.from_numpy(z["head_w"]), torch.from_numpy(z["head_b"]), epochs=2, drop_muls=m[:2])
+        return w2, ref_losses, G.gcn_forward(w2, X, A, m[2])
+
+    w2, ref_losses, ref_Z = oracle((1, 2, 3))
+    err_loss = np.abs(np.asarray(losses) - np.asarray(ref_losses)).max()
+    err_Z = (Z - ref_Z).abs().max().item()
+    print(f"gcn train mode N={n}: loss err {err_loss:.2e}, train-mode Z err {err_Z:.2e}")
+    assert err_loss <= 2e-6, (losses, ref_losses)
+    for k in w2:
+        upd_ref, upd = w2[k] - w0[k], sd[k] - w0[k]
+        e = (upd - upd_ref).abs().max().item()
+        print(f"  update {k}: err {e:.2e} (|update| max {upd_ref.abs().max().item():.2e})")
+        assert e <= 2e-5 + 0.02 * upd_ref.abs().max().item(), k
+    assert err_Z <= 1e-4
+    # negative controls: the masks of the next call, and the element index built with another row stride
+    for what, args in (("next step's masks", ((2, 3, 4),)), ("row stride hid + 4", ((1, 2, 3), hid + 4))):
+        _, bad_losses, bad_Z = oracle(*args)
+        frac = ((Z - bad_Z).abs() > 1e-4).float().mean().item()
+        print(f"  control, {what}: Z differs beyond the bound on {frac:.3f} of the elements")
+        assert frac >= 0.25, what

@@ -12,6 +12,32 @@ from ultrafnd_git_amd.build import DIAG_LIB, build_diag  # noqa: E402
 
 _d = None
 
+_FP = C.c_void_p
+
+
+class NtProb(C.Structure):      # csrc/gemm_f32.hpp
+    _fields_ = [("X", _FP), ("W", _FP), ("bias", _FP), ("Y", _FP), ("Z", _FP)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "ldx", "ldw", "ldy", "ldz", "act")] + \
+               [("drop_p", C.c_float), ("drop_layer", C.c_uint32), ("ksplit", C.c_int)]
+
+
+class NnProb(C.Structure):
+    _fields_ = [("dY", _FP), ("W", _FP), ("out", _FP), ("actZ", _FP), ("add", _FP)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "lddy", "ldw", "ldo", "ldz", "ldadd")] + \
+               [("drop_p", C.c_float), ("drop_layer", C.c_uint32), ("drop_ld", C.c_int), ("nsplit", C.c_int)]
+
+
+class TnProb(C.Structure):
+    _fields_ = [("dY", _FP), ("X", _FP), ("dW", _FP), ("db", _FP)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "lddy", "ldx", "ldw", "seg_rows", "seg_dy", "seg_x")]
+
+
+# enum GemmF32Form (csrc/gemm_f32.hpp), in its order
+GEMM_F32_FORMS = ("nt16<4>", "nt16<2>", "nt<1,4>", "nt<1,2>", "nt<2,4>", "nt<2,2>", "nn16", "nn<4>", "nn<2>", "nn<1>",
+                  "tn<4,0,0>", "tn<2,0,0>", "tn<-1,0,0>", "tn<4,1,0>", "tn<2,1,0>",
+                  "tn<4,0,1>", "tn<2,0,1>", "tn<-1,0,1>", "tn<4,1,1>", "tn<2,1,1>")
+GEMM_F32_KINDS = {"nt": (0, NtProb), "nn": (1, NnProb), "tn": (2, TnProb)}
+
 
 def diag() -> C.CDLL:
     global _d
@@ -31,6 +57,15 @@ def diag() -> C.CDLL:
         d.ufnd_diag_gemm_pp_stamps.restype = I
         d.ufnd_diag_where.argtypes = [P, I, C.c_uint64, P]
         d.ufnd_diag_where.restype = I
+        IP = C.POINTER(I)
+        d.ufnd_diag_gemm_f32_nt.argtypes = [C.POINTER(NtProb), I, P, IP, IP, P]
+        d.ufnd_diag_gemm_f32_nn.argtypes = [C.POINTER(NnProb), I, P, IP, IP, P]
+        d.ufnd_diag_gemm_f32_tn.argtypes = [C.POINTER(TnProb), I, IP, IP, P]
+        d.ufnd_diag_gemm_f32_plan.argtypes = [I, P, I, IP, IP]
+        for f in (d.ufnd_diag_gemm_f32_nt, d.ufnd_diag_gemm_f32_nn, d.ufnd_diag_gemm_f32_tn, d.ufnd_diag_gemm_f32_plan):
+            f.restype = I
+        d.ufnd_diag_gemm_f32_sizes.argtypes = [IP]
+        d.ufnd_diag_gemm_f32_sizes.restype = None
         _d = d
     return _d
 
@@ -38,3 +73,31 @@ def diag() -> C.CDLL:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed (code {rc}): {diag().ufnd_diag_last_error().decode()}")
+
+
+def gemm_f32_plan(kind: str, probs) -> tuple:
+    """Host-only validation + choice of a launch of the fp32 GEMM family: (rc, form name or None, grid, error text).  `probs` is
+    a list of NtProb / NnProb / TnProb; their pointers are never dereferenced (no GPU needed)."""
+    k, T = GEMM_F32_KINDS[kind]
+    arr = (T * max(1, len(probs)))(*probs)
+    form, grid = C.c_int(-1), C.c_int(0)
+    rc = diag().ufnd_diag_gemm_f32_plan(k, C.cast(arr, C.c_void_p), len(probs), C.byref(form), C.byref(grid))
+    if rc != 0:
+        return rc, None, 0, diag().ufnd_diag_last_error().decode()
+    return 0, GEMM_F32_FORMS[form.value], grid.value, ""
+
+
+def gemm_f32_launch(kind: str, probs, state_ptr, stream) -> tuple:
+    """Launch nt / nn / tn on `stream` (state_ptr: device ufnd_step_state or None; ignored by tn).  Returns (form name, grid)."""
+    k, T = GEMM_F32_KINDS[kind]
+    arr = (T * len(probs))(*probs)
+    form, grid = C.c_int(-1), C.c_int(0)
+    d = diag()
+    if kind == "nt":
+        rc = d.ufnd_diag_gemm_f32_nt(arr, len(probs), state_ptr, C.byref(form), C.byref(grid), stream)
+    elif kind == "nn":
+        rc = d.ufnd_diag_gemm_f32_nn(arr, len(probs), state_ptr, C.byref(form), C.byref(grid), stream)
+    else:
+        rc = d.ufnd_diag_gemm_f32_tn(arr, len(probs), C.byref(form), C.byref(grid), stream)
+    check(rc, f"ufnd_diag_gemm_f32_{kind}")
+    return GEMM_F32_FORMS[form.value], grid.value

@@ -628,13 +628,15 @@ __global__ __launch_bounds__(256) void tn_kernel(const TnArgs args) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
-// host launchers (argument checks guard every assumption the kernels make)
+// host launchers (argument checks guard every assumption the kernels make).  Each launcher is two steps: choose_* validates the
+// problems, fills the kernel arguments and names the instantiation and its grid without touching the device; run_* launches it.
 // ------------------------------------------------------------------------------------------
-int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream) {
+namespace {
+
+int choose_nt(const NtProb* probs, int nprob, NtArgs& a, GemmF32Form* form, int* grid) {
   UFND_REQUIRE(nprob >= 1 && nprob <= UFND_GEMM_MAX_PROB, "nt: %d problems", nprob);
-  NtArgs a;
+  UFND_REQUIRE(probs, "nt: null problem array");
   a.nprob = nprob;
-  a.st = st;
   int total = 0, maxM = 0;
   bool vec4 = true;
   for (int i = 0; i < nprob; ++i) {
@@ -666,9 +668,8 @@ int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStre
         total += (a.p[i].N / 16) * ufnd_cdiv(a.p[i].M, 16);
       }
       a.begin[nprob] = total;
-      if (vec4) hipLaunchKernelGGL((nt16_kernel<4>), dim3(total), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((nt16_kernel<2>), dim3(total), dim3(256), 0, stream, a);
-      UFND_CHECK_LAUNCH();
+      *form = vec4 ? GEMM_F32_NT16_W4 : GEMM_F32_NT16_W2;
+      *grid = total;
       return UFND_OK;
     }
   }
@@ -682,22 +683,37 @@ int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStre
     total += (a.p[i].N / 32) * ufnd_cdiv(a.p[i].M, 32 * MT) * a.p[i].ksplit;
   }
   a.begin[nprob] = total;
-  if (MT == 1) {
-    if (vec4) hipLaunchKernelGGL((nt_kernel<1, 4>), dim3(total), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((nt_kernel<1, 2>), dim3(total), dim3(256), 0, stream, a);
-  } else {
-    if (vec4) hipLaunchKernelGGL((nt_kernel<2, 4>), dim3(total), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((nt_kernel<2, 2>), dim3(total), dim3(256), 0, stream, a);
+  *form = MT == 1 ? (vec4 ? GEMM_F32_NT_M1_W4 : GEMM_F32_NT_M1_W2) : (vec4 ? GEMM_F32_NT_M2_W4 : GEMM_F32_NT_M2_W2);
+  *grid = total;
+  return UFND_OK;
+}
+
+int run_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream, GemmF32Form* form_out, int* grid_out) {
+  NtArgs a;
+  GemmF32Form form;
+  int grid;
+  const int rc = choose_nt(probs, nprob, a, &form, &grid);
+  if (rc != UFND_OK) return rc;
+  a.st = st;
+  if (form_out) *form_out = form;
+  if (grid_out) *grid_out = grid;
+  switch (form) {
+    case GEMM_F32_NT16_W4: hipLaunchKernelGGL((nt16_kernel<4>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NT16_W2: hipLaunchKernelGGL((nt16_kernel<2>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NT_M1_W4: hipLaunchKernelGGL((nt_kernel<1, 4>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NT_M1_W2: hipLaunchKernelGGL((nt_kernel<1, 2>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NT_M2_W4: hipLaunchKernelGGL((nt_kernel<2, 4>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NT_M2_W2: hipLaunchKernelGGL((nt_kernel<2, 2>), dim3(grid), dim3(256), 0, stream, a); break;
+    default: UFND_REQUIRE(false, "nt: form %d", (int)form);
   }
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
 
-int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream) {
+int choose_nn(const NnProb* probs, int nprob, NnArgs& a, GemmF32Form* form, int* grid) {
   UFND_REQUIRE(nprob >= 1 && nprob <= UFND_GEMM_MAX_PROB, "nn: %d problems", nprob);
-  NnArgs a;
+  UFND_REQUIRE(probs, "nn: null problem array");
   a.nprob = nprob;
-  a.st = st;
   bool vec4 = true;
   for (int i = 0; i < nprob; ++i) {
     const NnProb& p = probs[i];
@@ -707,10 +723,17 @@ int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStre
     UFND_REQUIRE(p.K % 2 == 0 && p.ldw % 2 == 0 && ufnd_aligned(p.W, 8), "nn[%d]: W alignment", i);
     UFND_REQUIRE(p.nsplit >= 1 && p.nsplit <= 64, "nn[%d]: nsplit=%d", i, p.nsplit);
     UFND_REQUIRE((long long)p.M * p.K < (1ll << 31), "nn[%d]: M*K too large", i);
+    // the mask is the dropout that followed the activation in the forward: the kernels regenerate it inside the activation
+    // backward, so a mask without actZ would be dropped without a word
+    UFND_REQUIRE(!(p.drop_p > 0.0f) || p.actZ, "nn[%d]: drop_p=%g without actZ (the dropout mask belongs to the activation backward)", i,
+                 (double)p.drop_p);
+    // the mask's element index m * drop_ld + k is formed in 32 bits and must name one element per (m, k)
+    UFND_REQUIRE(!(p.drop_p > 0.0f) || (p.drop_ld >= p.K && (long long)p.M * p.drop_ld < (1ll << 31)),
+                 "nn[%d]: drop_ld=%d with K=%d, M=%d (drop_ld >= K and M*drop_ld < 2^31)", i, p.drop_ld, p.K, p.M);
     if (!(p.K % 4 == 0 && p.ldw % 4 == 0 && ufnd_aligned(p.W, 16))) vec4 = false;
     a.p[i] = p;
   }
-  {      // narrow layers: 16x16 tiles (chosen by the layers' widths only, never by the batch: see launch_nt)
+  {      // narrow layers: 16x16 tiles (chosen by the layers' widths only, never by the batch: see choose_nt)
     int s32 = 0;
     bool plain = true;
     for (int i = 0; i < nprob; ++i) {
@@ -724,8 +747,8 @@ int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStre
         total += ufnd_cdiv(a.p[i].K, 16) * ufnd_cdiv(a.p[i].M, 16);
       }
       a.begin[nprob] = total;
-      hipLaunchKernelGGL(nn16_kernel, dim3(total), dim3(256), 0, stream, a);
-      UFND_CHECK_LAUNCH();
+      *form = GEMM_F32_NN16;
+      *grid = total;
       return UFND_OK;
     }
   }
@@ -748,16 +771,34 @@ int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStre
     total += ufnd_cdiv(a.p[i].K, 32 * VEC) * ufnd_cdiv(a.p[i].M, 32) * a.p[i].nsplit;
   }
   a.begin[nprob] = total;
-  if (VEC == 4) hipLaunchKernelGGL((nn_kernel<4>), dim3(total), dim3(256), 0, stream, a);
-  else if (VEC == 2) hipLaunchKernelGGL((nn_kernel<2>), dim3(total), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((nn_kernel<1>), dim3(total), dim3(256), 0, stream, a);
+  *form = VEC == 4 ? GEMM_F32_NN_V4 : (VEC == 2 ? GEMM_F32_NN_V2 : GEMM_F32_NN_V1);
+  *grid = total;
+  return UFND_OK;
+}
+
+int run_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream, GemmF32Form* form_out, int* grid_out) {
+  NnArgs a;
+  GemmF32Form form;
+  int grid;
+  const int rc = choose_nn(probs, nprob, a, &form, &grid);
+  if (rc != UFND_OK) return rc;
+  a.st = st;
+  if (form_out) *form_out = form;
+  if (grid_out) *grid_out = grid;
+  switch (form) {
+    case GEMM_F32_NN16: hipLaunchKernelGGL(nn16_kernel, dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NN_V4: hipLaunchKernelGGL((nn_kernel<4>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NN_V2: hipLaunchKernelGGL((nn_kernel<2>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_NN_V1: hipLaunchKernelGGL((nn_kernel<1>), dim3(grid), dim3(256), 0, stream, a); break;
+    default: UFND_REQUIRE(false, "nn: form %d", (int)form);
+  }
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
 
-int launch_tn(const TnProb* probs, int nprob, hipStream_t stream) {
+int choose_tn(const TnProb* probs, int nprob, TnArgs& a, GemmF32Form* form, int* grid) {
   UFND_REQUIRE(nprob >= 1 && nprob <= UFND_GEMM_MAX_PROB, "tn: %d problems", nprob);
-  TnArgs a;
+  UFND_REQUIRE(probs, "tn: null problem array");
   a.nprob = nprob;
   bool vec4 = true;
   for (int i = 0; i < nprob; ++i) {
@@ -795,24 +836,45 @@ int launch_tn(const TnProb* probs, int nprob, hipStream_t stream) {
     total += (q.N / 32) * ufnd_cdiv(q.K, 32 * a.vec[i]);
   }
   a.begin[nprob] = total;
-  if (seg) {              // gathered factors: the same two forms, rows addressed by segment
-    if (minM >= 128) {
-      if (vec4) hipLaunchKernelGGL((tn_kernel<4, 1, 1>), dim3(total), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((tn_kernel<2, 1, 1>), dim3(total), dim3(256), 0, stream, a);
-    } else {
-      if (mixed) hipLaunchKernelGGL((tn_kernel<-1, 0, 1>), dim3(ufnd_cdiv(total, 4)), dim3(256), 0, stream, a);
-      else if (vec4) hipLaunchKernelGGL((tn_kernel<4, 0, 1>), dim3(ufnd_cdiv(total, 4)), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((tn_kernel<2, 0, 1>), dim3(ufnd_cdiv(total, 4)), dim3(256), 0, stream, a);
-    }
-  } else if (minM >= 128) {      // batch rows split over the four waves of a workgroup (one workgroup per tile)
-    if (vec4) hipLaunchKernelGGL((tn_kernel<4, 1>), dim3(total), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((tn_kernel<2, 1>), dim3(total), dim3(256), 0, stream, a);
-  } else {
-    const int blocks = ufnd_cdiv(total, 4);
-    if (mixed) hipLaunchKernelGGL((tn_kernel<-1>), dim3(blocks), dim3(256), 0, stream, a);
-    else if (vec4) hipLaunchKernelGGL((tn_kernel<4>), dim3(blocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((tn_kernel<2>), dim3(blocks), dim3(256), 0, stream, a);
+  if (minM >= 128) {      // batch rows split over the four waves of a workgroup (one workgroup per tile)
+    *form = seg ? (vec4 ? GEMM_F32_TN_V4_MSPLIT_SEG : GEMM_F32_TN_V2_MSPLIT_SEG) : (vec4 ? GEMM_F32_TN_V4_MSPLIT : GEMM_F32_TN_V2_MSPLIT);
+    *grid = total;
+  } else {                // one wave per tile; segmented rows (gathered factors) are the same forms, rows addressed by segment
+    if (mixed) *form = seg ? GEMM_F32_TN_MIXED_SEG : GEMM_F32_TN_MIXED;
+    else if (vec4) *form = seg ? GEMM_F32_TN_V4_SEG : GEMM_F32_TN_V4;
+    else *form = seg ? GEMM_F32_TN_V2_SEG : GEMM_F32_TN_V2;
+    *grid = ufnd_cdiv(total, 4);
+  }
+  return UFND_OK;
+}
+
+int run_tn(const TnProb* probs, int nprob, hipStream_t stream, GemmF32Form* form_out, int* grid_out) {
+  TnArgs a;
+  GemmF32Form form;
+  int grid;
+  const int rc = choose_tn(probs, nprob, a, &form, &grid);
+  if (rc != UFND_OK) return rc;
+  if (form_out) *form_out = form;
+  if (grid_out) *grid_out = grid;
+  switch (form) {
+    case GEMM_F32_TN_V4: hipLaunchKernelGGL((tn_kernel<4>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V2: hipLaunchKernelGGL((tn_kernel<2>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_MIXED: hipLaunchKernelGGL((tn_kernel<-1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V4_MSPLIT: hipLaunchKernelGGL((tn_kernel<4, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V2_MSPLIT: hipLaunchKernelGGL((tn_kernel<2, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V4_SEG: hipLaunchKernelGGL((tn_kernel<4, 0, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V2_SEG: hipLaunchKernelGGL((tn_kernel<2, 0, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_MIXED_SEG: hipLaunchKernelGGL((tn_kernel<-1, 0, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V4_MSPLIT_SEG: hipLaunchKernelGGL((tn_kernel<4, 1, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    case GEMM_F32_TN_V2_MSPLIT_SEG: hipLaunchKernelGGL((tn_kernel<2, 1, 1>), dim3(grid), dim3(256), 0, stream, a); break;
+    default: UFND_REQUIRE(false, "tn: form %d", (int)form);
   }
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
+
+}  // namespace
+
+int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream) { return run_nt(probs, nprob, st, stream, nullptr, nullptr); }
+int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream) { return run_nn(probs, nprob, st, stream, nullptr, nullptr); }
+int launch_tn(const TnProb* probs, int nprob, hipStream_t stream) { return run_tn(probs, nprob, stream, nullptr, nullptr); }
