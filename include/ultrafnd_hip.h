@@ -448,6 +448,15 @@ int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* b
                                  const ufnd_gemm_ln* ln, void* stream);
 int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
                                       int heads, void* stream);
+
+/* CLIPAttention of one layer in ONE launch, for samples of T <= 64 rows (ViT-B/32 at 224^2: T = 50): ufnd_qkv_attention_bf16's fusion
+ * with one workgroup per (256 / T whole samples, head) -- a 256 x 192 x H tile [q_h | k_h | v_h] whose row tiles start every
+ * (256 / T) T rows -- and no key mask.  X (N*T, H) bf16, Wqkv (3H, H) / bqkv (3H), ln as ufnd_qkv_attention_bf16 (NULL: plain
+ * projection); ctx (N*T, H) bf16 is bit-identical to ufnd_gemm_bf16[_ln] + ufnd_attention_bf16 and the only output.  Nothing past
+ * row N*T of X is read.  T outside 1 .. 64 is refused: use the two-launch form.
+ * Replaces modeling_clip.py CLIPAttention (q / k / v Linears + eager attention) of the frozen visual encoder. */
+int ufnd_qkv_attention_bf16_vit(const void* X, const void* Wqkv, const float* bqkv, void* ctx, int N, int T, int heads, int ldx, int ldw,
+                                const ufnd_gemm_ln* ln, void* stream);
 int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, const float* beta, void* out_bf16, float* out_f32, int capacity,
                         int H, float eps, const int* m_live, void* stream);
 int ufnd_masked_meanpool_l2_live(const float* hidden, const int32_t* mask, const int32_t* cu_seqlens, float* out, int B, int L, int H,

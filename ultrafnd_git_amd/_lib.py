@@ -184,6 +184,7 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_gemm_bf16_ln_live": [P] * 6 + [I] * 9 + [C.POINTER(GemmLn), P, P],
         "ufnd_qkv_attention_bf16_packed": [P, P, P, P, P, P, I, I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_qkv_attention_bf16_bins": [P] * 8 + [I, I, I, I, I, C.POINTER(GemmLn), P],
+        "ufnd_qkv_attention_bf16_vit": [P, P, P, P, I, I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_attention_bf16_varlen_masked": [P, P, P, P, I, I, I, P],
         "ufnd_layernorm_live": [P, I, P, P, P, P, I, I, F, P, P],
         "ufnd_masked_meanpool_l2_live": [P, P, P, P, I, I, I, P],

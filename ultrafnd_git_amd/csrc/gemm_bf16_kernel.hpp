@@ -89,6 +89,8 @@ struct GemmArgs {
   // tiles past *att_nbins exit at entry (see the ATT notes at the kernel)
   const int32_t* att_bins;
   const int* att_nbins;
+  // ATT kernels, short-sample geometry (BM = 256): every sample is att_t <= 64 contiguous rows, a row tile holds 256 / att_t whole samples
+  int att_t;
 };
 
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
@@ -153,6 +155,15 @@ template <int V> struct IntC { static constexpr int value = V; };
 //          Measured (bench group of 128 samples, MI355X): 768 -> ~544 live workgroups, but one 149-KiB workgroup per CU keeps
 //          both at 3 rounds (89 -> 86 us per launch); the step gains 3 % (profiles/slot_bins_summary.md), presumably because the
 //          concurrent visual stream fills the CUs the emptier last round leaves (inferred, not traced).
+// ATT = 1, short samples (BM = 256, BN = 192, MI = 16, LNX = 1; the ViT: T = att_t <= 64 rows per sample, 50 at 224^2 / 32): the
+//          projection of S = 256 / T whole samples for ONE head, tile column c = column (c / 64) * att_h + 64 head + c % 64 of
+//          the stacked projection, i.e. [q_h | k_h | v_h]; grid = ceil(samples / S) x heads.  Row tile tm starts at row tm S T (the
+//          row-tile stride is S T, not BM): its 256 - S T tail rows are the next tile's first rows, projected and never used as
+//          queries; rows at or past M = samples x T read the last row (DMA source, row statistics, fold guard).  Three LDS images
+//          (q, k, v; 256 rows x 128 B, swizzled by the TILE row, since samples start at rows that are no multiple of 16), then
+//          attention_kernel<64, 2>'s per-query operation sequence on them: one 64-key block per sample, key k >= T reads the
+//          sample's row T - 1 and gets the -inf bias (exactly that kernel's clamped load and bias), units of (sample, 32 queries)
+//          dealt round-robin to the eight waves.  ctx is the only global output, bit-identical to the two launches.
 // waves per SIMD the register allocation must leave room for: tiles whose LDS footprint lets two workgroups share a CU
 // (<= 80 KiB) only do so if two workgroups' waves also fit the register file (8-wave blocks: 128 registers per lane)
 constexpr int gemm_waves_per_simd(int BM, int BN, int WM, int WN, int STA, int STB, int MI, int LNX, int ATT) {
@@ -165,7 +176,8 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(ge
 void gemm_bf16_kernel(const GemmArgs a) {
   static_assert(!BWD || (!LNX && !ATT && !ABL && !DBG), "backward forms are plain kernels");
   static_assert(MI == 16 || MI == 32, "MFMA shape");
-  static_assert(!ATT || (BM == 128 && BN == 384 && MI == 16 && WM * WN == 8 && LNX == 1), "fused attention tile");
+  static_assert(!ATT || (((BM == 128 && BN == 384) || (BM == 256 && BN == 192)) && MI == 16 && WM * WN == 8 && LNX == 1), "fused attention tile");
+  constexpr bool VIT = ATT && BM == 256;         // the short-sample geometry: one head per workgroup, 256 / att_t samples per row tile
   using acc_t = typename std::conditional<MI == 16, f32x4, f32x16>::type;
   constexpr int AR = MI * MI / 64;               // accumulator registers per MFMA tile
   constexpr int KQ = MI == 16 ? 1 : 2;           // MFMA k-steps per k-half (32 k)
@@ -186,7 +198,9 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // ATT: six 16-KiB images (Q, K, V of two heads; 128 tokens x 128 B) + 4 x 128 key biases (one row per 32-row slot), behind
   // the C staging patches (they overlay the operand ring, which is dead by then)
   constexpr int ATT_OFF = (CBYTES + 1023) & ~1023;
-  constexpr int ATT_END = ATT ? ATT_OFF + 6 * 16384 + 2048 : 0;
+  // (short samples: three 32-KiB images, 256 tile rows x 128 B, + one row of 64 key biases)
+  constexpr int ATT_IMG = BM * 128;
+  constexpr int ATT_END = ATT ? ATT_OFF + (VIT ? 3 * ATT_IMG + 256 : 6 * ATT_IMG + 2048) : 0;
   constexpr int STAT_OFF0 = (RING > CBYTES) ? RING : CBYTES;
   constexpr int STAT_OFF = STAT_OFF0 > ATT_END ? STAT_OFF0 : ATT_END;  // LNX: {mean, rstd} per tile row, behind the ring (and the images)
   constexpr int SMEM = STAT_OFF + (LNX ? BM * 8 + 64 : 0);      // (+ 16 floats: the waves' guard maxima)
@@ -253,8 +267,13 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // (r & 31) < scnt_j (clamped to the slot's last live row); an empty slot (scnt_j = 0) re-reads slot 0's first row.  Descriptor
   // of slot j (ufnd_text_pack_bins): {cu[b] + 32 s, (b << 10) | (s << 8) | n_b}, meta -1 = empty.
   int srow[4] = {0, 0, 0, 0}, scnt[4] = {0, 0, 0, 0}, smeta[4] = {-1, -1, -1, -1};
-  const bool slots = ATT && a.att_bins != nullptr;
-  if constexpr (ATT) {
+  const bool slots = ATT && !VIT && a.att_bins != nullptr;
+  // short samples: the tile holds S whole samples (S T rows) from row tm S T on
+  const int vit_s = VIT ? BM / a.att_t : 0, vit_st = vit_s * a.att_t;
+  if constexpr (VIT) {
+    arow0 = tm * vit_st;
+    alen = mlive - arow0 < vit_st ? mlive - arow0 : vit_st;      // (rows past it: the next tile's, or clamped; never stored, not in the guard)
+  } else if constexpr (ATT) {
     if (slots) {
       const int32_t* bd = a.att_bins + (size_t)tm * 8;
 #pragma unroll
@@ -345,7 +364,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int c = ppos ^ ((r >> 1) & 7);
       int gr = n0 + r;
       gr = gr < a.N ? gr : a.N - 1;
-      if constexpr (ATT) gr = (r >> 7) * a.att_h + tn * 128 + (r & 127);     // [q | k | v] rows of this head pair
+      if constexpr (VIT) gr = (r >> 6) * a.att_h + tn * 64 + (r & 63);       // [q | k | v] rows of this head
+      else if constexpr (ATT) gr = (r >> 7) * a.att_h + tn * 128 + (r & 127);     // [q | k | v] rows of this head pair
       dma16(a.W + (size_t)gr * a.ldw + k0 + c * 8, buf + p * 1024);
     }
   };
@@ -384,7 +404,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
     }
   }
   int att_mk = 1;
-  if constexpr (ATT) {      // this sample's key mask: requested now, used after the K loop (older than every DMA piece)
+  if constexpr (ATT && !VIT) {      // this sample's key mask: requested now, used after the K loop (older than every DMA piece)
     if (slots) {            // slot bins: thread t holds key t % 128 of slot t / 128's sample (wave-uniform slot)
       const int j = (int)threadIdx.x >> 7, k = threadIdx.x & 127;
       const int mt = j == 0 ? smeta[0] : j == 1 ? smeta[1] : j == 2 ? smeta[2] : smeta[3];
@@ -589,7 +609,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
 #pragma unroll
   for (int j = 0; j < NT; ++j) { bj[j] = 0.f; csj[j] = 0.f; }
   // global column of tile column c
-  auto gcol = [&](int c) { return ATT ? (c >> 7) * a.att_h + tn * 128 + (c & 127) : n0 + c; };
+  auto gcol = [&](int c) { return VIT ? (c >> 6) * a.att_h + tn * 64 + (c & 63) : ATT ? (c >> 7) * a.att_h + tn * 128 + (c & 127) : n0 + c; };
   if (a.bias) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) bj[j] = a.bias[gcol(wn * TN + j * MI + fr)];
@@ -762,8 +782,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
           bf16x8 o;
 #pragma unroll
           for (int q = 0; q < 8; ++q) o[q] = (__bf16)v[q];
-          const int sw = img >= 4 ? (ch ^ (((trow >> 1) & 3) << 1)) : (ch ^ ((trow >> 1) & 7));      // V images: the transposed-read swizzle
-          *reinterpret_cast<bf16x8*>(smem + ATT_OFF + img * 16384 + trow * 128 + (sw << 4)) = o;
+          const int sw = img >= (VIT ? 2 : 4) ? (ch ^ (((trow >> 1) & 3) << 1)) : (ch ^ ((trow >> 1) & 7));      // V images: the transposed-read swizzle
+          *reinterpret_cast<bf16x8*>(smem + ATT_OFF + img * ATT_IMG + trow * 128 + (sw << 4)) = o;
           continue;
         }
         if (!live) continue;
@@ -802,7 +822,94 @@ void gemm_bf16_kernel(const GemmArgs a) {
     stamp[8] = __builtin_amdgcn_s_memtime();       // projection epilogue done (images written), attention starts
     stamp[9] = __builtin_amdgcn_s_memrealtime();
   }
-  if constexpr (ATT) {
+  if constexpr (VIT) {
+    // ---- attention of the tile's samples for this head on the LDS images: attention_kernel<64, 2>'s operations per query (one
+    // 64-key block; a key or query at or past T reads the sample's last row, as that kernel's clamped loads do)
+    const int T = a.att_t;
+    float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 3 * ATT_IMG);
+    if (threadIdx.x < 64) kbias[threadIdx.x] = (int)threadIdx.x < T ? 0.0f : -INFINITY;
+    __syncthreads();
+    const int g4 = lane >> 4, f16 = lane & 15;
+    const char* qimg = smem + ATT_OFF;
+    const char* kimg = smem + ATT_OFF + ATT_IMG;
+    const char* vimg = smem + ATT_OFF + 2 * ATT_IMG;
+    const int nqb = (T + 31) >> 5, nsamp = alen > 0 ? alen / T : 0;      // (alen is a whole number of samples: M = samples x T)
+    const bool any_masked = __any(kbias[lane] != 0.0f);                  // (wave-uniform; false only at T = 64)
+    constexpr int KT = 4;
+    for (int u = wave; u < nsamp * nqb; u += NW) {
+      const int smp = u / nqb, q0 = (u - smp * nqb) * 32, r0 = smp * T;      // r0: tile row of the sample's row 0
+      bf16x8 qf[2][2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const int q = q0 + qt * 16 + f16, qc = q < T ? q : T - 1;
+        qf[qt][0] = lds_frag(qimg, r0 + qc, g4);
+        qf[qt][1] = lds_frag(qimg, r0 + qc, g4 + 4);
+      }
+      f32x4 o[4][2];
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+      f32x4 sc[KT][2];
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+          const int key = kt * 16 + f16;
+          const bf16x8 kf = lds_frag(kimg, r0 + (key < T ? key : T - 1), g4 + 4 * kk);
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
+        }
+      bf16x8 pf[KT / 2][2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const float alpha = online_softmax_block<KT>(sc, qt, kbias, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
+        if (!__all(alpha == 1.0f)) {
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
+        }
+      }
+#pragma unroll
+      for (int ksd = 0; ksd < KT / 2; ++ksd) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const int qq = f16 >> 2, pp = f16 & 3;
+          const int k0 = 32 * ksd + 4 * g4 + qq, k1 = k0 + 16;
+          const int key0 = r0 + (k0 < T ? k0 : T - 1), key1 = r0 + (k1 < T ? k1 : T - 1);      // tile rows
+          const int ch = 2 * dt + (pp >> 1);
+          const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+          const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+          const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
+          const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
+          union { s16x4 s2[2]; bf16x8 v; } uu;
+          uu.s2[0] = t0;
+          uu.s2[1] = t1;
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uu.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        float l = l_run[qt];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        const int q = q0 + qt * 16 + f16;
+        if (q >= T) continue;
+        __bf16* dst = a.att_ctx + (size_t)(arow0 + r0 + q) * a.att_h + tn * 64 + 4 * g4;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
+          *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
+        }
+      }
+    }
+  } else if constexpr (ATT) {
     // ---- attention of the tile's two heads on the LDS images (attention.hip's per-wave schedule, L = 128 = two key blocks)
     constexpr float NEG_MASK = -3.0e38f;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 6 * 16384);

@@ -272,12 +272,20 @@ class _EncoderBase(nn.Module):
     def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None, nbins=None):
         """Fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer.  cu: sample b's rows are
         cu[b] .. cu[b+1] of the packed pass (None: the padded batch); bins, nbins (ufnd_text_pack_bins, with cu): one workgroup per
-        bin of up to four samples and head pair (None: one per sample and head pair)."""
+        bin of up to four samples and head pair (None: one per sample and head pair).  Samples of Lq <= 64 rows (the ViT's 50) take
+        the short-sample geometry, ufnd_qkv_attention_bf16_vit: 256 // Lq whole samples and one head per workgroup, no key mask."""
         ln = None
         if a_stats is not None:
             ln = L.GemmLn()
             ln.a_stats, ln.colsum, ln.a_parts, ln.a_eps, ln.r_eps, ln.width = a_stats.data_ptr(), colsum.data_ptr(), a_stats.shape[1], eps, eps, self.hidden
             ln.guard = self._guard_buf(A.device).data_ptr()
+        if Lq <= 64:
+            if mask_i32 is not None or cu is not None or bins is not None:
+                raise L.UltrafndHipError("_qkv_attn: the short-sample kernel (Lq <= 64) takes no key mask, cu or bins")
+            L.check(L.lib().ufnd_qkv_attention_bf16_vit(A.data_ptr(), W.data_ptr(), L.ptr(bias), ctx.data_ptr(), B, Lq, heads, A.stride(0),
+                                                        W.stride(0), ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
+                    "ufnd_qkv_attention_bf16_vit")
+            return
         L.check(L.lib().ufnd_qkv_attention_bf16_bins(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), L.ptr(bins),
                                                      L.ptr(nbins), ctx.data_ptr(), B, Lq, heads, A.stride(0), W.stride(0),
                                                      ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
@@ -541,6 +549,9 @@ class ClipVisualEncoder(_EncoderBase):
         self.layers, self.inter = layers, intermediate
         self.patch, self.image, self.proj, self.eps = patch, image, projection_dim, eps
         self.n_patches = (image // patch) ** 2
+        # samples of at most 64 tokens: Q/K/V projection + attention of a layer as ONE launch (ufnd_qkv_attention_bf16_vit); bit-identical
+        # to the two-launch form (off: a GEMM into qkv and an attention launch per layer)
+        self.fuse_qkv_attention = True
         w, V, init = self._w, "vision_model.", self._seeded_init()
         w[V + "embeddings.class_embedding"] = init((hidden,))
         w[V + "embeddings.patch_embedding.weight"] = init((hidden, 3, patch, patch))
@@ -633,11 +644,15 @@ class ClipVisualEncoder(_EncoderBase):
         LayerNorms need (module docstring)."""
         eps, stA, st, T = self.eps, b["st0"], b["st"], self.n_patches + 1
         rb = self.residual_dtype == "bf16"       # the stream is hb itself, updated in place (a tile reads exactly what it rewrites)
+        fuse = self.fuse_qkv_attention and T <= 64
         for i, ly in enumerate(layers):
             st1, st2 = st[2 * i], st[2 * i + 1]
             last = i == len(layers) - 1
-            self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
-            self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
+            if fuse:
+                self._qkv_attn(b["hb"], ly["wqkvf"], ly["bqkvf"], None, b["ctx"], N, T, self.heads, a_stats=stA, colsum=ly["csqkv"], eps=eps)
+            else:
+                self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
+                self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
             self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else b["xf"], out_bf16=b["hb"], residual=None if rb else b["xf"],
                           residual_bf16=b["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
             self._gemm_ln(b["hb"], ly["w1f"], ly["bif"], out_bf16=b["m"], act=ACT_QUICK_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
@@ -649,10 +664,14 @@ class ClipVisualEncoder(_EncoderBase):
         """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf."""
         H, T, eps = self.hidden, self.n_patches + 1, self.eps
         M = N * T
+        fuse = self.fuse_qkv_attention and T <= 64
         for ly in layers:
             self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps)
-            self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
-            self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
+            if fuse:
+                self._qkv_attn(b["hb"], ly["wqkv"], ly["bqkv"], None, b["ctx"], N, T, self.heads)
+            else:
+                self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
+                self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
             self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["xf"], residual=b["xf"], which="out")
             self._ln(b["xf"], H, ly["g2"], ly["b2n"], b["hb"], None, M, H, eps)
             self._gemm(b["hb"], ly["w1"], ly["bi"], out_bf16=b["m"], act=ACT_QUICK_GELU, which="ffn1")
