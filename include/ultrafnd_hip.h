@@ -587,6 +587,35 @@ int ufnd_gcn_pretrain_step(const float* x, const float* adj, int ld_adj, const u
                            const ufnd_step_state* state, float* loss, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The reference's post graph: src/models/gnn/graph_builder.py
+ *   cosine_knn :4-28, add_ocr_overlap_weights :30-45, add_temporal_inconsistency :47-59, build_dense_adj :61-68.
+ * ---------------------------------------------------------------------------------- */
+
+/* Floats of the workspace of ufnd_cosine_knn (the normalised, column-padded copy of X); 0 for sizes it refuses. */
+size_t ufnd_cosine_knn_workspace_floats(int N, int D, int k);
+
+/* idx (N, k) int32, contiguous: row i's k nearest rows of X (N, D) row stride ldx by cosine similarity, i itself excluded,
+ * ordered by (similarity descending, index ascending), so ties go to the lower index.  Every row is divided by
+ * (its L2 norm + 1e-9) in fp32; S = Xn Xn^T runs on the exact-fp32 MFMA and is never stored: a workgroup keeps the running
+ * lists of its 32 query rows on chip while the columns stream past.  No atomics: two calls give the same bits.
+ * 1 <= k <= 64 and k < N; D >= 1, ldx >= D; workspace 16-B aligned. */
+int ufnd_cosine_knn(const float* X, int ldx, int N, int D, int k, int32_t* idx, float* workspace, void* stream);
+
+#define UFND_ADJ_KNN 1
+#define UFND_ADJ_OCR 2
+#define UFND_ADJ_TEMPORAL 4
+/* adj (N, N) row stride ld in ONE pass, `flags` = any non-empty subset of the three above, applied in the reference's order:
+ *   KNN       adj is overwritten: 1 where j is in idx[i], i is in idx[j] or i == j, else 0 (idx (N, k) from ufnd_cosine_knn).
+ *             Without it the entry updates the adj it is given in place.
+ *   OCR       i != j with ov = |set_i ^ set_j| > 0: a = (float)((double)a + alpha * log1p((double)ov)).  Sets as CSR, exactly
+ *             as for ufnd_ocr_adjacency.
+ *   TEMPORAL  i != j: a = fl(a * fl(1 + fl(fl(beta) * fl(|delay_i - delay_j|)))), every operation rounded to fp32
+ *             (delay (N) fp32).
+ * The diagonal is never weighted.  Pointers of parts not asked for may be NULL. */
+int ufnd_dense_adj(const int32_t* idx, int k, const int32_t* offsets, const int32_t* tokens, const float* delay, double alpha,
+                   double beta, int N, float* adj, int ld, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The integrated trainer variant's in-graph GNN: src/training/forensic_trainer_integrated.py
  *   build_adj_from_ocr_sets :77-98 (weighted Jaccard adjacency of the mini-batch), _pack_batch / _forward :203-224,
  *   src/models/gnn/gnn_model.py GNNModel :7-41 (lin1 -> A_norm -> ReLU -> dropout -> A_norm -> lin2), trained WITH the head.

@@ -38,6 +38,10 @@ def parse_args():
     p.add_argument("--no_graph", action="store_true", help="launch kernels eagerly instead of replaying a hipGraph")
     p.add_argument("--grad_accum_steps", type=int, default=1,
                    help="micro-batches of --batch_size rows per optimizer step (gradient accumulation); 1 = off")
+    p.add_argument("--gnn_graph", choices=("ocr", "knn"), default="ocr",
+                   help="graph behind gnn_feat when the cache has no gnn_Z: the trainer's OCR-Jaccard graph, or the graph builder's "
+                        "cosine kNN graph with OCR-overlap and delay weights")
+    p.add_argument("--gnn_knn_k", type=int, default=8, help="neighbours per post of --gnn_graph knn (1..64)")
     return p.parse_args()
 
 
@@ -69,7 +73,8 @@ def main():
                       out_dir=str(out_dir), batch_size=args.batch_size, epochs=args.epochs, lr=args.lr,
                       weight_decay=args.weight_decay, gnn_dim=args.gnn_dim, gnn_overlap_thresh=args.gnn_overlap_thresh,
                       seed=args.seed, use_mps=False, use_gnn=(not args.no_gnn), save_best=True, device=f"cuda:{local}",
-                      use_graph=not args.no_graph, grad_accum_steps=args.grad_accum_steps)
+                      use_graph=not args.no_graph, grad_accum_steps=args.grad_accum_steps,
+                      gnn_graph=args.gnn_graph, gnn_knn_k=args.gnn_knn_k)
     cache = synthetic_cache(args.synthetic, seed=args.seed, gnn_dim=args.gnn_dim) if args.synthetic else None
     trainer = ForensicTrainer(cfg, cache=cache)
     if not args.eval_only:

@@ -110,6 +110,8 @@ PATH_MAX_POINTS = 64                        # ufnd_path_points: points per call
 ATTR_SLICE_ROWS = 32                        # its partials: ceil(B / 32) * W floats
 MAX_ROWS = 65536                            # check_dims: rows of one call
 BWD_NO_LINEAR_GRADS = 16          # OR-ed into the phase / flags: the factor form of the gradient exchange (dp.FactorExchange)
+ADJ_KNN, ADJ_OCR, ADJ_TEMPORAL = 1, 2, 4   # ufnd_dense_adj flags
+KNN_MAX_K = 64                              # ufnd_cosine_knn: neighbours per row
 ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 
@@ -242,6 +244,12 @@ def _declare_encoders(lib: C.CDLL) -> None:
     lib.ufnd_gcn_forward.restype = I
     lib.ufnd_gcn_pretrain_step.argtypes = [P, P, I, C.POINTER(GcnParams), P, P, P, P, P, P, I, I, I, I, F, F, F, I, P, P, P]
     lib.ufnd_gcn_pretrain_step.restype = I
+    lib.ufnd_cosine_knn_workspace_floats.argtypes = [I, I, I]
+    lib.ufnd_cosine_knn_workspace_floats.restype = S
+    lib.ufnd_cosine_knn.argtypes = [P, I, I, I, I, P, P, P]
+    lib.ufnd_cosine_knn.restype = I
+    lib.ufnd_dense_adj.argtypes = [P, I, P, P, P, D, D, I, P, I, I, P]
+    lib.ufnd_dense_adj.restype = I
     lib.ufnd_ocr_adjacency_weighted.argtypes = [P, P, I, D, P, I, P]
     lib.ufnd_ocr_adjacency_weighted.restype = I
     lib.ufnd_node_features.argtypes = [P, I, P, I, P, I, P, I, I, I, I, I, I, P, P]

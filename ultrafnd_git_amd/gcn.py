@@ -143,14 +143,28 @@ def pretrain_gnn(gnn: SimpleGCN, X: torch.Tensor, Adj: torch.Tensor, gnn_dim: in
 
 
 def build_gnn_embeddings(cache: Dict, gnn_dim: int = 128, overlap_thresh: float = 0.12, device="cuda",
-                         pretrain_epochs: int = 2) -> Tuple[SimpleGCN, torch.Tensor, torch.Tensor, torch.Tensor]:
+                         pretrain_epochs: int = 2, graph: str = "ocr",
+                         knn_k: int = 8) -> Tuple[SimpleGCN, torch.Tensor, torch.Tensor, torch.Tensor]:
     """ForensicTrainer._build_gnn (forensic_trainer.py:184-211): node features, OCR-Jaccard adjacency,
     SimpleGCN(416, 2*gnn_dim, gnn_dim, dropout 0.2), two pre-training steps, then the cached node embeddings
     Z = gnn(X, Adj) -- computed, as in the reference, with the module still in train mode (its dropout is
-    active in that forward).  Returns (gnn, X, Adj, Z)."""
+    active in that forward).  Returns (gnn, X, Adj, Z).
+
+    graph="knn": the adjacency is the reference graph builder's instead, graph_builder.build_dense_adj(node features,
+    ocr_sets, delay_scores, knn_k): every post has knn_k cosine neighbours, phrase overlap and delay differences re-weight
+    the edges.  cache["ocr_sets"] defaults to N empty sets and cache["delay_scores"] to zeros (a temporal factor of exactly
+    1), so a cache with neither still gets a graph."""
+    if graph not in ("ocr", "knn"):
+        raise ValueError(f'graph={graph!r}: "ocr" or "knn"')
     dev = torch.device(device)
     X = torch.from_numpy(node_features(cache)).to(dev)
-    Adj = build_adj_from_ocr(cache["ocr_sets"], overlap_thresh, dev)
+    if graph == "knn":
+        from .graph_builder import build_dense_adj
+        n = X.shape[0]
+        delay = cache["delay_scores"] if "delay_scores" in cache else np.zeros(n, dtype=np.float32)
+        Adj = build_dense_adj(X, cache["ocr_sets"] if "ocr_sets" in cache else [set()] * n, delay, k=knn_k)
+    else:
+        Adj = build_adj_from_ocr(cache["ocr_sets"], overlap_thresh, dev)
     gnn = SimpleGCN(in_dim=X.shape[1], hid=2 * gnn_dim, out_dim=gnn_dim, dropout=0.2).to(dev)
     pretrain_gnn(gnn, X, Adj, gnn_dim, epochs=pretrain_epochs)
     Z = gnn(X, Adj)

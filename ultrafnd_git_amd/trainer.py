@@ -26,6 +26,8 @@ Out of scope: FakeSVRawDataset / build_gnn_cache_from_raw_
 preprocessing needing the FakeSV corpus): the trainer takes the cache dict they would have produced.  When that
 cache carries `ocr_sets` instead of `gnn_Z`, the graph side of the reference's construction (OCR-Jaccard
 adjacency, SimpleGCN, its two pre-training steps; forensic_trainer.py:184-224) runs here too (gcn.py).
+`TrainConfig.gnn_graph="knn"` builds that graph with the reference's graph builder instead (graph_builder.py: cosine kNN
+over the node features, re-weighted by phrase overlap and delay differences), which needs no `ocr_sets`.
 """
 from __future__ import annotations
 
@@ -110,13 +112,27 @@ class TrainConfig:
     # world; the gradient applied is the mean of the micro-batches' mean-CE gradients).  1 = off: every path as before, bit for
     # bit.  An init-only option kept as the attribute cfg.grad_accum_steps, like encoder_dropout.
     grad_accum_steps: InitVar[int] = 1
+    # the graph behind the cached gnn_feat table: "ocr" = the reference trainer's OCR-Jaccard graph (posts without OCR text are
+    # isolated nodes); "knn" = the reference's graph builder (graph_builder.build_dense_adj: every post gets gnn_knn_k cosine
+    # neighbours from its node features, phrase overlap and delay differences re-weight those edges).  Init-only options kept as
+    # attributes, like grad_accum_steps.
+    gnn_graph: InitVar[str] = "ocr"
+    gnn_knn_k: InitVar[int] = 8
 
-    def __post_init__(self, encoder_dropout: Optional[float], grad_accum_steps: int = 1):
+    def __post_init__(self, encoder_dropout: Optional[float], grad_accum_steps: int = 1, gnn_graph: str = "ocr", gnn_knn_k: int = 8):
         self.encoder_dropout = None if encoder_dropout is None else dropout_prob("encoder_dropout", encoder_dropout)
         k = grad_accum_steps
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
             raise ValueError(f"grad_accum_steps={k!r}: an integer >= 1 (micro-batches per optimizer step)")
         self.grad_accum_steps = int(k)
+        if gnn_graph not in ("ocr", "knn"):
+            raise ValueError(f'gnn_graph={gnn_graph!r}: "ocr" (OCR-Jaccard graph) or "knn" (cosine kNN + OCR + temporal weights)')
+        if isinstance(gnn_knn_k, bool) or not isinstance(gnn_knn_k, (int, np.integer)) or not 1 <= int(gnn_knn_k) <= L.KNN_MAX_K:
+            raise ValueError(f"gnn_knn_k={gnn_knn_k!r}: an integer in 1..{L.KNN_MAX_K} (neighbours per post)")
+        if gnn_graph == "knn" and self.gnn_in_graph:
+            raise ValueError('gnn_graph="knn" with gnn_in_graph=True: the integrated variant builds a zero-diagonal OCR graph per '
+                             'mini-batch; the kNN graph (unit diagonal) feeds the cached gnn_feat table only')
+        self.gnn_graph, self.gnn_knn_k = gnn_graph, int(gnn_knn_k)
 
 
 def apply_encoder_dropout(cfg: "TrainConfig", text_encoder, visual_encoder) -> None:
@@ -137,6 +153,8 @@ class ForensicTrainer:
         if cfg.grad_exchange == "factors" and k_acc > 1:
             raise ValueError('grad_exchange="factors" forms the Linear gradients from ONE micro-batch\'s factor panels and cannot '
                              f'accumulate: grad_accum_steps={k_acc} needs grad_exchange "all_reduce" or "rs_ag"')
+        if cfg.gnn_graph == "knn" and cfg.gnn_in_graph:       # (also refused at construction; fields can be set afterwards)
+            raise ValueError('gnn_graph="knn" with gnn_in_graph=True: the mini-batch graph of the integrated variant expects a zero diagonal')
         os.makedirs(cfg.out_dir, exist_ok=True)
         self.device = torch.device(cfg.device)
         if self.device.type != "cuda":
@@ -174,12 +192,13 @@ class ForensicTrainer:
             cache = dict(cache)
             cache.setdefault("gnn_Z", np.zeros((len(cache["labels"]), cfg.gnn_dim), dtype=np.float32))    # (placeholder: never read)
         if "gnn_Z" not in cache:
-            if "ocr_sets" not in cache:
+            if "ocr_sets" not in cache and cfg.gnn_graph != "knn":
                 raise KeyError("cache needs either 'gnn_Z' (N, gnn_dim) or 'ocr_sets' (N phrase sets) to build it from "
                                "(forensic_trainer.py:184-211)")
             # ForensicTrainer._build_gnn: node features, OCR-Jaccard adjacency, SimpleGCN, two pre-training steps
             from .gcn import build_gnn_embeddings
-            self.gnn, self.X, self.Adj, Z = build_gnn_embeddings(cache, cfg.gnn_dim, cfg.gnn_overlap_thresh, self.device)
+            self.gnn, self.X, self.Adj, Z = build_gnn_embeddings(cache, cfg.gnn_dim, cfg.gnn_overlap_thresh, self.device,
+                                                                         graph=cfg.gnn_graph, knn_k=cfg.gnn_knn_k)
             cache = dict(cache)
             cache["gnn_Z"] = Z.detach()
         self.cache = cache
