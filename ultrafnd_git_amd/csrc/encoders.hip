@@ -443,8 +443,8 @@ extern "C" int ufnd_layernorm(const float* x, int ldx, const float* gamma, const
                               float* out_f32, int M, int H, float eps, void* stream_) {
   UFND_REQUIRE(x && gamma && beta && (out_bf16 || out_f32) && M >= 1, "layernorm: null argument");
   UFND_REQUIRE(h_ok(H), "layernorm: H=%d (supported 256/512/768/1024)", H);
-  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16),
-               "layernorm: alignment");
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16) &&
+                   (!out_f32 || ufnd_aligned(out_f32, 16)) && (!out_bf16 || ufnd_aligned(out_bf16, 8)), "layernorm: alignment");
   NI_LAUNCH(H, layernorm_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, x, ldx, gamma, beta, (__bf16*)out_bf16,
             out_f32, M, H, eps, (const int*)nullptr);
   UFND_CHECK_LAUNCH();
@@ -485,7 +485,8 @@ extern "C" int ufnd_bert_embed(const int64_t* ids, const float* word, const floa
                                int vocab, float eps, void* stream_) {
   UFND_REQUIRE(ids && word && pos && type0 && ((gamma && beta) || (!gamma && !beta)) && (x_bf16 || x_f32), "bert_embed: null argument");
   UFND_REQUIRE(h_ok(H) && B >= 1 && L >= 1 && vocab >= 1, "bert_embed: B=%d L=%d H=%d vocab=%d", B, L, H, vocab);
-  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed: alignment");
+  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16) &&
+                   (!x_f32 || ufnd_aligned(x_f32, 16)) && (!x_bf16 || ufnd_aligned(x_bf16, 8)), "bert_embed: alignment");
   const int M = B * L;
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
             (__bf16*)x_bf16, x_f32, M, L, H, vocab, eps, (const int32_t*)nullptr, (const int*)nullptr);
@@ -528,7 +529,8 @@ extern "C" int ufnd_bert_embed_live(const int64_t* ids, const int32_t* row_src, 
                                     int L, int H, int vocab, float eps, void* stream_) {
   UFND_REQUIRE(ids && row_src && m_live && word && pos && type0 && gamma && beta && (x_bf16 || x_f32), "bert_embed_live: null argument");
   UFND_REQUIRE(h_ok(H) && capacity >= 1 && L >= 1 && vocab >= 1, "bert_embed_live: capacity=%d L=%d H=%d vocab=%d", capacity, L, H, vocab);
-  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16), "bert_embed_live: alignment");
+  UFND_REQUIRE(ufnd_aligned(word, 16) && ufnd_aligned(pos, 16) && ufnd_aligned(type0, 16) &&
+                   (!x_f32 || ufnd_aligned(x_f32, 16)) && (!x_bf16 || ufnd_aligned(x_bf16, 8)), "bert_embed_live: alignment");
   NI_LAUNCH(H, bert_embed_kernel, dim3(ufnd_cdiv(capacity, 4)), (hipStream_t)stream_, ids, word, pos, type0, gamma, beta,
             (__bf16*)x_bf16, x_f32, capacity, L, H, vocab, eps, row_src, m_live);
   UFND_CHECK_LAUNCH();
@@ -539,8 +541,8 @@ extern "C" int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, 
                                    int capacity, int H, float eps, const int* m_live, void* stream_) {
   UFND_REQUIRE(x && gamma && beta && (out_bf16 || out_f32) && m_live && capacity >= 1, "layernorm_live: null argument");
   UFND_REQUIRE(h_ok(H), "layernorm_live: H=%d (supported 256/512/768/1024)", H);
-  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16),
-               "layernorm_live: alignment");
+  UFND_REQUIRE(ldx % 4 == 0 && ldx >= H && ufnd_aligned(x, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16) &&
+                   (!out_f32 || ufnd_aligned(out_f32, 16)) && (!out_bf16 || ufnd_aligned(out_bf16, 8)), "layernorm_live: alignment");
   NI_LAUNCH(H, layernorm_kernel, dim3(ufnd_cdiv(capacity, 4)), (hipStream_t)stream_, x, ldx, gamma, beta, (__bf16*)out_bf16,
             out_f32, capacity, H, eps, m_live);
   UFND_CHECK_LAUNCH();
@@ -576,6 +578,7 @@ extern "C" int ufnd_vit_assemble(const float* patch_emb, const float* cls, const
   UFND_REQUIRE(h_ok(H), "vit_assemble: H=%d", H);
   const int M = N * (P + 1);
   UFND_REQUIRE(!stats || ufnd_aligned(stats, 16), "vit_assemble: stats alignment");
+  UFND_REQUIRE((!x_f32 || ufnd_aligned(x_f32, 16)) && (!x_bf16 || ufnd_aligned(x_bf16, 8)), "vit_assemble: alignment");
   NI_LAUNCH(H, vit_assemble_kernel, dim3(ufnd_cdiv(M, 4)), (hipStream_t)stream_, patch_emb, cls, pos, gamma, beta, x_f32,
             (__bf16*)x_bf16, stats, M, P, H, eps);
   UFND_CHECK_LAUNCH();
