@@ -64,6 +64,8 @@ def diag() -> C.CDLL:
         d.ufnd_diag_gemm_f32_plan.argtypes = [I, P, I, IP, IP]
         for f in (d.ufnd_diag_gemm_f32_nt, d.ufnd_diag_gemm_f32_nn, d.ufnd_diag_gemm_f32_tn, d.ufnd_diag_gemm_f32_plan):
             f.restype = I
+        d.ufnd_diag_gemm_bf16_plan.argtypes = [I] + [P] * 7 + [I] * 11 + [C.POINTER(L.GemmLn), IP]
+        d.ufnd_diag_gemm_bf16_plan.restype = I
         d.ufnd_diag_gemm_f32_sizes.argtypes = [IP]
         d.ufnd_diag_gemm_f32_sizes.restype = None
         _d = d
@@ -101,3 +103,20 @@ def gemm_f32_launch(kind: str, probs, state_ptr, stream) -> tuple:
         rc = d.ufnd_diag_gemm_f32_tn(arr, len(probs), C.byref(form), C.byref(grid), stream)
     check(rc, f"ufnd_diag_gemm_f32_{kind}")
     return GEMM_F32_FORMS[form.value], grid.value
+
+
+GEMM_BF16_ENTRIES = {"tile": -1, "gemm": 0, "ex": 1, "ln": 2, "dgrad": 3}
+GEMM_BF16_PLAN_FIELDS = ("tile", "m_tiles", "n_tiles", "xcd_cols", "stat_parts", "bm", "bn", "sta", "stb", "ln_aware", "prod", "bwd")
+
+
+def gemm_bf16_plan(entry: str, *, A=0, W=0, bias=None, residual=None, aux=None, out_bf16=None, out_f32=None, M=0, N=0, K=0, lda=0,
+                   ldw=0, ldr=0, ldaux=0, ldo=0, ldf=0, act=0, tile=-1, ln=None) -> tuple:
+    """Host-only validation + tile choice + grid of one call of ufnd_gemm_bf16 ("gemm"), ufnd_gemm_bf16_ex ("ex"), ufnd_gemm_bf16_ln
+    ("ln", ln: L.GemmLn) or ufnd_gemm_bf16_dgrad ("dgrad"); "tile": the table row of `tile`.  Addresses are integers that are never
+    dereferenced (no GPU needed).  Returns (rc, dict of GEMM_BF16_PLAN_FIELDS or None, error text)."""
+    out = (C.c_int * len(GEMM_BF16_PLAN_FIELDS))()
+    rc = diag().ufnd_diag_gemm_bf16_plan(GEMM_BF16_ENTRIES[entry], A, W, bias, residual, aux, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldaux,
+                                         ldo, ldf, act, tile, C.byref(ln) if ln is not None else None, out)
+    if rc != 0:
+        return rc, None, diag().ufnd_diag_last_error().decode()
+    return 0, dict(zip(GEMM_BF16_PLAN_FIELDS, out)), ""

@@ -3,6 +3,7 @@
 // build and the UFND_GEMM_FORCE_CFG override.  Used by tools/gemm_sweep.py and tools/gemm_stamps.py.
 #define UFND_DIAG 1
 #include "../gemm_bf16_kernel.hpp"
+#include "../gemm_bf16_checks.hpp"
 
 // out = act(A W^T + bias) + residual with an explicit tile; tile_cfg + 100 / + 200 select the timing-only ablations.
 extern "C" int ufnd_diag_gemm_bf16_ex(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
@@ -70,5 +71,59 @@ extern "C" int ufnd_diag_qkv_attention_stamps(const void* X, const void* Wqkv, c
   a.xcd_cols = (a.n_tiles % 2 == 0 && a.m_tiles >= 4) ? 2 : 1;
   hipLaunchKernelGGL((gemm_bf16_kernel<128, 384, 2, 4, 3, 2, 16, 0, 1, 1, 1>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
   UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+// Validation, tile choice and launch geometry of one call of the product's one-tile entries, on the host only: nothing is launched
+// and no operand is dereferenced -- the pointers only have to carry the alignment of the real ones -- so this answers on a machine
+// without a GPU (tests/test_gemm_bf16_cases.py).  The argument checks are the product entries' own (gemm_bf16_checks.hpp), the
+// choice is auto_cfg / xcd_cols_for / stat_parts_for as launch_cfg applies them.
+//   entry  0 ufnd_gemm_bf16 (automatic tile), 1 ufnd_gemm_bf16_ex (tile_cfg), 2 ufnd_gemm_bf16_ln (ln->tile_cfg), 3 ufnd_gemm_bf16_dgrad;
+//         -1: the table row of tile `tile_cfg` only (returns UFND_ERR_INVALID past the table's end)
+//   out   {tile, m_tiles, n_tiles, xcd_cols, out_stats partials per row (0 without out_stats), bm, bn, A ring depth, W ring depth,
+//          ln_aware, part of the product library, has a backward kernel}
+// The persistent form (gemm_bf16_pp.hpp) is not planned here: its automatic choice reads the device's CU count.  A shape it could
+// take (ufnd_diag_pp_shape_ok) is refused for the automatic forward entries, and so is UFND_GEMM_TILE_PERSISTENT.
+int ufnd_diag_pp_shape_ok(int M, int N, int K);      // gemm_pp_diag.hip
+extern "C" int ufnd_diag_gemm_bf16_plan(int entry, const void* A, const void* W, const float* bias, const float* residual, const void* aux,
+                                        const void* out_bf16, const float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldaux,
+                                        int ldo, int ldf, int act, int tile_cfg, const ufnd_gemm_ln* ln, int* out) {
+  UFND_REQUIRE(out, "gemm_bf16_plan: null result pointer");
+  UFND_REQUIRE(entry >= -1 && entry <= 3, "gemm_bf16_plan: entry %d", entry);
+  int cfg = tile_cfg, rc = UFND_OK, parts = 0;
+  if (entry == -1) {
+    UFND_REQUIRE(cfg >= 0 && cfg < kNumTiles, "gemm_bf16_plan: no tile %d", cfg);
+    M = N = K = 0;
+  } else if (entry == 3) {
+    rc = gemm_bf16_dgrad_check_args(A, W, residual, aux, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldaux, ldo, ldf, act);
+    if (rc != UFND_OK) return rc;
+    cfg = auto_cfg(M, N, K);
+    rc = gemm_bf16_dgrad_check_tile(cfg, N);
+    if (rc != UFND_OK) return rc;
+  } else {
+    if (entry == 2) {
+      rc = gemm_bf16_ln_check_args(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln);
+      if (rc != UFND_OK) return rc;
+      cfg = ln->tile_cfg;
+    } else {
+      rc = gemm_bf16_check_args(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act);
+      if (rc != UFND_OK) return rc;
+      if (entry == 0) cfg = -1;
+    }
+    UFND_REQUIRE(cfg != UFND_GEMM_TILE_PERSISTENT && !(cfg < 0 && ufnd_diag_pp_shape_ok(M, N, K)),
+                 "gemm_bf16_plan: the persistent form may take this call (its choice needs the device): not planned here");
+    if (cfg < 0) cfg = auto_cfg(M, N, K);
+    rc = entry == 2 ? gemm_bf16_ln_check_tile(cfg, M, N, K, ln) : gemm_bf16_check_tile(cfg, N);
+    if (rc != UFND_OK) return rc;
+    if (entry == 2 && ln->out_stats) parts = stat_parts_for(cfg, N);
+  }
+  const TileCfg& t = kTiles[cfg];
+  const int m_tiles = entry < 0 ? 0 : ufnd_cdiv(M, t.bm), n_tiles = entry < 0 ? 0 : N / t.bn;      // (as launch_cfg)
+  out[0] = cfg;
+  out[1] = m_tiles;
+  out[2] = n_tiles;
+  out[3] = entry < 0 ? 0 : xcd_cols_for(M, N, K, m_tiles, n_tiles);
+  out[4] = parts;
+  out[5] = t.bm; out[6] = t.bn; out[7] = t.sta; out[8] = t.stb; out[9] = t.lnx; out[10] = t.prod; out[11] = gemm_bwd_tile(cfg) ? 1 : 0;
   return UFND_OK;
 }

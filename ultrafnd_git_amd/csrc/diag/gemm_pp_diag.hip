@@ -23,3 +23,6 @@ extern "C" int ufnd_diag_gemm_pp_stamps(const void* A, const void* W, void* out_
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
+
+// whether the persistent form's shape conditions hold (the host-only plan entry of gemm_diag.hip refuses to plan such a call)
+int ufnd_diag_pp_shape_ok(int M, int N, int K) { return pp_shape_ok(M, N, K) ? 1 : 0; }

@@ -2,6 +2,7 @@
 // launcher: gemm_bf16_kernel.hpp.  No environment overrides, no ablation kernels, no stamps here: those live in
 // diag/gemm_diag.hip (libultrafnd_hip_diag.so).
 #include "gemm_bf16_kernel.hpp"
+#include "gemm_bf16_checks.hpp"
 
 // the persistent, software-pipelined form (gemm_bf16_pp.hpp), compiled in gemm_bf16_pp.hip
 #define UFND_GEMM_TILE_PP UFND_GEMM_TILE_PERSISTENT
@@ -27,22 +28,15 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* src, __bf16
 extern "C" int ufnd_gemm_bf16_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
                                    float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
                                    int tile_cfg, const int* m_live, void* stream_) {
-  UFND_REQUIRE(A && W && (out_bf16 || out_f32), "gemm_bf16: null operand");
-  UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "gemm_bf16: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
-  UFND_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ufnd_aligned(A, 16) && ufnd_aligned(W, 16),
-               "gemm_bf16: A/W strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!residual || (ldr % 4 == 0 && ldr >= N && ufnd_aligned(residual, 16)), "gemm_bf16: residual alignment");
-  UFND_REQUIRE(!out_f32 || (ldf % 4 == 0 && ldf >= N && ufnd_aligned(out_f32, 16)), "gemm_bf16: out_f32 alignment");
-  UFND_REQUIRE(!out_bf16 || (ldo % 8 == 0 && ldo >= N && ufnd_aligned(out_bf16, 16)), "gemm_bf16: out_bf16 alignment");
-  UFND_REQUIRE(!bias || ufnd_aligned(bias, 4), "gemm_bf16: bias alignment");
-  UFND_REQUIRE(act >= 0 && act <= 2, "gemm_bf16: act=%d", act);
+  int rc = gemm_bf16_check_args(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act);
+  if (rc != UFND_OK) return rc;
   GemmArgs a{(const __bf16*)A, (const __bf16*)W, bias, residual, (__bf16*)out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, 0, 0, nullptr};
   a.m_live = m_live;
   if (tile_cfg == UFND_GEMM_TILE_PP || (tile_cfg < 0 && ufnd_pp_pick(&a))) return ufnd_pp_launch(&a, stream_);      // the persistent, software-pipelined form
   const int cfg = tile_cfg < 0 ? auto_cfg(M, N, K) : tile_cfg;
-  UFND_REQUIRE(cfg < kNumTiles && kTiles[cfg].built, "gemm_bf16: tile config %d is not part of this library (ufnd_gemm_bf16_tile_info)", cfg);
-  UFND_REQUIRE(N % kTiles[cfg].bn == 0, "gemm_bf16: tile config %d needs N %% %d == 0", cfg, kTiles[cfg].bn);
-  int rc = launch_cfg(cfg, 0, a, (hipStream_t)stream_);
+  rc = gemm_bf16_check_tile(cfg, N);
+  if (rc != UFND_OK) return rc;
+  rc = launch_cfg(cfg, 0, a, (hipStream_t)stream_);
   if (rc != UFND_OK) return rc;
   UFND_CHECK_LAUNCH();
   return UFND_OK;
@@ -63,12 +57,6 @@ extern "C" int ufnd_gemm_bf16_tile_info(int tile_cfg, int* bm, int* bn, int* ln_
 }
 extern "C" int ufnd_gemm_bf16_tile_count(void) { return kNumTiles; }
 
-static int stat_parts_for(int cfg, int N) {
-  const TileCfg& t = kTiles[cfg];
-  const int tn = t.bn / t.wn;
-  if (!t.built || !t.lnx || N % t.bn != 0 || tn % 32 != 0 || (N / 32) % 2 != 0 || N / 32 > 24) return 0;
-  return N / 32;
-}
 extern "C" int ufnd_gemm_bf16_stat_parts(int M, int N, int K) {
   // the automatic choice of an out_stats call on the bf16 residual stream (ufnd_gemm_ln.residual_bf16, bf16 output only) can be the
   // persistent form (pp_pick: the configs[3] geometry's out-projection, 65,536 rows): ask the same dispatch the call will take
@@ -95,31 +83,8 @@ extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias
 extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
                                       float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
                                       const ufnd_gemm_ln* ln, const int* m_live, void* stream_) {
-  UFND_REQUIRE(A && W && ln && (out_bf16 || out_f32), "gemm_bf16_ln: null operand");
-  UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "gemm_bf16_ln: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
-  UFND_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ufnd_aligned(A, 16) && ufnd_aligned(W, 16),
-               "gemm_bf16_ln: A/W strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!residual || (ldr % 4 == 0 && ldr >= N && ufnd_aligned(residual, 16)), "gemm_bf16_ln: residual alignment");
-  UFND_REQUIRE(!out_f32 || (ldf % 4 == 0 && ldf >= N && ufnd_aligned(out_f32, 16)), "gemm_bf16_ln: out_f32 alignment");
-  UFND_REQUIRE(!out_bf16 || (ldo % 8 == 0 && ldo >= N && ufnd_aligned(out_bf16, 16)), "gemm_bf16_ln: out_bf16 alignment");
-  UFND_REQUIRE(!bias || ufnd_aligned(bias, 16), "gemm_bf16_ln: bias must be 16-B aligned");
-  UFND_REQUIRE(act >= 0 && act <= 2, "gemm_bf16_ln: act=%d", act);
-  UFND_REQUIRE(!(ln->a_stats && ln->r_stats), "gemm_bf16_ln: a_stats and r_stats are mutually exclusive");
-  UFND_REQUIRE(!(residual && ln->residual_bf16), "gemm_bf16_ln: residual (fp32) and residual_bf16 are mutually exclusive");
-  UFND_REQUIRE(!ln->residual_bf16 || (ln->ldrb % 8 == 0 && ln->ldrb >= N && ufnd_aligned(ln->residual_bf16, 16)), "gemm_bf16_ln: residual_bf16 alignment");
-  UFND_REQUIRE(ln->a_stats || act == UFND_ACT_NONE, "gemm_bf16_ln: an activation is only fused together with a folded LayerNorm (a_stats)");
-  UFND_REQUIRE(ln->width > 0, "gemm_bf16_ln: width (the LayerNorm dimension) must be positive");
-  if (ln->a_stats) {
-    UFND_REQUIRE(!residual && !ln->residual_bf16 && !ln->out_stats,
-                 "gemm_bf16_ln: a folded LayerNorm (a_stats) takes no residual and writes no out_stats (that epilogue is compiled without them)");
-    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "gemm_bf16_ln: colsum / a_stats alignment");
-    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0, "gemm_bf16_ln: a_parts=%d (even, 2..24)", ln->a_parts);
-  }
-  if (ln->r_stats) {
-    UFND_REQUIRE((residual || ln->residual_bf16) && ln->r_gamma && ln->r_beta && ufnd_aligned(ln->r_gamma, 16) && ufnd_aligned(ln->r_beta, 16) &&
-                     ufnd_aligned(ln->r_stats, 16), "gemm_bf16_ln: r_stats needs residual, r_gamma, r_beta (16-B aligned)");
-    UFND_REQUIRE(ln->r_parts >= 2 && ln->r_parts <= 24 && ln->r_parts % 2 == 0, "gemm_bf16_ln: r_parts=%d (even, 2..24)", ln->r_parts);
-  }
+  int rc = gemm_bf16_ln_check_args(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln);
+  if (rc != UFND_OK) return rc;
   GemmArgs a{(const __bf16*)A, (const __bf16*)W, bias, residual, (__bf16*)out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, 0, 0, nullptr};
   a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.r_stats = ln->r_stats; a.r_gamma = ln->r_gamma; a.r_beta = ln->r_beta;
   a.out_stats = ln->out_stats; a.a_parts = ln->a_parts; a.r_parts = ln->r_parts; a.a_eps = ln->a_eps; a.r_eps = ln->r_eps;
@@ -130,12 +95,9 @@ extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float*
   a.m_live = m_live;
   if (ln->tile_cfg == UFND_GEMM_TILE_PP || (ln->tile_cfg < 0 && ufnd_pp_pick(&a))) return ufnd_pp_launch(&a, stream_);      // the persistent, software-pipelined form
   const int cfg = ln->tile_cfg < 0 ? auto_cfg(M, N, K) : ln->tile_cfg;
-  UFND_REQUIRE(cfg < kNumTiles && kTiles[cfg].built && kTiles[cfg].lnx && N % kTiles[cfg].bn == 0,
-               "gemm_bf16_ln: no LayerNorm-aware kernel for M=%d N=%d K=%d (tile %d)", M, N, K, cfg);
-  if (ln->out_stats) {
-    UFND_REQUIRE(stat_parts_for(cfg, N) > 0 && ufnd_aligned(ln->out_stats, 16), "gemm_bf16_ln: out_stats unsupported for this shape / tile");
-  }
-  int rc = launch_cfg(cfg, 4, a, (hipStream_t)stream_);
+  rc = gemm_bf16_ln_check_tile(cfg, M, N, K, ln);
+  if (rc != UFND_OK) return rc;
+  rc = launch_cfg(cfg, 4, a, (hipStream_t)stream_);
   if (rc != UFND_OK) return rc;
   UFND_CHECK_LAUNCH();
   return UFND_OK;

@@ -12,6 +12,7 @@
 //   db     = column sums of dy, produced by the same pass that transposes dy (two-stage, fixed order)
 #define UFND_GEMM_ONLY_BWD 1
 #include "gemm_bf16_kernel.hpp"
+#include "gemm_bf16_checks.hpp"
 
 namespace {
 
@@ -253,23 +254,16 @@ int wgrad_slices(int n_out, int k_in, int m_tokens, int cfg) {
 
 extern "C" int ufnd_gemm_bf16_dgrad(const void* dY, const void* Wt, const float* residual, const void* aux, void* out_bf16, float* out_f32,
                                     int M, int N, int K, int lda, int ldw, int ldr, int ldaux, int ldo, int ldf, int act, void* stream_) {
-  UFND_REQUIRE(dY && Wt && (out_bf16 || out_f32), "gemm_bf16_dgrad: null operand");
-  UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "gemm_bf16_dgrad: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
-  UFND_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ufnd_aligned(dY, 16) && ufnd_aligned(Wt, 16),
-               "gemm_bf16_dgrad: operand strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!residual || (ldr % 4 == 0 && ldr >= N && ufnd_aligned(residual, 16)), "gemm_bf16_dgrad: residual alignment");
-  UFND_REQUIRE(!out_f32 || (ldf % 4 == 0 && ldf >= N && ufnd_aligned(out_f32, 16)), "gemm_bf16_dgrad: out_f32 alignment");
-  UFND_REQUIRE(!out_bf16 || (ldo % 8 == 0 && ldo >= N && ufnd_aligned(out_bf16, 16)), "gemm_bf16_dgrad: out_bf16 alignment");
-  UFND_REQUIRE(act == UFND_ACT_NONE || act == UFND_ACT_GELU_BWD || act == UFND_ACT_QUICK_GELU_BWD, "gemm_bf16_dgrad: act=%d", act);
-  UFND_REQUIRE((act == UFND_ACT_NONE) == (aux == nullptr), "gemm_bf16_dgrad: aux (the pre-activations) goes with an activation backward, and only with one");
-  UFND_REQUIRE(!aux || (!residual && ldaux % 8 == 0 && ldaux >= N && ufnd_aligned(aux, 16)), "gemm_bf16_dgrad: aux alignment (and no residual beside it)");
+  int rc = gemm_bf16_dgrad_check_args(dY, Wt, residual, aux, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldaux, ldo, ldf, act);
+  if (rc != UFND_OK) return rc;
   GemmArgs a{(const __bf16*)dY, (const __bf16*)Wt, nullptr, residual, (__bf16*)out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, 0, 0, nullptr};
   a.aux = (const __bf16*)aux;
   a.ldaux = ldaux;
   a.ksplit = 1;
   const int cfg = auto_cfg(M, N, K);
-  UFND_REQUIRE(N % kTiles[cfg].bn == 0, "gemm_bf16_dgrad: tile %d needs N %% %d == 0", cfg, kTiles[cfg].bn);
-  int rc = launch_cfg(cfg, 6, a, (hipStream_t)stream_);
+  rc = gemm_bf16_dgrad_check_tile(cfg, N);
+  if (rc != UFND_OK) return rc;
+  rc = launch_cfg(cfg, 6, a, (hipStream_t)stream_);
   if (rc != UFND_OK) return rc;
   UFND_CHECK_LAUNCH();
   return UFND_OK;

@@ -1077,13 +1077,17 @@ void gemm_bf16_kernel(const GemmArgs a) {
 #define UFND_TILE_BUILT(PROD_) (PROD_)
 #endif
 
-struct TileCfg { int bm, bn, threads, wn, lnx, built; };
+// (sta / stb: the LDS ring depths of the A / W operand; prod: part of the product library -- `built` is 1 for every tile in the
+//  diagnostics library)
+struct TileCfg { int bm, bn, threads, wn, lnx, built, sta, stb, prod; };
 static const TileCfg kTiles[] = {
-#define X(id, BM_, BN_, WM_, WN_, SA_, SB_, MI_, LN_, PROD_) {BM_, BN_, WM_ * WN_ * 64, WN_, LN_, UFND_TILE_BUILT(PROD_)},
+#define X(id, BM_, BN_, WM_, WN_, SA_, SB_, MI_, LN_, PROD_) {BM_, BN_, WM_ * WN_ * 64, WN_, LN_, UFND_TILE_BUILT(PROD_), SA_, SB_, PROD_},
     UFND_GEMM_TILES(X)
 #undef X
 };
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// tiles with a backward (BWD) instantiation: the ones the automatic choice can return (gemm_bf16_bwd.hip)
+constexpr bool gemm_bwd_tile(int id) { return id == 15 || id == 16 || id == 17 || id == 20 || id == 22; }
 
 // Column split of the grid over the XCDs (see the kernel): worth it where the weight operand (N x K) outweighs the
 // activation operand (M x K) per launch AND both halves still give every XCD whole row panels.
@@ -1114,7 +1118,7 @@ static int launch_cfg(int cfg, int mode, GemmArgs& a, hipStream_t stream) {
   // gemm_bf16_bwd.hip: only the backward kernels (mode 6) of the tiles the automatic choice can return
 #define X(id, BM_, BN_, WM_, WN_, SA_, SB_, MI_, LN_, PROD_)                                                                      \
   case id:                                                                                                                        \
-    if constexpr (id == 15 || id == 16 || id == 17 || id == 20 || id == 22) {                                                     \
+    if constexpr (gemm_bwd_tile(id)) {                                                                                            \
       hipLaunchKernelGGL((gemm_bf16_kernel<BM_, BN_, WM_, WN_, SA_, SB_, MI_, 0, 0, 0, 0, 1>), grid, block, 0, stream, a);        \
     } else {                                                                                                                      \
       ufnd_set_error("gemm_bf16 backward: tile %d has no backward kernel", id);                                                   \
