@@ -792,7 +792,10 @@ int ufnd_transpose_bf16(const void* src, int src_is_f32, int rows, int cols, int
  * log2 domain -- what ufnd_attention_bf16_bwd recomputes P from. */
 int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads, void* stream);
 /* dqkv (B L, 3H) bf16 = the gradients of the fused q | k | v rows, from dctx (B L, H) bf16, the forward's qkv, ctx and lse.
- * workspace: ufnd_attention_bwd_workspace_floats floats (delta = rowsum(dO o O)).  Three launches (delta; dQ; dK and dV). */
+ * workspace: ufnd_attention_bwd_workspace_floats floats (delta = rowsum(dO o O)).  Three launches (delta; dQ; dK and dV).
+ * A masked key of a sample that has a live key gets dK = dV = 0 exactly.  A sample WITHOUT a live key is the forward's uniform
+ * average (P = 1 / L over all L keys, lse = the mask constant -3e38, which is how its rows are recognised: lse > -1e30 fails) and
+ * is differentiated as such: dV_j = (1 / L) sum_i dO_i for every key, dS = (dP - delta) / (8 L). */
 size_t ufnd_attention_bwd_workspace_floats(int B, int L, int heads);
 int ufnd_attention_bf16_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* key_mask, void* dqkv,
                             float* workspace, int B, int L, int heads, void* stream);

@@ -17,7 +17,9 @@
 // S and dP are computed twice (7 products instead of 5): no gradient is summed across workgroups -- no atomics, no second
 // pass, bitwise reproducible -- and attention is a few percent of an encoder layer's FLOPs at these lengths.
 // Masked keys (HF semantics, as the forward): score = the finfo.min-like constant, so P = 0 for them wherever a row has a
-// live key; keys / queries beyond L contribute exactly zero.
+// live key; keys / queries beyond L contribute exactly zero.  A sample WITHOUT a live key is the forward's uniform average:
+// its lse is the mask constant itself (-3e38 + log2 L = -3e38 in fp32), from which no P can be recomputed, so such a row is
+// recognised by the forward's own test (lse > -1.0e30f fails) and gets P = 1 / L for the L keys.
 //
 // Training dropout (DROP, ufnd_attention_bf16_bwd_dropout; the forward used O = (m o P) V with the same mask m):
 //   dV = (m o P)^T dO,  dP = m o (dO V^T),  dS = P o (dP - delta)
@@ -150,6 +152,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
     kscale = 1.0f / (1.0f - dr.p);
   }
 
+  const float inv_L = 1.0f / (float)L;
   f32x4 acc0[4][2], acc1[4][2];      // pass 1: dQ^T (acc0); pass 2: dK^T (acc0), dV^T (acc1)
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -235,7 +238,10 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const __bf16* qkv, c
             ls = wv0[r];
             dl = wv1[r];
           }
-          const float p = fast_exp2(sc2 - ls);
+          // a query without a live key (the forward's uniform average: its lse is the mask constant, m_run > -1.0e30f fails): P = 1 / L
+          // over the L keys -- exp2(sc2 - ls) would be exp2(0) = 1 there.  Every other row keeps its bits (a select).
+          float p = fast_exp2(sc2 - ls);
+          p = (ls > -1.0e30f) ? p : (sc2 > -INFINITY ? inv_L : 0.0f);
           if constexpr (DROP) {
             const float dsv = p * (dp[rt][t][r] * dm[r] - dl) * scale;
             pf[rt >> 1][t][(rt & 1) * 4 + r] = (__bf16)(p * dm[r]);
