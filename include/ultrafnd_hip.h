@@ -893,6 +893,55 @@ int ufnd_token_attribution(const float* g, int ldg, const float* s, int lds, con
 int ufnd_vit_unpatchify_attribution(const float* dpatches, const float* x, const float* base, float* grad, float* pixels, float* patch_sums,
                                     int N, int image, int patch, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Audio encoder (wav2vec2-base geometry; csrc/audio.hip, ultrafnd_git_amd/audio.py).  Frames are rows, channel-last, in
+ * per-clip slabs: after conv0 clip b owns rows b S1 .. b S1 + T1_b - 1 of a (B S1, 512) bf16 buffer (S1 a multiple of 64), every
+ * stride-2 layer halves the slab.  A valid output row reads valid input rows only; slab-tail rows hold garbage nothing valid reads.
+ * Every reduction below runs a fixed tree that depends on the clip's own length only: a clip's results do not depend on its batch.
+ * ------------------------------------------------------------------------------------------- */
+#define UFND_AUDIO_MIN_SAMPLES 400      /* one output frame of the seven-layer feature extractor */
+#define UFND_WAVE_CHUNK 4096            /* samples per partial of ufnd_wave_normalize */
+#define UFND_CONV0_CHUNK 256            /* frames per partial of ufnd_w2v2_conv0 */
+
+/* Wav2Vec2FeatureExtractor(do_normalize): out[b, i] = (wave[b, i] - mean_b) / sqrt(var_b + 1e-7) for i < lengths[b] (population
+ * variance over the clip's own samples; samples past lengths[b] are neither read nor written).  wave, out (B, n_max) fp32;
+ * lengths (B) int32 on the device, each in [UFND_AUDIO_MIN_SAMPLES, n_max]; ws: 3 B ceil(n_max / UFND_WAVE_CHUNK) floats.
+ * Partials per chunk are {pivot, sum, sum of squares about the pivot} in fp32, combined in float64 (Chan). */
+int ufnd_wave_normalize(const float* wave, const int32_t* lengths, float* out, float* ws, int B, int n_max, void* stream);
+
+/* Layer 0 of the feature extractor: Conv1d(1 -> 512, k = 10, s = 5, no bias) + GroupNorm(512, 512) (per clip and channel over
+ * the clip's T1_b = (lengths[b] - 10) / 5 + 1 frames, biased variance, affine) + GELU.  Two passes that both recompute the conv
+ * from the wave: the fp32 conv output is never stored.  wave (B, n_max) fp32 (normalised); w (512, 10); out_bf16 rows b S1 + t;
+ * out_f32 (optional, tests): the same rows before the bf16 rounding.  ws: 3 B 512 ceil(S1 / UFND_CONV0_CHUNK) + 2 B 512 floats. */
+int ufnd_w2v2_conv0(const float* wave, const int32_t* lengths, const float* w, const float* gamma, const float* beta, void* out_bf16,
+                    float* out_f32, float* ws, int B, int n_max, int S1, float eps, void* stream);
+
+/* A strided Conv1d over frames-as-rows as ONE bf16 GEMM with an overlapping-row A operand (no unfold buffer): output row r is
+ * act(W . A[r lda .. r lda + K) + bias), i.e. ufnd_gemm_bf16 with lda < K allowed (lda = stride C, K = k C, W tap-major (N, k C)).
+ * The caller owns the rows past M the last rows read: A must hold (M - 1) lda + K elements.  lda % 8 == 0, K % 64 == 0,
+ * N % 64 == 0; same kernel and tile choice as ufnd_gemm_bf16 (whose entries keep requiring lda >= K). */
+int ufnd_conv1d_rows_bf16(const void* A, const void* W, const float* bias, void* out_bf16, float* out_f32, int M, int N, int K, int lda,
+                          int ldw, int ldo, int ldf, int act, void* stream);
+
+/* Positional conv, step 1: x (B S, 768) bf16 -> 16 group-major, edge-padded panels packed[g] (Mp, 48) bf16, Mp = B Sp + 128,
+ * Sp = S + 128: row b Sp + 64 + t of panel g = x[b S + t, 48 g .. 48 g + 47] for t < frames[b], zero for every other row of the
+ * clip's Sp rows (the conv's zero padding sits at the CLIP's edges) and for the 128 spare rows behind the last clip, which the
+ * last rows of the GEMM below read: every row of every panel is written, nothing depends on what `packed` held.  Conv1d(768, 768, k = 128, pad = 64, groups = 16) is then 16
+ * ufnd_conv1d_rows_bf16 calls with lda = 48, K = 6144, N = 64 (48 padded). */
+int ufnd_w2v2_pos_pack(const void* x_bf16, const int32_t* frames, void* packed, int B, int S, void* stream);
+/* Step 2: y[b S + t, 48 g + o] = x[b S + t, 48 g + o] + conv[g][b Sp + t][o] for t < frames[b] (conv (16, B Sp, 64) fp32 holds
+ * GELU(conv + bias)), zero for the slab's other rows (so that nothing downstream of here reads garbage). */
+int ufnd_w2v2_pos_add(const float* x, const float* conv, const int32_t* frames, float* y, int B, int S, void* stream);
+
+/* frames[b] = the feature extractor's output length for lengths[b] samples; key_mask (B, S) = 1 for t < frames[b]. */
+int ufnd_w2v2_frames(const int32_t* lengths, int32_t* frames, int32_t* key_mask, int B, int S, void* stream);
+
+/* out.mean(dim=1) over a clip's valid frames: ufnd_masked_meanpool_l2's first phase (same grouping, same order), no L2. */
+int ufnd_masked_meanpool(const float* hidden, const int32_t* mask, float* out, int B, int L, int H, void* stream);
+
+/* Y (M, N) = X (M, K) W^T + bias in exact fp32 (the skinny-GEMM family of the head; N % 32 == 0, 16-B aligned rows). */
+int ufnd_linear_f32(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

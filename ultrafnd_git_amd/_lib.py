@@ -114,6 +114,7 @@ ADJ_KNN, ADJ_OCR, ADJ_TEMPORAL = 1, 2, 4   # ufnd_dense_adj flags
 KNN_MAX_K = 64                              # ufnd_cosine_knn: neighbours per row
 ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
+AUDIO_MIN_SAMPLES, WAVE_CHUNK, CONV0_CHUNK = 400, 4096, 256      # UFND_AUDIO_MIN_SAMPLES, UFND_WAVE_CHUNK, UFND_CONV0_CHUNK
 
 _lib: Optional[C.CDLL] = None
 
@@ -225,6 +226,16 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_dropout_residual_layernorm": [P, I, P, I, P, P, P, P, P, I, I, F, C.POINTER(Dropout), P],
         "ufnd_layernorm_dropout": [P, I, P, P, P, P, I, I, F, C.POINTER(Dropout), P],
         "ufnd_layernorm_bwd_dropout": [P, I, P, P, I, P, I, P, P, I, P, P, P, I, I, I, F, C.POINTER(Dropout), I, P],
+    })
+    sigs.update({      # the audio encoder (csrc/audio.hip)
+        "ufnd_wave_normalize": [P, P, P, P, I, I, P],
+        "ufnd_w2v2_conv0": [P] * 8 + [I, I, I, F, P],
+        "ufnd_conv1d_rows_bf16": [P] * 5 + [I] * 8 + [P],
+        "ufnd_w2v2_pos_pack": [P, P, P, I, I, P],
+        "ufnd_w2v2_pos_add": [P, P, P, P, I, I, P],
+        "ufnd_w2v2_frames": [P, P, P, I, I, P],
+        "ufnd_masked_meanpool": [P, P, P, I, I, I, P],
+        "ufnd_linear_f32": [P, P, P, P, I, I, I, P],
     })
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

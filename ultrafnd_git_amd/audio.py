@@ -1,0 +1,343 @@
+"""Frozen, forward-only audio encoder that produces the `audio` (B, 128) input of the fusion step, MI355X-native.
+
+  Wav2Vec2AudioEncoder  replaces SpectralForensics._w2v2_features (src/core_blocks/audio_blocks.py:111-139): utterance
+                        normalisation (Wav2Vec2FeatureExtractor do_normalize) -> Wav2Vec2Model (wav2vec2-base geometry)
+                        .last_hidden_state -> mean over time -> Linear(768, 128); batched over clips instead of one record at a
+                        time on the CPU.
+  SpectralForensics     the reference's class name and extract(audio, sr), bound to the encoder above.
+
+Weights keep HF's `Wav2Vec2Model` state_dict names (plus proj.weight / proj.bias), so real checkpoints load unchanged.
+
+Layout: frames are rows, channel-last, in per-clip slabs.  After conv layer 0 clip b owns rows
+b S1 .. b S1 + T1_b - 1 of a (B S1, 512) bf16 buffer, S1 a multiple of 64; each stride-2 layer halves the slab, so ONE
+overlapping-row GEMM launch per conv layer covers all clips and the transformer runs on slabs of S = S1 / 64 rows.  A valid
+output row reads valid input rows only; slab-tail rows are garbage until the positional conv's add kernel zeroes them.
+
+Every clip is computed as if it were alone: its own normalisation, GroupNorm statistics, attention keys and mean.  A clip's
+feature is bit-identical alone and inside any batch, and from run to run (no atomics; fixed reduction trees; a GEMM row's
+arithmetic does not depend on the tile it lands in).  No CPU path.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .encoders import ACT_GELU, BertTextEncoder, _bf16, _EncoderBase, _TextPass
+
+CONV_KERNELS = (10, 3, 3, 3, 3, 2, 2)
+CONV_STRIDES = (5, 2, 2, 2, 2, 2, 2)
+CONV_DIM = 512
+POS_KERNEL, POS_GROUPS = 128, 16
+MIN_SAMPLES = L.AUDIO_MIN_SAMPLES
+STAGES = ("conv0", "conv", "pos", "layers")
+
+
+def frame_counts(n: int) -> List[int]:
+    """Frames after each of the seven conv layers for a clip of n samples: T_out = (T_in - k) // s + 1."""
+    out, t = [], int(n)
+    for k, s in zip(CONV_KERNELS, CONV_STRIDES):
+        t = (t - k) // s + 1
+        out.append(t)
+    return out
+
+
+def frame_count(n: int) -> int:
+    """Wav2Vec2Model._get_feat_extract_output_lengths for the wav2vec2-base geometry."""
+    return frame_counts(n)[-1]
+
+
+def slab_rows(n_max: int) -> int:
+    """S1: rows of a clip's slab after conv layer 0 -- the frames of the longest clip rounded up to a multiple of 64."""
+    return (frame_counts(n_max)[0] + 63) // 64 * 64
+
+
+def tap_major(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d weight (out, in, k) -> (out, k in): the weight of the overlapping-row GEMM (row r = k in contiguous elements from
+    frame s r on, channel-last)."""
+    return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def resolve_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """The positional conv's weight_norm(dim=2) parametrisation: w = g v / ||v||, the norm over dims (0, 1) per tap;
+    g = original0 (1, 1, k), v = original1 (out, in / groups, k)."""
+    return g * v / v.norm(p=2, dim=(0, 1), keepdim=True)
+
+
+def pos_group_weights(w: torch.Tensor, bias: torch.Tensor):
+    """Grouped conv weight (768, 48, 128) and bias (768) -> per-group tap-major GEMM weights (16, 64, 128 * 48) and biases
+    (16, 64): group g's 48 output rows padded with zero rows to the GEMM's 64-column granule."""
+    G, k = POS_GROUPS, w.shape[2]
+    co, ci = w.shape[0] // G, w.shape[1]
+    wg = torch.zeros(G, 64, k * ci, dtype=w.dtype, device=w.device)
+    bg = torch.zeros(G, 64, dtype=bias.dtype, device=bias.device)
+    wg[:, :co] = w.view(G, co, ci, k).permute(0, 1, 3, 2).reshape(G, co, k * ci)
+    bg[:, :co] = bias.view(G, co)
+    return wg.contiguous(), bg.contiguous()
+
+
+class Wav2Vec2AudioEncoder(_EncoderBase):
+    def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, out_dim: int = 128,
+                 conv_dim: Sequence[int] = (CONV_DIM,) * 7, conv_kernel: Sequence[int] = CONV_KERNELS, conv_stride: Sequence[int] = CONV_STRIDES,
+                 conv_bias: bool = False, feat_extract_norm: str = "group", num_conv_pos_embeddings: int = POS_KERNEL,
+                 num_conv_pos_embedding_groups: int = POS_GROUPS, do_stable_layer_norm: bool = False, hidden_act: str = "gelu",
+                 eps: float = 1e-5):
+        # the wav2vec2-base geometry only (transformers.Wav2Vec2Config() defaults); anything else is refused by name
+        for name, got, want in (("hidden", hidden, 768), ("heads", heads, 12), ("conv_dim", tuple(conv_dim), (CONV_DIM,) * 7),
+                                ("conv_kernel", tuple(conv_kernel), CONV_KERNELS), ("conv_stride", tuple(conv_stride), CONV_STRIDES),
+                                ("conv_bias", bool(conv_bias), False), ("feat_extract_norm", feat_extract_norm, "group"),
+                                ("num_conv_pos_embeddings", num_conv_pos_embeddings, POS_KERNEL),
+                                ("num_conv_pos_embedding_groups", num_conv_pos_embedding_groups, POS_GROUPS),
+                                ("do_stable_layer_norm", bool(do_stable_layer_norm), False), ("hidden_act", hidden_act, "gelu")):
+            if got != want:
+                raise ValueError(f"{name}={got!r}: Wav2Vec2AudioEncoder is built for the wav2vec2-base geometry ({name}={want!r})")
+        if intermediate % 64 or out_dim % 32 or layers < 1:
+            raise ValueError(f"intermediate={intermediate} (a multiple of 64), out_dim={out_dim} (a multiple of 32), layers={layers} (>= 1)")
+        super().__init__(hidden, heads, fold_ln=False, residual_dtype="fp32")      # the plain (unfolded-LayerNorm) layer form
+        self.layers, self.inter, self.out_dim, self.eps = layers, intermediate, out_dim, eps
+        w, init = self._w, self._seeded_init()
+        F, E = "feature_extractor.conv_layers.", "encoder."
+        cin = 1
+        for i, k in enumerate(CONV_KERNELS):
+            w[F + f"{i}.conv.weight"] = init((CONV_DIM, cin, k), std=(2.0 / (k * cin)) ** 0.5)      # (HF: kaiming_normal_)
+            cin = CONV_DIM
+        w[F + "0.layer_norm.weight"], w[F + "0.layer_norm.bias"] = torch.ones(CONV_DIM), torch.zeros(CONV_DIM)      # GroupNorm(512, 512)
+        w["feature_projection.layer_norm.weight"], w["feature_projection.layer_norm.bias"] = torch.ones(CONV_DIM), torch.zeros(CONV_DIM)
+        w["feature_projection.projection.weight"] = init((hidden, CONV_DIM))
+        w["feature_projection.projection.bias"] = torch.zeros(hidden)
+        v = init((hidden, hidden // POS_GROUPS, POS_KERNEL), std=2.0 * (1.0 / (POS_KERNEL * hidden)) ** 0.5)
+        w[E + "pos_conv_embed.conv.bias"] = torch.zeros(hidden)
+        w[E + "pos_conv_embed.conv.parametrizations.weight.original0"] = v.norm(p=2, dim=(0, 1), keepdim=True)
+        w[E + "pos_conv_embed.conv.parametrizations.weight.original1"] = v
+        w[E + "layer_norm.weight"], w[E + "layer_norm.bias"] = torch.ones(hidden), torch.zeros(hidden)
+        for i in range(layers):
+            P = E + f"layers.{i}."
+            for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+                w[P + f"attention.{n}.weight"] = init((hidden, hidden))
+                w[P + f"attention.{n}.bias"] = torch.zeros(hidden)
+            w[P + "layer_norm.weight"], w[P + "layer_norm.bias"] = torch.ones(hidden), torch.zeros(hidden)
+            w[P + "feed_forward.intermediate_dense.weight"] = init((intermediate, hidden))
+            w[P + "feed_forward.intermediate_dense.bias"] = torch.zeros(intermediate)
+            w[P + "feed_forward.output_dense.weight"] = init((hidden, intermediate))
+            w[P + "feed_forward.output_dense.bias"] = torch.zeros(hidden)
+            w[P + "final_layer_norm.weight"], w[P + "final_layer_norm.bias"] = torch.ones(hidden), torch.zeros(hidden)
+        w["proj.weight"] = init((out_dim, hidden))
+        w["proj.bias"] = torch.zeros(out_dim)
+
+    # ---- operands
+    def _pack(self):
+        if self._packed is None:
+            w, F, E, layers = self._w, "feature_extractor.conv_layers.", "encoder.", []
+            for i in range(self.layers):
+                P = E + f"layers.{i}."
+                # HF scales q by 1 / sqrt(64) before Q K^T; the attention kernel scales the scores: the same product
+                layers.append({
+                    "wqkv": _bf16(torch.cat([w[P + f"attention.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)),
+                    "bqkv": torch.cat([w[P + f"attention.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous(),
+                    "wo": _bf16(w[P + "attention.out_proj.weight"]), "bo": w[P + "attention.out_proj.bias"],
+                    "g1": w[P + "layer_norm.weight"], "b1": w[P + "layer_norm.bias"],
+                    "w1": _bf16(w[P + "feed_forward.intermediate_dense.weight"]), "bi": w[P + "feed_forward.intermediate_dense.bias"],
+                    "w2": _bf16(w[P + "feed_forward.output_dense.weight"]), "b2": w[P + "feed_forward.output_dense.bias"],
+                    "g2": w[P + "final_layer_norm.weight"], "b2n": w[P + "final_layer_norm.bias"]})
+            pos_w = resolve_weight_norm(w[E + "pos_conv_embed.conv.parametrizations.weight.original0"],
+                                        w[E + "pos_conv_embed.conv.parametrizations.weight.original1"])
+            wg, bg = pos_group_weights(pos_w, w[E + "pos_conv_embed.conv.bias"])
+            self._packed = {"layers": layers,
+                            "w0": w[F + "0.conv.weight"].reshape(CONV_DIM, CONV_KERNELS[0]).contiguous(),
+                            "conv": [_bf16(tap_major(w[F + f"{i}.conv.weight"])) for i in range(1, 7)],
+                            "wfp": _bf16(w["feature_projection.projection.weight"]),
+                            "wpos": _bf16(wg), "bpos": bg}
+        return self._packed
+
+    def _workbufs(self, B: int, n_max: int, S1: int) -> dict:
+        """The work buffers of one pass as views of ONE grow-only store per buffer (self._bufs[name], flat): clip lengths vary freely
+        (a cache builder sees a new n_max with almost every group), so nothing is keyed by the shape -- device memory is that of the
+        largest pass seen, whatever the number of distinct lengths.  Slab strides come from S1, never from a store's size, so a row's
+        bits do not depend on what ran before.  Nothing relies on a buffer's initial content."""
+        dev, H, S = self.device, self.hidden, S1 // 64
+        M, Sp = B * S, S1 // 64 + POS_KERNEL
+        bf, f32, i32 = torch.bfloat16, torch.float32, torch.int32
+        nwc, nfc = -(-n_max // L.WAVE_CHUNK), -(-S1 // L.CONV0_CHUNK)
+        shapes = {
+            "frames": ((B,), i32), "mask": ((B, S), i32),
+            "xn": ((B, n_max), f32), "ws_wave": ((3 * B * nwc,), f32),
+            "ws_conv0": ((3 * B * CONV_DIM * nfc + 2 * B * CONV_DIM,), f32),
+            # conv ping-pong (+ 8 rows: the last slab's tail rows read up to k - 2 rows past their slab)
+            "ca": ((B * S1 + 8, CONV_DIM), bf), "cb": ((B * S1 // 2 + 8, CONV_DIM), bf),
+            "cf": ((M, CONV_DIM), f32), "fb": ((M, CONV_DIM), bf),
+            "x0b": ((M, H), bf), "x0f": ((M, H), f32),
+            "packed": ((POS_GROUPS, B * Sp + POS_KERNEL, H // POS_GROUPS), bf),
+            "pconv": ((POS_GROUPS, B * Sp, 64), f32),
+            "xb": ((M, H), bf), "xf": ((M, H), f32), "y": ((M, H), f32),
+            "x1b": ((M, H), bf), "x1f": ((M, H), f32),
+            "qkv": ((M, 3 * H), bf), "ctx": ((M, H), bf), "h": ((M, self.inter), bf),
+            "pooled": ((B, H), f32), "feat": ((B, self.out_dim), f32)}
+        views = {}
+        for name, (shape, dt) in shapes.items():
+            n = 1
+            for d in shape:
+                n *= d
+            store = self._bufs.get(name)
+            if store is None or store.numel() < n or store.device != dev:
+                self._bufs[name] = store = torch.empty(n, dtype=dt, device=dev)
+            views[name] = store[:n].view(shape)
+        return views
+
+    def workspace_bytes(self) -> int:
+        """Device bytes the work buffers hold: those of the largest pass so far."""
+        return sum(t.numel() * t.element_size() for t in self._bufs.values())
+
+    _self_attention = BertTextEncoder._self_attention
+    _layers = BertTextEncoder._layers
+
+    def _conv_rows(self, A, W, bias, M, lda, out_bf16=None, out_f32=None):
+        N, K = W.shape
+        L.check(L.lib().ufnd_conv1d_rows_bf16(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(out_bf16), L.ptr(out_f32), M, N, K, lda, W.stride(0),
+                                              out_bf16.stride(0) if out_bf16 is not None else 0, out_f32.stride(0) if out_f32 is not None else 0,
+                                              ACT_GELU, L.stream_ptr(A.device)), "ufnd_conv1d_rows_bf16")
+
+    @staticmethod
+    def _lengths(waves: torch.Tensor, lengths) -> List[int]:
+        if waves.dim() != 2:
+            raise ValueError(f"waves: expected (B, n_max), got {tuple(waves.shape)}")
+        B, n_max = waves.shape
+        lens = [n_max] * B if lengths is None else [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B:
+            raise ValueError(f"lengths: {len(lens)} entries for {B} clips")
+        for n in lens:
+            if n < MIN_SAMPLES or n > n_max:
+                raise ValueError(f"clip length {n}: at least {MIN_SAMPLES} samples (one output frame) and at most n_max={n_max}")
+        return lens
+
+    def _run(self, waves: torch.Tensor, lengths=None, n_layers: Optional[int] = None, stage: str = "layers", conv0_f32: Optional[torch.Tensor] = None,
+             pool: bool = True):
+        """One pass over (B, n_max) zero-padded clips up to `stage`: (work buffers, lengths, S1)."""
+        lens = self._lengths(waves, lengths)
+        self._require_hip()
+        dev = self.device
+        waves = waves[:, :max(lens)]      # (padding past the longest clip is never read)
+        B, n_max = waves.shape
+        S1 = slab_rows(n_max)
+        S, M, H, s = S1 // 64, B * (S1 // 64), self.hidden, L.stream_ptr(dev)
+        p, b, w, lib = self._pack(), self._workbufs(B, n_max, S1), self._w, L.lib()
+        x = L.f32c(waves.to(dev))
+        ln = torch.tensor(lens, dtype=torch.int32).to(dev)
+        F = "feature_extractor.conv_layers."
+        L.check(lib.ufnd_w2v2_frames(ln.data_ptr(), b["frames"].data_ptr(), b["mask"].data_ptr(), B, S, s), "ufnd_w2v2_frames")
+        L.check(lib.ufnd_wave_normalize(x.data_ptr(), ln.data_ptr(), b["xn"].data_ptr(), b["ws_wave"].data_ptr(), B, n_max, s), "ufnd_wave_normalize")
+        L.check(lib.ufnd_w2v2_conv0(b["xn"].data_ptr(), ln.data_ptr(), p["w0"].data_ptr(), w[F + "0.layer_norm.weight"].data_ptr(),
+                                    w[F + "0.layer_norm.bias"].data_ptr(), b["ca"].data_ptr(), L.ptr(conv0_f32), b["ws_conv0"].data_ptr(), B, n_max, S1,
+                                    self.eps, s), "ufnd_w2v2_conv0")
+        if stage == "conv0":
+            return b, lens, S1
+        src, dst, rows = b["ca"], b["cb"], S1
+        for i, W in enumerate(p["conv"]):      # layers 1-6: each halves the slab; ONE launch covers all clips
+            rows //= 2
+            if i < 5:
+                self._conv_rows(src, W, None, B * rows, 2 * CONV_DIM, out_bf16=dst)
+            else:
+                self._conv_rows(src, W, None, B * rows, 2 * CONV_DIM, out_f32=b["cf"])      # (fp32: the LayerNorm that follows)
+            src, dst = dst, src
+        if stage == "conv":
+            return b, lens, S1
+        self._ln(b["cf"], CONV_DIM, w["feature_projection.layer_norm.weight"], w["feature_projection.layer_norm.bias"], b["fb"], None, M, CONV_DIM, self.eps)
+        self._gemm(b["fb"], p["wfp"], w["feature_projection.projection.bias"], out_bf16=b["x0b"], out_f32=b["x0f"])
+        # x + GELU(pos_conv(x)): pack -> 16 overlapping-row GEMMs (one per group) -> add; then encoder.layer_norm
+        L.check(lib.ufnd_w2v2_pos_pack(b["x0b"].data_ptr(), b["frames"].data_ptr(), b["packed"].data_ptr(), B, S, s), "ufnd_w2v2_pos_pack")
+        for g in range(POS_GROUPS):
+            self._conv_rows(b["packed"][g], p["wpos"][g], p["bpos"][g], B * (S + POS_KERNEL), H // POS_GROUPS, out_f32=b["pconv"][g])
+        L.check(lib.ufnd_w2v2_pos_add(b["x0f"].data_ptr(), b["pconv"].data_ptr(), b["frames"].data_ptr(), b["y"].data_ptr(), B, S, s), "ufnd_w2v2_pos_add")
+        self._ln(b["y"], H, w["encoder.layer_norm.weight"], w["encoder.layer_norm.bias"], b["xb"], b["xf"], M, H, self.eps)
+        if stage == "pos":
+            return b, lens, S1
+        layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
+        self._layers(layers, b, _TextPass(B, S, b["mask"], fuse=False))
+        if pool:
+            L.check(lib.ufnd_masked_meanpool(b["xf"].data_ptr(), b["mask"].data_ptr(), b["pooled"].data_ptr(), B, S, H, s), "ufnd_masked_meanpool")
+            L.check(lib.ufnd_linear_f32(b["pooled"].data_ptr(), w["proj.weight"].data_ptr(), w["proj.bias"].data_ptr(), b["feat"].data_ptr(), B,
+                                        self.out_dim, H, s), "ufnd_linear_f32")
+        return b, lens, S1
+
+    @torch.no_grad()
+    def normalized(self, waves: torch.Tensor, lengths=None) -> List[torch.Tensor]:
+        """Wav2Vec2FeatureExtractor(do_normalize) of every clip: a list of (n_b,) fp32 tensors (for the tests)."""
+        b, lens, _ = self._run(waves, lengths, stage="conv0")
+        return [b["xn"][i, :n].clone() for i, n in enumerate(lens)]
+
+    @torch.no_grad()
+    def pooled(self, waves: torch.Tensor, lengths=None) -> torch.Tensor:
+        """The mean over each clip's valid frames before the projection, (B, 768) fp32 (a copy; for the tests)."""
+        return self._run(waves, lengths)[0]["pooled"].clone()
+
+    @torch.no_grad()
+    def last_hidden_state(self, waves: torch.Tensor, lengths=None, n_layers: Optional[int] = None, stage: str = "layers") -> List[torch.Tensor]:
+        """Per clip, its valid frames (T_b, C) fp32 at a checkpoint (copies):
+          stage="conv0"   conv layer 0 + GroupNorm + GELU before the bf16 rounding            (T1_b, 512)
+          stage="conv"    the conv stack's output, extract_features before its LayerNorm      (T_b, 512)
+          stage="pos"     after the positional conv and encoder.layer_norm                    (T_b, 768)
+          stage="layers"  Wav2Vec2Model.hidden_states[n_layers] (all layers by default)       (T_b, 768)"""
+        if stage not in STAGES:
+            raise ValueError(f"stage={stage!r}: one of {STAGES}")
+        if stage == "conv0":
+            lens = self._lengths(waves, lengths)
+            S1 = slab_rows(max(lens))
+            f = torch.zeros(len(lens) * S1, CONV_DIM, dtype=torch.float32, device=self.device)
+            self._run(waves, lengths, stage=stage, conv0_f32=f)
+            return [f[i * S1:i * S1 + frame_counts(n)[0]].clone() for i, n in enumerate(lens)]
+        b, lens, S1 = self._run(waves, lengths, n_layers=n_layers, stage=stage, pool=False)
+        S, src = S1 // 64, b["cf"] if stage == "conv" else b["xf"]
+        return [src[i * S:i * S + frame_count(n)].clone() for i, n in enumerate(lens)]
+
+    @torch.no_grad()
+    def forward(self, waves: torch.Tensor, lengths=None) -> torch.Tensor:
+        """waves (B, n_max) fp32, zero-padded; lengths (B,) sample counts (default: all n_max) -> (B, out_dim) fp32 features
+        (a view of an internal buffer, valid until the next call)."""
+        return self._run(waves, lengths)[0]["feat"]
+
+
+class SpectralForensics:
+    """The reference's audio feature extractor (src/core_blocks/audio_blocks.py), its wav2vec2 branch, on the GPU."""
+
+    def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32):
+        self.dim = int(dim)
+        self.encoder = encoder if encoder is not None else Wav2Vec2AudioEncoder(out_dim=self.dim).to(device)
+        if self.encoder.out_dim != self.dim:
+            raise ValueError(f"dim={self.dim} but the encoder projects to {self.encoder.out_dim}")
+        self.max_batch = int(max_batch)
+
+    @staticmethod
+    def _mono_16k(audio, sr: int) -> np.ndarray:
+        if isinstance(audio, str):
+            raise TypeError("SpectralForensics.extract: a str (text proxy) is not supported: the reference's _hash_embed uses Python's salted "
+                            "hash(), so its vectors are not reproducible from run to run")
+        if int(sr) != 16000:
+            raise ValueError(f"sr={sr}: SpectralForensics takes 16 kHz audio (the reference resamples with librosa, which is not part of this package)")
+        wav = audio.detach().cpu().numpy() if torch.is_tensor(audio) else np.asarray(audio)
+        wav = wav.astype(np.float32)
+        if wav.ndim == 2:      # (C, T) -> mono, as _ensure_mono_16k
+            wav = wav.mean(axis=0)
+        if wav.ndim != 1:
+            raise ValueError(f"audio: expected (T,) or (C, T), got {wav.shape}")
+        return wav
+
+    def extract(self, audio_or_text, sr: int = 16000) -> np.ndarray:
+        """One clip -> (dim,) float32."""
+        wav = self._mono_16k(audio_or_text, sr)
+        return self.encoder(torch.from_numpy(wav)[None]).cpu().numpy()[0]
+
+    def extract_batch(self, waves, sr: int = 16000) -> np.ndarray:
+        """A list of clips -> (N, dim) float32: the batched entry of a cache builder.  Clips are sorted by length and run in groups
+        of at most max_batch neighbours, which bounds the padding; every row equals extract() of its clip bit for bit."""
+        wavs = [self._mono_16k(a, sr) for a in waves]
+        out = np.zeros((len(wavs), self.dim), dtype=np.float32)
+        order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
+        for s0 in range(0, len(order), self.max_batch):
+            idx = order[s0:s0 + self.max_batch]
+            n_max = max(len(wavs[i]) for i in idx)
+            batch = torch.zeros(len(idx), n_max)
+            for r, i in enumerate(idx):
+                batch[r, :len(wavs[i])] = torch.from_numpy(wavs[i])
+            out[idx] = self.encoder(batch, [len(wavs[i]) for i in idx]).cpu().numpy()
+        return out

@@ -494,6 +494,17 @@ extern "C" int ufnd_bert_embed(const int64_t* ids, const float* word, const floa
   return UFND_OK;
 }
 
+// the first phase alone: the masked mean, no L2 (the audio encoder's out.mean(dim=1) over a clip's valid frames)
+extern "C" int ufnd_masked_meanpool(const float* hidden, const int32_t* mask, float* out, int B, int L, int H, void* stream_) {
+  UFND_REQUIRE(hidden && mask && out, "meanpool: null argument");
+  UFND_REQUIRE(B >= 1 && B <= 65535 && L >= 1, "meanpool: B=%d L=%d (1 <= B <= 65535 clips, L >= 1 rows)", B, L);
+  UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool: H=%d (multiple of 256)", H);
+  hipLaunchKernelGGL(meanpool_kernel<false>, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H,
+                     (const int32_t*)nullptr);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 extern "C" int ufnd_masked_meanpool_l2(const float* hidden, const int32_t* mask, float* out, int B, int L, int H,
                                        void* stream_) {
   UFND_REQUIRE(hidden && mask && out && B >= 1 && L >= 1, "meanpool: null argument");

@@ -48,6 +48,32 @@ extern "C" int ufnd_gemm_bf16_ex(const void* A, const void* W, const float* bias
   return ufnd_gemm_bf16_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, tile_cfg, nullptr, stream_);
 }
 
+// A strided Conv1d over frames-as-rows (the audio feature extractor, csrc/audio.hip): the same kernel with an OVERLAPPING-row A
+// operand, lda < K.  The kernel forms an A address as A + row * lda + k0 + 8 * chunk (issueA) and nothing else: no address
+// computation uses lda as a bound on K, and a row index is clamped to M - 1, so the furthest element read is (M - 1) lda + K - 1,
+// which the caller's buffer must hold.  The one-tile kernels only: the persistent form keeps 32-bit byte offsets sized for lda >= K
+// operands and is not offered here.  Its own argument check -- the public GEMM entries keep requiring lda >= K.
+extern "C" int ufnd_conv1d_rows_bf16(const void* A, const void* W, const float* bias, void* out_bf16, float* out_f32, int M, int N, int K, int lda,
+                                     int ldw, int ldo, int ldf, int act, void* stream_) {
+  UFND_REQUIRE(A && W && (out_bf16 || out_f32), "conv1d_rows: null operand");
+  UFND_REQUIRE(M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0, "conv1d_rows: M=%d N=%d K=%d (need N%%64==0, K%%64==0)", M, N, K);
+  UFND_REQUIRE(lda >= 8 && lda % 8 == 0 && ldw % 8 == 0 && ldw >= K && ufnd_aligned(A, 16) && ufnd_aligned(W, 16),
+               "conv1d_rows: lda=%d ldw=%d (multiples of 8, ldw >= K) and 16-B aligned pointers", lda, ldw);
+  UFND_REQUIRE((long long)M * lda + K < (1ll << 31), "conv1d_rows: M=%d lda=%d K=%d (the A operand must stay below 2^31 elements)", M, lda, K);
+  UFND_REQUIRE(!out_f32 || (ldf % 4 == 0 && ldf >= N && ufnd_aligned(out_f32, 16)), "conv1d_rows: out_f32 alignment");
+  UFND_REQUIRE(!out_bf16 || (ldo % 8 == 0 && ldo >= N && ufnd_aligned(out_bf16, 16)), "conv1d_rows: out_bf16 alignment");
+  UFND_REQUIRE(!bias || ufnd_aligned(bias, 4), "conv1d_rows: bias alignment");
+  UFND_REQUIRE(act >= 0 && act <= 2, "conv1d_rows: act=%d", act);
+  GemmArgs a{(const __bf16*)A, (const __bf16*)W, bias, nullptr, (__bf16*)out_bf16, out_f32, M, N, K, lda, ldw, 0, ldo, ldf, act, 0, 0, nullptr};
+  const int cfg = auto_cfg(M, N, K);
+  int rc = gemm_bf16_check_tile(cfg, N);
+  if (rc != UFND_OK) return rc;
+  rc = launch_cfg(cfg, 0, a, (hipStream_t)stream_);
+  if (rc != UFND_OK) return rc;
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 extern "C" int ufnd_gemm_bf16_tile_info(int tile_cfg, int* bm, int* bn, int* ln_aware) {
   if (tile_cfg < 0 || tile_cfg >= kNumTiles || !kTiles[tile_cfg].built) return 0;
   if (bm) *bm = kTiles[tile_cfg].bm;
