@@ -236,14 +236,17 @@ int ufnd_head_backward(const ufnd_dims* d, const ufnd_fusion_params* fusion, con
                        void* side_stream, int join, int phase);
 
 /* F.cross_entropy(logits, y), mean reduction, + its gradient (forensic_trainer.py:287).
- * labels int64 (B).  loss_rows (B) or NULL; d_logits (B,2) = (softmax - onehot)/B or NULL.
- * state->loss receives the mean (summed in a fixed order: bit-reproducible). */
+ * labels int64 (B, 8-B aligned).  loss_rows (B) or NULL: each row's own loss, NOT divided by B; d_logits (B,2) = (softmax - onehot)/B
+ * or NULL.  state->loss receives the mean (summed in a fixed order: bit-reproducible).  The row's -log p_c is logf(S) - (l_c - max)
+ * with S = sum exp(l_c - max): nothing is rounded at the logits' common magnitude (a shift of both logits changes no output bit as
+ * long as the shifted logits are exact). */
 int ufnd_softmax_ce(const float* logits, const int64_t* labels, int B, float* loss_rows, float* d_logits,
                     ufnd_step_state* state, void* stream);
 
 /* nn.CrossEntropyLoss(weight=(w0, w1), label_smoothing=eps), mean reduction (normalised by the sum of the
  * target-class weights), + its gradient: the criterion of the integrated trainer variant
- * (src/training/forensic_trainer_integrated.py:154-166).  eps = 0, w = (1, 1) is ufnd_softmax_ce. */
+ * (src/training/forensic_trainer_integrated.py:154-166).  eps = 0, w = (1, 1) is ufnd_softmax_ce in state->loss and d_logits;
+ * loss_rows here are each row's term DIVIDED by the weight sum (they add up to state->loss), B times smaller than ufnd_softmax_ce's. */
 int ufnd_softmax_ce_weighted(const float* logits, const int64_t* labels, int B, float w0, float w1, float label_smoothing,
                              float* loss_rows, float* d_logits, ufnd_step_state* state, void* stream);
 

@@ -193,6 +193,7 @@ extern "C" int ufnd_grad_accumulate(float* dst, const float* src, size_t n, int 
   UFND_REQUIRE(dst && src && n > 0, "grad_accumulate: null argument");
   UFND_REQUIRE(n % 4 == 0 && ufnd_aligned(dst, 16) && ufnd_aligned(src, 16), "grad_accumulate: n %% 4 == 0 and 16-B alignment required");
   UFND_REQUIRE(dst + n <= src || src + n <= dst, "grad_accumulate: dst and src overlap");
+  UFND_REQUIRE(ufnd_aligned(state, 8), "grad_accumulate: state must be 8-B aligned");      // (a null state is aligned)
   size_t want = (n / 4 + 511) / 512;      // two float4 per thread and sweep, as the AdamW pass
   const int blocks = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
   if (overwrite)
@@ -206,6 +207,7 @@ extern "C" int ufnd_grad_accumulate(float* dst, const float* src, size_t n, int 
 extern "C" int ufnd_grad_norm(const float* grad, size_t n, float* partials, ufnd_step_state* state, void* stream_) {
   UFND_REQUIRE(grad && partials && state && n > 0, "grad_norm: null argument");
   UFND_REQUIRE(n % 4 == 0 && ufnd_aligned(grad, 16), "grad_norm: n %% 4 == 0 and 16-B alignment required");
+  UFND_REQUIRE(ufnd_aligned(state, 8) && ufnd_aligned(partials, 4), "grad_norm: state must be 8-B and partials 4-B aligned");
   hipStream_t stream = (hipStream_t)stream_;
   size_t want = (n / 4 + 1023) / 1024;  // >= 4 float4 per thread
   const int blocks = (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
@@ -221,6 +223,7 @@ extern "C" int ufnd_adamw_step(float* param, const float* grad, float* exp_avg, 
   UFND_REQUIRE(param && grad && exp_avg && exp_avg_sq && state && n > 0, "adamw_step: null argument");
   UFND_REQUIRE(n % 4 == 0 && ufnd_aligned(param, 16) && ufnd_aligned(grad, 16) && ufnd_aligned(exp_avg, 16) &&
                    ufnd_aligned(exp_avg_sq, 16), "adamw_step: n %% 4 == 0 and 16-B alignment required");
+  UFND_REQUIRE(ufnd_aligned(state, 8), "adamw_step: state must be 8-B aligned");
   size_t want = (n / 4 + 511) / 512;
   const int blocks = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq,
@@ -231,6 +234,7 @@ extern "C" int ufnd_adamw_step(float* param, const float* grad, float* exp_avg, 
 
 extern "C" int ufnd_step_advance(ufnd_step_state* state, void* stream_) {
   UFND_REQUIRE(state, "step_advance: null state");
+  UFND_REQUIRE(ufnd_aligned(state, 8), "step_advance: state must be 8-B aligned");
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream_, state);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
@@ -243,6 +247,7 @@ extern "C" int ufnd_clip_adamw_step(float* param, const float* grad, float* exp_
   UFND_REQUIRE(param && grad && exp_avg && exp_avg_sq && partials && state && n > 0, "clip_adamw_step: null argument");
   UFND_REQUIRE(n % 4 == 0 && ufnd_aligned(param, 16) && ufnd_aligned(grad, 16) && ufnd_aligned(exp_avg, 16) &&
                    ufnd_aligned(exp_avg_sq, 16), "clip_adamw_step: n %% 4 == 0 and 16-B alignment required");
+  UFND_REQUIRE(ufnd_aligned(state, 8) && ufnd_aligned(partials, 4), "clip_adamw_step: state must be 8-B and partials 4-B aligned");
   hipStream_t stream = (hipStream_t)stream_;
   size_t want = (n / 4 + 1023) / 1024;
   const int nb = (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));

@@ -98,6 +98,19 @@ __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 __device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
+// One two-class row of F.cross_entropy: n_c = -log p_c and p_c.  Nothing is rounded at the logits' common magnitude: the
+// differences d_c = l_c - max are formed first (one is 0, the other minus the gap, each rounded relative to the gap), and
+// n_c = log(S) - d_c, p_c = exp(d_c) / S with S = exp(d_0) + exp(d_1) in [1, 2].  (max + log(S) - l_c, the earlier form, rounds
+// the log-sum-exp at ulp(|max|): logits (1027, 1024) gave their row loss of 0.0486 on a grid of 1.2e-4.)  Shared by
+// softmax_ce_kernel, softmax_ce_ws_kernel and node_head's fused row, which must agree bit for bit.
+struct CeRow { float n0, n1, p0, p1; };
+__device__ __forceinline__ CeRow ce_row(float l0, float l1) {
+  const float mx = fmaxf(l0, l1);
+  const float d0 = l0 - mx, d1 = l1 - mx;
+  const float e0 = __expf(d0), e1 = __expf(d1);
+  const float S = e0 + e1, ls = logf(S);
+  return CeRow{ls - d0, ls - d1, e0 / S, e1 / S};
+}
 
 // ---------------------------------------------------------------- split-K epilogue
 // Y = drop(act(sum_s PART[s] + bias)), Z = pre-activation.   (M*N % 4 == 0)
@@ -628,12 +641,11 @@ __global__ __launch_bounds__(256) void node_head_kernel(const float* hh, const f
     probs[row * 2] = e0 / (e0 + e1);
     probs[row * 2 + 1] = e1 / (e0 + e1);
     if (labels) {      // fused head step: this row of F.cross_entropy (forensic_trainer.py:287), the expressions of softmax_ce_kernel
-      const float cm = fmaxf(l0, l1);
-      const float lse = cm + logf(__expf(l0 - cm) + __expf(l1 - cm));
+      const CeRow ce = ce_row(l0, l1);
       const int y = (int)labels[row];
-      loss_rows[row] = lse - (y ? l1 : l0);
-      dlog[row * 2] = (__expf(l0 - lse) - (y == 0 ? 1.f : 0.f)) / (float)B;
-      dlog[row * 2 + 1] = (__expf(l1 - lse) - (y == 1 ? 1.f : 0.f)) / (float)B;
+      loss_rows[row] = y ? ce.n1 : ce.n0;
+      dlog[row * 2] = (ce.p0 - (y == 0 ? 1.f : 0.f)) / (float)B;
+      dlog[row * 2 + 1] = (ce.p1 - (y == 1 ? 1.f : 0.f)) / (float)B;
     }
   }
 }
@@ -931,15 +943,14 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits, co
   __shared__ float sh[4];
   float part = 0;
   for (int r = threadIdx.x; r < B; r += 256) {
-    const float l0 = logits[r * 2], l1 = logits[r * 2 + 1], mx = fmaxf(l0, l1);
-    const float lse = mx + logf(__expf(l0 - mx) + __expf(l1 - mx));
+    const CeRow ce = ce_row(logits[r * 2], logits[r * 2 + 1]);
     const int y = (int)labels[r];
-    const float lr = lse - (y ? l1 : l0);
+    const float lr = y ? ce.n1 : ce.n0;
     if (loss_rows) loss_rows[r] = lr;
     part += lr;
     if (dlog) {
-      dlog[r * 2] = (__expf(l0 - lse) - (y == 0 ? 1.f : 0.f)) / (float)B;
-      dlog[r * 2 + 1] = (__expf(l1 - lse) - (y == 1 ? 1.f : 0.f)) / (float)B;
+      dlog[r * 2] = (ce.p0 - (y == 0 ? 1.f : 0.f)) / (float)B;
+      dlog[r * 2 + 1] = (ce.p1 - (y == 1 ? 1.f : 0.f)) / (float)B;
     }
   }
   part = wave_sum(part);
@@ -961,18 +972,17 @@ __global__ __launch_bounds__(256) void softmax_ce_ws_kernel(const float* logits,
   __syncthreads();
   const float W = (shw[0] + shw[1]) + (shw[2] + shw[3]);
   for (int r = threadIdx.x; r < B; r += 256) {
-    const float l0 = logits[r * 2], l1 = logits[r * 2 + 1], mx = fmaxf(l0, l1);
-    const float lse = mx + logf(__expf(l0 - mx) + __expf(l1 - mx));
+    const CeRow ce = ce_row(logits[r * 2], logits[r * 2 + 1]);
     const int y = (int)labels[r];
     const float wy = y ? w1 : w0;
-    const float n0 = lse - l0, n1 = lse - l1;                       // -log p_c
+    const float n0 = ce.n0, n1 = ce.n1;                             // -log p_c
     const float lr = (1.0f - eps) * wy * (y ? n1 : n0) + 0.5f * eps * (w0 * n0 + w1 * n1);
     if (loss_rows) loss_rows[r] = lr / W;
     part += lr;
     if (dlog) {
       const float k = (1.0f - eps) * wy + 0.5f * eps * (w0 + w1);
-      dlog[r * 2] = (__expf(l0 - lse) * k - (y == 0 ? (1.0f - eps) * wy : 0.f) - 0.5f * eps * w0) / W;
-      dlog[r * 2 + 1] = (__expf(l1 - lse) * k - (y == 1 ? (1.0f - eps) * wy : 0.f) - 0.5f * eps * w1) / W;
+      dlog[r * 2] = (ce.p0 * k - (y == 0 ? (1.0f - eps) * wy : 0.f) - 0.5f * eps * w0) / W;
+      dlog[r * 2 + 1] = (ce.p1 * k - (y == 1 ? (1.0f - eps) * wy : 0.f) - 0.5f * eps * w1) / W;
     }
   }
   part = wave_sum(part);
@@ -1909,6 +1919,7 @@ extern "C" int ufnd_head_backward(const ufnd_dims* d, const ufnd_fusion_params* 
 extern "C" int ufnd_softmax_ce_weighted(const float* logits, const int64_t* labels, int B, float w0, float w1, float label_smoothing,
                                         float* loss_rows, float* d_logits, ufnd_step_state* state, void* stream_) {
   UFND_REQUIRE(logits && labels && state && B >= 1, "softmax_ce_weighted: null argument");
+  UFND_REQUIRE(ufnd_aligned(labels, 8) && ufnd_aligned(state, 8), "softmax_ce_weighted: labels and state must be 8-B aligned");
   UFND_REQUIRE(w0 > 0.0f && w1 > 0.0f && label_smoothing >= 0.0f && label_smoothing < 1.0f, "softmax_ce_weighted: w=(%g,%g) eps=%g", w0, w1,
                label_smoothing);
   hipLaunchKernelGGL(softmax_ce_ws_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, labels, B, w0, w1, label_smoothing,
@@ -1920,6 +1931,7 @@ extern "C" int ufnd_softmax_ce_weighted(const float* logits, const int64_t* labe
 extern "C" int ufnd_softmax_ce(const float* logits, const int64_t* labels, int B, float* loss_rows, float* d_logits,
                                ufnd_step_state* state, void* stream_) {
   UFND_REQUIRE(logits && labels && state && B >= 1, "softmax_ce: null argument");
+  UFND_REQUIRE(ufnd_aligned(labels, 8) && ufnd_aligned(state, 8), "softmax_ce: labels and state must be 8-B aligned");
   hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, labels, B, loss_rows, d_logits,
                      state);
   UFND_CHECK_LAUNCH();
