@@ -431,7 +431,11 @@ int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, 
  *                                  cu_seqlens[b] .. cu_seqlens[b+1] (at most max_len of them), key_mask (B, max_len) indexed by position
  *                                  (NULL: every key valid); ctx rows are packed like qkv's
  *   ufnd_layernorm_live            ufnd_layernorm over the first *m_live of `capacity` rows
- *   ufnd_masked_meanpool_l2_live   ufnd_masked_meanpool_l2 over the packed rows: the same groups and summation order */
+ *   ufnd_masked_meanpool_l2_live   ufnd_masked_meanpool_l2 over the packed rows: the same groups and summation order
+ *   ufnd_ln_masked_meanpool_l2_live  ufnd_layernorm_live (fp32 rows) + ufnd_masked_meanpool_l2_live without the rows in between: one
+ *                                  workgroup per sample normalises y's rows cu_seqlens[b] .. cu_seqlens[b+1] in registers and adds the
+ *                                  ones mask (B, L) keeps, in ufnd_masked_meanpool_l2_live's order; out (B, H) is bit-identical to
+ *                                  the two entries', and no row past cu_seqlens[B] is read */
 int ufnd_text_pack(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, void* stream);
 int ufnd_text_pack_bins(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, int32_t* bins, int32_t* nbins,
                         void* stream);
@@ -464,6 +468,8 @@ int ufnd_layernorm_live(const float* x, int ldx, const float* gamma, const float
                         int H, float eps, const int* m_live, void* stream);
 int ufnd_masked_meanpool_l2_live(const float* hidden, const int32_t* mask, const int32_t* cu_seqlens, float* out, int B, int L, int H,
                                  void* stream);
+int ufnd_ln_masked_meanpool_l2_live(const float* y, const float* gamma, const float* beta, float eps, const int32_t* mask,
+                                    const int32_t* cu_seqlens, float* out, int B, int L, int H, void* stream);
 
 /* BertEmbeddings: LayerNorm(word[ids] + position[0..L) + token_type[0]).  Tables fp32.
  *   ids (B,L) int64 in [0,vocab).  Outputs (B*L,H): bf16 and fp32. */

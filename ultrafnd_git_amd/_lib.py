@@ -191,6 +191,7 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_attention_bf16_varlen_masked": [P, P, P, P, I, I, I, P],
         "ufnd_layernorm_live": [P, I, P, P, P, P, I, I, F, P, P],
         "ufnd_masked_meanpool_l2_live": [P, P, P, P, I, I, I, P],
+        "ufnd_ln_masked_meanpool_l2_live": [P, P, P, F, P, P, P, I, I, I, P],
         "ufnd_vit_patchify": [P, P, I, I, I, P],
         "ufnd_vit_assemble": [P] * 8 + [I, I, I, F, P],
         "ufnd_gemm_bf16_ln": [P] * 6 + [I] * 9 + [C.POINTER(GemmLn), P],

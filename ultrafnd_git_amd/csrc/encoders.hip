@@ -174,6 +174,63 @@ __global__ __launch_bounds__(256) void meanpool_kernel(const float* hidden, cons
     *reinterpret_cast<f32x4*>(out + (size_t)b * H + col) = s / denom;
   }
 }
+// LayerNorm + the masked mean of the packed pass in one kernel: layernorm_kernel's rows never reach memory.  One workgroup per
+// sample; wave g normalises the sample's tokens g, g + 4, ... (a whole row per wave, ln_row: layernorm_kernel's arithmetic) and
+// adds them in that order where the mask keeps them -- meanpool_kernel<true>'s groups, order and (p0 + p1) + (p2 + p3)
+// combination, so the mean is bit-identical to the two launches'.  Eight rows of a wave are requested and normalised together.
+template <int NI>
+__global__ __launch_bounds__(256) void ln_meanpool_kernel(const float* y, const float* gamma, const float* beta, float eps, const int32_t* mask,
+                                                          const int32_t* cu, float* out, int L, int H) {
+  __shared__ f32x4 part[4][NI][64];
+  __shared__ float cnts[4];
+  const int b = blockIdx.x, grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const size_t r0 = (size_t)cu[b];
+  const int n = cu[b + 1] - cu[b];      // rows of the sample (positions past them are masked)
+  f32x4 acc[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float cnt = 0.0f;
+  for (int l0 = grp; l0 < n; l0 += 32) {
+    int mk[8];
+    f32x4 v[8][NI];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int l = l0 + 4 * u;
+      mk[u] = l < n ? mask[(size_t)b * L + l] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int l = l0 + 4 * u < n ? l0 + 4 * u : n - 1;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) v[u][i] = ld4(y + (r0 + l) * H + 4 * lane + 256 * i);
+    }
+    // every requested row is normalised, kept or not (a row past the sample is its last row again): eight independent reduction
+    // chains the scheduler may interleave, where a branch per row would run them one after the other
+#pragma unroll
+    for (int u = 0; u < 8; ++u) ln_row<NI>(v[u], H, eps, gamma, beta, lane);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (mk[u] != 0) {      // (wave-uniform: one mask word per row)
+#pragma unroll
+        for (int i = 0; i < NI; ++i) acc[i] += v[u][i];
+        cnt += 1.0f;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) part[grp][i][lane] = acc[i];
+  if (lane == 0) cnts[grp] = cnt;
+  __syncthreads();
+  if (grp == 0) {
+    const float denom = fmaxf((cnts[0] + cnts[1]) + (cnts[2] + cnts[3]), 1e-6f);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const f32x4 s = (part[0][i][lane] + part[1][i][lane]) + (part[2][i][lane] + part[3][i][lane]);
+      *reinterpret_cast<f32x4*>(out + (size_t)b * H + 4 * lane + 256 * i) = s / denom;
+    }
+  }
+}
+
 // ufnd_text_pack: one workgroup.  n_b = 1 + the last kept position of sample b (0 for an all-masked sample); cu = exclusive prefix sum
 // of n_b (cu[B] = the live row count); row_src[cu[b] + l] = b L + l for l < n_b.
 // Slot bins (bins != NULL, L <= 128): sample b takes c_b = ceil(n_b / 32) contiguous 32-row slots of one 4-slot bin
@@ -565,6 +622,20 @@ extern "C" int ufnd_masked_meanpool_l2_live(const float* hidden, const int32_t* 
   UFND_REQUIRE(hidden && mask && cu_seqlens && out && B >= 1 && L >= 1, "meanpool_live: null argument");
   UFND_REQUIRE(H >= 256 && H % 256 == 0 && ufnd_aligned(hidden, 16) && ufnd_aligned(out, 16), "meanpool_live: H=%d (multiple of 256)", H);
   hipLaunchKernelGGL(meanpool_kernel<true>, dim3(H / 256, B), dim3(256), 0, (hipStream_t)stream_, hidden, mask, out, L, H, cu_seqlens);
+  UFND_CHECK_LAUNCH();
+  hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+// ufnd_layernorm_live (fp32 output) + ufnd_masked_meanpool_l2_live in two launches instead of three, without the (capacity, H)
+// buffer between them: bit-identical features (ln_meanpool_kernel)
+extern "C" int ufnd_ln_masked_meanpool_l2_live(const float* y, const float* gamma, const float* beta, float eps, const int32_t* mask,
+                                               const int32_t* cu_seqlens, float* out, int B, int L, int H, void* stream_) {
+  UFND_REQUIRE(y && gamma && beta && mask && cu_seqlens && out && B >= 1 && L >= 1, "ln_meanpool_live: null argument");
+  UFND_REQUIRE(h_ok(H), "ln_meanpool_live: H=%d (supported 256/512/768/1024)", H);
+  UFND_REQUIRE(ufnd_aligned(y, 16) && ufnd_aligned(gamma, 16) && ufnd_aligned(beta, 16) && ufnd_aligned(out, 16), "ln_meanpool_live: alignment");
+  NI_LAUNCH(H, ln_meanpool_kernel, dim3(B), (hipStream_t)stream_, y, gamma, beta, eps, mask, cu_seqlens, out, L, H);
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, out, H);
   UFND_CHECK_LAUNCH();

@@ -394,7 +394,8 @@ class BertTextEncoder(_EncoderBase):
     def _pass(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True) -> dict:
         """One pass over a (B, L) batch: embeddings, the first n_layers layers (all by default) and, with pool, the pooled features.
         packed: over the rows ufnd_text_pack keeps, their count on the device (forward's unpad paragraph); otherwise over all B L rows.
-        Returns the work buffers: last_hidden_state in "xf" (packed: its live rows), the features in "feat"."""
+        Returns the work buffers: last_hidden_state in "xf" (packed: its live rows), the features in "feat".  A packed, folded pass that
+        pools never writes "xf": one kernel normalises the last layer's sums and pools them (ufnd_ln_masked_meanpool_l2_live)."""
         self._require_hip()
         dev = self.device
         B, Lq = input_ids.shape
@@ -422,8 +423,16 @@ class BertTextEncoder(_EncoderBase):
         else:
             L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
-        (self._layers_folded if "st" in b else self._layers)(layers, b, t)
-        if pool and packed:
+        ln_pool = pool and packed and "st" in b
+        if "st" in b:
+            self._layers_folded(layers, b, t, final_ln=not ln_pool)
+        else:
+            self._layers(layers, b, t)
+        if ln_pool:       # bit-identical to the final LayerNorm into "xf" + the pooling below
+            L.check(L.lib().ufnd_ln_masked_meanpool_l2_live(b["y2"].data_ptr(), layers[-1]["g2"].data_ptr(), layers[-1]["b2n"].data_ptr(), self.eps,
+                                                            mask.data_ptr(), b["cu"].data_ptr(), b["feat"].data_ptr(), B, Lq, H, s),
+                    "ufnd_ln_masked_meanpool_l2_live")
+        elif pool and packed:
             L.check(L.lib().ufnd_masked_meanpool_l2_live(b["xf"].data_ptr(), mask.data_ptr(), b["cu"].data_ptr(), b["feat"].data_ptr(), B, Lq, H, s),
                     "ufnd_masked_meanpool_l2_live")
         elif pool:
@@ -459,9 +468,10 @@ class BertTextEncoder(_EncoderBase):
             self._gemm(b["h"], ly["w2"], ly["b2"], out_f32=b["y"], residual=b["x1f"], which="ffn2", m_live=live)
             self._ln(b["y"], H, ly["g2"], ly["b2n"], b["xb"], b["xf"], M, H, eps, m_live=live)
 
-    def _layers_folded(self, layers, b, t: _TextPass) -> None:
+    def _layers_folded(self, layers, b, t: _TextPass, final_ln: bool = True) -> None:
         """The layers without a LayerNorm kernel between Linears (module docstring).  y1 / y2 are the
-        PRE-LayerNorm sums of the attention and the feed-forward halves (fp32 + bf16 + row statistics)."""
+        PRE-LayerNorm sums of the attention and the feed-forward halves (fp32 + bf16 + row statistics).  final_ln=False leaves the
+        last layer's sums in y2 and their LayerNorm to the caller."""
         M, H, eps, live = t.B * t.Lq, self.hidden, self.eps, t.live
         y1, y2, st = b["y"], b["y2"], b["st"]
         rb = self.residual_dtype == "bf16"
@@ -485,7 +495,8 @@ class BertTextEncoder(_EncoderBase):
                           residual_bf16=b["y1b"] if rb else None, r_stats=st1, r_gamma=ly["g1"], r_beta=ly["b1"], out_stats=st2, eps=eps,
                           which="ffn2", m_live=live)      # (the last layer's fp32 sums feed the final, materialised LayerNorm)
             prev = ly
-        self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps, m_live=live)           # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
+        if final_ln:
+            self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps, m_live=live)       # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
 
     @torch.no_grad()
     def last_hidden_state(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, n_layers: Optional[int] = None) -> torch.Tensor:
@@ -552,6 +563,10 @@ class ClipVisualEncoder(_EncoderBase):
         # samples of at most 64 tokens: Q/K/V projection + attention of a layer as ONE launch (ufnd_qkv_attention_bf16_vit); bit-identical
         # to the two-launch form (off: a GEMM into qkv and an attention launch per layer)
         self.fuse_qkv_attention = True
+        # the embeddings read the class-token row of each frame only (CLIPVisionModelWithProjection pools last_hidden_state[:, 0]): past
+        # its attention the last layer runs over those N rows, not over all N T (forward, image_embeds; hidden_state keeps every row).
+        # A row's arithmetic does not depend on the launch it is part of, so the features are bit-identical (off: all rows)
+        self.cls_tail = True
         w, V, init = self._w, "vision_model.", self._seeded_init()
         w[V + "embeddings.class_embedding"] = init((hidden,))
         w[V + "embeddings.patch_embedding.weight"] = init((hidden, 3, patch, patch))
@@ -607,15 +622,20 @@ class ClipVisualEncoder(_EncoderBase):
             p1 = self._fold_parts(M)
             if p1:
                 # st0: the assembled embeddings' statistics; st[2i] / st[2i+1]: layer i's attention / feed-forward half
-                self._bufs[key].update({"st0": torch.zeros(M, 2, 2, **f32), "st": torch.zeros(2 * self.layers, M, p1, 2, **f32)})
+                # stc: the last layer's two statistics buffers over the class-token rows alone (_cls_rows; statistics are indexed by
+                # row number, so a strided view of st will not do)
+                self._bufs[key].update({"st0": torch.zeros(M, 2, 2, **f32), "st": torch.zeros(2 * self.layers, M, p1, 2, **f32),
+                                        "stc": torch.zeros(2, N, p1, 2, **f32)})
                 self._guard_buf(dev)
+            else:
+                self._bufs[key]["hc"] = torch.empty(N, H, **bf)      # (_cls_rows: the last layer_norm2 of the class-token rows)
         return self._bufs[key]
 
     @torch.no_grad()
     def image_embeds(self, frames: torch.Tensor) -> torch.Tensor:
         """frames (N,3,S,S) fp32 -> un-normalised projected embeddings (N, 512)
         (CLIPVisionModelWithProjection.image_embeds)."""
-        return self._run(frames[:, None])[0]
+        return self._run(frames[:, None], cls_tail=self.cls_tail)[0]
 
     @torch.no_grad()
     def hidden_state(self, frames: torch.Tensor, n_layers: Optional[int] = None) -> torch.Tensor:
@@ -639,9 +659,22 @@ class ClipVisualEncoder(_EncoderBase):
                                           L.ptr(b["hb"]) if "st0" in b else None, L.ptr(b.get("st0")),
                                           N, self.n_patches, self.hidden, self.eps, s), "ufnd_vit_assemble")
 
-    def _blocks_folded(self, layers, b, N) -> None:
+    def _cls_rows(self, b, N) -> dict:
+        """The work buffers over the class-token rows alone, as the last layer past its attention takes them: N-row views of ctx / hb /
+        xf with row stride T H, the first N rows of m, the statistics in stc.  Unfolded, hb only carries layer_norm2's output to FFN1
+        and ufnd_layernorm writes dense rows: the compact hc stands in for it."""
+        T = self.n_patches + 1
+        r = {k: b[k].view(N, T * self.hidden)[:, :self.hidden] for k in ("ctx", "hb", "xf")}
+        r["m"] = b["m"][:N]
+        if "stc" in b:
+            r["st1"], r["st2"] = b["stc"][0], b["stc"][1]
+        else:
+            r["hb"] = b["hc"]
+        return r
+
+    def _blocks_folded(self, layers, b, N, cls_tail: bool = False) -> None:
         """Pre-LN blocks without LayerNorm kernels: hb is the bf16 rounding of the residual stream xf, st* the row statistics its
-        LayerNorms need (module docstring)."""
+        LayerNorms need (module docstring).  cls_tail: the last layer's out-projection, FFN1 and FFN2 over the class-token rows only."""
         eps, stA, st, T = self.eps, b["st0"], b["st"], self.n_patches + 1
         rb = self.residual_dtype == "bf16"       # the stream is hb itself, updated in place (a tile reads exactly what it rewrites)
         fuse = self.fuse_qkv_attention and T <= 64
@@ -653,29 +686,35 @@ class ClipVisualEncoder(_EncoderBase):
             else:
                 self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
                 self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
-            self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else b["xf"], out_bf16=b["hb"], residual=None if rb else b["xf"],
-                          residual_bf16=b["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
-            self._gemm_ln(b["hb"], ly["w1f"], ly["bif"], out_bf16=b["m"], act=ACT_QUICK_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
-            self._gemm_ln(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"] if (last or not rb) else None, out_bf16=b["hb"],
-                          residual=None if rb else b["xf"], residual_bf16=b["hb"] if rb else None, out_stats=st2, eps=eps, which="ffn2")
+            r = b
+            if last and cls_tail:      # (K / V and the attention needed every row; nothing past them does)
+                r = self._cls_rows(b, N)
+                st1, st2 = r["st1"], r["st2"]
+            self._gemm_ln(r["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else r["xf"], out_bf16=r["hb"], residual=None if rb else r["xf"],
+                          residual_bf16=r["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
+            self._gemm_ln(r["hb"], ly["w1f"], ly["bif"], out_bf16=r["m"], act=ACT_QUICK_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1")
+            self._gemm_ln(r["m"], ly["w2"], ly["b2"], out_f32=r["xf"] if (last or not rb) else None, out_bf16=r["hb"],
+                          residual=None if rb else r["xf"], residual_bf16=r["hb"] if rb else None, out_stats=st2, eps=eps, which="ffn2")
             stA = st2
 
-    def _blocks(self, layers, b, N) -> None:
-        """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf."""
+    def _blocks(self, layers, b, N, cls_tail: bool = False) -> None:
+        """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf.  cls_tail: as _blocks_folded."""
         H, T, eps = self.hidden, self.n_patches + 1, self.eps
         M = N * T
         fuse = self.fuse_qkv_attention and T <= 64
-        for ly in layers:
+        for i, ly in enumerate(layers):
             self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps)
             if fuse:
                 self._qkv_attn(b["hb"], ly["wqkv"], ly["bqkv"], None, b["ctx"], N, T, self.heads)
             else:
                 self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
                 self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
-            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["xf"], residual=b["xf"], which="out")
-            self._ln(b["xf"], H, ly["g2"], ly["b2n"], b["hb"], None, M, H, eps)
-            self._gemm(b["hb"], ly["w1"], ly["bi"], out_bf16=b["m"], act=ACT_QUICK_GELU, which="ffn1")
-            self._gemm(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"], residual=b["xf"], which="ffn2")
+            r = self._cls_rows(b, N) if (cls_tail and i == len(layers) - 1) else b
+            xf = r["xf"]
+            self._gemm(r["ctx"], ly["wo"], ly["bo"], out_f32=xf, residual=xf, which="out")
+            self._ln(xf, xf.stride(0), ly["g2"], ly["b2n"], r["hb"], None, xf.shape[0], H, eps)
+            self._gemm(r["hb"], ly["w1"], ly["bi"], out_bf16=r["m"], act=ACT_QUICK_GELU, which="ffn1")
+            self._gemm(r["m"], ly["w2"], ly["b2"], out_f32=xf, residual=xf, which="ffn2")
 
     def _pooled_projection(self, p, b, N) -> None:
         """post-LN on the CLS rows (row stride T*H), bias-free projection into b["e"]."""
@@ -683,8 +722,9 @@ class ClipVisualEncoder(_EncoderBase):
         self._ln(b["xf"], (self.n_patches + 1) * H, w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"], b["pooled"], None, N, H, self.eps)
         self._gemm(b["pooled"], p["wproj"], None, out_f32=b["e"])
 
-    def _run(self, frames5: torch.Tensor, n_layers: Optional[int] = None):
-        """One pass over (B, F) frames: (the (B F, projection_dim) embeddings, the work buffers)."""
+    def _run(self, frames5: torch.Tensor, n_layers: Optional[int] = None, cls_tail: bool = False):
+        """One pass over (B, F) frames: (the (B F, projection_dim) embeddings, the work buffers).  cls_tail: the caller reads the
+        embeddings only, so the last layer may leave every row but the class tokens' behind its attention (hidden_state: never)."""
         self._require_hip()
         B, Fr = frames5.shape[:2]
         if tuple(frames5.shape[2:]) != (3, self.image, self.image):
@@ -693,7 +733,7 @@ class ClipVisualEncoder(_EncoderBase):
         p, b = self._pack(), self._workbufs(B, Fr)
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
         self._embed(fr, p, b, B * Fr)
-        (self._blocks_folded if "st0" in b else self._blocks)(layers, b, B * Fr)
+        (self._blocks_folded if "st0" in b else self._blocks)(layers, b, B * Fr, cls_tail)
         self._pooled_projection(p, b, B * Fr)
         return b["e"], b
 
@@ -705,7 +745,7 @@ class ClipVisualEncoder(_EncoderBase):
         if strict:
             return self._strict(lambda: self.forward(frames))
         B, Fr = frames.shape[:2]
-        e, b = self._run(frames)
+        e, b = self._run(frames, cls_tail=self.cls_tail)
         L.check(L.lib().ufnd_l2norm_frames(e.data_ptr(), b["feat"].data_ptr(), B, Fr, self.proj, L.stream_ptr(self.device)),
                 "ufnd_l2norm_frames")
         return b["feat"]
