@@ -951,6 +951,52 @@ int ufnd_masked_meanpool(const float* hidden, const int32_t* mask, float* out, i
 /* Y (M, N) = X (M, K) W^T + bias in exact fp32 (the skinny-GEMM family of the head; N % 32 == 0, 16-B aligned rows). */
 int ufnd_linear_f32(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * CLIP text tower (CLIPTextModelWithProjection, ViT-B/32 geometry: hidden 512, 8 heads x 64, 12 pre-LN quick-GELU layers, 77
+ * positions) and the text-image semantic analyzer (src/models/semantic_forgery.py).  Frozen, forward only.  The layers are the
+ * entries above (ufnd_gemm_bf16[_live], ufnd_layernorm[_live]) around the causal attention; csrc/clip_text.hip holds the rest.
+ *
+ * Causal attention: ufnd_attention_bf16 / ufnd_attention_bf16_varlen_masked with key k visible to query q iff k <= q and
+ * key_mask (NULL: all ones; (B, L) resp. (B, max_len) int32) keeps it.  Precondition: key 0 of every sample is kept, so that
+ * every query sees a key; a row whose every visible key is masked is unspecified.  A workgroup never reads a key block past its
+ * last query.
+ *
+ * The live-row pass.  Under the causal mask no row after a sample's pooled position e(b) can influence row e(b), so the tower
+ * runs over rows 0 .. e(b) of each sample only:
+ *   ufnd_clip_text_pack   ids (B, L) int64 -> e (B): the pooled position by HF's rule -- eos_token_id == 2: the first position of
+ *                         the largest id (argmax), otherwise the first position equal to eos_token_id (0 if there is none);
+ *                         cu_seqlens (B + 1) with cu[b+1] - cu[b] = e[b] + 1, cu[B] = the live row count (the m_live of the
+ *                         *_live entries); row_src[cu[b] + l] = b L + l.  One workgroup, a wave per sample, a fixed-order scan.
+ *   ufnd_clip_text_embed[_live]  x = token_embedding[id] + position_embedding[l] -> x_f32 and its bf16 rounding x_bf16 (both
+ *                         required); ids outside [0, vocab) are clamped; L <= max_position.  _live: over the first *m_live of
+ *                         `capacity` packed rows (row r is token row_src[r]).
+ *   ufnd_clip_text_pool   final_layer_norm of row e(b) of each sample -> out_bf16 (B, H), the A operand of the text_projection
+ *                         GEMM.  cu_seqlens NULL: x is the padded (B L, H) stream, row b L + e[b]; otherwise the packed one, row
+ *                         cu_seqlens[b+1] - 1.
+ * H in {256, 512, 768, 1024}; B <= 16384 for the pack. */
+int ufnd_attention_bf16_causal(const void* qkv, const int32_t* key_mask, void* ctx, int B, int L, int heads, void* stream);
+int ufnd_attention_bf16_causal_varlen(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
+                                      int heads, void* stream);
+int ufnd_clip_text_pack(const int64_t* ids, int B, int L, int eos_token_id, int32_t* e, int32_t* cu_seqlens, int32_t* row_src, void* stream);
+int ufnd_clip_text_embed(const int64_t* ids, const float* token_embedding, const float* position_embedding, void* x_bf16, float* x_f32, int B,
+                         int L, int H, int vocab, int max_position, void* stream);
+int ufnd_clip_text_embed_live(const int64_t* ids, const int32_t* row_src, const int* m_live, const float* token_embedding,
+                              const float* position_embedding, void* x_bf16, float* x_f32, int capacity, int L, int H, int vocab,
+                              int max_position, void* stream);
+int ufnd_clip_text_pool(const float* x, const int32_t* e, const int32_t* cu_seqlens, const float* gamma, const float* beta, void* out_bf16, int B,
+                        int L, int H, float eps, void* stream);
+
+/* SemanticForgeryAnalyzer's head, eval-mode arithmetic, all fp32: t = GELU(text Wt^T + bt), i = GELU(image Wi^T + bi) (exact erf),
+ * out_text = l2n(t), out_image = l2n(i), out_gap = l2n(t - i) with l2n(x) = x / (||x|| + 1e-9).  text / image (B, K), Wt / Wi
+ * (D, K), outputs (B, D); D % 32 == 0, K % 4 == 0, 16-B aligned rows; workspace: 2 B D floats (the pre-activations).  The two
+ * products are one launch of the exact-fp32 skinny GEMM (ufnd_linear_f32's kernels). */
+int ufnd_semantic_head(const float* text, const float* image, const float* wt, const float* bt, const float* wi, const float* bi,
+                       float* workspace, float* out_text, float* out_image, float* out_gap, int B, int D, int K, void* stream);
+
+/* similarity[b] = <t_b, i_b> / ((||t_b|| + 1e-9) (||i_b|| + 1e-9)), clamped to [-1, 1]: the diagonal of CLIPModel's logits_per_text without
+ * logit_scale; conflict[b] = 1 - (similarity[b] + 1) / 2 in [0, 1].  text / image (B, D) fp32, D % 4 == 0. */
+int ufnd_clip_similarity(const float* text, const float* image, float* similarity, float* conflict, int B, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

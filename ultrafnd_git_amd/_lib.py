@@ -238,6 +238,16 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_masked_meanpool": [P, P, P, I, I, I, P],
         "ufnd_linear_f32": [P, P, P, P, I, I, I, P],
     })
+    sigs.update({      # the CLIP text tower and the semantic analyzer (csrc/clip_text.hip; the causal attention: csrc/attention.hip)
+        "ufnd_attention_bf16_causal": [P, P, P, I, I, I, P],
+        "ufnd_attention_bf16_causal_varlen": [P, P, P, P, I, I, I, P],
+        "ufnd_clip_text_pack": [P, I, I, I, P, P, P, P],
+        "ufnd_clip_text_embed": [P] * 5 + [I] * 5 + [P],
+        "ufnd_clip_text_embed_live": [P] * 7 + [I] * 5 + [P],
+        "ufnd_clip_text_pool": [P] * 6 + [I, I, I, F, P],
+        "ufnd_semantic_head": [P] * 10 + [I, I, I, P],
+        "ufnd_clip_similarity": [P, P, P, P, I, I, P],
+    })
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

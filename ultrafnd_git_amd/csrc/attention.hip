@@ -28,6 +28,14 @@
 
 namespace {
 
+// Experiment switches of tools/clip_text_throughput.py (python -m ultrafnd_git_amd.build --defs=...): the causal entries without the
+// key-block and wave skipping (UFND_CAUSAL_SKIP=0), and in the 4-wave, 128-query form (UFND_CAUSAL_WAVES=4)
+#ifndef UFND_CAUSAL_SKIP
+#define UFND_CAUSAL_SKIP 1
+#endif
+#ifndef UFND_CAUSAL_WAVES
+#define UFND_CAUSAL_WAVES 2
+#endif
 constexpr int QB = 128;          // queries per workgroup (4 waves x 32; the short-sequence form: 2 waves, 64 queries)
 constexpr float NEG_MASK = -3.0e38f;
 
@@ -41,7 +49,12 @@ __device__ __forceinline__ bf16x8 k_frag(const char* tile, int row, int chunk) {
 // half its waves on clamped duplicate queries there, and its 216 registers allow 8 waves per CU either way -- twice the
 // samples in flight with 2-wave workgroups (a block is one dependent chain: loads -> S -> softmax -> O -> store).
 // DROP: the Philox draws need ~170 registers in the 2-wave form; at three waves per SIMD it spilled, so it runs at two.
-template <int KB, int NW = 4, bool DROP = false>
+// CAUSAL (the CLIP text tower, ufnd_attention_bf16_causal[_varlen]): key k is visible to query q iff k <= q and the key mask keeps it.
+// A workgroup walks the key blocks up to the one that holds its last query; a wave skips the blocks past its own last query (every
+// probability there is +0 once the wave has seen key 0, which the entries' precondition makes visible) and, when all its queries are
+// clamped duplicates (nothing of it is stored), every block; the per-element test runs
+// in the blocks that cross a wave's diagonal only, on the 4 keys a lane holds per tile (attn_softmax.hpp).
+template <int KB, int NW = 4, bool DROP = false, bool CAUSAL = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2 && !DROP ? 3 : 2))) void attention_kernel(const __bf16* qkv, const int32_t* mask, __bf16* ctx, int L,
                                                         int heads, float scale_log2e, const int32_t* cu, float* lse, int nqb,
                                                         ufnd_dropout dr) {
@@ -62,6 +75,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     L = cu[b + 1] - cu[b];
     if (qb * (NW * 32) >= L) return;      // (block-uniform, before any barrier)
   }
+  int kend = L;      // keys the workgroup walks
+  if constexpr (CAUSAL && UFND_CAUSAL_SKIP) kend = (qb + 1) * (NW * 32) < L ? (qb + 1) * (NW * 32) : L;      // (block-uniform, before any barrier): 1 + its last query
 
   // Q fragments (B operand): lane (query fr, g) holds Q[query][8g + 32kk .. +7]
   bf16x8 qf[2][2];
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     }
   };
   if constexpr (PREFETCH) load_block(0);
-  for (int kb0 = 0; kb0 < L; kb0 += KB) {
+  for (int kb0 = 0; kb0 < kend; kb0 += KB) {
     __syncthreads();  // previous block's LDS reads are done
     // ---- stage K and V tiles (row-major 128-B rows, swizzled 16-B chunks) and the key bias
     if constexpr (!PREFETCH) load_block(kb0);
@@ -129,9 +144,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     if (tid < KB) kbias[tid] = breg;
     __syncthreads();
     if constexpr (PREFETCH) {
-      if (kb0 + KB < L) load_block(kb0 + KB);
+      if (kb0 + KB < kend) load_block(kb0 + KB);
     }
 
+    const int wq0 = qb * (NW * 32) + wave * 32;      // the wave's first query
+    if constexpr (CAUSAL && UFND_CAUSAL_SKIP) {
+      if (kb0 > wq0 + 31 || wq0 >= L) continue;      // (wave-uniform; both barriers of the iteration are behind us / at the loop top)
+    }
     if constexpr (KB == 64) {
       if (masked_block_is_noop(kbias, lane, m_run)) continue;      // (attn_softmax.hpp; both barriers of the iteration are behind us / at the loop top)
     }
@@ -154,6 +173,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     // ---- online softmax (scores kept in the log2 domain: exp(x) = exp2(x * log2 e)); attn_softmax.hpp
     bool any_masked = __any(kbias[lane] != 0.0f);            // (the block's key-bias words, 64 per pass; wave-uniform)
     if constexpr (KB == 128) any_masked = any_masked || __any(kbias[64 + lane] != 0.0f);
+    if constexpr (CAUSAL) any_masked = any_masked || kb0 + KB - 1 > wq0;      // the block crosses the wave's diagonal
     bf16x8 pf[KT / 2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
@@ -168,7 +188,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
           dm[kt] = f32x4{m4[0], m4[1], m4[2], m4[3]};
         }
       }
-      const float alpha = online_softmax_block<KT, DROP>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf, dm);
+      const float alpha = online_softmax_block<KT, DROP, CAUSAL>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf, dm,
+                                                                 qrow[qt] - kb0 - 4 * g, NEG_MASK);
       if (!__all(alpha == 1.0f)) {       // (the running maximum rarely moves after the first blocks: skip the rescale then)
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
@@ -274,6 +295,38 @@ extern "C" int ufnd_attention_bf16_lse_dropout(const void* qkv, const int32_t* k
   else
     hipLaunchKernelGGL((attention_kernel<64, 4, true>), dim3(ufnd_cdiv(L, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
                        (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB), *drop);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+// Causal forms (the CLIP text tower; L <= 4096 like the others, built for its L <= 77): workgroups of 2 waves and 64 queries, so that
+// at L = 77 query block 0 never touches key block 1 and only one wave of four runs on clamped duplicate queries.
+constexpr int CQ = 32 * UFND_CAUSAL_WAVES;      // queries per workgroup of the causal forms
+// Precondition: key 0 of every sample is visible (key_mask[b][0] != 0); rows whose every visible key is masked are unspecified.
+extern "C" int ufnd_attention_bf16_causal(const void* qkv, const int32_t* key_mask, void* ctx, int B, int L, int heads, void* stream_) {
+  UFND_REQUIRE(qkv && ctx, "attention_causal: null operand");
+  UFND_REQUIRE(B >= 1 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention_causal: B=%d L=%d heads=%d", B, L, heads);
+  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_causal: 16-B alignment required");
+  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(L, CQ) < (1ll << 31), "attention_causal: grid too large");
+  const float scale_log2e = 0.125f * 1.44269504088896340736f;
+  const int nqb = ufnd_cdiv(L, CQ);
+  hipLaunchKernelGGL((attention_kernel<64, UFND_CAUSAL_WAVES, false, true>), dim3(nqb * heads * B), dim3(2 * CQ), 0, (hipStream_t)stream_, (const __bf16*)qkv, key_mask,
+                     (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, (float*)nullptr, nqb, ufnd_dropout{});
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_attention_bf16_causal_varlen(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
+                                                 int heads, void* stream_) {
+  UFND_REQUIRE(qkv && ctx && cu_seqlens, "attention_causal_varlen: null operand");
+  UFND_REQUIRE(B >= 1 && B <= 65535 && max_len >= 1 && max_len <= 4096 && heads >= 1 && heads <= 64,
+               "attention_causal_varlen: B=%d max_len=%d heads=%d", B, max_len, heads);
+  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_causal_varlen: 16-B alignment required");
+  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(max_len, CQ) < (1ll << 31), "attention_causal_varlen: grid too large");
+  const float scale_log2e = 0.125f * 1.44269504088896340736f;
+  const int nqb = ufnd_cdiv(max_len, CQ);
+  hipLaunchKernelGGL((attention_kernel<64, UFND_CAUSAL_WAVES, false, true>), dim3(nqb * heads * B), dim3(2 * CQ), 0, (hipStream_t)stream_, (const __bf16*)qkv, key_mask,
+                     (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr, nqb, ufnd_dropout{});
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

@@ -25,10 +25,13 @@ __device__ __forceinline__ bool masked_block_is_noop(const float* kb, int lane, 
 
 // DROP (attention.hip's training forward with dropout): pf gets exp2(score - m_new) * dm[kt][r] -- the dropout multiplier applied in fp32
 // just before the bf16 rounding -- while l_run keeps summing the UNDROPPED probabilities (HF: dropout after the softmax).
-template <int KT, bool DROP = false>
+// CAUSAL (attention.hip's causal entries; the caller passes any_masked = true for a block that crosses the diagonal): key 16 kt + r
+// of this lane's four-key groups is visible iff 16 kt + r <= qk (qk = the lane's query - the block's first key - 4 g); a live key
+// above the diagonal scores causal_neg, the key mask's own constant.
+template <int KT, bool DROP = false, bool CAUSAL = false>
 __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const int qt, const float* kbias, const bool any_masked, const int g,
                                                       const float scale_log2e, float& m_run, float& l_run, bf16x8 (&pf)[KT / 2][2],
-                                                      const f32x4* dm = nullptr) {
+                                                      const f32x4* dm = nullptr, const int qk = 0, const float causal_neg = 0.0f) {
 #pragma clang fp contract(off)
   float mx = -INFINITY, lsum = 0.0f, m_new, alpha;
   if (any_masked) {
@@ -37,7 +40,10 @@ __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const i
       const f32x4 kbv = *reinterpret_cast<const f32x4*>(kbias + kt * 16 + 4 * g);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = (kbv[r] == 0.0f) ? s[kt][qt][r] * scale_log2e : kbv[r];
+        float v = (kbv[r] == 0.0f) ? s[kt][qt][r] * scale_log2e : kbv[r];
+        if constexpr (CAUSAL) {
+          if (kbv[r] == 0.0f && 16 * kt + r > qk) v = causal_neg;
+        }
         s[kt][qt][r] = v;
         mx = fmaxf(mx, v);
       }

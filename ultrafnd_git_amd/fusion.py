@@ -42,7 +42,8 @@ class ForensicCoAttention(nn.Module):
 
 class _SemanticParams(nn.Module):
     """The two unused Linear(512,512) the reference registers through SemanticForgeryAnalyzer
-    (src/models/semantic_forgery.py:73-82): kept only so checkpoints interchange."""
+    (src/models/semantic_forgery.py:73-82): the fusion forward never reads them (nor does the reference's); kept so checkpoints
+    interchange, and run by semantic.SemanticForgeryAnalyzer.from_fusion, which shares them."""
 
     def __init__(self):
         super().__init__()
