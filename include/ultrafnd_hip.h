@@ -581,7 +581,9 @@ size_t ufnd_gcn_workspace_floats(int N, int in_dim, int hid, int out_dim, int tr
 
 /* SimpleGCN.forward: z = lin2(A_norm @ dropout(gelu(lin1(A_norm @ x)))), A_norm = D^-1/2 (adj + I) D^-1/2 with
  * D = rowsum(adj + I) + 1e-9.  x (N, in_dim), adj (N, N) row stride ld_adj, z (N, out_dim).  dropout_p > 0 =
- * train mode (counter-based mask keyed by state->seed / state->step); in_dim % 4 == 0, hid and out_dim % 32 == 0. */
+ * train mode (counter-based mask keyed by state->seed / state->step); in_dim % 4 == 0, hid and out_dim % 32 == 0.
+ * adj need not be symmetric (a directed or asymmetrically weighted graph is fine): the backward passes of
+ * ufnd_gcn_pretrain_step and ufnd_gnn_backward multiply by A_norm^T, as autograd does. */
 int ufnd_gcn_forward(const float* x, const float* adj, int ld_adj, const ufnd_gcn_params* p, float* z, float* workspace, int N,
                      int in_dim, int hid, int out_dim, float dropout_p, const ufnd_step_state* state, void* stream);
 
@@ -648,7 +650,8 @@ size_t ufnd_gnn_workspace_floats(int N, int in_dim, int hid, int out_dim);
  * what ufnd_gnn_backward needs. */
 int ufnd_gnn_forward(const float* x, const float* adj, int ld_adj, const ufnd_gcn_params* p, float* z, float* workspace, int N,
                      int in_dim, int hid, int out_dim, float dropout_p, const ufnd_step_state* state, void* stream);
-/* its autograd backward for a gradient d_z (N, out_dim) at z: the four parameter gradients (overwritten). */
+/* its autograd backward for a gradient d_z (N, out_dim) at z: the four parameter gradients (overwritten).  Correct for any
+ * adj, symmetric or not (the forward leaves A_norm^T in the workspace). */
 int ufnd_gnn_backward(const float* x, const ufnd_gcn_params* p, float* g_w1, float* g_b1, float* g_w2, float* g_b2, const float* d_z,
                       float* workspace, int N, int in_dim, int hid, int out_dim, float dropout_p, const ufnd_step_state* state,
                       void* stream);

@@ -75,6 +75,27 @@ __global__ __launch_bounds__(256) void gcn_norm_adj_kernel(const float* __restri
   an[(size_t)row * Np + c] = v;
 }
 
+// ant = an^T bit for bit: ant[i][j] = dinv[j] (adj[j][i] + [i == j]) dinv[i] in an[j][i]'s operation order, zero in the pad
+// columns j >= N.  The backward products need A_norm^T (the forward multiplies by A_norm from the left); adj may be directed.
+// 32 x 32 tiles through LDS so that adj is read and ant written along rows.  grid (Np / 32, cdiv(N, 32)), 256 threads.
+__global__ __launch_bounds__(256) void gcn_norm_adj_t_kernel(const float* __restrict__ adj, int ld, const float* __restrict__ dinv,
+                                                             int N, int Np, float* __restrict__ ant) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;       // ant rows i0.., ant columns j0..
+  for (int r = ty; r < 32; r += 8) {
+    const int j = j0 + r, i = i0 + tx;                        // source element adj[j][i]
+    float v = 0.0f;
+    if (j < N && i < N) v = dinv[j] * (adj[(size_t)j * ld + i] + (i == j ? 1.0f : 0.0f)) * dinv[i];
+    tile[r][tx] = v;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int i = i0 + r, j = j0 + tx;
+    if (i < N) ant[(size_t)i * Np + j] = tile[tx][r];
+  }
+}
+
 // dst rows [0, N) = src rows, rows [N, Np) = 0  (operand of the NN product: its row count is the padded contraction)
 __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__ src, int lds_, int N, int Np, int F,
                                                        float* __restrict__ dst) {
@@ -198,13 +219,13 @@ __global__ __launch_bounds__(256) void node_features_kernel(const float* __restr
 }
 
 struct GnnWs {
-  float *an, *dinv, *Y1, *U, *H, *G, *dG, *dH, *dU, *dY1;
+  float *an, *dinv, *Y1, *U, *H, *G, *dG, *dH, *dU, *dY1, *ant;
   int Np;
 };
 size_t gnn_layout(float* base, int N, int F, int hid, int out, GnnWs* w);
 
 struct GcnWs {
-  float *an, *xp, *P, *U1, *H, *Q, *dinv, *rowsum, *dZ, *dQ, *dU1, *grad, *loss_rows;
+  float *an, *xp, *P, *U1, *H, *Q, *dinv, *rowsum, *dZ, *dQ, *dU1, *grad, *loss_rows, *ant;
   int Np;
 };
 
@@ -230,6 +251,7 @@ size_t gcn_layout(float* base, int N, int F, int hid, int out, int train, GcnWs*
     t.dU1 = take((size_t)N * hid);
     t.grad = take((size_t)hid * F + hid + (size_t)out * hid + out);
     t.loss_rows = take(N);
+    t.ant = take((size_t)N * Np);      // A_norm^T, for the backward
   }
   if (w) *w = t;
   return o;
@@ -251,6 +273,7 @@ size_t gnn_layout(float* base, int N, int F, int hid, int out, GnnWs* w) {
   t.dH = take((size_t)N * hid);
   t.dU = take((size_t)Np * hid);
   t.dY1 = take((size_t)N * hid);
+  t.ant = take((size_t)N * Np);       // A_norm^T, written by the forward for the backward
   (void)F; (void)out;
   if (w) *w = t;
   return o;
@@ -354,8 +377,10 @@ extern "C" int ufnd_gcn_pretrain_step(const float* x, const float* adj, int ld_a
     hipError_t e = hipMemsetAsync(w.dQ + (size_t)N * hid, 0, (size_t)(w.Np - N) * hid * sizeof(float), stream);
     if (e != hipSuccess) { ufnd_set_error("gcn: memset failed: %s", hipGetErrorString(e)); return UFND_ERR_LAUNCH; }
   }
-  // dU1 = (A_norm dQ) * gelu'(U1) * dropout mask     (A_norm is symmetric)
-  NnProb du{w.an, w.dQ, w.dU1, w.U1, nullptr, N, w.Np, hid, w.Np, hid, hid, hid, 0, dropout_p, LAYER_GCN, hid, 1};
+  hipLaunchKernelGGL(gcn_norm_adj_t_kernel, dim3(w.Np / 32, ufnd_cdiv(N, 32)), dim3(256), 0, stream, adj, ld_adj, w.dinv, N, w.Np, w.ant);
+  UFND_CHECK_LAUNCH();
+  // dU1 = (A_norm^T dQ) * gelu'(U1) * dropout mask
+  NnProb du{w.ant, w.dQ, w.dU1, w.U1, nullptr, N, w.Np, hid, w.Np, hid, hid, hid, 0, dropout_p, LAYER_GCN, hid, 1};
   rc = launch_nn(&du, 1, state, stream);
   if (rc != UFND_OK) return rc;
   TnProb t1{w.dU1, w.P, gw1, gb1, N, hid, in_dim, hid, in_dim, in_dim};                                    // dW1 = dU1^T P, db1
@@ -413,6 +438,8 @@ extern "C" int ufnd_gnn_forward(const float* x, const float* adj, int ld_adj, co
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(gcn_norm_adj_kernel, dim3(ufnd_cdiv(Np, 256), N), dim3(256), 0, stream, adj, ld_adj, w.dinv, N, Np, w.an);
   UFND_CHECK_LAUNCH();
+  hipLaunchKernelGGL(gcn_norm_adj_t_kernel, dim3(Np / 32, ufnd_cdiv(N, 32)), dim3(256), 0, stream, adj, ld_adj, w.dinv, N, Np, w.ant);
+  UFND_CHECK_LAUNCH();
   auto zero_pad = [&](float* buf) -> int {
     if (Np > N) {
       hipError_t e = hipMemsetAsync(buf + (size_t)N * hid, 0, (size_t)(Np - N) * hid * sizeof(float), stream);
@@ -463,14 +490,14 @@ extern "C" int ufnd_gnn_backward(const float* x, const ufnd_gcn_params* p, float
   NnProb dg{d_z, p->w2, w.dG, nullptr, nullptr, N, out_dim, hid, out_dim, hid, hid, 0, 0, 0.0f, 0, 0, 1};           // dG = dZ W2
   if ((rc = launch_nn(&dg, 1, nullptr, stream)) != UFND_OK) return rc;
   if ((rc = zero_pad(w.dG)) != UFND_OK) return rc;
-  NnProb dh{w.an, w.dG, w.dH, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                     // dH = A_norm dG (symmetric)
+  NnProb dh{w.ant, w.dG, w.dH, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                    // dH = A_norm^T dG
   if ((rc = launch_nn(&dh, 1, nullptr, stream)) != UFND_OK) return rc;
   const size_t n = (size_t)N * hid;
   hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)w.dH, (const float*)w.U,
                      w.dU, n, dropout_p, state);
   UFND_CHECK_LAUNCH();
   if ((rc = zero_pad(w.dU)) != UFND_OK) return rc;
-  NnProb dy{w.an, w.dU, w.dY1, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                    // dY1 = A_norm dU
+  NnProb dy{w.ant, w.dU, w.dY1, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                   // dY1 = A_norm^T dU
   if ((rc = launch_nn(&dy, 1, nullptr, stream)) != UFND_OK) return rc;
   TnProb t1{w.dY1, x, g_w1, g_b1, N, hid, in_dim, hid, in_dim, in_dim};                                             // dW1 = dY1^T X, db1
   return launch_tn(&t1, 1, stream);

@@ -6,7 +6,7 @@ Mirrors
   src/training/forensic_trainer_integrated.py:77-98   build_adj_from_ocr_sets: weighted Jaccard adjacency of a mini-batch
 The module's parameters live in a flat arena (ArenaModule), so the trainer can put it in the SAME arena as the fusion head and
 the classifier: one gradient range for the norm, the clip, AdamW and the data-parallel exchange.  `forward` keeps what
-`backward(d_z)` needs; there is no CPU path.
+`backward(d_z)` needs; there is no CPU path.  `adj` need not be symmetric: the backward multiplies by A_norm^T, as autograd does.
 """
 from __future__ import annotations
 
