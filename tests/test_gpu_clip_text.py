@@ -312,3 +312,61 @@ def test_analyzer_with_frames_and_with_the_text_proxy(frames_per_sample):
     assert sorted(out) == ["clip_similarity", "semantic_conflict", "semantic_gap", "semantic_image", "semantic_text"]
     with pytest.raises(KeyError):
         an({"title_ids": ids, "title_mask": mask})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the helpers the tower shares with the BERT text encoder: the pack kernels' scan, and LayerNorm inside the pool kernel
+@pytest.mark.parametrize("B", (1, 5, 1025, 2049))
+def test_pack_scan_is_the_text_pack_scan(B):
+    """ufnd_clip_text_pack's cu / row_src against ufnd_text_pack's on the mask l <= e(b), and both against numpy: L = 8, random pooled
+    positions that include 0 and L - 1, both pooling rules.  B = 1025 and 2049 give the scan 2 and 3 samples per thread."""
+    from ultrafnd_git_amd import _lib as Lb
+    lib, Lq, s = Lb.lib(), 8, Lb.stream_ptr(torch.device(DEV))
+    rng = np.random.default_rng(B)
+    es = [np.array([0]), np.array([Lq - 1])] if B == 1 else [rng.integers(0, Lq, size=B)]
+    if B > 1:
+        es[0][0], es[0][-1], es[0][B // 2] = 0, Lq - 1, Lq - 1
+    for e in es:
+        want_cu = np.concatenate([[0], np.cumsum(e + 1)]).astype(np.int32)
+        want_src = np.concatenate([b * Lq + np.arange(e[b] + 1) for b in range(B)]).astype(np.int32)
+        mask = (np.arange(Lq)[None, :] <= e[:, None]).astype(np.int32)
+        cu_t, src_t = torch.full((B + 1,), -1, dtype=torch.int32, device=DEV), torch.full((B * Lq,), -1, dtype=torch.int32, device=DEV)
+        Lb.check(lib.ufnd_text_pack(torch.from_numpy(mask).to(DEV).data_ptr(), B, Lq, cu_t.data_ptr(), src_t.data_ptr(), s), "ufnd_text_pack")
+        for eos in (R.EOS, 2):      # the first position equal to eos / the first position of the largest id
+            ids = rng.integers(3, 40, size=(B, Lq)).astype(np.int64)
+            ids[np.arange(B), e] = eos if eos != 2 else 50
+            e_c = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+            cu_c, src_c = torch.full((B + 1,), -1, dtype=torch.int32, device=DEV), torch.full((B * Lq,), -1, dtype=torch.int32, device=DEV)
+            Lb.check(lib.ufnd_clip_text_pack(torch.from_numpy(ids).to(DEV).data_ptr(), B, Lq, eos, e_c.data_ptr(), cu_c.data_ptr(), src_c.data_ptr(), s),
+                     "ufnd_clip_text_pack")
+            n = int(want_cu[B])
+            assert np.array_equal(e_c.cpu().numpy(), e.astype(np.int32)), (B, eos)
+            assert np.array_equal(cu_c.cpu().numpy(), want_cu) and np.array_equal(cu_t.cpu().numpy(), want_cu), (B, eos)
+            assert np.array_equal(src_c.cpu().numpy()[:n], want_src) and np.array_equal(src_t.cpu().numpy()[:n], want_src), (B, eos)
+            assert torch.equal(cu_c, cu_t) and torch.equal(src_c[:n], src_t[:n]), (B, eos)
+            assert bool((src_c[n:] == -1).all()) and bool((src_t[n:] == -1).all()), (B, eos)      # nothing written past the live rows
+
+
+@pytest.mark.parametrize("H", (256, 512, 768, 1024))
+def test_pool_is_layernorm_of_the_pooled_rows(H):
+    """ufnd_clip_text_pool's bf16 output, bit for bit ufnd_layernorm's on the gathered rows e(b): B = 5, L = 7, fp32 rows with a non-zero
+    mean, random e; the padded form (cu NULL: row b L + e[b]) and the packed form (row cu[b + 1] - 1)."""
+    from ultrafnd_git_amd import _lib as Lb
+    lib, B, Lq, eps, s = Lb.lib(), 5, 7, 1e-5, Lb.stream_ptr(torch.device(DEV))
+    g = torch.Generator().manual_seed(H)
+    x = (torch.randn(B * Lq, H, generator=g) * 1.7 + 0.9 + torch.randn(B * Lq, 1, generator=g)).to(DEV)
+    gamma, beta = (1.0 + 0.3 * torch.randn(H, generator=g)).to(DEV), (0.2 * torch.randn(H, generator=g)).to(DEV)
+    e = torch.randint(0, Lq, (B,), generator=g).to(torch.int32)
+    e[0], e[1] = 0, Lq - 1
+    cu = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(e.long() + 1, 0)]).to(torch.int32)
+    e_d, cu_d = e.to(DEV), cu.to(DEV)
+    for name, cu_arg, rows in (("padded", None, torch.arange(B) * Lq + e.long()), ("packed", cu_d, cu[1:].long() - 1)):
+        got = torch.full((B, H), float("nan"), dtype=torch.bfloat16, device=DEV)
+        Lb.check(lib.ufnd_clip_text_pool(x.data_ptr(), e_d.data_ptr(), Lb.ptr(cu_arg), gamma.data_ptr(), beta.data_ptr(), got.data_ptr(), B, Lq, H, eps, s),
+                 "ufnd_clip_text_pool")
+        xg = x[rows.to(DEV)].contiguous()
+        want = torch.full((B, H), float("nan"), dtype=torch.bfloat16, device=DEV)
+        Lb.check(lib.ufnd_layernorm(xg.data_ptr(), H, gamma.data_ptr(), beta.data_ptr(), want.data_ptr(), None, B, H, eps, s), "ufnd_layernorm")
+        torch.cuda.synchronize()
+        assert not bool(torch.isnan(want.float()).any())
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16)), (H, name)

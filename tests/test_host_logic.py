@@ -240,3 +240,93 @@ def test_head_step_aux_buffer_and_pointer_follow_the_classifier(tmp_path, use_au
     hs.stage_aux(b, aux)
     if eff:
         assert torch.equal(b["aux"], aux)
+
+
+# ---- the encoders' layer tables (layer_keys) and the arena layout they feed (groups()): checkpoints depend on both
+_BERT_REST = ["embeddings.word_embeddings.weight", "embeddings.position_embeddings.weight", "embeddings.token_type_embeddings.weight",
+              "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"]
+_VIT_REST = ["vision_model.embeddings.class_embedding", "vision_model.embeddings.patch_embedding.weight",
+             "vision_model.embeddings.position_embedding.weight", "vision_model.pre_layrnorm.weight", "vision_model.pre_layrnorm.bias",
+             "vision_model.post_layernorm.weight", "vision_model.post_layernorm.bias", "visual_projection.weight"]
+_CLIP_TEXT_REST = ["text_model.embeddings.token_embedding.weight", "text_model.embeddings.position_embedding.weight",
+                   "text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias", "text_projection.weight"]
+_W2V2_REST = ([f"feature_extractor.conv_layers.{i}.conv.weight" for i in range(7)] +
+              ["feature_extractor.conv_layers.0.layer_norm.weight", "feature_extractor.conv_layers.0.layer_norm.bias",
+               "feature_projection.layer_norm.weight", "feature_projection.layer_norm.bias", "feature_projection.projection.weight",
+               "feature_projection.projection.bias", "encoder.pos_conv_embed.conv.bias",
+               "encoder.pos_conv_embed.conv.parametrizations.weight.original0", "encoder.pos_conv_embed.conv.parametrizations.weight.original1",
+               "encoder.layer_norm.weight", "encoder.layer_norm.bias", "proj.weight", "proj.bias"])
+_LAYER_NAMES = ["qkv_w", "qkv_b", "o_w", "o_b", "g1", "b1n", "w1", "b1", "w2", "b2", "g2", "b2n"]
+
+
+def _tiny_encoder(name):
+    """(a 2-layer encoder, its keys outside the layers): only the one asked for is built."""
+    if name == "bert":
+        from ultrafnd_git_amd.encoders import BertTextEncoder
+        return BertTextEncoder(layers=2, vocab_size=64, max_position=16), _BERT_REST
+    if name == "vit":
+        from ultrafnd_git_amd.encoders import ClipVisualEncoder
+        return ClipVisualEncoder(layers=2), _VIT_REST
+    if name == "clip_text":
+        from ultrafnd_git_amd.semantic import ClipTextEncoder
+        return ClipTextEncoder(vocab_size=64, num_hidden_layers=2), _CLIP_TEXT_REST
+    from ultrafnd_git_amd.audio import Wav2Vec2AudioEncoder
+    return Wav2Vec2AudioEncoder(layers=2, intermediate=256), _W2V2_REST
+
+
+@pytest.mark.parametrize("name", ["bert", "vit", "clip_text", "w2v2"])
+def test_layer_keys_and_the_non_layer_keys_are_exactly_the_state_dict(name):
+    """layer_keys(i) over the layers plus the keys outside the layers: every state_dict key once, nothing else; the twelve names, each a
+    list of keys (three for the stacked Q/K/V, one otherwise); memoised."""
+    enc, rest = _tiny_encoder(name)
+    keys = list(rest)
+    for i in range(2):
+        k = enc.layer_keys(i)
+        assert list(k) == _LAYER_NAMES and enc.layer_keys(i) is k
+        assert [len(k[n]) for n in _LAYER_NAMES] == [3, 3] + [1] * 10
+        assert all(f".{i}." in key for n in _LAYER_NAMES for key in k[n])
+        keys += [key for n in _LAYER_NAMES for key in k[n]]
+    sd = enc.state_dict()
+    assert len(keys) == len(set(keys)) and set(keys) == set(sd.keys())
+    k = enc.layer_keys(1)
+    H = enc.hidden
+    assert [tuple(sd[x].shape) for x in k["qkv_w"] + k["o_w"]] == [(H, H)] * 4 and tuple(sd[k["w1"][0]].shape) == (enc.inter, H)
+    assert tuple(sd[k["w2"][0]].shape) == (H, enc.inter) and tuple(sd[k["b1"][0]].shape) == (enc.inter,)
+    assert all(tuple(sd[k[n][0]].shape) == (H,) for n in ("o_b", "g1", "b1n", "b2", "g2", "b2n"))
+
+
+def test_backprop_groups_are_the_recorded_arena_order():
+    """TextBackprop.groups() / VisualBackprop.groups() at 2 layers against the key lists recorded before the layer table moved into the
+    encoders: the arena layout (order, and which tensors are adjacent) is what checkpoints and the stacked Q/K/V views depend on."""
+    from ultrafnd_git_amd.encoder_train import TextBackprop, VisualBackprop
+
+    def bert_layer(i):
+        P = f"encoder.layer.{i}."
+        return [[P + "output.LayerNorm.weight"], [P + "output.LayerNorm.bias"], [P + "output.dense.weight"], [P + "output.dense.bias"],
+                [P + "intermediate.dense.weight"], [P + "intermediate.dense.bias"], [P + "attention.output.LayerNorm.weight"],
+                [P + "attention.output.LayerNorm.bias"], [P + "attention.output.dense.weight"], [P + "attention.output.dense.bias"],
+                [P + "attention.self.query.weight", P + "attention.self.key.weight", P + "attention.self.value.weight"],
+                [P + "attention.self.query.bias", P + "attention.self.key.bias", P + "attention.self.value.bias"]]
+
+    def vit_layer(i):
+        P = f"vision_model.encoder.layers.{i}."
+        return [[P + "mlp.fc2.weight"], [P + "mlp.fc2.bias"], [P + "mlp.fc1.weight"], [P + "mlp.fc1.bias"], [P + "layer_norm2.weight"],
+                [P + "layer_norm2.bias"], [P + "self_attn.out_proj.weight"], [P + "self_attn.out_proj.bias"],
+                [P + "self_attn.q_proj.weight", P + "self_attn.k_proj.weight", P + "self_attn.v_proj.weight"],
+                [P + "self_attn.q_proj.bias", P + "self_attn.k_proj.bias", P + "self_attn.v_proj.bias"], [P + "layer_norm1.weight"],
+                [P + "layer_norm1.bias"]]
+
+    want_text = bert_layer(1) + bert_layer(0) + [["embeddings.LayerNorm.weight"], ["embeddings.LayerNorm.bias"],
+                                                 ["embeddings.position_embeddings.weight"], ["embeddings.token_type_embeddings.weight"],
+                                                 ["embeddings.word_embeddings.weight"]]
+    want_vis = ([["visual_projection.weight"], ["vision_model.post_layernorm.weight"], ["vision_model.post_layernorm.bias"]] +
+                vit_layer(1) + vit_layer(0) +
+                [["vision_model.pre_layrnorm.weight"], ["vision_model.pre_layrnorm.bias"], ["vision_model.embeddings.position_embedding.weight"],
+                 ["vision_model.embeddings.class_embedding"], ["vision_model.embeddings.patch_embedding.weight"]])
+    for bp, enc, want in ((TextBackprop, _tiny_encoder("bert")[0], want_text), (VisualBackprop, _tiny_encoder("vit")[0], want_vis)):
+        got = bp(enc).groups()
+        assert [[k for k, _ in g] for g in got] == want
+        sd = enc.state_dict()
+        assert all(shape == tuple(sd[k].shape) for g in got for k, shape in g)
+        lin = bp(enc).linears()
+        assert lin["1.qkv"] == (enc.layer_keys(1)["qkv_w"], enc.layer_keys(1)["qkv_b"]) and lin["0.w2"] == (enc.layer_keys(0)["w2"], enc.layer_keys(0)["b2"])

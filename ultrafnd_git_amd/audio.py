@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .encoders import ACT_GELU, BertTextEncoder, _bf16, _EncoderBase, _TextPass
+from .encoders import ACT_GELU, _bf16, _EncoderBase
 
 CONV_KERNELS = (10, 3, 3, 3, 3, 2, 2)
 CONV_STRIDES = (5, 2, 2, 2, 2, 2, 2)
@@ -79,6 +79,14 @@ def pos_group_weights(w: torch.Tensor, bias: torch.Tensor):
 
 
 class Wav2Vec2AudioEncoder(_EncoderBase):
+    LAYER_PREFIX = "encoder.layers.{}."
+    LAYER_NAMES = {"qkv_w": [f"attention.{n}.weight" for n in ("q_proj", "k_proj", "v_proj")],
+                   "qkv_b": [f"attention.{n}.bias" for n in ("q_proj", "k_proj", "v_proj")],
+                   "o_w": ["attention.out_proj.weight"], "o_b": ["attention.out_proj.bias"], "g1": ["layer_norm.weight"], "b1n": ["layer_norm.bias"],
+                   "w1": ["feed_forward.intermediate_dense.weight"], "b1": ["feed_forward.intermediate_dense.bias"],
+                   "w2": ["feed_forward.output_dense.weight"], "b2": ["feed_forward.output_dense.bias"],
+                   "g2": ["final_layer_norm.weight"], "b2n": ["final_layer_norm.bias"]}
+
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, out_dim: int = 128,
                  conv_dim: Sequence[int] = (CONV_DIM,) * 7, conv_kernel: Sequence[int] = CONV_KERNELS, conv_stride: Sequence[int] = CONV_STRIDES,
                  conv_bias: bool = False, feat_extract_norm: str = "group", num_conv_pos_embeddings: int = POS_KERNEL,
@@ -129,22 +137,12 @@ class Wav2Vec2AudioEncoder(_EncoderBase):
     # ---- operands
     def _pack(self):
         if self._packed is None:
-            w, F, E, layers = self._w, "feature_extractor.conv_layers.", "encoder.", []
-            for i in range(self.layers):
-                P = E + f"layers.{i}."
-                # HF scales q by 1 / sqrt(64) before Q K^T; the attention kernel scales the scores: the same product
-                layers.append({
-                    "wqkv": _bf16(torch.cat([w[P + f"attention.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)),
-                    "bqkv": torch.cat([w[P + f"attention.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous(),
-                    "wo": _bf16(w[P + "attention.out_proj.weight"]), "bo": w[P + "attention.out_proj.bias"],
-                    "g1": w[P + "layer_norm.weight"], "b1": w[P + "layer_norm.bias"],
-                    "w1": _bf16(w[P + "feed_forward.intermediate_dense.weight"]), "bi": w[P + "feed_forward.intermediate_dense.bias"],
-                    "w2": _bf16(w[P + "feed_forward.output_dense.weight"]), "b2": w[P + "feed_forward.output_dense.bias"],
-                    "g2": w[P + "final_layer_norm.weight"], "b2n": w[P + "final_layer_norm.bias"]})
+            # (HF scales q by 1 / sqrt(64) before Q K^T; the attention kernel scales the scores: the same product)
+            w, F, E = self._w, "feature_extractor.conv_layers.", "encoder."
             pos_w = resolve_weight_norm(w[E + "pos_conv_embed.conv.parametrizations.weight.original0"],
                                         w[E + "pos_conv_embed.conv.parametrizations.weight.original1"])
             wg, bg = pos_group_weights(pos_w, w[E + "pos_conv_embed.conv.bias"])
-            self._packed = {"layers": layers,
+            self._packed = {"layers": self._pack_layers(),
                             "w0": w[F + "0.conv.weight"].reshape(CONV_DIM, CONV_KERNELS[0]).contiguous(),
                             "conv": [_bf16(tap_major(w[F + f"{i}.conv.weight"])) for i in range(1, 7)],
                             "wfp": _bf16(w["feature_projection.projection.weight"]),
@@ -188,9 +186,6 @@ class Wav2Vec2AudioEncoder(_EncoderBase):
     def workspace_bytes(self) -> int:
         """Device bytes the work buffers hold: those of the largest pass so far."""
         return sum(t.numel() * t.element_size() for t in self._bufs.values())
-
-    _self_attention = BertTextEncoder._self_attention
-    _layers = BertTextEncoder._layers
 
     def _conv_rows(self, A, W, bias, M, lda, out_bf16=None, out_f32=None):
         N, K = W.shape
@@ -253,7 +248,7 @@ class Wav2Vec2AudioEncoder(_EncoderBase):
         if stage == "pos":
             return b, lens, S1
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
-        self._layers(layers, b, _TextPass(B, S, b["mask"], fuse=False))
+        self._post_ln_layers(layers, b, self._two_launch(b, "ufnd_attention_bf16", operands=(b["mask"],), B=B, Lq=S), M)      # (padded slabs, a key mask)
         if pool:
             L.check(lib.ufnd_masked_meanpool(b["xf"].data_ptr(), b["mask"].data_ptr(), b["pooled"].data_ptr(), B, S, H, s), "ufnd_masked_meanpool")
             L.check(lib.ufnd_linear_f32(b["pooled"].data_ptr(), w["proj.weight"].data_ptr(), w["proj.bias"].data_ptr(), b["feat"].data_ptr(), B,

@@ -240,93 +240,91 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
   }
 }
 
+// One launch of attention_kernel as an entry describes it.  The checks, the form and the grid are decided here, once.
+constexpr int CQ = 32 * UFND_CAUSAL_WAVES;      // queries per workgroup of the causal forms
+struct AttnLaunch {
+  const char* name;                  // the entry's name in its messages
+  const void* qkv;
+  const int32_t* key_mask;
+  void* ctx;
+  int B, L, heads;                   // (varlen: L is max_len)
+  bool varlen = false;               // packed rows: sample b's are cu[b] .. cu[b+1].  A flag of its own, because a varlen entry
+  const int32_t* cu = nullptr;       // refuses a NULL cu: cu == nullptr alone would silently select the padded form
+  float* lse = nullptr;
+  bool dropout = false;              // train-mode dropout on the probabilities: needs lse and drop
+  const ufnd_dropout* drop = nullptr;
+  bool causal = false;
+};
+
+template <int NW, bool DROP, bool CAUSAL>
+void launch_form(const AttnLaunch& a, int nqb, hipStream_t stream) {
+  const float scale_log2e = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
+  hipLaunchKernelGGL((attention_kernel<64, NW, DROP, CAUSAL>), dim3(nqb * a.heads * a.B), dim3(NW * 64), 0, stream, (const __bf16*)a.qkv, a.key_mask,
+                     (__bf16*)a.ctx, a.L, a.heads, scale_log2e, a.cu, a.lse, nqb, DROP ? *a.drop : ufnd_dropout{});
+}
+
+// Forms.  Causal (the CLIP text tower; built for its L <= 77): workgroups of UFND_CAUSAL_WAVES = 2 waves and 64 queries, so that at
+// L = 77 query block 0 never touches key block 1 and only one wave of four runs on clamped duplicate queries.  Otherwise
+// 4 waves and 128 queries, except for padded samples of L <= 64 (the ViT's 50), which take the 2-wave form (attention_kernel).
+int attention_launch(const AttnLaunch& a, void* stream_) {
+  UFND_REQUIRE(a.qkv && a.ctx && (!a.varlen || a.cu) && (!a.dropout || (a.lse && a.drop && a.drop->state)), "%s: null operand", a.name);
+  if (a.dropout) UFND_REQUIRE(a.drop->p > 0.0f && a.drop->p < 1.0f, "%s: p=%g (0 < p < 1; p = 0 is ufnd_attention_bf16_lse)", a.name, (double)a.drop->p);
+  UFND_REQUIRE(a.B >= 1 && (!a.varlen || a.B <= 65535) && a.L >= 1 && a.L <= 4096 && a.heads >= 1 && a.heads <= 64, "%s: B=%d %s=%d heads=%d", a.name,
+               a.B, a.varlen ? "max_len" : "L", a.L, a.heads);
+  UFND_REQUIRE(ufnd_aligned(a.qkv, 16) && ufnd_aligned(a.ctx, 16), "%s: 16-B alignment required", a.name);
+  const bool two_waves = !a.causal && !a.varlen && a.L <= 64;
+  const int nqb = ufnd_cdiv(a.L, a.causal ? CQ : (two_waves ? 64 : QB));
+  // (vacuous for ufnd_attention_bf16_varlen_masked, which never had this check: B <= 65535, heads <= 64 and nqb <= 32 stay below 2^31)
+  UFND_REQUIRE((long long)a.B * a.heads * nqb < (1ll << 31), "%s: grid too large", a.name);
+  if (a.dropout) UFND_REQUIRE(ufnd_attn_dropout_fits(a.B, a.L, a.heads), "%s: B=%d L=%d heads=%d overflows the 32-bit dropout counter", a.name, a.B, a.L, a.heads);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (a.causal) launch_form<UFND_CAUSAL_WAVES, false, true>(a, nqb, stream);
+  else if (a.dropout && two_waves) launch_form<2, true, false>(a, nqb, stream);
+  else if (a.dropout) launch_form<4, true, false>(a, nqb, stream);
+  else if (two_waves) launch_form<2, false, false>(a, nqb, stream);
+  else launch_form<4, false, false>(a, nqb, stream);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 }  // namespace
 
-extern "C" int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads,
-                                       void* stream_);
-extern "C" int ufnd_attention_bf16(const void* qkv, const int32_t* key_mask, void* ctx, int B, int L, int heads,
-                                   void* stream_) {
-  return ufnd_attention_bf16_lse(qkv, key_mask, ctx, nullptr, B, L, heads, stream_);
+extern "C" int ufnd_attention_bf16(const void* qkv, const int32_t* key_mask, void* ctx, int B, int L, int heads, void* stream_) {
+  return attention_launch({"attention", qkv, key_mask, ctx, B, L, heads}, stream_);
 }
 
 extern "C" int ufnd_attention_bf16_lse(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads,
                                        void* stream_) {
-  UFND_REQUIRE(qkv && ctx, "attention: null operand");
-  UFND_REQUIRE(B >= 1 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention: B=%d L=%d heads=%d", B, L, heads);
-  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention: 16-B alignment required");
-  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(L, QB) < (1ll << 31), "attention: grid too large");
-  const float scale_log2e = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
-  if (L <= 64)
-    hipLaunchKernelGGL((attention_kernel<64, 2>), dim3(heads * B), dim3(128), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, 1, ufnd_dropout{});
-  else
-    hipLaunchKernelGGL((attention_kernel<64, 4>), dim3(ufnd_cdiv(L, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB), ufnd_dropout{});
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
+  AttnLaunch a{"attention", qkv, key_mask, ctx, B, L, heads};
+  a.lse = lse;
+  return attention_launch(a, stream_);
 }
 
 extern "C" int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B,
                                                  int max_len, int heads, void* stream_) {
-  UFND_REQUIRE(qkv && ctx && cu_seqlens, "attention_varlen: null operand");
-  UFND_REQUIRE(B >= 1 && B <= 65535 && max_len >= 1 && max_len <= 4096 && heads >= 1 && heads <= 64, "attention_varlen: B=%d max_len=%d heads=%d",
-               B, max_len, heads);
-  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_varlen: 16-B alignment required");
-  const float scale_log2e = 0.125f * 1.44269504088896340736f;
-  hipLaunchKernelGGL((attention_kernel<64, 4>), dim3(ufnd_cdiv(max_len, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
-                     (const __bf16*)qkv, key_mask, (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr,
-                     ufnd_cdiv(max_len, QB), ufnd_dropout{});
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
+  AttnLaunch a{"attention_varlen", qkv, key_mask, ctx, B, max_len, heads};
+  a.varlen = true, a.cu = cu_seqlens;
+  return attention_launch(a, stream_);
 }
 
 extern "C" int ufnd_attention_bf16_lse_dropout(const void* qkv, const int32_t* key_mask, void* ctx, float* lse, int B, int L, int heads,
                                                const ufnd_dropout* drop, void* stream_) {
-  UFND_REQUIRE(qkv && ctx && lse && drop && drop->state, "attention_dropout: null operand");
-  UFND_REQUIRE(drop->p > 0.0f && drop->p < 1.0f, "attention_dropout: p=%g (0 < p < 1; p = 0 is ufnd_attention_bf16_lse)", (double)drop->p);
-  UFND_REQUIRE(B >= 1 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention_dropout: B=%d L=%d heads=%d", B, L, heads);
-  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_dropout: 16-B alignment required");
-  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(L, QB) < (1ll << 31), "attention_dropout: grid too large");
-  UFND_REQUIRE(ufnd_attn_dropout_fits(B, L, heads), "attention_dropout: B=%d L=%d heads=%d overflows the 32-bit dropout counter", B, L, heads);
-  const float scale_log2e = 0.125f * 1.44269504088896340736f;
-  if (L <= 64)
-    hipLaunchKernelGGL((attention_kernel<64, 2, true>), dim3(heads * B), dim3(128), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, 1, *drop);
-  else
-    hipLaunchKernelGGL((attention_kernel<64, 4, true>), dim3(ufnd_cdiv(L, QB) * heads * B), dim3(256), 0, (hipStream_t)stream_,
-                       (const __bf16*)qkv, key_mask, (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, lse, ufnd_cdiv(L, QB), *drop);
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
+  AttnLaunch a{"attention_dropout", qkv, key_mask, ctx, B, L, heads};
+  a.lse = lse, a.dropout = true, a.drop = drop;
+  return attention_launch(a, stream_);
 }
 
-// Causal forms (the CLIP text tower; L <= 4096 like the others, built for its L <= 77): workgroups of 2 waves and 64 queries, so that
-// at L = 77 query block 0 never touches key block 1 and only one wave of four runs on clamped duplicate queries.
-constexpr int CQ = 32 * UFND_CAUSAL_WAVES;      // queries per workgroup of the causal forms
-// Precondition: key 0 of every sample is visible (key_mask[b][0] != 0); rows whose every visible key is masked are unspecified.
+// Precondition of the causal entries: key 0 of every sample is visible (key_mask[b][0] != 0); rows whose every visible key is masked
+// are unspecified.
 extern "C" int ufnd_attention_bf16_causal(const void* qkv, const int32_t* key_mask, void* ctx, int B, int L, int heads, void* stream_) {
-  UFND_REQUIRE(qkv && ctx, "attention_causal: null operand");
-  UFND_REQUIRE(B >= 1 && L >= 1 && L <= 4096 && heads >= 1 && heads <= 64, "attention_causal: B=%d L=%d heads=%d", B, L, heads);
-  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_causal: 16-B alignment required");
-  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(L, CQ) < (1ll << 31), "attention_causal: grid too large");
-  const float scale_log2e = 0.125f * 1.44269504088896340736f;
-  const int nqb = ufnd_cdiv(L, CQ);
-  hipLaunchKernelGGL((attention_kernel<64, UFND_CAUSAL_WAVES, false, true>), dim3(nqb * heads * B), dim3(2 * CQ), 0, (hipStream_t)stream_, (const __bf16*)qkv, key_mask,
-                     (__bf16*)ctx, L, heads, scale_log2e, (const int32_t*)nullptr, (float*)nullptr, nqb, ufnd_dropout{});
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
+  AttnLaunch a{"attention_causal", qkv, key_mask, ctx, B, L, heads};
+  a.causal = true;
+  return attention_launch(a, stream_);
 }
 
 extern "C" int ufnd_attention_bf16_causal_varlen(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
                                                  int heads, void* stream_) {
-  UFND_REQUIRE(qkv && ctx && cu_seqlens, "attention_causal_varlen: null operand");
-  UFND_REQUIRE(B >= 1 && B <= 65535 && max_len >= 1 && max_len <= 4096 && heads >= 1 && heads <= 64,
-               "attention_causal_varlen: B=%d max_len=%d heads=%d", B, max_len, heads);
-  UFND_REQUIRE(ufnd_aligned(qkv, 16) && ufnd_aligned(ctx, 16), "attention_causal_varlen: 16-B alignment required");
-  UFND_REQUIRE((long long)B * heads * ufnd_cdiv(max_len, CQ) < (1ll << 31), "attention_causal_varlen: grid too large");
-  const float scale_log2e = 0.125f * 1.44269504088896340736f;
-  const int nqb = ufnd_cdiv(max_len, CQ);
-  hipLaunchKernelGGL((attention_kernel<64, UFND_CAUSAL_WAVES, false, true>), dim3(nqb * heads * B), dim3(2 * CQ), 0, (hipStream_t)stream_, (const __bf16*)qkv, key_mask,
-                     (__bf16*)ctx, max_len, heads, scale_log2e, cu_seqlens, (float*)nullptr, nqb, ufnd_dropout{});
-  UFND_CHECK_LAUNCH();
-  return UFND_OK;
+  AttnLaunch a{"attention_causal_varlen", qkv, key_mask, ctx, B, max_len, heads};
+  a.varlen = a.causal = true, a.cu = cu_seqlens;
+  return attention_launch(a, stream_);
 }

@@ -3,7 +3,7 @@
 // Frames are rows, channel-last, in per-clip slabs (include/ultrafnd_hip.h).  Every reduction is a fixed tree over the clip's own
 // samples / frames: fp32 partials per fixed-size chunk about a pivot (the chunk's first value), combined in chunk order in
 // float64 (Chan's update).  No atomics; a clip's results are the same bits alone and inside any batch, on every run.
-#include "common.hpp"
+#include "rowwise.hpp"
 #include "gemm_f32.hpp"
 
 // (the statistics below are sums of exactly the values the apply passes recompute: no contraction may differ between the passes)
@@ -29,15 +29,6 @@ __device__ __forceinline__ int w2v2_frames(int n) {
 __device__ __forceinline__ int clip_len(const int32_t* lengths, int b, int n_max) {
   const int n = lengths[b];
   return n < n_max ? n : n_max;
-}
-
-// block-wide sum in a fixed order: DPP wave sums, then the four waves' totals in wave order
-__device__ __forceinline__ float block_sum4(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ---- utterance normalisation.  Partials: grid (chunks, B); chunk c of clip b -> ws[(b nch + c) 3 ..] = {pivot, s, q}

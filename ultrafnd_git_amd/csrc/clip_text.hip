@@ -7,20 +7,15 @@
 //   head     exact-erf GELU of the two projections and l2n(t), l2n(i), l2n(t - i), all fp32
 //   similarity  the row-wise cosine of text and image embeddings and the conflict score 1 - (cos + 1) / 2
 // One wave per row or sample, fixed reduction trees, no atomics: a sample's results are the same bits alone and inside any batch.
-#include "common.hpp"
+#include "rowwise.hpp"
 #include "gemm_f32.hpp"
 
 namespace {
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
-// ---- pack: one workgroup, a wave per sample, then a fixed-order scan (the shape of ufnd_text_pack)
-constexpr int PACK_THREADS = 1024, PACK_MAX_B = 16384;
+// ---- pack: one workgroup, a wave per sample, then the fixed-order scan ufnd_text_pack runs (pack_scan_rows)
 __global__ __launch_bounds__(PACK_THREADS) void clip_text_pack_kernel(const int64_t* ids, int B, int L, int eos, int32_t* e, int32_t* cu,
                                                                       int32_t* row_src) {
   __shared__ int lens[PACK_MAX_B];
-  __shared__ int wsum[PACK_THREADS / 64];
-  __shared__ int total;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int b = wave; b < B; b += PACK_THREADS / 64) {
     // eos == 2 (the legacy configs): the first position of the largest id; otherwise the first position equal to eos, 0 if there is
@@ -47,37 +42,7 @@ __global__ __launch_bounds__(PACK_THREADS) void clip_text_pack_kernel(const int6
       e[b] = pos;
     }
   }
-  __syncthreads();
-  // exclusive scan: thread t owns the contiguous samples [t per, (t + 1) per)
-  const int per = (B + PACK_THREADS - 1) / PACK_THREADS, b0 = tid * per, b1 = min(b0 + per, B);
-  int own = 0;
-  for (int b = b0; b < b1; ++b) own += lens[b];
-  int inc = own;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += y;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  int run = base + inc - own;
-  for (int b = b0; b < b1; ++b) {
-    const int n = lens[b];
-    lens[b] = run;      // (only this thread touches its samples' slots)
-    cu[b] = run;
-    run += n;
-  }
-  if (tid == PACK_THREADS - 1) {
-    cu[B] = run;
-    total = run;
-  }
-  __syncthreads();
-  for (int b = wave; b < B; b += PACK_THREADS / 64) {
-    const int r0 = lens[b], n = (b + 1 < B ? lens[b + 1] : total) - r0;
-    for (int l = lane; l < n; l += 64) row_src[r0 + l] = b * L + l;
-  }
+  pack_scan_rows(lens, B, L, cu, row_src);
 }
 
 // ---- embed: one wave per row of H = 256 NI columns
@@ -102,7 +67,7 @@ __global__ __launch_bounds__(256) void clip_text_embed_kernel(const int64_t* ids
   }
 }
 
-// ---- pool: LayerNorm of row e(b) (padded: b L + e[b]; packed: cu[b + 1] - 1), ufnd_layernorm's arithmetic, bf16 out
+// ---- pool: LayerNorm of row e(b) (padded: b L + e[b]; packed: cu[b + 1] - 1), ufnd_layernorm's arithmetic (ln_row), bf16 out
 template <int NI>
 __global__ __launch_bounds__(256) void clip_text_pool_kernel(const float* x, const int32_t* e, const int32_t* cu, const float* gamma, const float* beta,
                                                              __bf16* out, int B, int L, int H, float eps) {
@@ -113,40 +78,10 @@ __global__ __launch_bounds__(256) void clip_text_pool_kernel(const float* x, con
   eb = eb < 0 ? 0 : (eb >= L ? L - 1 : eb);      // (the pack kernel's own output; this keeps a foreign e inside the sample)
   const size_t row = cu ? (size_t)cu[b + 1] - 1 : (size_t)b * L + eb;
   f32x4 v[NI];
-  float s = 0.0f;
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    v[i] = ld4(x + row * H + 4 * lane + 256 * i);
-    s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-  }
-  const float mean = wave_sum(s) / (float)H;
-  float q = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float d = v[i][k] - mean;
-      q += d * d;
-    }
-  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int col = 4 * lane + 256 * i;
-    const f32x4 gm = ld4(gamma + col), bt = ld4(beta + col);
-    bf16x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (__bf16)((v[i][k] - mean) * rstd * gm[k] + bt[k]);
-    *reinterpret_cast<bf16x4*>(out + (size_t)b * H + col) = o;
-  }
-}
-
-// block-wide sum in a fixed order: DPP wave sums, then the four waves' totals in wave order
-__device__ __forceinline__ float block_sum4(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
+  for (int i = 0; i < NI; ++i) v[i] = ld4(x + row * H + 4 * lane + 256 * i);
+  ln_row<NI>(v, H, eps, gamma, beta, lane);
+  store_row<NI>(v, out, nullptr, b, H, lane);
 }
 
 // ---- head epilogue: one workgroup per sample.  z (2, B, D): the two Linears' pre-activations (text, image).
@@ -192,18 +127,6 @@ __global__ __launch_bounds__(256) void clip_similarity_kernel(const float* t, co
     conflict[b] = 1.0f - (c + 1.0f) * 0.5f;
   }
 }
-
-inline bool h_ok(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
-
-#define NI_LAUNCH(H, kernel, grid, stream, ...)                                                      \
-  do {                                                                                               \
-    switch ((H) / 256) {                                                                             \
-      case 1: hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__); break;         \
-      case 2: hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, stream, __VA_ARGS__); break;         \
-      case 3: hipLaunchKernelGGL(kernel<3>, grid, dim3(256), 0, stream, __VA_ARGS__); break;         \
-      default: hipLaunchKernelGGL(kernel<4>, grid, dim3(256), 0, stream, __VA_ARGS__); break;        \
-    }                                                                                                \
-  } while (0)
 
 int embed_checks(const char* what, const int64_t* ids, const float* tok, const float* pos, void* x_bf16, float* x_f32, int rows, int L, int H, int vocab,
                  int max_pos) {

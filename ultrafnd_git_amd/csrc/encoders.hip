@@ -1,63 +1,9 @@
 // Row-wise pieces of the two encoders: LayerNorm, BERT embeddings, masked mean-pool + L2,
 // ViT patchify / token assembly, frame pooling.  All HBM-bound: one wave per row, 16-B loads,
 // wave-shuffle reductions, fp32 statistics; outputs feed the bf16 GEMMs directly.
-#include "common.hpp"
+#include "rowwise.hpp"
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
-// normalise NI*4 values per lane (row of H = 256*NI) held in v[]; returns via v[]
-template <int NI>
-__device__ __forceinline__ void ln_row(f32x4 (&v)[NI], int H, float eps, const float* gamma, const float* beta, int lane) {
-  float s = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NI; ++i) s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-  const float mean = wave_sum(s) / (float)H;
-  float q = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float d = v[i][k] - mean;
-      q += d * d;
-    }
-  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int col = 4 * lane + 256 * i;
-    const f32x4 gm = ld4(gamma + col), bt = ld4(beta + col);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[i][k] = (v[i][k] - mean) * rstd * gm[k] + bt[k];
-  }
-}
-
-template <int NI>
-__device__ __forceinline__ void store_row(const f32x4 (&v)[NI], __bf16* ob, float* of, size_t row, int H, int lane) {
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int col = 4 * lane + 256 * i;
-    if (of) *reinterpret_cast<f32x4*>(of + row * H + col) = v[i];
-    if (ob) {
-      bf16x4 o = {(__bf16)v[i][0], (__bf16)v[i][1], (__bf16)v[i][2], (__bf16)v[i][3]};
-      *reinterpret_cast<bf16x4*>(ob + row * H + col) = o;
-    }
-  }
-}
-
-// {sum, sum of squares} of the row held in v[] -> stats[row] as TWO partials ({s, q}, {0, 0}): the
-// layout ufnd_gemm_bf16_ln reads its a_stats in (even partial counts)
-template <int NI>
-__device__ __forceinline__ void row_stats(const f32x4 (&v)[NI], float* stats, size_t row, int lane) {
-  float s = 0.0f, q = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { s += v[i][k]; q += v[i][k] * v[i][k]; }
-  s = wave_sum(s);
-  q = wave_sum(q);
-  if (lane == 0) *reinterpret_cast<f32x4*>(stats + row * 4) = f32x4{s, q, 0.0f, 0.0f};
-}
 
 template <int NI>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, int ldx, const float* gamma, const float* beta,
@@ -240,13 +186,10 @@ __global__ __launch_bounds__(256) void ln_meanpool_kernel(const float* y, const 
 // every bin fills its slots from slot 0 on, samples in ascending order within a class.  This is an optimal packing (no bin
 // count is lower) and a function of the n_b alone.  Bin i is 8 ints: slot j's {cu[b] + 32 s, (b << 10) | (s << 8) | n_b} for
 // slot s of sample b, {0, -1} if empty; *nbins = the bin count (0 when every sample is all-masked).
-constexpr int PACK_THREADS = 1024, PACK_MAX_B = 16384;
 __global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src,
                                                                  int32_t* bins, int32_t* nbins) {
   __shared__ int lens[PACK_MAX_B];
-  __shared__ int wsum[PACK_THREADS / 64];
   __shared__ long long csum[PACK_THREADS / 64];
-  __shared__ int total;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int b = wave; b < B; b += PACK_THREADS / 64) {      // a wave per sample: the largest kept position + 1
     int last = 0;
@@ -255,38 +198,9 @@ __global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* 
     for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
     if (lane == 0) lens[b] = last;
   }
-  __syncthreads();
-  // exclusive scan: thread t owns the contiguous samples [t per, (t + 1) per)
-  const int per = (B + PACK_THREADS - 1) / PACK_THREADS, b0 = tid * per, b1 = min(b0 + per, B);
-  int own = 0;
-  for (int b = b0; b < b1; ++b) own += lens[b];
-  int inc = own;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += y;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  int run = base + inc - own;
-  for (int b = b0; b < b1; ++b) {
-    const int n = lens[b];
-    lens[b] = run;      // (only this thread touches its samples' slots)
-    cu[b] = run;
-    run += n;
-  }
-  if (tid == PACK_THREADS - 1) {
-    cu[B] = run;
-    total = run;
-  }
-  __syncthreads();
-  for (int b = wave; b < B; b += PACK_THREADS / 64) {
-    const int r0 = lens[b], n = (b + 1 < B ? lens[b + 1] : total) - r0;
-    for (int l = lane; l < n; l += 64) row_src[r0 + l] = b * L + l;
-  }
+  const int total = pack_scan_rows(lens, B, L, cu, row_src);      // (rowwise.hpp: cu, row_src; lens[b] = cu[b])
   if (!bins) return;
+  const int per = (B + PACK_THREADS - 1) / PACK_THREADS, b0 = tid * per, b1 = min(b0 + per, B);      // the scan's samples of this thread
   // ranks within the slot classes: four 16-bit counters in one 64-bit scan (counts <= PACK_MAX_B < 2^16)
   auto nrows = [&](int b) { return (b + 1 < B ? lens[b + 1] : total) - lens[b]; };
   long long cown = 0;
@@ -418,11 +332,7 @@ __global__ __launch_bounds__(256) void l2norm_frames_kernel(const float* e, floa
     const float* row = e + ((size_t)b * F + f) * D;
     float sq = 0.0f;
     for (int c = threadIdx.x; c < D; c += 256) sq += row[c] * row[c];
-    sq = wave_sum(sq);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    const float nrm = sqrtf((sh[0] + sh[1]) + (sh[2] + sh[3])) + 1e-9f;
+    const float nrm = sqrtf(block_sum4(sq, sh)) + 1e-9f;
     int n = 0;
     for (int c = threadIdx.x; c < D; c += 256, ++n) acc[n] += row[c] / nrm;
   }
@@ -437,11 +347,7 @@ __global__ __launch_bounds__(256) void l2norm_frames_kernel(const float* e, floa
     acc[n] /= (float)F;
     sq += acc[n] * acc[n];
   }
-  sq = wave_sum(sq);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  const float nrm = sqrtf((sh[0] + sh[1]) + (sh[2] + sh[3])) + 1e-9f;
+  const float nrm = sqrtf(block_sum4(sq, sh)) + 1e-9f;
   n = 0;
   for (int c = threadIdx.x; c < D; c += 256, ++n) out[(size_t)b * D + c] = acc[n] / nrm;
 }
@@ -474,25 +380,6 @@ __global__ __launch_bounds__(256) void field_mean_l2_kernel(const float* parts, 
   k = 0;
   for (int c = threadIdx.x; c < D; c += 256, ++k) out[(size_t)n * D + c] = cnt ? acc[k] / nrm : 0.0f;
 }
-
-#define NI_LAUNCH(H, KERNEL, GRID, STREAM, ...)                                                       \
-  do {                                                                                                \
-    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);         \
-    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);    \
-    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);    \
-    else hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                    \
-  } while (0)
-
-// the same over a kernel with a second template argument T
-#define NI_LAUNCH_T(H, KERNEL, T, GRID, STREAM, ...)                                                       \
-  do {                                                                                                     \
-    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);           \
-    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
-    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
-    else hipLaunchKernelGGL((KERNEL<4, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                      \
-  } while (0)
-
-inline bool h_ok(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
 
 }  // namespace
 

@@ -5,11 +5,9 @@
 // ascending order): no atomics, bitwise reproducible.
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "rowwise.hpp"
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // y = (x - mean) rstd gamma + beta  ->  dx = rstd (g - mean(g) - xh mean(g xh)),  g = dy gamma,  xh = (x - mean) rstd
 // (+ `add`: the gradient arriving over the residual branch).  dgamma / dbeta partials per block: part[blk][0/1][H].
@@ -332,24 +330,6 @@ __global__ __launch_bounds__(256) void act_bf16_kernel(const __bf16* __restrict_
   }
 }
 
-#define NI_LAUNCH(H, KERNEL, GRID, STREAM, ...)                                                       \
-  do {                                                                                                \
-    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);         \
-    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);    \
-    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);    \
-    else hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                    \
-  } while (0)
-
-// the same over a kernel with a second template argument T
-#define NI_LAUNCH_T(H, KERNEL, T, GRID, STREAM, ...)                                                       \
-  do {                                                                                                     \
-    if ((H) == 256) hipLaunchKernelGGL((KERNEL<1, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);           \
-    else if ((H) == 512) hipLaunchKernelGGL((KERNEL<2, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
-    else if ((H) == 768) hipLaunchKernelGGL((KERNEL<3, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
-    else hipLaunchKernelGGL((KERNEL<4, T>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                      \
-  } while (0)
-
-inline bool h_ok(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
 inline int ln_bwd_blocks(int M) { const int b = ufnd_cdiv(M, 8); return b < 1 ? 1 : (b > 256 ? 256 : b); }
 
 }  // namespace

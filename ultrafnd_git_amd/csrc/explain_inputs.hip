@@ -4,11 +4,10 @@
 // reductions, block sums added in a fixed order -- no atomics, a rerun gives the same bits.
 #include <hip/hip_runtime.h>
 
-#include "common.hpp"
+#include "rowwise.hpp"
 
 namespace {
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 struct PathAlphas {

@@ -10,6 +10,7 @@
 //        (t, v, a, u) feeds ONE stacked GEMM forward and ONE stacked GEMM backward.
 // Row kernels use one 64-lane wave per sample; lane l owns columns 4l..4l+3 (+256 i).
 #include "gemm_f32.hpp"
+#include "rowwise.hpp"
 
 namespace {
 
@@ -94,7 +95,6 @@ ClfWs carve_clf(const ufnd_dims& d, int B, float* base) {
   return w;
 }
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 __device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }

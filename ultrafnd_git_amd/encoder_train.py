@@ -89,7 +89,6 @@ class _Backprop:
         self.saved: Optional[dict] = None
         self._refresh = None               # (device table, items, tiles, names left to the per-Linear path) of the grouped operand refresh
         self._views: Dict[Tuple, torch.Tensor] = {}
-        self._lk_cache: Dict[int, dict] = {}
         self._pending_ln = None            # (job, scratch, buffer index) of a LayerNorm backward's deferred dgamma / dbeta finish (rides in the next Linear's finish launch)
         self._wg_side = None               # the stream of the weight-gradient products
         self._wg_open = False
@@ -176,11 +175,8 @@ class _Backprop:
         return buf[o0:o0 + n].view((rows,) + rest)
 
     def _lk(self, i: int) -> dict:
-        """The parameter names of layer i (built once: a dozen formatted strings per layer per pass otherwise)."""
-        k = self._lk_cache.get(i)
-        if k is None:
-            k = self._lk_cache[i] = self._lk_build(i)
-        return k
+        """The parameter names of layer i: the encoder's own table (memoised there)."""
+        return self.enc.layer_keys(i)
 
     def master(self, keys: List[str]) -> torch.Tensor:
         """A master tensor (or adjacent ones stacked): the arena's view, or -- frozen -- the encoder's own."""
@@ -418,16 +414,6 @@ def _act(x: torch.Tensor, out: torch.Tensor, act: int) -> None:
 class TextBackprop(_Backprop):
     """BertTextEncoder with a backward: BertModel (post-LN) -> masked mean-pool -> L2."""
 
-    def _lk_build(self, i: int) -> dict:
-        P = f"encoder.layer.{i}."
-        return {"qkv_w": [P + f"attention.self.{n}.weight" for n in ("query", "key", "value")],
-                "qkv_b": [P + f"attention.self.{n}.bias" for n in ("query", "key", "value")],
-                "o_w": [P + "attention.output.dense.weight"], "o_b": [P + "attention.output.dense.bias"],
-                "g1": [P + "attention.output.LayerNorm.weight"], "b1n": [P + "attention.output.LayerNorm.bias"],
-                "w1": [P + "intermediate.dense.weight"], "b1": [P + "intermediate.dense.bias"],
-                "w2": [P + "output.dense.weight"], "b2": [P + "output.dense.bias"],
-                "g2": [P + "output.LayerNorm.weight"], "b2n": [P + "output.LayerNorm.bias"]}
-
     def groups(self):
         w, out = self.enc._w, []
         for i in reversed(range(self.enc.layers)):
@@ -600,15 +586,6 @@ class VisualBackprop(_Backprop):
     """ClipVisualEncoder with a backward: CLIP ViT (pre-LN) -> pooled CLS -> projection -> frame pooling."""
 
     V = "vision_model."
-
-    def _lk_build(self, i: int) -> dict:
-        P = self.V + f"encoder.layers.{i}."
-        return {"qkv_w": [P + f"self_attn.{n}.weight" for n in ("q_proj", "k_proj", "v_proj")],
-                "qkv_b": [P + f"self_attn.{n}.bias" for n in ("q_proj", "k_proj", "v_proj")],
-                "o_w": [P + "self_attn.out_proj.weight"], "o_b": [P + "self_attn.out_proj.bias"],
-                "g1": [P + "layer_norm1.weight"], "b1n": [P + "layer_norm1.bias"],
-                "w1": [P + "mlp.fc1.weight"], "b1": [P + "mlp.fc1.bias"], "w2": [P + "mlp.fc2.weight"], "b2": [P + "mlp.fc2.bias"],
-                "g2": [P + "layer_norm2.weight"], "b2n": [P + "layer_norm2.bias"]}
 
     def groups(self):
         w, V, out = self.enc._w, self.V, []

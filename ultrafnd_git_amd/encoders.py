@@ -38,7 +38,7 @@ from __future__ import annotations
 import ctypes
 import warnings
 from collections import OrderedDict
-from typing import Dict, NamedTuple, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -116,6 +116,7 @@ class _EncoderBase(nn.Module):
         self._guard: Optional[torch.Tensor] = None      # device float: largest |mean| / std any folded LayerNorm has seen
         self._w: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         self._packed: Optional[dict] = None
+        self._layer_keys: Dict[int, dict] = {}
         self._bufs: Dict[Tuple, dict] = {}
         self.weights_version = 0      # bumped whenever the packed operands are invalidated (captured graphs name them)
 
@@ -127,6 +128,36 @@ class _EncoderBase(nn.Module):
         def init(shape, std=0.02):
             return torch.randn(shape, generator=g) * std
         return init
+
+    # ---- the layer table: the third-party names of a layer's tensors, and the operands packed from them
+    LAYER_PREFIX: str                  # "...{}." : the prefix of layer i's keys
+    LAYER_NAMES: Dict[str, list]       # name -> the key suffixes behind it
+
+    def layer_keys(self, i: int) -> Dict[str, list]:
+        """The state_dict keys of layer i: qkv_w / qkv_b (query, key, value: stacked row-wise into one Linear), o_w / o_b, w1 / b1, w2 / b2
+        (the four Linears) and g1 / b1n, g2 / b2n (the two LayerNorms, in the order they run), each a list of keys.  Built once per
+        layer: a pass that formats a dozen strings per layer pays for them in host time."""
+        k = self._layer_keys.get(i)
+        if k is None:
+            P = self.LAYER_PREFIX.format(i)
+            k = self._layer_keys[i] = {name: [P + sfx for sfx in sfxs] for name, sfxs in self.LAYER_NAMES.items()}
+        return k
+
+    def _pack_layers(self, extra=None) -> list:
+        """The layers' operands: bf16 MFMA weights (Q/K/V stacked into one (3H, H) matrix), fp32 biases and LayerNorm parameters.
+        extra(layers, wq, w1): called per layer, right after layers[-1] is built, with the fp32 stacked Q/K/V weight and FFN1 weight
+        while they are at hand -- where BERT and the ViT add their folded forms on top."""
+        w, layers = self._w, []
+        for i in range(self.layers):
+            k = self.layer_keys(i)
+            wq = torch.cat([w[n] for n in k["qkv_w"]], 0)
+            layers.append({"wqkv": _bf16(wq), "bqkv": torch.cat([w[n] for n in k["qkv_b"]], 0).contiguous(),
+                           "wo": _bf16(w[k["o_w"][0]]), "bo": w[k["o_b"][0]], "g1": w[k["g1"][0]], "b1": w[k["b1n"][0]],
+                           "w1": _bf16(w[k["w1"][0]]), "bi": w[k["b1"][0]], "w2": _bf16(w[k["w2"][0]]), "b2": w[k["b2"][0]],
+                           "g2": w[k["g2"][0]], "b2n": w[k["b2n"][0]]})
+            if extra is not None:
+                extra(layers, wq, w[k["w1"][0]])
+        return layers
 
     # ---- state_dict with the third-party names
     def state_dict(self, *args, **kwargs):
@@ -291,25 +322,74 @@ class _EncoderBase(nn.Module):
                                                      ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
                 "ufnd_qkv_attention_bf16_bins")
 
-    def _attn(self, qkv, mask_i32, ctx, B, Lq, heads):
-        L.check(L.lib().ufnd_attention_bf16(qkv.data_ptr(), L.ptr(mask_i32), ctx.data_ptr(), B, Lq, heads,
-                                            L.stream_ptr(qkv.device)), "ufnd_attention_bf16")
+    # ---- the layer loops.  `attend(A, W, bias, **fold)` is the pass's own: a layer's Q/K/V projection of A (folded: of LayerNorm(A),
+    # fold = a_stats, colsum) and its attention into b["ctx"] -- one fused launch (_qkv_attn), or _two_launch around an attention entry
+    def _two_launch(self, b, entry: str, operands: tuple, B: int, Lq: int, live=None):
+        """attend as two launches: the projection GEMM into b["qkv"], then the attention entry(b["qkv"], *operands, b["ctx"], B, Lq,
+        heads, stream).  operands: the tensors (or None) the entry takes between qkv and ctx -- (key_mask,) for the padded forms,
+        (cu_seqlens, key_mask) for the packed ones.  The call's arguments are put together here, once per pass."""
+        fn = getattr(L.lib(), entry)
+        call = (b["qkv"].data_ptr(), *(L.ptr(t) for t in operands), b["ctx"].data_ptr(), B, Lq, self.heads, L.stream_ptr(self.device))
+
+        def attend(A, W, bias, a_stats=None, colsum=None):
+            if a_stats is None:
+                self._gemm(A, W, bias, out_bf16=b["qkv"], which="qkv", m_live=live)
+            else:
+                self._gemm_ln(A, W, bias, out_bf16=b["qkv"], a_stats=a_stats, colsum=colsum, eps=self.eps, which="qkv", m_live=live)
+            L.check(fn(*call), entry)
+        return attend
+
+    def _post_ln_layers(self, layers, b, attend, M: int, live=None) -> None:
+        """Post-LN layers (BERT, wav2vec2) with one LayerNorm kernel per LayerNorm, over the work buffers' M rows (live: the first
+        *live of them).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
+        H, eps = self.hidden, self.eps
+        for ly in layers:
+            attend(b["xb"], ly["wqkv"], ly["bqkv"])
+            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["y"], residual=b["xf"], which="out", m_live=live)
+            self._ln(b["y"], H, ly["g1"], ly["b1"], b["x1b"], b["x1f"], M, H, eps, m_live=live)
+            self._gemm(b["x1b"], ly["w1"], ly["bi"], out_bf16=b["h"], act=ACT_GELU, which="ffn1", m_live=live)
+            self._gemm(b["h"], ly["w2"], ly["b2"], out_f32=b["y"], residual=b["x1f"], which="ffn2", m_live=live)
+            self._ln(b["y"], H, ly["g2"], ly["b2n"], b["xb"], b["xf"], M, H, eps, m_live=live)
+
+    def _pre_ln_blocks(self, layers, b, attend, M: int, act: int, live=None, tail=None) -> None:
+        """Pre-LN blocks (both CLIP towers) with one LayerNorm kernel per LayerNorm, on the fp32 residual stream b["xf"] (M rows; live:
+        the first *live of them).  tail(): the buffers the last layer runs over past its attention (the ViT's class-token rows)."""
+        H, eps = self.hidden, self.eps
+        for i, ly in enumerate(layers):
+            self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps, m_live=live)
+            attend(b["hb"], ly["wqkv"], ly["bqkv"])
+            r = tail() if (tail is not None and i == len(layers) - 1) else b
+            xf = r["xf"]
+            self._gemm(r["ctx"], ly["wo"], ly["bo"], out_f32=xf, residual=xf, which="out", m_live=live)
+            self._ln(xf, xf.stride(0), ly["g2"], ly["b2n"], r["hb"], None, xf.shape[0], H, eps, m_live=live)
+            self._gemm(r["hb"], ly["w1"], ly["bi"], out_bf16=r["m"], act=act, which="ffn1", m_live=live)
+            self._gemm(r["m"], ly["w2"], ly["b2"], out_f32=xf, residual=xf, which="ffn2", m_live=live)
 
 
-class _TextPass(NamedTuple):
-    """What the layer loops need to know about one BertTextEncoder pass.  A padded pass has no live / cu / bins / nbins."""
-    B: int
-    Lq: int
-    mask: torch.Tensor                      # (B, L) int32, 1 = a key to attend to
-    fuse: bool                              # a layer's Q/K/V projection + attention as one launch (_qkv_attn)
-    live: Optional[int] = None              # packed rows: the device address of the live row count, cu[B] (m_live of the wrappers)
-    cu: Optional[torch.Tensor] = None       # packed rows: sample b's rows are cu[b] .. cu[b+1]
-    bins: Optional[torch.Tensor] = None     # packed rows, fused: the slot bins of ufnd_text_pack_bins ...
-    nbins: Optional[torch.Tensor] = None    # ... and their count
+def _live_ptr(cu: torch.Tensor) -> int:
+    """The device address of a packed pass's live row count: the last entry of its cu_seqlens (B + 1 int32), which the pack kernel
+    writes.  The m_live of the wrappers above."""
+    return cu.data_ptr() + 4 * (cu.numel() - 1)
+
+
+# CLIP's layer names, vision and text tower alike
+_CLIP_LAYER = {"qkv_w": [f"self_attn.{n}.weight" for n in ("q_proj", "k_proj", "v_proj")],
+               "qkv_b": [f"self_attn.{n}.bias" for n in ("q_proj", "k_proj", "v_proj")],
+               "o_w": ["self_attn.out_proj.weight"], "o_b": ["self_attn.out_proj.bias"], "g1": ["layer_norm1.weight"], "b1n": ["layer_norm1.bias"],
+               "w1": ["mlp.fc1.weight"], "b1": ["mlp.fc1.bias"], "w2": ["mlp.fc2.weight"], "b2": ["mlp.fc2.bias"],
+               "g2": ["layer_norm2.weight"], "b2n": ["layer_norm2.bias"]}
 
 
 # =============================================================================================
 class BertTextEncoder(_EncoderBase):
+    LAYER_PREFIX = "encoder.layer.{}."
+    LAYER_NAMES = {"qkv_w": [f"attention.self.{n}.weight" for n in ("query", "key", "value")],
+                   "qkv_b": [f"attention.self.{n}.bias" for n in ("query", "key", "value")],
+                   "o_w": ["attention.output.dense.weight"], "o_b": ["attention.output.dense.bias"],
+                   "g1": ["attention.output.LayerNorm.weight"], "b1n": ["attention.output.LayerNorm.bias"],
+                   "w1": ["intermediate.dense.weight"], "b1": ["intermediate.dense.bias"], "w2": ["output.dense.weight"], "b2": ["output.dense.bias"],
+                   "g2": ["output.LayerNorm.weight"], "b2n": ["output.LayerNorm.bias"]}
+
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
                  vocab_size: int = 30522, max_position: int = 512, type_vocab: int = 2, eps: float = 1e-12,
                  fold_ln: bool = True, residual_dtype: str = "bf16", hidden_dropout_prob: float = 0.0,
@@ -346,27 +426,17 @@ class BertTextEncoder(_EncoderBase):
             w[P + "output.LayerNorm.weight"] = torch.ones(hidden)
             w[P + "output.LayerNorm.bias"] = torch.zeros(hidden)
 
+    def _fold_layer(self, layers, wq, w1) -> None:
+        # folded forms: intermediate.dense consumes LayerNorm_1; the NEXT layer's Q/K/V consume LayerNorm_2
+        ly = layers[-1]
+        ly["w1f"], ly["cs1"], ly["bif"] = self._fold(w1, ly["bi"], ly["g1"], ly["b1"])
+        if len(layers) > 1:
+            prev = layers[-2]
+            ly["wqkvf"], ly["csqkv"], ly["bqkvf"] = self._fold(wq, ly["bqkv"], prev["g2"], prev["b2n"])
+
     def _pack(self):
         if self._packed is None:
-            w, layers = self._w, []
-            for i in range(self.layers):
-                P = f"encoder.layer.{i}."
-                layers.append({
-                    "wqkv": _bf16(torch.cat([w[P + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)),
-                    "bqkv": torch.cat([w[P + f"attention.self.{n}.bias"] for n in ("query", "key", "value")], 0).contiguous(),
-                    "wo": _bf16(w[P + "attention.output.dense.weight"]), "bo": w[P + "attention.output.dense.bias"],
-                    "g1": w[P + "attention.output.LayerNorm.weight"], "b1": w[P + "attention.output.LayerNorm.bias"],
-                    "w1": _bf16(w[P + "intermediate.dense.weight"]), "bi": w[P + "intermediate.dense.bias"],
-                    "w2": _bf16(w[P + "output.dense.weight"]), "b2": w[P + "output.dense.bias"],
-                    "g2": w[P + "output.LayerNorm.weight"], "b2n": w[P + "output.LayerNorm.bias"]})
-                ly = layers[-1]
-                # folded forms: intermediate.dense consumes LayerNorm_1; the NEXT layer's Q/K/V consume LayerNorm_2
-                ly["w1f"], ly["cs1"], ly["bif"] = self._fold(w[P + "intermediate.dense.weight"], ly["bi"], ly["g1"], ly["b1"])
-                if i > 0:
-                    prev = layers[-2]
-                    wq = torch.cat([w[P + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
-                    ly["wqkvf"], ly["csqkv"], ly["bqkvf"] = self._fold(wq, ly["bqkv"], prev["g2"], prev["b2n"])
-            self._packed = {"layers": layers}
+            self._packed = {"layers": self._pack_layers(self._fold_layer)}
         return self._packed
 
     def _workbufs(self, B: int, Lq: int) -> dict:
@@ -405,29 +475,36 @@ class BertTextEncoder(_EncoderBase):
         mask = attention_mask.to(dev, torch.int32).contiguous()
         p, b, w = self._pack(), self._workbufs(B, Lq), self._w
         M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
-        t = _TextPass(B, Lq, mask, fuse=self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0)
-        if packed:
-            t = t._replace(cu=b["cu"], live=b["cu"].data_ptr() + 4 * B)          # cu[B]: the live row count, written by the pack kernel
-            if t.fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
-                t = t._replace(bins=b["bins"], nbins=b["nbins"])
-                L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, b["cu"].data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
-                                                    b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
-            else:
-                L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, b["cu"].data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
+        fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0      # a layer's Q/K/V projection + attention as one launch
+        cu = b["cu"] if packed else None                 # packed rows: sample b's are cu[b] .. cu[b+1] ...
+        live = _live_ptr(cu) if packed else None         # ... and cu[B], their count, stays on the device: the pack kernel writes it
+        if packed and fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
+            L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
+                                                b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
+        elif packed:
+            L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
         tables = [w["embeddings." + n].data_ptr() for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight",
                                                             "LayerNorm.weight", "LayerNorm.bias")]
         outs = (b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr())      # (bf16 stream, folded: nothing reads the fp32 copy)
         if packed:
-            L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), t.live, *tables, *outs, M, Lq, H, self.vocab, self.eps, s),
+            L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, *tables, *outs, M, Lq, H, self.vocab, self.eps, s),
                     "ufnd_bert_embed_live")
         else:
             L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
         ln_pool = pool and packed and "st" in b
-        if "st" in b:
-            self._layers_folded(layers, b, t, final_ln=not ln_pool)
+        if fuse:
+            bins, nbins = (b["bins"], b["nbins"]) if packed else (None, None)
+            attend = lambda A, W, bias, **fold: self._qkv_attn(A, W, bias, mask, b["ctx"], B, Lq, self.heads, eps=self.eps, cu=cu, bins=bins,
+                                                               nbins=nbins, **fold)
+        elif packed:
+            attend = self._two_launch(b, "ufnd_attention_bf16_varlen_masked", operands=(cu, mask), B=B, Lq=Lq, live=live)
         else:
-            self._layers(layers, b, t)
+            attend = self._two_launch(b, "ufnd_attention_bf16", operands=(mask,), B=B, Lq=Lq)
+        if "st" in b:
+            self._layers_folded(layers, b, attend, M, live, final_ln=not ln_pool)
+        else:
+            self._post_ln_layers(layers, b, attend, M, live)
         if ln_pool:       # bit-identical to the final LayerNorm into "xf" + the pooling below
             L.check(L.lib().ufnd_ln_masked_meanpool_l2_live(b["y2"].data_ptr(), layers[-1]["g2"].data_ptr(), layers[-1]["b2n"].data_ptr(), self.eps,
                                                             mask.data_ptr(), b["cu"].data_ptr(), b["feat"].data_ptr(), B, Lq, H, s),
@@ -439,40 +516,11 @@ class BertTextEncoder(_EncoderBase):
             L.check(L.lib().ufnd_masked_meanpool_l2(b["xf"].data_ptr(), mask.data_ptr(), b["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
         return b
 
-    def _self_attention(self, t: _TextPass, b, A, W, bias, a_stats=None, colsum=None) -> None:
-        """A layer's Q/K/V projection of A (of LayerNorm(A), folded, with a_stats / colsum) and its attention into b["ctx"]: one fused
-        launch, or the GEMM into b["qkv"] followed by the attention over the padded batch or over the packed rows."""
-        if t.fuse:
-            self._qkv_attn(A, W, bias, t.mask, b["ctx"], t.B, t.Lq, self.heads, a_stats=a_stats, colsum=colsum, eps=self.eps,
-                           cu=t.cu, bins=t.bins, nbins=t.nbins)
-            return
-        if a_stats is None:
-            self._gemm(A, W, bias, out_bf16=b["qkv"], which="qkv", m_live=t.live)
-        else:
-            self._gemm_ln(A, W, bias, out_bf16=b["qkv"], a_stats=a_stats, colsum=colsum, eps=self.eps, which="qkv", m_live=t.live)
-        if t.cu is None:
-            self._attn(b["qkv"], t.mask, b["ctx"], t.B, t.Lq, self.heads)
-        else:
-            L.check(L.lib().ufnd_attention_bf16_varlen_masked(b["qkv"].data_ptr(), t.cu.data_ptr(), t.mask.data_ptr(), b["ctx"].data_ptr(), t.B, t.Lq,
-                                                              self.heads, L.stream_ptr(self.device)), "ufnd_attention_bf16_varlen_masked")
-
-    def _layers(self, layers, b, t: _TextPass) -> None:
-        """The encoder layers with one LayerNorm kernel per LayerNorm, over the work buffers' rows (pass t: all of them, or the live
-        ones).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
-        M, H, eps, live = t.B * t.Lq, self.hidden, self.eps, t.live
-        for ly in layers:
-            self._self_attention(t, b, b["xb"], ly["wqkv"], ly["bqkv"])
-            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["y"], residual=b["xf"], which="out", m_live=live)
-            self._ln(b["y"], H, ly["g1"], ly["b1"], b["x1b"], b["x1f"], M, H, eps, m_live=live)
-            self._gemm(b["x1b"], ly["w1"], ly["bi"], out_bf16=b["h"], act=ACT_GELU, which="ffn1", m_live=live)
-            self._gemm(b["h"], ly["w2"], ly["b2"], out_f32=b["y"], residual=b["x1f"], which="ffn2", m_live=live)
-            self._ln(b["y"], H, ly["g2"], ly["b2n"], b["xb"], b["xf"], M, H, eps, m_live=live)
-
-    def _layers_folded(self, layers, b, t: _TextPass, final_ln: bool = True) -> None:
+    def _layers_folded(self, layers, b, attend, M: int, live=None, final_ln: bool = True) -> None:
         """The layers without a LayerNorm kernel between Linears (module docstring).  y1 / y2 are the
         PRE-LayerNorm sums of the attention and the feed-forward halves (fp32 + bf16 + row statistics).  final_ln=False leaves the
         last layer's sums in y2 and their LayerNorm to the caller."""
-        M, H, eps, live = t.B * t.Lq, self.hidden, self.eps, t.live
+        H, eps = self.hidden, self.eps
         y1, y2, st = b["y"], b["y2"], b["st"]
         rb = self.residual_dtype == "bf16"
         prev = None
@@ -480,12 +528,12 @@ class BertTextEncoder(_EncoderBase):
             st1, st2 = st[2 * i], st[2 * i + 1]
             last = i == len(layers) - 1
             if prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
-                self._self_attention(t, b, b["xb"], ly["wqkv"], ly["bqkv"])
+                attend(b["xb"], ly["wqkv"], ly["bqkv"])
                 self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else b["xf"],
                               residual_bf16=b["xb"] if rb else None, out_stats=st1, eps=eps, which="out", m_live=live)
             else:
                 stp = st[2 * i - 1]           # the previous layer's feed-forward half
-                self._self_attention(t, b, b["y2b"], ly["wqkvf"], ly["bqkvf"], a_stats=stp, colsum=ly["csqkv"])
+                attend(b["y2b"], ly["wqkvf"], ly["bqkvf"], a_stats=stp, colsum=ly["csqkv"])
                 self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else y2,
                               residual_bf16=b["y2b"] if rb else None, r_stats=stp, r_gamma=prev["g2"], r_beta=prev["b2n"], out_stats=st1,
                               eps=eps, which="out", m_live=live)
@@ -550,6 +598,8 @@ class BertTextEncoder(_EncoderBase):
 
 # =============================================================================================
 class ClipVisualEncoder(_EncoderBase):
+    LAYER_PREFIX, LAYER_NAMES = "vision_model.encoder.layers.{}.", _CLIP_LAYER
+
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, patch: int = 32,
                  image: int = 224, projection_dim: int = 512, eps: float = 1e-5, fold_ln: bool = True, residual_dtype: str = "bf16",
                  attention_dropout: float = 0.0):
@@ -584,25 +634,16 @@ class ClipVisualEncoder(_EncoderBase):
         w[V + "post_layernorm.weight"], w[V + "post_layernorm.bias"] = torch.ones(hidden), torch.zeros(hidden)
         w["visual_projection.weight"] = init((projection_dim, hidden))
 
+    def _fold_layer(self, layers, wq, w1) -> None:
+        ly = layers[-1]
+        ly["wqkvf"], ly["csqkv"], ly["bqkvf"] = self._fold(wq, ly["bqkv"], ly["g1"], ly["b1"])
+        ly["w1f"], ly["cs1"], ly["bif"] = self._fold(w1, ly["bi"], ly["g2"], ly["b2n"])
+
     def _pack(self):
         if self._packed is None:
-            w, V, layers = self._w, "vision_model.", []
-            for i in range(self.layers):
-                P = V + f"encoder.layers.{i}."
-                layers.append({
-                    "wqkv": _bf16(torch.cat([w[P + f"self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)),
-                    "bqkv": torch.cat([w[P + f"self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous(),
-                    "wo": _bf16(w[P + "self_attn.out_proj.weight"]), "bo": w[P + "self_attn.out_proj.bias"],
-                    "g1": w[P + "layer_norm1.weight"], "b1": w[P + "layer_norm1.bias"],
-                    "w1": _bf16(w[P + "mlp.fc1.weight"]), "bi": w[P + "mlp.fc1.bias"],
-                    "w2": _bf16(w[P + "mlp.fc2.weight"]), "b2": w[P + "mlp.fc2.bias"],
-                    "g2": w[P + "layer_norm2.weight"], "b2n": w[P + "layer_norm2.bias"]})
-                ly = layers[-1]
-                wq = torch.cat([w[P + f"self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-                ly["wqkvf"], ly["csqkv"], ly["bqkvf"] = self._fold(wq, ly["bqkv"], ly["g1"], ly["b1"])
-                ly["w1f"], ly["cs1"], ly["bif"] = self._fold(w[P + "mlp.fc1.weight"], ly["bi"], ly["g2"], ly["b2n"])
-            self._packed = {"layers": layers,
-                            "wpatch": _bf16(w[V + "embeddings.patch_embedding.weight"].reshape(self.hidden, -1)),
+            w = self._w
+            self._packed = {"layers": self._pack_layers(self._fold_layer),
+                            "wpatch": _bf16(w["vision_model.embeddings.patch_embedding.weight"].reshape(self.hidden, -1)),
                             "wproj": _bf16(w["visual_projection.weight"])}
         return self._packed
 
@@ -672,23 +713,18 @@ class ClipVisualEncoder(_EncoderBase):
             r["hb"] = b["hc"]
         return r
 
-    def _blocks_folded(self, layers, b, N, cls_tail: bool = False) -> None:
+    def _blocks_folded(self, layers, b, attend, tail=None) -> None:
         """Pre-LN blocks without LayerNorm kernels: hb is the bf16 rounding of the residual stream xf, st* the row statistics its
-        LayerNorms need (module docstring).  cls_tail: the last layer's out-projection, FFN1 and FFN2 over the class-token rows only."""
-        eps, stA, st, T = self.eps, b["st0"], b["st"], self.n_patches + 1
+        LayerNorms need (module docstring).  tail (_cls_rows): the last layer's out-projection, FFN1 and FFN2 over the class-token rows only."""
+        eps, stA, st = self.eps, b["st0"], b["st"]
         rb = self.residual_dtype == "bf16"       # the stream is hb itself, updated in place (a tile reads exactly what it rewrites)
-        fuse = self.fuse_qkv_attention and T <= 64
         for i, ly in enumerate(layers):
             st1, st2 = st[2 * i], st[2 * i + 1]
             last = i == len(layers) - 1
-            if fuse:
-                self._qkv_attn(b["hb"], ly["wqkvf"], ly["bqkvf"], None, b["ctx"], N, T, self.heads, a_stats=stA, colsum=ly["csqkv"], eps=eps)
-            else:
-                self._gemm_ln(b["hb"], ly["wqkvf"], ly["bqkvf"], out_bf16=b["qkv"], a_stats=stA, colsum=ly["csqkv"], eps=eps, which="qkv")
-                self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
+            attend(b["hb"], ly["wqkvf"], ly["bqkvf"], a_stats=stA, colsum=ly["csqkv"])
             r = b
-            if last and cls_tail:      # (K / V and the attention needed every row; nothing past them does)
-                r = self._cls_rows(b, N)
+            if last and tail is not None:      # (K / V and the attention needed every row; nothing past them does)
+                r = tail()
                 st1, st2 = r["st1"], r["st2"]
             self._gemm_ln(r["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else r["xf"], out_bf16=r["hb"], residual=None if rb else r["xf"],
                           residual_bf16=r["hb"] if rb else None, out_stats=st1, eps=eps, which="out")
@@ -696,25 +732,6 @@ class ClipVisualEncoder(_EncoderBase):
             self._gemm_ln(r["m"], ly["w2"], ly["b2"], out_f32=r["xf"] if (last or not rb) else None, out_bf16=r["hb"],
                           residual=None if rb else r["xf"], residual_bf16=r["hb"] if rb else None, out_stats=st2, eps=eps, which="ffn2")
             stA = st2
-
-    def _blocks(self, layers, b, N, cls_tail: bool = False) -> None:
-        """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf.  cls_tail: as _blocks_folded."""
-        H, T, eps = self.hidden, self.n_patches + 1, self.eps
-        M = N * T
-        fuse = self.fuse_qkv_attention and T <= 64
-        for i, ly in enumerate(layers):
-            self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps)
-            if fuse:
-                self._qkv_attn(b["hb"], ly["wqkv"], ly["bqkv"], None, b["ctx"], N, T, self.heads)
-            else:
-                self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv")
-                self._attn(b["qkv"], None, b["ctx"], N, T, self.heads)
-            r = self._cls_rows(b, N) if (cls_tail and i == len(layers) - 1) else b
-            xf = r["xf"]
-            self._gemm(r["ctx"], ly["wo"], ly["bo"], out_f32=xf, residual=xf, which="out")
-            self._ln(xf, xf.stride(0), ly["g2"], ly["b2n"], r["hb"], None, xf.shape[0], H, eps)
-            self._gemm(r["hb"], ly["w1"], ly["bi"], out_bf16=r["m"], act=ACT_QUICK_GELU, which="ffn1")
-            self._gemm(r["m"], ly["w2"], ly["b2"], out_f32=xf, residual=xf, which="ffn2")
 
     def _pooled_projection(self, p, b, N) -> None:
         """post-LN on the CLS rows (row stride T*H), bias-free projection into b["e"]."""
@@ -732,9 +749,18 @@ class ClipVisualEncoder(_EncoderBase):
         fr = L.f32c(frames5.to(self.device)).view(B * Fr, 3, self.image, self.image)
         p, b = self._pack(), self._workbufs(B, Fr)
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
-        self._embed(fr, p, b, B * Fr)
-        (self._blocks_folded if "st0" in b else self._blocks)(layers, b, B * Fr, cls_tail)
-        self._pooled_projection(p, b, B * Fr)
+        N, T = B * Fr, self.n_patches + 1
+        self._embed(fr, p, b, N)
+        if self.fuse_qkv_attention and T <= 64:
+            attend = lambda A, W, bias, **fold: self._qkv_attn(A, W, bias, None, b["ctx"], N, T, self.heads, eps=self.eps, **fold)
+        else:
+            attend = self._two_launch(b, "ufnd_attention_bf16", operands=(None,), B=N, Lq=T)      # (no key mask: every patch is a key)
+        tail = (lambda: self._cls_rows(b, N)) if cls_tail else None
+        if "st0" in b:
+            self._blocks_folded(layers, b, attend, tail)
+        else:
+            self._pre_ln_blocks(layers, b, attend, N * T, ACT_QUICK_GELU, tail=tail)
+        self._pooled_projection(p, b, N)
         return b["e"], b
 
     @torch.no_grad()

@@ -30,10 +30,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .encoders import ACT_QUICK_GELU, ClipVisualEncoder, _bf16, _EncoderBase
+from .encoders import _CLIP_LAYER, ACT_QUICK_GELU, ClipVisualEncoder, _bf16, _EncoderBase, _live_ptr
 
 
 class ClipTextEncoder(_EncoderBase):
+    LAYER_PREFIX, LAYER_NAMES = "text_model.encoder.layers.{}.", _CLIP_LAYER
+
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 512, intermediate_size: int = 2048, projection_dim: int = 512,
                  num_hidden_layers: int = 12, num_attention_heads: int = 8, max_position_embeddings: int = 77, hidden_act: str = "quick_gelu",
                  layer_norm_eps: float = 1e-5, attention_dropout: float = 0.0, pad_token_id: int = 1, bos_token_id: int = 49406,
@@ -67,19 +69,8 @@ class ClipTextEncoder(_EncoderBase):
 
     def _pack(self):
         if self._packed is None:
-            w, T, layers = self._w, "text_model.", []
-            for i in range(self.layers):
-                P = T + f"encoder.layers.{i}."
-                # HF scales q by 1 / sqrt(64) before Q K^T; the attention kernel scales the scores: the same product
-                layers.append({
-                    "wqkv": _bf16(torch.cat([w[P + f"self_attn.{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)),
-                    "bqkv": torch.cat([w[P + f"self_attn.{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0).contiguous(),
-                    "wo": _bf16(w[P + "self_attn.out_proj.weight"]), "bo": w[P + "self_attn.out_proj.bias"],
-                    "g1": w[P + "layer_norm1.weight"], "b1": w[P + "layer_norm1.bias"],
-                    "w1": _bf16(w[P + "mlp.fc1.weight"]), "bi": w[P + "mlp.fc1.bias"],
-                    "w2": _bf16(w[P + "mlp.fc2.weight"]), "b2": w[P + "mlp.fc2.bias"],
-                    "g2": w[P + "layer_norm2.weight"], "b2n": w[P + "layer_norm2.bias"]})
-            self._packed = {"layers": layers, "wproj": _bf16(w["text_projection.weight"])}
+            # (HF scales q by 1 / sqrt(64) before Q K^T; the attention kernel scales the scores: the same product)
+            self._packed = {"layers": self._pack_layers(), "wproj": _bf16(self._w["text_projection.weight"])}
         return self._packed
 
     def _workbufs(self, B: int, Lq: int) -> dict:
@@ -94,25 +85,6 @@ class ClipTextEncoder(_EncoderBase):
                                # ufnd_clip_text_pack: the pooled positions, cu_seqlens (B + 1; cu[B] = the live row count), row -> (b, pos)
                                "e": torch.zeros(B, **i32), "cu": torch.zeros(B + 1, **i32), "row_src": torch.zeros(M, **i32)}
         return self._bufs[key]
-
-    def _blocks(self, layers, b, B: int, Lq: int, mask: torch.Tensor, packed: bool) -> None:
-        """Pre-LN blocks with one LayerNorm kernel per LayerNorm, on the fp32 residual stream xf (the shape of ClipVisualEncoder._blocks)
-        around the causal attention; packed: over the live rows, their count on the device."""
-        M, H, eps, s = B * Lq, self.hidden, self.eps, L.stream_ptr(self.device)
-        live = b["cu"].data_ptr() + 4 * B if packed else None
-        for ly in layers:
-            self._ln(b["xf"], H, ly["g1"], ly["b1"], b["hb"], None, M, H, eps, m_live=live)
-            self._gemm(b["hb"], ly["wqkv"], ly["bqkv"], out_bf16=b["qkv"], which="qkv", m_live=live)
-            if packed:
-                L.check(L.lib().ufnd_attention_bf16_causal_varlen(b["qkv"].data_ptr(), b["cu"].data_ptr(), mask.data_ptr(), b["ctx"].data_ptr(), B, Lq,
-                                                                  self.heads, s), "ufnd_attention_bf16_causal_varlen")
-            else:
-                L.check(L.lib().ufnd_attention_bf16_causal(b["qkv"].data_ptr(), mask.data_ptr(), b["ctx"].data_ptr(), B, Lq, self.heads, s),
-                        "ufnd_attention_bf16_causal")
-            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["xf"], residual=b["xf"], which="out", m_live=live)
-            self._ln(b["xf"], H, ly["g2"], ly["b2n"], b["hb"], None, M, H, eps, m_live=live)
-            self._gemm(b["hb"], ly["w1"], ly["bi"], out_bf16=b["m"], act=ACT_QUICK_GELU, which="ffn1", m_live=live)
-            self._gemm(b["m"], ly["w2"], ly["b2"], out_f32=b["xf"], residual=b["xf"], which="ffn2", m_live=live)
 
     def _run(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True) -> dict:
         """One pass over a (B, L) batch: pooled positions, embeddings, the first n_layers layers (all by default; 0: none) and, with pool,
@@ -129,17 +101,22 @@ class ClipTextEncoder(_EncoderBase):
         mask = attention_mask.to(dev, torch.int32).contiguous()
         p, b, w, lib = self._pack(), self._workbufs(B, Lq), self._w, L.lib()
         M, H, s, T = B * Lq, self.hidden, L.stream_ptr(dev), "text_model."
+        live = _live_ptr(b["cu"]) if packed else None      # packed: every launch runs over the live rows, their count on the device
         L.check(lib.ufnd_clip_text_pack(ids.data_ptr(), B, Lq, self.eos_token_id, b["e"].data_ptr(), b["cu"].data_ptr(), b["row_src"].data_ptr(), s),
                 "ufnd_clip_text_pack")
         tables = (w[T + "embeddings.token_embedding.weight"].data_ptr(), w[T + "embeddings.position_embedding.weight"].data_ptr())
         if packed:
-            L.check(lib.ufnd_clip_text_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), b["cu"].data_ptr() + 4 * B, *tables, b["xb"].data_ptr(),
+            L.check(lib.ufnd_clip_text_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, *tables, b["xb"].data_ptr(),
                                                   b["xf"].data_ptr(), M, Lq, H, self.vocab, self.max_position, s), "ufnd_clip_text_embed_live")
         else:
             L.check(lib.ufnd_clip_text_embed(ids.data_ptr(), *tables, b["xb"].data_ptr(), b["xf"].data_ptr(), B, Lq, H, self.vocab, self.max_position, s),
                     "ufnd_clip_text_embed")
         layers = p["layers"] if n_layers is None else p["layers"][:max(0, int(n_layers))]
-        self._blocks(layers, b, B, Lq, mask, packed)
+        if packed:
+            attend = self._two_launch(b, "ufnd_attention_bf16_causal_varlen", operands=(b["cu"], mask), B=B, Lq=Lq, live=live)
+        else:
+            attend = self._two_launch(b, "ufnd_attention_bf16_causal", operands=(mask,), B=B, Lq=Lq)
+        self._pre_ln_blocks(layers, b, attend, M, ACT_QUICK_GELU, live=live)
         if pool:
             L.check(lib.ufnd_clip_text_pool(b["xf"].data_ptr(), b["e"].data_ptr(), b["cu"].data_ptr() if packed else None,
                                             w[T + "final_layer_norm.weight"].data_ptr(), w[T + "final_layer_norm.bias"].data_ptr(), b["pooled"].data_ptr(),
@@ -164,7 +141,7 @@ class ClipTextEncoder(_EncoderBase):
         if n_layers is None:
             w, T = self._w, "text_model."
             self._ln(b["xf"], self.hidden, w[T + "final_layer_norm.weight"], w[T + "final_layer_norm.bias"], None, b["lh"], B * Lq, self.hidden, self.eps,
-                     m_live=b["cu"].data_ptr() + 4 * B if packed else None)
+                     m_live=_live_ptr(b["cu"]) if packed else None)
             src = b["lh"]
         if not packed:
             return src.view(B, Lq, self.hidden).clone()
