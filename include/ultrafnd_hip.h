@@ -427,6 +427,20 @@ int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, 
  *   ufnd_qkv_attention_bf16_packed ufnd_qkv_attention_bf16 with sample b's rows at cu_seqlens[b] .. cu_seqlens[b+1] (key_mask (B, 128))
  *   ufnd_qkv_attention_bf16_bins   ..._packed with one workgroup per bin of ufnd_text_pack_bins (up to four samples) and head pair;
  *                                  the grid keeps B x heads / 2, workgroups of bins past *nbins exit at entry; bit-identical ctx
+ *   ufnd_text_pack_tiles           ufnd_text_pack (L <= 128, B <= UFND_TEXT_TILE_MAX_B) + sample tiles: whole samples placed back to back in
+ *                                  256-row tiles by first-fit-decreasing on n_b (ties: ascending b; at most UFND_TEXT_TILE_SAMPLES samples per
+ *                                  tile, which can only bind where samples of fewer than 16 rows meet), a function of the n_b alone;
+ *                                  samples with n_b = 0 take no rows.  tiles ((B + 1) / 2, UFND_TEXT_TILE_INTS), tile t:
+ *                                  [0] samples, [1] live rows, [2] units, [3] 0; [4 + 2 j], [5 + 2 j]: sample j's {cu[b], (b << 16) | (r0 << 8)
+ *                                  | n_b}, r0 = the tile row of its row 0 (samples in placement order, r0 ascending, n_b descending);
+ *                                  [UFND_TEXT_TILE_UNIT0 + u]: attention unit u = j | (q << 8), queries 32 q .. of sample j, sample-major;
+ *                                  [UFND_TEXT_TILE_ROWMAP + r]: the global row of tile row r (rows past the live ones: the tile's first
+ *                                  row); [UFND_TEXT_TILE_KBIAS + r]: the float key bias of tile row r, 0 where mask keeps the token,
+ *                                  -3e38 otherwise (holes, rows past the live ones); *ntiles = the tile count.  bins, nbins (both or
+ *                                  neither): ufnd_text_pack_bins' table as well, from the same launch
+ *   ufnd_qkv_attention_bf16_tiles  ufnd_qkv_attention_bf16_packed with one workgroup per tile of ufnd_text_pack_tiles and HEAD (a
+ *                                  256 x 192 x H tile [q_h | k_h | v_h], any head count); the grid is cap_tiles x heads, workgroups of
+ *                                  tiles past *ntiles exit at entry; the key mask is the table's; bit-identical ctx
  *   ufnd_attention_bf16_varlen_masked  ufnd_attention_bf16 per sample over the packed fused-QKV rows: sample b's rows are
  *                                  cu_seqlens[b] .. cu_seqlens[b+1] (at most max_len of them), key_mask (B, max_len) indexed by position
  *                                  (NULL: every key valid); ctx rows are packed like qkv's
@@ -455,6 +469,17 @@ int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* b
                                  const ufnd_gemm_ln* ln, void* stream);
 int ufnd_attention_bf16_varlen_masked(const void* qkv, const int32_t* cu_seqlens, const int32_t* key_mask, void* ctx, int B, int max_len,
                                       int heads, void* stream);
+#define UFND_TEXT_TILE_MAX_B 512
+#define UFND_TEXT_TILE_SAMPLES 16
+#define UFND_TEXT_TILE_UNITS 24
+#define UFND_TEXT_TILE_UNIT0 36
+#define UFND_TEXT_TILE_ROWMAP 64
+#define UFND_TEXT_TILE_KBIAS 320
+#define UFND_TEXT_TILE_INTS 576
+int ufnd_text_pack_tiles(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, int32_t* tiles, int32_t* ntiles,
+                         int32_t* bins, int32_t* nbins, void* stream);
+int ufnd_qkv_attention_bf16_tiles(const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles, const int32_t* ntiles, void* ctx,
+                                  int cap_tiles, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream);
 
 /* CLIPAttention of one layer in ONE launch, for samples of T <= 64 rows (ViT-B/32 at 224^2: T = 50): ufnd_qkv_attention_bf16's fusion
  * with one workgroup per (256 / T whole samples, head) -- a 256 x 192 x H tile [q_h | k_h | v_h] whose row tiles start every

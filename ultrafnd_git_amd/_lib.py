@@ -182,11 +182,13 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_masked_meanpool_l2": [P, P, P, I, I, I, P],
         "ufnd_text_pack": [P, I, I, P, P, P],
         "ufnd_text_pack_bins": [P, I, I, P, P, P, P, P],
+        "ufnd_text_pack_tiles": [P, I, I, P, P, P, P, P, P, P],
         "ufnd_bert_embed_live": [P] * 10 + [I, I, I, I, F, P],
         "ufnd_gemm_bf16_live": [P] * 6 + [I] * 10 + [P, P],
         "ufnd_gemm_bf16_ln_live": [P] * 6 + [I] * 9 + [C.POINTER(GemmLn), P, P],
         "ufnd_qkv_attention_bf16_packed": [P, P, P, P, P, P, I, I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_qkv_attention_bf16_bins": [P] * 8 + [I, I, I, I, I, C.POINTER(GemmLn), P],
+        "ufnd_qkv_attention_bf16_tiles": [P] * 6 + [I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_qkv_attention_bf16_vit": [P, P, P, P, I, I, I, I, I, C.POINTER(GemmLn), P],
         "ufnd_attention_bf16_varlen_masked": [P, P, P, P, I, I, I, P],
         "ufnd_layernorm_live": [P, I, P, P, P, P, I, I, F, P, P],

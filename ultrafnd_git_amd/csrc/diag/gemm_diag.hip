@@ -74,6 +74,32 @@ extern "C" int ufnd_diag_qkv_attention_stamps(const void* X, const void* Wqkv, c
   return UFND_OK;
 }
 
+// The same stamps for the sample-tile form (ufnd_qkv_attention_bf16_tiles over a table of ufnd_text_pack_tiles); 10 stamps per workgroup
+// of the cap_tiles x heads grid, workgroups past *ntiles leave theirs untouched.
+extern "C" int ufnd_diag_qkv_attention_tiles_stamps(const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles, const int32_t* ntiles,
+                                                    void* ctx, int cap_tiles, int heads, const ufnd_gemm_ln* ln, unsigned long long* stamps,
+                                                    void* stream_) {
+  UFND_REQUIRE(X && Wqkv && ctx && stamps && tiles && ntiles && cap_tiles >= 1 && heads >= 1, "diag qkv_attention_tiles: bad argument");
+  const int H = heads * 64;
+  GemmArgs a{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, cap_tiles * 256, 3 * H, H, H, H, 0, 0, 0, UFND_ACT_NONE, 0, 0, stamps};
+  if (ln && ln->a_stats) {
+    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
+    a.inv_h = 1.0f / (float)ln->width;
+    a.guard = ln->guard;
+  }
+  a.att_bins = tiles;
+  a.att_nbins = ntiles;
+  a.att_ctx = (__bf16*)ctx;
+  a.att_h = H;
+  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;
+  a.m_tiles = cap_tiles;
+  a.n_tiles = heads;
+  a.xcd_cols = 1;
+  hipLaunchKernelGGL((gemm_bf16_kernel<256, 192, 4, 2, 3, 2, 16, 0, 1, 1, 2>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 // Validation, tile choice and launch geometry of one call of the product's one-tile entries, on the host only: nothing is launched
 // and no operand is dereferenced -- the pointers only have to carry the alignment of the real ones -- so this answers on a machine
 // without a GPU (tests/test_gemm_bf16_cases.py).  The argument checks are the product entries' own (gemm_bf16_checks.hpp), the

@@ -186,20 +186,10 @@ __global__ __launch_bounds__(256) void ln_meanpool_kernel(const float* y, const 
 // every bin fills its slots from slot 0 on, samples in ascending order within a class.  This is an optimal packing (no bin
 // count is lower) and a function of the n_b alone.  Bin i is 8 ints: slot j's {cu[b] + 32 s, (b << 10) | (s << 8) | n_b} for
 // slot s of sample b, {0, -1} if empty; *nbins = the bin count (0 when every sample is all-masked).
-__global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src,
-                                                                 int32_t* bins, int32_t* nbins) {
-  __shared__ int lens[PACK_MAX_B];
+// (the slot bins, by every thread of the pack workgroup after pack_scan_rows: lens[b] = cu[b], total = cu[B])
+__device__ __forceinline__ void pack_slot_bins(const int* lens, int total, int B, int32_t* bins, int32_t* nbins) {
   __shared__ long long csum[PACK_THREADS / 64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  for (int b = wave; b < B; b += PACK_THREADS / 64) {      // a wave per sample: the largest kept position + 1
-    int last = 0;
-    for (int l = lane; l < L; l += 64) last = mask[(size_t)b * L + l] != 0 ? l + 1 : last;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
-    if (lane == 0) lens[b] = last;
-  }
-  const int total = pack_scan_rows(lens, B, L, cu, row_src);      // (rowwise.hpp: cu, row_src; lens[b] = cu[b])
-  if (!bins) return;
   const int per = (B + PACK_THREADS - 1) / PACK_THREADS, b0 = tid * per, b1 = min(b0 + per, B);      // the scan's samples of this thread
   // ranks within the slot classes: four 16-bit counters in one 64-bit scan (counts <= PACK_MAX_B < 2^16)
   auto nrows = [&](int b) { return (b + 1 < B ? lens[b + 1] : total) - lens[b]; };
@@ -264,6 +254,177 @@ __global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* 
     }
   }
   if (tid == 0) *nbins = nb;
+}
+
+__global__ __launch_bounds__(PACK_THREADS) void text_pack_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src,
+                                                                 int32_t* bins, int32_t* nbins) {
+  __shared__ int lens[PACK_MAX_B];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int b = wave; b < B; b += PACK_THREADS / 64) {      // a wave per sample: the largest kept position + 1
+    int last = 0;
+    for (int l = lane; l < L; l += 64) last = mask[(size_t)b * L + l] != 0 ? l + 1 : last;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if (lane == 0) lens[b] = last;
+  }
+  const int total = pack_scan_rows(lens, B, L, cu, row_src);      // (rowwise.hpp: cu, row_src; lens[b] = cu[b])
+  if (bins) pack_slot_bins(lens, total, B, bins, nbins);
+}
+
+// ufnd_text_pack_tiles: ufnd_text_pack + the sample tiles of ufnd_qkv_attention_bf16_tiles (the table's layout: ultrafnd_hip.h).  Whole
+// samples, back to back, in 256-row tiles by first-fit-decreasing: samples in descending n_b (ties: ascending b) each go to the first
+// tile with n_b free rows and fewer than TILE_CAP samples.  Any two samples fit one tile, so first fit leaves at most one tile with a
+// single sample: (B + 1) / 2 tiles always suffice.  The rank of a sample is counted (B <= 512: B comparisons per thread); wave 0 then
+// places the samples in rank order with the tiles' free rows and sample counts in registers -- tile 64 c + lane in element c of its
+// lanes -- one ballot per sample; the other threads then write the descriptors, the row map and the key biases, a thread per tile its
+// unit list.  bins != NULL: the slot bins as well.
+constexpr int TILE_MAX_B = UFND_TEXT_TILE_MAX_B, TILE_CAP = UFND_TEXT_TILE_SAMPLES, TILE_INTS = UFND_TEXT_TILE_INTS, TILE_MAX = TILE_MAX_B / 2;
+__global__ __launch_bounds__(PACK_THREADS) void text_pack_tiles_kernel(const int32_t* mask, int B, int L, int32_t* cu, int32_t* row_src,
+                                                                       int32_t* tiles, int32_t* ntiles, int32_t* bins, int32_t* nbins) {
+  __shared__ int lens[TILE_MAX_B], order[TILE_MAX_B], place[TILE_MAX_B];
+  __shared__ __attribute__((aligned(16))) int nb[TILE_MAX_B];      // n_b (0 past B: the rank loop reads whole groups of four)
+  __shared__ int t_rows[TILE_MAX], t_cnt[TILE_MAX], t_cu0[TILE_MAX];
+  __shared__ unsigned char t_n[TILE_MAX * TILE_CAP];
+  __shared__ unsigned long long kept[TILE_MAX_B][2];      // the mask row of sample b as bits (positions 0-63, 64-127)
+  __shared__ int nlive_s, nt_s;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (tid == 0) nlive_s = 0;
+  if (tid >= B && tid < TILE_MAX_B) nb[tid] = 0;
+  // a wave per sample, four samples' loads in flight: the mask row as two ballots, n_b = the largest kept position + 1
+  constexpr int NWV = PACK_THREADS / 64;
+  for (int b0 = wave; b0 < B; b0 += 4 * NWV) {
+    int v[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int b = b0 + NWV * j, l = lane + 64 * h;
+        v[j][h] = (b < B && l < L) ? mask[(size_t)b * L + l] : 0;
+      }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = b0 + NWV * j;
+      if (b >= B) break;
+      const unsigned long long m0 = __ballot(v[j][0] != 0), m1 = __ballot(v[j][1] != 0);
+      const int last = m1 ? 128 - __clzll((long long)m1) : (m0 ? 64 - __clzll((long long)m0) : 0);
+      if (lane == 0) {
+        lens[b] = last;
+        nb[b] = last;
+        kept[b][0] = m0;
+        kept[b][1] = m1;
+      }
+    }
+  }
+  const int total = pack_scan_rows(lens, B, L, cu, row_src);      // (rowwise.hpp: cu, row_src; lens[b] = cu[b]; barriers inside)
+  if (bins) pack_slot_bins(lens, total, B, bins, nbins);          // (ufnd_text_pack_bins' table too, where the caller keeps both current)
+  if (tid < B && nb[tid] > 0) {                 // rank in descending n_b, ties in ascending b
+    const int n = nb[tid];
+    int rank = 0;
+#pragma unroll 4
+    for (int b = 0; b < B; b += 4) {
+      const int4 v = *reinterpret_cast<const int4*>(nb + b);
+      rank += (v.x > n || (v.x == n && b < tid)) + (v.y > n || (v.y == n && b + 1 < tid)) + (v.z > n || (v.z == n && b + 2 < tid)) +
+              (v.w > n || (v.w == n && b + 3 < tid));
+    }
+    order[rank] = tid;
+    atomicAdd(&nlive_s, 1);
+  }
+  __syncthreads();
+  const int nl = nlive_s;
+  if (wave == 0) {
+    // st[c] of a lane: tile 64 c + lane's (samples << 16) | rows used; key[c]: its free rows, -1 once it holds TILE_CAP samples
+    int st[TILE_MAX / 64], key[TILE_MAX / 64];
+#pragma unroll
+    for (int c = 0; c < TILE_MAX / 64; ++c) { st[c] = 0; key[c] = 256; }
+    // up to 128 samples need at most 64 tiles, so every sample finds its tile in chunk 0: one short dependent chain per sample (ballot,
+    // first set bit, the chosen lane's update), which is what this kernel's duration is made of (about 0.1 us a sample)
+    for (int i0 = 0; nl <= 128 && i0 < nl; i0 += 64) {
+      const int vn = i0 + lane < nl ? nb[order[i0 + lane]] : 0;
+      const int cnt = min(64, nl - i0);
+      int s0 = st[0], k0 = key[0];
+      for (int j = 0; j < cnt; ++j) {
+        const int n = __builtin_amdgcn_readlane(vn, j);
+        const bool mine = lane == __ffsll((long long)__ballot(k0 >= n)) - 1;
+        if (mine) place[i0 + j] = (lane << 12) | ((s0 >> 16) << 8) | (s0 & 0xffff);
+        s0 += mine ? (1 << 16) + n : 0;
+        k0 = s0 < (TILE_CAP << 16) ? 256 - (s0 & 0xffff) : -1;
+      }
+      st[0] = s0;
+      key[0] = k0;
+    }
+    for (int i0 = 0; nl > 128 && i0 < nl; i0 += 64) {
+      const int vn = i0 + lane < nl ? nb[order[i0 + lane]] : 0;
+      const int cnt = min(64, nl - i0);
+      int pv = 0;      // lane j: where sample i0 + j went, (tile << 12) | (slot << 8) | its first tile row
+      // (no LDS traffic inside: the loop is one dependent chain per sample -- ballot, first set bit, the chosen lane's update -- and the
+      //  placements collect in pv, lane j's for sample i0 + j)
+      for (int j = 0; j < cnt; ++j) {
+        const int n = __builtin_amdgcn_readlane(vn, j);
+        bool placed = false;
+#pragma unroll
+        for (int c = 0; c < TILE_MAX / 64; ++c) {      // (the first 64 tiles take 128 samples or more: the later chunks are rarely reached)
+          const unsigned long long m = placed ? 0ull : __ballot(key[c] >= n);
+          if (m == 0) continue;
+          const int l = __ffsll((long long)m) - 1;
+          const int was = __builtin_amdgcn_readlane(st[c], l);
+          pv = lane == j ? ((64 * c + l) << 12) | ((was >> 16) << 8) | (was & 0xffff) : pv;
+          st[c] += lane == l ? (1 << 16) + n : 0;
+          key[c] = st[c] < (TILE_CAP << 16) ? 256 - (st[c] & 0xffff) : -1;
+          placed = true;
+        }
+      }
+      if (i0 + lane < nl) place[i0 + lane] = pv;
+    }
+    int nt = 0;
+#pragma unroll
+    for (int c = 0; c < TILE_MAX / 64; ++c) {
+      nt += __popcll(__ballot(st[c] != 0));
+      t_rows[64 * c + lane] = st[c] & 0xffff;
+      t_cnt[64 * c + lane] = st[c] >> 16;
+    }
+    if (lane == 0) {
+      nt_s = nt;
+      *ntiles = nt;
+    }
+  }
+  __syncthreads();
+  const int nt = nt_s;
+  if (tid < nl) {      // the descriptor of the sample of rank tid
+    const int b = order[tid], p = place[tid], t = p >> 12, slot = (p >> 8) & 15, r0 = p & 255;
+    tiles[(size_t)t * TILE_INTS + 4 + 2 * slot] = lens[b];
+    tiles[(size_t)t * TILE_INTS + 5 + 2 * slot] = (b << 16) | (r0 << 8) | nb[b];
+    t_n[t * TILE_CAP + slot] = (unsigned char)nb[b];
+    if (slot == 0) t_cu0[t] = lens[b];
+  }
+  for (int i = wave; i < nl; i += NWV) {      // a wave per sample: row map and key biases of its rows
+    const int b = order[i], n = nb[b], p = place[i], r0 = p & 255, row0 = lens[b];
+    int32_t* td = tiles + (size_t)(p >> 12) * TILE_INTS;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k >= n) continue;
+      td[UFND_TEXT_TILE_ROWMAP + r0 + k] = row0 + k;
+      td[UFND_TEXT_TILE_KBIAS + r0 + k] = __float_as_int(((kept[b][h] >> lane) & 1) ? 0.0f : -3.0e38f);
+    }
+  }
+  __syncthreads();      // (t_n, t_cu0: written by the samples' threads, read by the tiles')
+  if (tid < nt) {      // header and unit list of tile tid
+    int32_t* td = tiles + (size_t)tid * TILE_INTS;
+    const int cnt = t_cnt[tid];
+    int u = 0;
+    for (int j = 0; j < cnt; ++j)
+      for (int q = 0; q < (t_n[tid * TILE_CAP + j] + 31) >> 5; ++q) td[UFND_TEXT_TILE_UNIT0 + u++] = j | (q << 8);
+    td[0] = cnt;
+    td[1] = t_rows[tid];
+    td[2] = u;
+    td[3] = 0;
+  }
+  for (int idx = tid; idx < nt * 256; idx += PACK_THREADS) {      // rows past a tile's live ones: its first row, masked
+    const int t = idx >> 8, r = idx & 255;
+    if (r < t_rows[t]) continue;
+    tiles[(size_t)t * TILE_INTS + UFND_TEXT_TILE_ROWMAP + r] = t_cu0[t];
+    tiles[(size_t)t * TILE_INTS + UFND_TEXT_TILE_KBIAS + r] = __float_as_int(-3.0e38f);
+  }
 }
 
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* x, int H) {
@@ -475,6 +636,16 @@ extern "C" int ufnd_text_pack_bins(const int32_t* mask, int B, int L, int32_t* c
   UFND_REQUIRE(mask && cu_seqlens && row_src && bins && nbins, "text_pack_bins: null argument");
   UFND_REQUIRE(B >= 1 && B <= PACK_MAX_B && L >= 1 && L <= 128, "text_pack_bins: B=%d L=%d (B <= %d, L <= 128)", B, L, PACK_MAX_B);
   hipLaunchKernelGGL(text_pack_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src, bins, nbins);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+extern "C" int ufnd_text_pack_tiles(const int32_t* mask, int B, int L, int32_t* cu_seqlens, int32_t* row_src, int32_t* tiles,
+                                    int32_t* ntiles, int32_t* bins, int32_t* nbins, void* stream_) {
+  UFND_REQUIRE(mask && cu_seqlens && row_src && tiles && ntiles && !bins == !nbins, "text_pack_tiles: null argument");
+  UFND_REQUIRE(B >= 1 && B <= TILE_MAX_B && L >= 1 && L <= 128, "text_pack_tiles: B=%d L=%d (B <= %d, L <= 128)", B, L, TILE_MAX_B);
+  hipLaunchKernelGGL(text_pack_tiles_kernel, dim3(1), dim3(PACK_THREADS), 0, (hipStream_t)stream_, mask, B, L, cu_seqlens, row_src, tiles, ntiles,
+                     bins, nbins);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

@@ -184,6 +184,37 @@ extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, con
   return UFND_OK;
 }
 
+// The packed form over sample tiles (ufnd_text_pack_tiles): one workgroup per (256-row tile of whole samples, head)
+extern "C" int ufnd_qkv_attention_bf16_tiles(const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles, const int32_t* ntiles,
+                                             void* ctx, int cap_tiles, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
+  UFND_REQUIRE(X && Wqkv && ctx && tiles && ntiles, "qkv_attention_tiles: null operand");
+  UFND_REQUIRE(heads >= 1 && heads <= 64 && cap_tiles >= 1 && cap_tiles <= (UFND_TEXT_TILE_MAX_B + 1) / 2, "qkv_attention_tiles: cap_tiles=%d heads=%d",
+               cap_tiles, heads);
+  const int H = heads * 64;
+  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
+               "qkv_attention_tiles: strides must be multiples of 8 and pointers 16-B aligned");
+  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "qkv_attention_tiles: bias alignment");
+  GemmArgs a{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, cap_tiles * 256, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
+  if (ln && ln->a_stats) {
+    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "qkv_attention_tiles: colsum / a_stats alignment");
+    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "qkv_attention_tiles: a_parts=%d width=%d", ln->a_parts, ln->width);
+    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
+    a.inv_h = 1.0f / (float)ln->width;
+    a.guard = ln->guard;
+  }
+  a.att_bins = tiles;
+  a.att_nbins = ntiles;
+  a.att_ctx = (__bf16*)ctx;
+  a.att_h = H;
+  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
+  a.m_tiles = cap_tiles;
+  a.n_tiles = heads;
+  a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a tile share its A rows in one L2
+  hipLaunchKernelGGL((gemm_bf16_kernel<256, 192, 4, 2, 3, 2, 16, 0, 0, 1, 2>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 // The same for samples of T <= 64 rows (CLIPAttention of a ViT layer: T = 50): one workgroup per (256 / T whole samples, head).
 extern "C" int ufnd_qkv_attention_bf16_vit(const void* X, const void* Wqkv, const float* bqkv, void* ctx, int N, int T, int heads, int ldx,
                                            int ldw, const ufnd_gemm_ln* ln, void* stream_) {

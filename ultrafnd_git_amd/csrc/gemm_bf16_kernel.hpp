@@ -89,6 +89,7 @@ struct GemmArgs {
   // tiles past *att_nbins exit at entry (see the ATT notes at the kernel)
   const int32_t* att_bins;
   const int* att_nbins;
+  // ATT = 2 (sample tiles): att_bins is the tile table of ufnd_text_pack_tiles (UFND_TEXT_TILE_INTS ints per tile), att_nbins its tile count
   // ATT kernels, short-sample geometry (BM = 256): every sample is att_t <= 64 contiguous rows, a row tile holds 256 / att_t whole samples
   int att_t;
 };
@@ -164,6 +165,14 @@ template <int V> struct IntC { static constexpr int value = V; };
 //          attention_kernel<64, 2>'s per-query operation sequence on them: one 64-key block per sample, key k >= T reads the
 //          sample's row T - 1 and gets the -inf bias (exactly that kernel's clamped load and bias), units of (sample, 32 queries)
 //          dealt round-robin to the eight waves.  ctx is the only global output, bit-identical to the two launches.
+// ATT = 2, sample tiles (BM = 256, BN = 192, MI = 16, LNX = 1; the packed text pass, samples of 1 to 128 rows): the short-sample geometry over a
+//          tile table (ufnd_text_pack_tiles): tile tm holds up to 16 whole samples back to back from tile row 0 on, placed by first-fit-decreasing
+//          (36 to 40 tiles x 12 heads per 128 bench samples against 534 to 588 slot-bin workgroups: two rounds instead of three).  A-operand rows
+//          and row statistics go through the table's row map, rows past the tile's live ones re-read its first row and store nothing.  Attention
+//          is attention.hip's at L = 128 per sample: two 64-key blocks from the sample's row 0, key k >= n reads the sample's row n - 1 and gets
+//          NEG_MASK, a live key's bias is its tile row's word of the table (the key-mask row, holes included), copied per unit into a 128-word row
+//          of the wave's own so that block reads stay aligned.  Units of (sample, 32 queries) in the table's order (descending length: the
+//          two-block units lead), round-robin over the eight waves.  Bit-identical live ctx rows, like the other fused forms.
 // waves per SIMD the register allocation must leave room for: tiles whose LDS footprint lets two workgroups share a CU
 // (<= 80 KiB) only do so if two workgroups' waves also fit the register file (8-wave blocks: 128 registers per lane)
 constexpr int gemm_waves_per_simd(int BM, int BN, int WM, int WN, int STA, int STB, int MI, int LNX, int ATT) {
@@ -176,8 +185,11 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(ge
 void gemm_bf16_kernel(const GemmArgs a) {
   static_assert(!BWD || (!LNX && !ATT && !ABL && !DBG), "backward forms are plain kernels");
   static_assert(MI == 16 || MI == 32, "MFMA shape");
-  static_assert(!ATT || (((BM == 128 && BN == 384) || (BM == 256 && BN == 192)) && MI == 16 && WM * WN == 8 && LNX == 1), "fused attention tile");
-  constexpr bool VIT = ATT && BM == 256;         // the short-sample geometry: one head per workgroup, 256 / att_t samples per row tile
+  static_assert(!ATT || (((BM == 128 && BN == 384 && ATT == 1) || (BM == 256 && BN == 192)) && MI == 16 && WM * WN == 8 && LNX == 1 && ATT <= 2),
+                "fused attention tile");
+  constexpr bool VIT = ATT == 1 && BM == 256;    // the short-sample geometry: one head per workgroup, 256 / att_t samples per row tile
+  constexpr bool TIL = ATT == 2;                 // sample tiles: one head per workgroup, whole variable-length samples packed into 256 rows
+  constexpr bool ONEH = VIT || TIL;              // tile columns [q_h | k_h | v_h] of one head, three 256-row LDS images
   using acc_t = typename std::conditional<MI == 16, f32x4, f32x16>::type;
   constexpr int AR = MI * MI / 64;               // accumulator registers per MFMA tile
   constexpr int KQ = MI == 16 ? 1 : 2;           // MFMA k-steps per k-half (32 k)
@@ -200,7 +212,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
   constexpr int ATT_OFF = (CBYTES + 1023) & ~1023;
   // (short samples: three 32-KiB images, 256 tile rows x 128 B, + one row of 64 key biases)
   constexpr int ATT_IMG = BM * 128;
-  constexpr int ATT_END = ATT ? ATT_OFF + (VIT ? 3 * ATT_IMG + 256 : 6 * ATT_IMG + 2048) : 0;
+  // (sample tiles: the three images + one key bias per tile row + a 128-key bias row per wave)
+  constexpr int ATT_END = ATT ? ATT_OFF + (TIL ? 3 * ATT_IMG + 1024 + 8 * 512 : VIT ? 3 * ATT_IMG + 256 : 6 * ATT_IMG + 2048) : 0;
   constexpr int STAT_OFF0 = (RING > CBYTES) ? RING : CBYTES;
   constexpr int STAT_OFF = STAT_OFF0 > ATT_END ? STAT_OFF0 : ATT_END;  // LNX: {mean, rstd} per tile row, behind the ring (and the images)
   constexpr int SMEM = STAT_OFF + (LNX ? BM * 8 + 64 : 0);      // (+ 16 floats: the waves' guard maxima)
@@ -267,12 +280,19 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // (r & 31) < scnt_j (clamped to the slot's last live row); an empty slot (scnt_j = 0) re-reads slot 0's first row.  Descriptor
   // of slot j (ufnd_text_pack_bins): {cu[b] + 32 s, (b << 10) | (s << 8) | n_b}, meta -1 = empty.
   int srow[4] = {0, 0, 0, 0}, scnt[4] = {0, 0, 0, 0}, smeta[4] = {-1, -1, -1, -1};
-  const bool slots = ATT && !VIT && a.att_bins != nullptr;
+  const bool slots = ATT == 1 && !VIT && a.att_bins != nullptr;
   // short samples: the tile holds S whole samples (S T rows) from row tm S T on
   const int vit_s = VIT ? BM / a.att_t : 0, vit_st = vit_s * a.att_t;
+  // sample tiles: this tile's part of the table (ufnd_text_pack_tiles: header, sample descriptors, unit list, row map, key biases);
+  // its first til_rows tile rows are live, the others re-read the tile's first row and store nothing
+  const int32_t* til = TIL ? a.att_bins + (size_t)tm * UFND_TEXT_TILE_INTS : nullptr;
+  int til_rows = 0;
+  if constexpr (TIL) til_rows = __builtin_amdgcn_readfirstlane(til[1]);
   if constexpr (VIT) {
     arow0 = tm * vit_st;
     alen = mlive - arow0 < vit_st ? mlive - arow0 : vit_st;      // (rows past it: the next tile's, or clamped; never stored, not in the guard)
+  } else if constexpr (TIL) {
+    // (arow0, alen and mlive decide nothing: every row goes through tile_row / tile_row_live and the sample descriptors)
   } else if constexpr (ATT) {
     if (slots) {
       const int32_t* bd = a.att_bins + (size_t)tm * 8;
@@ -296,6 +316,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
   }
   // global row of tile row tr (the A operand and its statistics), and whether that row is stored (and joins the fold guard)
   auto tile_row = [&](int tr) {
+    if constexpr (TIL) return (int)til[UFND_TEXT_TILE_ROWMAP + tr];
     if (slots) {
       const int j = tr >> 5, q = tr & 31;
       const int r0 = j == 0 ? srow[0] : j == 1 ? srow[1] : j == 2 ? srow[2] : srow[3];
@@ -306,6 +327,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
     return gr < mlive ? gr : mlive - 1;
   };
   auto tile_row_live = [&](int tr) {
+    if constexpr (TIL) return tr < til_rows;
     if (slots) {
       const int j = tr >> 5;
       return (tr & 31) < (j == 0 ? scnt[0] : j == 1 ? scnt[1] : j == 2 ? scnt[2] : scnt[3]);
@@ -364,7 +386,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const int c = ppos ^ ((r >> 1) & 7);
       int gr = n0 + r;
       gr = gr < a.N ? gr : a.N - 1;
-      if constexpr (VIT) gr = (r >> 6) * a.att_h + tn * 64 + (r & 63);       // [q | k | v] rows of this head
+      if constexpr (ONEH) gr = (r >> 6) * a.att_h + tn * 64 + (r & 63);      // [q | k | v] rows of this head
       else if constexpr (ATT) gr = (r >> 7) * a.att_h + tn * 128 + (r & 127);     // [q | k | v] rows of this head pair
       dma16(a.W + (size_t)gr * a.ldw + k0 + c * 8, buf + p * 1024);
     }
@@ -403,8 +425,12 @@ void gemm_bf16_kernel(const GemmArgs a) {
         }
     }
   }
+  float til_kb = 0.0f;      // sample tiles: tile row threadIdx.x's key bias (requested now, used after the K loop, like att_mk below)
+  if constexpr (TIL) {
+    if (threadIdx.x < BM) til_kb = __int_as_float(til[UFND_TEXT_TILE_KBIAS + threadIdx.x]);
+  }
   int att_mk = 1;
-  if constexpr (ATT && !VIT) {      // this sample's key mask: requested now, used after the K loop (older than every DMA piece)
+  if constexpr (ATT == 1 && !VIT) {      // this sample's key mask: requested now, used after the K loop (older than every DMA piece)
     if (slots) {            // slot bins: thread t holds key t % 128 of slot t / 128's sample (wave-uniform slot)
       const int j = (int)threadIdx.x >> 7, k = threadIdx.x & 127;
       const int mt = j == 0 ? smeta[0] : j == 1 ? smeta[1] : j == 2 ? smeta[2] : smeta[3];
@@ -609,7 +635,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
 #pragma unroll
   for (int j = 0; j < NT; ++j) { bj[j] = 0.f; csj[j] = 0.f; }
   // global column of tile column c
-  auto gcol = [&](int c) { return VIT ? (c >> 6) * a.att_h + tn * 64 + (c & 63) : ATT ? (c >> 7) * a.att_h + tn * 128 + (c & 127) : n0 + c; };
+  auto gcol = [&](int c) { return ONEH ? (c >> 6) * a.att_h + tn * 64 + (c & 63) : ATT ? (c >> 7) * a.att_h + tn * 128 + (c & 127) : n0 + c; };
   if (a.bias) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) bj[j] = a.bias[gcol(wn * TN + j * MI + fr)];
@@ -782,7 +808,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
           bf16x8 o;
 #pragma unroll
           for (int q = 0; q < 8; ++q) o[q] = (__bf16)v[q];
-          const int sw = img >= (VIT ? 2 : 4) ? (ch ^ (((trow >> 1) & 3) << 1)) : (ch ^ ((trow >> 1) & 7));      // V images: the transposed-read swizzle
+          const int sw = img >= (ONEH ? 2 : 4) ? (ch ^ (((trow >> 1) & 3) << 1)) : (ch ^ ((trow >> 1) & 7));      // V images: the transposed-read swizzle
           *reinterpret_cast<bf16x8*>(smem + ATT_OFF + img * ATT_IMG + trow * 128 + (sw << 4)) = o;
           continue;
         }
@@ -902,6 +928,116 @@ void gemm_bf16_kernel(const GemmArgs a) {
         const int q = q0 + qt * 16 + f16;
         if (q >= T) continue;
         __bf16* dst = a.att_ctx + (size_t)(arow0 + r0 + q) * a.att_h + tn * 64 + 4 * g4;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
+          *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
+        }
+      }
+    }
+  } else if constexpr (TIL) {
+    // ---- attention of the tile's samples for this head on the LDS images: attention.hip's per-query operation sequence at L = 128 (two
+    // 64-key blocks counted from the sample's row 0).  Key k of a sample of n rows whose row 0 is tile row r0 is tile row r0 + min(k, n - 1):
+    // a key at or past n reads a finite row of the sample and gets NEG_MASK, what a padding key gets in the padded batch; a live key's bias
+    // is its tile row's word (the sample's key-mask row, holes included).  A wave copies the 128 bias words of its unit's sample into a row
+    // of its own, so that the block reads are 16-B aligned wherever the sample starts.  Units of (sample, 32 queries) come from the tile's
+    // unit list -- samples in descending length, so the two-block units lead -- and are dealt round-robin to the eight waves.
+    constexpr float NEG_MASK = -3.0e38f;
+    float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 3 * ATT_IMG);
+    float* wbias = kbias + BM + wave * 128;
+    if (threadIdx.x < BM) kbias[threadIdx.x] = til_kb;
+    __syncthreads();
+    const int g4 = lane >> 4, f16 = lane & 15;
+    const char* qimg = smem + ATT_OFF;
+    const char* kimg = smem + ATT_OFF + ATT_IMG;
+    const char* vimg = smem + ATT_OFF + 2 * ATT_IMG;
+    int nunits = __builtin_amdgcn_readfirstlane(til[2]);
+    nunits = nunits < UFND_TEXT_TILE_UNITS ? nunits : UFND_TEXT_TILE_UNITS;
+    constexpr int KB = 64, KT = KB / 16;
+    for (int u = wave; u < nunits; u += NW) {
+      const int unit = __builtin_amdgcn_readfirstlane(til[UFND_TEXT_TILE_UNIT0 + u]);
+      const int sj = unit & (UFND_TEXT_TILE_SAMPLES - 1), q0 = ((unit >> 8) & 3) * 32;
+      const int grow0 = __builtin_amdgcn_readfirstlane(til[4 + 2 * sj]);       // the sample's global row 0
+      const int meta = __builtin_amdgcn_readfirstlane(til[5 + 2 * sj]);
+      const int r0 = (meta >> 8) & 255;                                        // the tile row of its row 0
+      int n = meta & 255;
+      n = n < 1 ? 1 : (n < BM - r0 ? n : BM - r0);                              // (a table the pack kernel wrote never needs it: no row leaves the images)
+      n = n < 128 ? n : 128;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        wbias[k] = k < n ? kbias[r0 + k] : NEG_MASK;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      bf16x8 qf[2][2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const int q = q0 + qt * 16 + f16, qc = q < n ? q : n - 1;
+        qf[qt][0] = lds_frag(qimg, r0 + qc, g4);
+        qf[qt][1] = lds_frag(qimg, r0 + qc, g4 + 4);
+      }
+      f32x4 o[4][2];
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+#pragma unroll
+      for (int kb0 = 0; kb0 < 128; kb0 += KB) {
+        if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
+        f32x4 sc[KT][2];
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int kt = 0; kt < KT; ++kt) {
+            const int key = kb0 + kt * 16 + f16;
+            const bf16x8 kf = lds_frag(kimg, r0 + (key < n ? key : n - 1), g4 + 4 * kk);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
+          }
+        const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
+        bf16x8 pf[KT / 2][2];
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          const float alpha = online_softmax_block<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
+          if (!__all(alpha == 1.0f)) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
+          }
+        }
+#pragma unroll
+        for (int ksd = 0; ksd < KT / 2; ++ksd) {
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            const int qq = f16 >> 2, pp = f16 & 3;
+            const int k0 = kb0 + 32 * ksd + 4 * g4 + qq, k1 = k0 + 16;
+            const int key0 = r0 + (k0 < n ? k0 : n - 1), key1 = r0 + (k1 < n ? k1 : n - 1);      // tile rows
+            const int ch = 2 * dt + (pp >> 1);
+            const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+            const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+            const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
+            const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
+            union { s16x4 s2[2]; bf16x8 v; } uu;
+            uu.s2[0] = t0;
+            uu.s2[1] = t1;
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uu.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        float l = l_run[qt];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        const int q = q0 + qt * 16 + f16;
+        if (q >= n) continue;
+        __bf16* dst = a.att_ctx + (size_t)(grow0 + q) * a.att_h + tn * 64 + 4 * g4;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};

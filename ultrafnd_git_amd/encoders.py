@@ -95,6 +95,38 @@ def text_slot_bin_count(n_rows) -> int:
     return len(text_slot_bins(n_rows))
 
 
+TEXT_TILE_ROWS, TEXT_TILE_SAMPLES, TEXT_TILE_MAX_B = 256, 16, 512      # ufnd_text_pack_tiles (UFND_TEXT_TILE_*)
+TEXT_TILE_INTS, TEXT_TILE_UNIT0, TEXT_TILE_ROWMAP, TEXT_TILE_KBIAS = 576, 36, 64, 320
+
+
+def text_tiles(n_rows) -> list:
+    """The sample tiles ufnd_text_pack_tiles computes on the device, from the per-sample row counts n_b (n_b <= 128): a list of tiles,
+    each a list of (b, r0) -- sample b's rows 0 .. n_b - 1 are tile rows r0 .. r0 + n_b - 1 -- in placement order.  First-fit-decreasing:
+    samples in descending n_b (ties: ascending b) go to the first tile with n_b of its 256 rows free and fewer than 16 samples; samples
+    with n_b = 0 take no rows.  The 16-sample cap can only bind where samples of fewer than 16 rows meet (17 samples of 16 rows or more
+    do not fit 256 rows): for longer samples this IS first-fit-decreasing."""
+    tiles, used = [], []
+    for b in sorted((b for b, n in enumerate(n_rows) if int(n) > 0), key=lambda b: (-int(n_rows[b]), b)):
+        n = int(n_rows[b])
+        if n > 128:
+            raise ValueError(f"text_tiles: n_b={n} (samples of at most 128 rows)")
+        for t, u in enumerate(used):
+            if u + n <= TEXT_TILE_ROWS and len(tiles[t]) < TEXT_TILE_SAMPLES:
+                break
+        else:
+            t = len(tiles)
+            tiles.append([])
+            used.append(0)
+        tiles[t].append((b, used[t]))
+        used[t] += n
+    return tiles
+
+
+def text_tile_count(n_rows) -> int:
+    """len(text_tiles(n_rows)): the workgroup rows the fused Q/K/V + attention runs over sample tiles."""
+    return len(text_tiles(n_rows))
+
+
 class _EncoderBase(nn.Module):
     """Weight store with third-party key names + lazily packed bf16 operands + per-shape buffers."""
 
@@ -300,10 +332,12 @@ class _EncoderBase(nn.Module):
         L.check(L.lib().ufnd_layernorm(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), L.ptr(out_bf16),
                                        L.ptr(out_f32), M, H, eps, L.stream_ptr(x.device)), "ufnd_layernorm")
 
-    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None, nbins=None):
+    def _qkv_attn(self, A, W, bias, mask_i32, ctx, B, Lq, heads, a_stats=None, colsum=None, eps=1e-5, cu=None, bins=None, nbins=None, tiles=None,
+                  ntiles=None):
         """Fused Q/K/V projection (+ folded LayerNorm of A) + attention, one launch per layer.  cu: sample b's rows are
         cu[b] .. cu[b+1] of the packed pass (None: the padded batch); bins, nbins (ufnd_text_pack_bins, with cu): one workgroup per
-        bin of up to four samples and head pair (None: one per sample and head pair).  Samples of Lq <= 64 rows (the ViT's 50) take
+        bin of up to four samples and head pair (None: one per sample and head pair); tiles, ntiles (ufnd_text_pack_tiles, instead of
+        cu and bins; the key mask is the table's): one workgroup per 256-row tile of whole samples and head.  Samples of Lq <= 64 rows (the ViT's 50) take
         the short-sample geometry, ufnd_qkv_attention_bf16_vit: 256 // Lq whole samples and one head per workgroup, no key mask."""
         ln = None
         if a_stats is not None:
@@ -316,6 +350,12 @@ class _EncoderBase(nn.Module):
             L.check(L.lib().ufnd_qkv_attention_bf16_vit(A.data_ptr(), W.data_ptr(), L.ptr(bias), ctx.data_ptr(), B, Lq, heads, A.stride(0),
                                                         W.stride(0), ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
                     "ufnd_qkv_attention_bf16_vit")
+            return
+        if tiles is not None:
+            L.check(L.lib().ufnd_qkv_attention_bf16_tiles(A.data_ptr(), W.data_ptr(), L.ptr(bias), tiles.data_ptr(), ntiles.data_ptr(), ctx.data_ptr(),
+                                                          tiles.shape[0], heads, A.stride(0), W.stride(0),
+                                                          ctypes.byref(ln) if ln is not None else None, L.stream_ptr(A.device)),
+                    "ufnd_qkv_attention_bf16_tiles")
             return
         L.check(L.lib().ufnd_qkv_attention_bf16_bins(A.data_ptr(), W.data_ptr(), L.ptr(bias), L.ptr(mask_i32), L.ptr(cu), L.ptr(bins),
                                                      L.ptr(nbins), ctx.data_ptr(), B, Lq, heads, A.stride(0), W.stride(0),
@@ -402,6 +442,13 @@ class BertTextEncoder(_EncoderBase):
         # 128-token samples: Q/K/V projection + attention of a layer as ONE launch (ufnd_qkv_attention_bf16); bit-identical
         # to the two-launch form, which every other length uses
         self.fuse_qkv_attention = True
+        # the packed pass's fused launch over sample tiles (ufnd_text_pack_tiles: whole samples in 256-row tiles, one head per workgroup);
+        # False: over slot bins (ufnd_text_pack_bins), which batches of more than TEXT_TILE_MAX_B samples use either way.  Bit-identical.
+        self.text_sample_tiles = True
+        # ... from this many slot-bin workgroups (B x heads / 2) on.  The tile form wins by cutting the launch's rounds and its CU-time;
+        # a batch whose slot bins get a compute unit each (256: one round either way) stays on them -- measured at B = 32, 12 heads:
+        # the tile workgroup is the longer one, the step 1 % slower (profiles/text_tile_pack_summary.md).
+        self.text_tile_min_grid = 257
         self.layers, self.inter, self.vocab, self.eps = layers, intermediate, vocab_size, eps
         self.max_position = max_position
         w, init = self._w, self._seeded_init()
@@ -452,6 +499,9 @@ class BertTextEncoder(_EncoderBase):
                                "cu": torch.zeros(B + 1, dtype=torch.int32, device=dev), "row_src": torch.zeros(M, dtype=torch.int32, device=dev),
                                # (L <= 128: ufnd_text_pack_bins) the fused Q/K/V + attention's slot bins and their count
                                "bins": torch.zeros(B, 8, dtype=torch.int32, device=dev), "nbins": torch.zeros(1, dtype=torch.int32, device=dev)}
+            if Lq <= 128 and B <= TEXT_TILE_MAX_B:      # (ufnd_text_pack_tiles) its sample tiles and their count
+                self._bufs[key].update({"tiles": torch.zeros((B + 1) // 2, TEXT_TILE_INTS, dtype=torch.int32, device=dev),
+                                        "ntiles": torch.zeros(1, dtype=torch.int32, device=dev)})
             p1 = self._fold_parts(M)
             if p1:
                 # one statistics buffer per folded LayerNorm of the pass (st[2i]: layer i's attention half, st[2i+1]: its
@@ -478,7 +528,12 @@ class BertTextEncoder(_EncoderBase):
         fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0      # a layer's Q/K/V projection + attention as one launch
         cu = b["cu"] if packed else None                 # packed rows: sample b's are cu[b] .. cu[b+1] ...
         live = _live_ptr(cu) if packed else None         # ... and cu[B], their count, stays on the device: the pack kernel writes it
-        if packed and fuse:      # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
+        tiled = packed and fuse and self.text_sample_tiles and "tiles" in b and B * (self.heads // 2) >= self.text_tile_min_grid
+        if tiled:                # (+ the sample tiles: the fused Q/K/V + attention runs one workgroup per 256-row tile of whole samples and head;
+                                 #  the slot bins stay current too: either launch form may follow this pack)
+            L.check(L.lib().ufnd_text_pack_tiles(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["tiles"].data_ptr(),
+                                                 b["ntiles"].data_ptr(), b["bins"].data_ptr(), b["nbins"].data_ptr(), s), "ufnd_text_pack_tiles")
+        elif packed and fuse:    # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
             L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
                                                 b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
         elif packed:
@@ -493,7 +548,10 @@ class BertTextEncoder(_EncoderBase):
             L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
         ln_pool = pool and packed and "st" in b
-        if fuse:
+        if tiled:
+            attend = lambda A, W, bias, **fold: self._qkv_attn(A, W, bias, None, b["ctx"], B, Lq, self.heads, eps=self.eps, tiles=b["tiles"],
+                                                               ntiles=b["ntiles"], **fold)
+        elif fuse:
             bins, nbins = (b["bins"], b["nbins"]) if packed else (None, None)
             attend = lambda A, W, bias, **fold: self._qkv_attn(A, W, bias, mask, b["ctx"], B, Lq, self.heads, eps=self.eps, cu=cu, bins=bins,
                                                                nbins=nbins, **fold)
