@@ -1025,6 +1025,54 @@ int ufnd_semantic_head(const float* text, const float* image, const float* wt, c
  * logit_scale; conflict[b] = 1 - (similarity[b] + 1) / 2 in [0, 1].  text / image (B, D) fp32, D % 4 == 0. */
 int ufnd_clip_similarity(const float* text, const float* image, float* similarity, float* conflict, int B, int D, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * The RoBERTa emotion classifier (RobertaForSequenceClassification: post-LN BERT layers, learned positions offset by the pad id,
+ * a tanh head on the <s> row) and AffectiveForensics (src/models/affective_forensics.py).  Frozen, forward only.  The layers are
+ * the text pass's entries above; csrc/affective.hip holds the rest.
+ *
+ *   ufnd_roberta_pack     ids (B, L) int64, mask (B, L) int32 -> pos_ids (B L) int32 by HF's create_position_ids_from_input_ids:
+ *                         cumsum(ids != pad) * (ids != pad) + pad, taken over the ids, not the mask; valid (B, optional): 1 where the
+ *                         mask keeps a token; and, when cu_seqlens / row_src are given (both or neither), exactly what
+ *                         ufnd_text_pack writes.  One workgroup, a wave per sample: a fixed-order wave prefix scan across 64-token
+ *                         chunks, no atomics.  Without cu_seqlens it is the position-id launch that goes with ufnd_text_pack_bins /
+ *                         ufnd_text_pack_tiles (L == 128) and with the padded pass.  B <= 16384.
+ *   ufnd_roberta_embed[_live]  LayerNorm(word[id] + position[pos_ids] + token_type[0]) -> x_bf16 and / or x_f32.  Ids are clamped
+ *                         into [0, vocab), position ids into [0, max_position); L <= max_position - pad_token_id - 1 is required
+ *                         (what the rule can produce then fits the table).  _live: over the first *m_live of `capacity` packed
+ *                         rows (row r is token row_src[r]).  H in {256, 512, 768, 1024}.
+ *   ufnd_gather_class_rows  the class (<s>) row of each sample -- stream row cu_seqlens[b], or b L when cu_seqlens is NULL -- of up to
+ *                         four row-indexed buffers into compact B-row ones: ctx and res_bf16 (bf16, H columns), res_f32 (fp32, H
+ *                         columns), stats (fp32, stat_floats per row: a folded LayerNorm's partials).  A source and its destination
+ *                         go together; absent pairs are NULL.  A sample without rows (cu[b] == cu[b+1]) gets zeros.  `capacity`:
+ *                         the sources' row count (a row index outside it is treated as "no rows").  This is what the last layer of
+ *                         a sequence classifier runs over past its attention.
+ *   ufnd_emotion_head     all fp32: z = x Wd^T + bd on the exact skinny GEMM (ufnd_linear_f32's kernels; workspace: B H floats), then
+ *                         one launch, one workgroup per sample, fixed-order reductions: logits = tanh(z) Wo^T + bo (B, C), class_probs
+ *                         = softmax(logits), the group sums f, a, j by `group` (C int32: -1 none, 0 fear, 1 anger, 2 joy, 4 + m for a
+ *                         label in several groups, m = bit 0 fear | bit 1 anger | bit 2 joy), probs (B, 3) = [f, a, j] / (f + a + j +
+ *                         1e-9), text_intensity = sigmoid(2.5 (f + a - 0.5 j)), intensity = clip(0.6 text_intensity + 0.4 arousal, 0,
+ *                         1) (arousal NULL: 0.5), valence = clip(0.5 + 0.5 (j - 0.5 (f + a)), 0, 1).  text_valid (B int32, optional): 0
+ *                         marks a sample without text -- its features count as zero (z = bd) and its probs are 0.  probs,
+ *                         text_intensity, intensity, valence: all four (with group) or none.  x (B, H), Wd (H, H), Wo (C, H);
+ *                         H % 32 == 0, H <= 1024, C <= 32, B <= 65535.
+ *   ufnd_audio_arousal    waves (B, T) fp32, lengths (B int32, NULL: T; clamped to [0, T]) -> clip(sigmoid(5 mean(x^2)), 0, 1): the
+ *                         reference's RMS-energy branch.  One workgroup per clip, a fixed-order tree, a clip is computed as if
+ *                         alone; length 0 gives sigmoid(0). */
+int ufnd_roberta_pack(const int64_t* ids, const int32_t* mask, int B, int L, int pad_token_id, int32_t* cu_seqlens, int32_t* row_src,
+                      int32_t* pos_ids, int32_t* valid, void* stream);
+int ufnd_roberta_embed(const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                       const float* beta, void* x_bf16, float* x_f32, int B, int L, int H, int vocab, int max_position, int pad_token_id, float eps,
+                       void* stream);
+int ufnd_roberta_embed_live(const int64_t* ids, const int32_t* pos_ids, const int32_t* row_src, const int* m_live, const float* word, const float* pos,
+                            const float* type0, const float* gamma, const float* beta, void* x_bf16, float* x_f32, int capacity, int L, int H,
+                            int vocab, int max_position, int pad_token_id, float eps, void* stream);
+int ufnd_gather_class_rows(const int32_t* cu_seqlens, const void* ctx, void* ctx_out, const void* res_bf16, void* res_bf16_out, const float* res_f32,
+                           float* res_f32_out, const float* stats, float* stats_out, int B, int L, int H, int stat_floats, int capacity, void* stream);
+int ufnd_emotion_head(const float* x, const float* wd, const float* bd, const float* wo, const float* bo, const int32_t* group,
+                      const int32_t* text_valid, const float* arousal, float* workspace, float* logits, float* class_probs, float* probs,
+                      float* text_intensity, float* intensity, float* valence, int B, int H, int C, void* stream);
+int ufnd_audio_arousal(const float* waves, const int32_t* lengths, float* arousal, int B, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

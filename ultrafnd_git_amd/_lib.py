@@ -250,6 +250,14 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_semantic_head": [P] * 10 + [I, I, I, P],
         "ufnd_clip_similarity": [P, P, P, P, I, I, P],
     })
+    sigs.update({      # the RoBERTa emotion classifier and AffectiveForensics (csrc/affective.hip)
+        "ufnd_roberta_pack": [P, P, I, I, I, P, P, P, P, P],
+        "ufnd_roberta_embed": [P] * 9 + [I] * 6 + [F, P],
+        "ufnd_roberta_embed_live": [P] * 11 + [I] * 6 + [F, P],
+        "ufnd_gather_class_rows": [P] * 9 + [I] * 5 + [P],
+        "ufnd_emotion_head": [P] * 15 + [I, I, I, P],
+        "ufnd_audio_arousal": [P, P, P, I, I, P],
+    })
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

@@ -379,17 +379,24 @@ class _EncoderBase(nn.Module):
             L.check(fn(*call), entry)
         return attend
 
-    def _post_ln_layers(self, layers, b, attend, M: int, live=None) -> None:
-        """Post-LN layers (BERT, wav2vec2) with one LayerNorm kernel per LayerNorm, over the work buffers' M rows (live: the first
-        *live of them).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"])."""
+    def _post_ln_layers(self, layers, b, attend, M: int, live=None, tail=None) -> None:
+        """Post-LN layers (BERT, wav2vec2, RoBERTa) with one LayerNorm kernel per LayerNorm, over the work buffers' M rows (live: the
+        first *live of them).  Leaves last_hidden_state in b["xf"] (and its bf16 rounding in b["xb"]).
+        tail(res_bf16, res_f32, stats): past its attention the last layer runs over the class rows only -- the call gathers them from
+        b["ctx"] and the given residual-side buffers into compact buffers of the same names (the copies: "rb", "rf", "rst") and
+        returns those; last_hidden_state's class rows are then in the returned buffers' "xf"."""
         H, eps = self.hidden, self.eps
-        for ly in layers:
+        for i, ly in enumerate(layers):
             attend(b["xb"], ly["wqkv"], ly["bqkv"])
-            self._gemm(b["ctx"], ly["wo"], ly["bo"], out_f32=b["y"], residual=b["xf"], which="out", m_live=live)
-            self._ln(b["y"], H, ly["g1"], ly["b1"], b["x1b"], b["x1f"], M, H, eps, m_live=live)
-            self._gemm(b["x1b"], ly["w1"], ly["bi"], out_bf16=b["h"], act=ACT_GELU, which="ffn1", m_live=live)
-            self._gemm(b["h"], ly["w2"], ly["b2"], out_f32=b["y"], residual=b["x1f"], which="ffn2", m_live=live)
-            self._ln(b["y"], H, ly["g2"], ly["b2n"], b["xb"], b["xf"], M, H, eps, m_live=live)
+            r, res = b, b["xf"]
+            if tail is not None and i == len(layers) - 1:
+                r = tail(None, b["xf"], None)
+                res, M, live = r["rf"], r["y"].shape[0], None
+            self._gemm(r["ctx"], ly["wo"], ly["bo"], out_f32=r["y"], residual=res, which="out", m_live=live)
+            self._ln(r["y"], H, ly["g1"], ly["b1"], r["x1b"], r["x1f"], M, H, eps, m_live=live)
+            self._gemm(r["x1b"], ly["w1"], ly["bi"], out_bf16=r["h"], act=ACT_GELU, which="ffn1", m_live=live)
+            self._gemm(r["h"], ly["w2"], ly["b2"], out_f32=r["y"], residual=r["x1f"], which="ffn2", m_live=live)
+            self._ln(r["y"], H, ly["g2"], ly["b2n"], r["xb"], r["xf"], M, H, eps, m_live=live)
 
     def _pre_ln_blocks(self, layers, b, attend, M: int, act: int, live=None, tail=None) -> None:
         """Pre-LN blocks (both CLIP towers) with one LayerNorm kernel per LayerNorm, on the fp32 residual stream b["xf"] (M rows; live:
@@ -511,41 +518,30 @@ class BertTextEncoder(_EncoderBase):
                 self._guard_buf(dev)
         return self._bufs[key]
 
-    def _pass(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True) -> dict:
+    def _check_length(self, Lq: int) -> None:
+        if Lq > self.max_position:
+            raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
+
+    def _pass(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True,
+              tail=None) -> dict:
         """One pass over a (B, L) batch: embeddings, the first n_layers layers (all by default) and, with pool, the pooled features.
         packed: over the rows ufnd_text_pack keeps, their count on the device (forward's unpad paragraph); otherwise over all B L rows.
         Returns the work buffers: last_hidden_state in "xf" (packed: its live rows), the features in "feat".  A packed, folded pass that
-        pools never writes "xf": one kernel normalises the last layer's sums and pools them (ufnd_ln_masked_meanpool_l2_live)."""
+        pools never writes "xf": one kernel normalises the last layer's sums and pools them (ufnd_ln_masked_meanpool_l2_live).
+        tail(b, cu, B, L): the layer loops' tail for this pass (a sequence classifier's class rows; never with pool)."""
         self._require_hip()
         dev = self.device
         B, Lq = input_ids.shape
-        if Lq > self.max_position:
-            raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
+        self._check_length(Lq)
         ids = input_ids.to(dev, torch.int64).contiguous()
         mask = attention_mask.to(dev, torch.int32).contiguous()
-        p, b, w = self._pack(), self._workbufs(B, Lq), self._w
-        M, H, s = B * Lq, self.hidden, L.stream_ptr(dev)
+        p, b = self._pack(), self._workbufs(B, Lq)
+        M = B * Lq
         fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0      # a layer's Q/K/V projection + attention as one launch
         cu = b["cu"] if packed else None                 # packed rows: sample b's are cu[b] .. cu[b+1] ...
         live = _live_ptr(cu) if packed else None         # ... and cu[B], their count, stays on the device: the pack kernel writes it
         tiled = packed and fuse and self.text_sample_tiles and "tiles" in b and B * (self.heads // 2) >= self.text_tile_min_grid
-        if tiled:                # (+ the sample tiles: the fused Q/K/V + attention runs one workgroup per 256-row tile of whole samples and head;
-                                 #  the slot bins stay current too: either launch form may follow this pack)
-            L.check(L.lib().ufnd_text_pack_tiles(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["tiles"].data_ptr(),
-                                                 b["ntiles"].data_ptr(), b["bins"].data_ptr(), b["nbins"].data_ptr(), s), "ufnd_text_pack_tiles")
-        elif packed and fuse:    # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
-            L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
-                                                b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
-        elif packed:
-            L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
-        tables = [w["embeddings." + n].data_ptr() for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight",
-                                                            "LayerNorm.weight", "LayerNorm.bias")]
-        outs = (b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr())      # (bf16 stream, folded: nothing reads the fp32 copy)
-        if packed:
-            L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, *tables, *outs, M, Lq, H, self.vocab, self.eps, s),
-                    "ufnd_bert_embed_live")
-        else:
-            L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
+        self._pack_embed(ids, mask, b, B, Lq, packed, fuse, tiled, live)
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
         ln_pool = pool and packed and "st" in b
         if tiled:
@@ -559,10 +555,12 @@ class BertTextEncoder(_EncoderBase):
             attend = self._two_launch(b, "ufnd_attention_bf16_varlen_masked", operands=(cu, mask), B=B, Lq=Lq, live=live)
         else:
             attend = self._two_launch(b, "ufnd_attention_bf16", operands=(mask,), B=B, Lq=Lq)
+        tail = None if tail is None else tail(b, cu, B, Lq)
         if "st" in b:
-            self._layers_folded(layers, b, attend, M, live, final_ln=not ln_pool)
+            self._layers_folded(layers, b, attend, M, live, final_ln=not ln_pool, tail=tail)
         else:
-            self._post_ln_layers(layers, b, attend, M, live)
+            self._post_ln_layers(layers, b, attend, M, live, tail=tail)
+        H, s = self.hidden, L.stream_ptr(dev)
         if ln_pool:       # bit-identical to the final LayerNorm into "xf" + the pooling below
             L.check(L.lib().ufnd_ln_masked_meanpool_l2_live(b["y2"].data_ptr(), layers[-1]["g2"].data_ptr(), layers[-1]["b2n"].data_ptr(), self.eps,
                                                             mask.data_ptr(), b["cu"].data_ptr(), b["feat"].data_ptr(), B, Lq, H, s),
@@ -574,35 +572,73 @@ class BertTextEncoder(_EncoderBase):
             L.check(L.lib().ufnd_masked_meanpool_l2(b["xf"].data_ptr(), mask.data_ptr(), b["feat"].data_ptr(), B, Lq, H, s), "ufnd_masked_meanpool_l2")
         return b
 
-    def _layers_folded(self, layers, b, attend, M: int, live=None, final_ln: bool = True) -> None:
+    def _pack_rows(self, mask, b, B: int, Lq: int, fuse: bool, tiled: bool) -> None:
+        """The packed pass's tables from the mask: cu_seqlens, row_src and, for the fused Q/K/V + attention, its slot bins / sample tiles."""
+        s = L.stream_ptr(self.device)
+        cu = b["cu"]
+        if tiled:                # (+ the sample tiles: the fused Q/K/V + attention runs one workgroup per 256-row tile of whole samples and head;
+                                 #  the slot bins stay current too: either launch form may follow this pack)
+            L.check(L.lib().ufnd_text_pack_tiles(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["tiles"].data_ptr(),
+                                                 b["ntiles"].data_ptr(), b["bins"].data_ptr(), b["nbins"].data_ptr(), s), "ufnd_text_pack_tiles")
+        elif fuse:               # (+ the slot bins: the fused Q/K/V + attention runs one workgroup per bin of up to four samples)
+            L.check(L.lib().ufnd_text_pack_bins(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), b["bins"].data_ptr(),
+                                                b["nbins"].data_ptr(), s), "ufnd_text_pack_bins")
+        else:
+            L.check(L.lib().ufnd_text_pack(mask.data_ptr(), B, Lq, cu.data_ptr(), b["row_src"].data_ptr(), s), "ufnd_text_pack")
+
+    def _embed_outs(self, b) -> tuple:
+        """The embedding kernel's (bf16, fp32) outputs: with the folded bf16 stream nothing reads the fp32 copy."""
+        return b["xb"].data_ptr(), None if ("st" in b and self.residual_dtype == "bf16") else b["xf"].data_ptr()
+
+    def _pack_embed(self, ids, mask, b, B: int, Lq: int, packed: bool, fuse: bool, tiled: bool, live) -> None:
+        """The pass's first launches: the packed pass's tables, then the embeddings into the residual stream."""
+        w, H, s = self._w, self.hidden, L.stream_ptr(self.device)
+        if packed:
+            self._pack_rows(mask, b, B, Lq, fuse, tiled)
+        tables = [w["embeddings." + n].data_ptr() for n in ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight",
+                                                            "LayerNorm.weight", "LayerNorm.bias")]
+        outs = self._embed_outs(b)
+        if packed:
+            L.check(L.lib().ufnd_bert_embed_live(ids.data_ptr(), b["row_src"].data_ptr(), live, *tables, *outs, B * Lq, Lq, H, self.vocab, self.eps, s),
+                    "ufnd_bert_embed_live")
+        else:
+            L.check(L.lib().ufnd_bert_embed(ids.data_ptr(), *tables, *outs, B, Lq, H, self.vocab, self.eps, s), "ufnd_bert_embed")
+
+    def _layers_folded(self, layers, b, attend, M: int, live=None, final_ln: bool = True, tail=None) -> None:
         """The layers without a LayerNorm kernel between Linears (module docstring).  y1 / y2 are the
         PRE-LayerNorm sums of the attention and the feed-forward halves (fp32 + bf16 + row statistics).  final_ln=False leaves the
-        last layer's sums in y2 and their LayerNorm to the caller."""
+        last layer's sums in y2 and their LayerNorm to the caller.  tail: as _post_ln_layers' (the compact buffers carry "st1" / "st2",
+        the last layer's statistics over the class rows alone: statistics are indexed by row number)."""
         H, eps = self.hidden, self.eps
-        y1, y2, st = b["y"], b["y2"], b["st"]
+        st = b["st"]
         rb = self.residual_dtype == "bf16"
-        prev = None
+        prev, r = None, b
         for i, ly in enumerate(layers):
             st1, st2 = st[2 * i], st[2 * i + 1]
             last = i == len(layers) - 1
             if prev is None:      # layer 0 consumes the embeddings' own (materialised) LayerNorm
                 attend(b["xb"], ly["wqkv"], ly["bqkv"])
-                self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else b["xf"],
-                              residual_bf16=b["xb"] if rb else None, out_stats=st1, eps=eps, which="out", m_live=live)
+                res_b, res_f, stp, rg, rbeta = b["xb"], b["xf"], None, None, None
             else:
                 stp = st[2 * i - 1]           # the previous layer's feed-forward half
                 attend(b["y2b"], ly["wqkvf"], ly["bqkvf"], a_stats=stp, colsum=ly["csqkv"])
-                self._gemm_ln(b["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=b["y1b"], residual=None if rb else y2,
-                              residual_bf16=b["y2b"] if rb else None, r_stats=stp, r_gamma=prev["g2"], r_beta=prev["b2n"], out_stats=st1,
-                              eps=eps, which="out", m_live=live)
-            self._gemm_ln(b["y1b"], ly["w1f"], ly["bif"], out_bf16=b["h"], act=ACT_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1",
+                res_b, res_f, rg, rbeta = b["y2b"], b["y2"], prev["g2"], prev["b2n"]
+            if last and tail is not None:      # (K / V and the attention needed every row; nothing past them does)
+                r = tail(res_b if rb else None, None if rb else res_f, stp)
+                res_b, res_f, stp = r["rb"], r["rf"], (r["rst"] if stp is not None else None)
+                st1, st2, M, live = r["st1"], r["st2"], r["y"].shape[0], None
+            y1, y2 = r["y"], r["y2"]
+            self._gemm_ln(r["ctx"], ly["wo"], ly["bo"], out_f32=None if rb else y1, out_bf16=r["y1b"], residual=None if rb else res_f,
+                          residual_bf16=res_b if rb else None, r_stats=stp, r_gamma=rg, r_beta=rbeta, out_stats=st1,
+                          eps=eps, which="out", m_live=live)
+            self._gemm_ln(r["y1b"], ly["w1f"], ly["bif"], out_bf16=r["h"], act=ACT_GELU, a_stats=st1, colsum=ly["cs1"], eps=eps, which="ffn1",
                           m_live=live)
-            self._gemm_ln(b["h"], ly["w2"], ly["b2"], out_f32=y2 if (last or not rb) else None, out_bf16=b["y2b"], residual=None if rb else y1,
-                          residual_bf16=b["y1b"] if rb else None, r_stats=st1, r_gamma=ly["g1"], r_beta=ly["b1"], out_stats=st2, eps=eps,
+            self._gemm_ln(r["h"], ly["w2"], ly["b2"], out_f32=y2 if (last or not rb) else None, out_bf16=r["y2b"], residual=None if rb else y1,
+                          residual_bf16=r["y1b"] if rb else None, r_stats=st1, r_gamma=ly["g1"], r_beta=ly["b1"], out_stats=st2, eps=eps,
                           which="ffn2", m_live=live)      # (the last layer's fp32 sums feed the final, materialised LayerNorm)
             prev = ly
         if final_ln:
-            self._ln(y2, H, prev["g2"], prev["b2n"], None, b["xf"], M, H, eps, m_live=live)       # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
+            self._ln(r["y2"], H, prev["g2"], prev["b2n"], None, r["xf"], M, H, eps, m_live=live)       # last_hidden_state is materialised once (fp32 only: no GEMM reads it)
 
     @torch.no_grad()
     def last_hidden_state(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, n_layers: Optional[int] = None) -> torch.Tensor:
