@@ -100,10 +100,11 @@ def test_ctx_is_bit_identical_to_gemm_plus_attention(N, heads, with_ln, with_bia
 
 @gpu
 @pytest.mark.parametrize("with_ln", [False, True])
-@pytest.mark.parametrize("N,T", [(9, 64), (13, 37), (20, 17), (300, 1)])
+@pytest.mark.parametrize("N,T", [(9, 64), (13, 37), (11, 31), (20, 17), (300, 1)])
 def test_other_sample_lengths(N, T, with_ln):
     """T = 64 (no key past T: the softmax's short path, four samples fill the tile exactly), T = 37 and 17 (6 and 15 samples per tile,
-    256 is no multiple of them), T = 1 (256 one-row samples per tile)."""
+    256 is no multiple of them), T = 31 (one query block whose second 16-query tile lacks its last query), T = 1 (256 one-row samples
+    per tile)."""
     _check_op(N, T, 12, with_ln, True)
 
 

@@ -22,8 +22,9 @@
 // Philox evaluation.  DESIGN.md section 4.
 #include "attn_softmax.hpp"
 
-// No implicit contraction: the fused projection + attention kernel (gemm_bf16_kernel.hpp, ATT) repeats this kernel's
-// arithmetic operation for operation and must produce the same bits; fused multiply-adds are spelled out.
+// No implicit contraction: the block body (scores, softmax, rescale, P V, normalise and store) is attn_softmax.hpp's, the very
+// code the fused projection + attention kernel (gemm_bf16_kernel.hpp, ATT) runs, so the two produce the same bits by construction;
+// fused multiply-adds are spelled out.
 #pragma clang fp contract(off)
 
 namespace {
@@ -38,10 +39,6 @@ namespace {
 #endif
 constexpr int QB = 128;          // queries per workgroup (4 waves x 32; the short-sequence form: 2 waves, 64 queries)
 constexpr float NEG_MASK = -3.0e38f;
-
-__device__ __forceinline__ bf16x8 k_frag(const char* tile, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-}
 
 // KB = keys per block (64: 162 registers, three workgroups per CU; 128: 240 registers, two -- measured at L = 512, B = 128 in round 3:
 // 218 against 211 us per launch, not selected)
@@ -102,11 +99,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
   }
 
   f32x4 o[4][2];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+  float m_run[2], l_run[2];
+  attn_init(o, m_run, l_run);
 
   // K / V blocks travel HBM -> registers -> LDS.  With several blocks to walk (the 4-wave form: L > 64) the loads of block k+1
   // are issued right after block k has been written to LDS and stay in flight under block k's S^T / softmax / PV work (the
@@ -154,23 +148,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
     if constexpr (KB == 64) {
       if (masked_block_is_noop(kbias, lane, m_run)) continue;      // (attn_softmax.hpp; both barriers of the iteration are behind us / at the loop top)
     }
-    // ---- S^T = K Q^T : 8 key tiles x 2 query tiles
+    // ---- S^T = K Q^T on the staged block (key k of the block is LDS row k)
     constexpr int KT = KB / 16;
+    const auto key_row = [](int k) { return k; };
     f32x4 s[KT][2];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) s[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        const bf16x8 kf = k_frag(ks, kt * 16 + fr, g + 4 * kk);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], s[kt][qt], 0, 0, 0);
-      }
+    attn_scores<KT>(ks, key_row, qf, fr, g, s);
 
-    // ---- online softmax (scores kept in the log2 domain: exp(x) = exp2(x * log2 e)); attn_softmax.hpp
+    // ---- online softmax
     bool any_masked = __any(kbias[lane] != 0.0f);            // (the block's key-bias words, 64 per pass; wave-uniform)
     if constexpr (KB == 128) any_masked = any_masked || __any(kbias[64 + lane] != 0.0f);
     if constexpr (CAUSAL) any_masked = any_masked || kb0 + KB - 1 > wq0;      // the block crosses the wave's diagonal
@@ -188,55 +172,21 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 2
           dm[kt] = f32x4{m4[0], m4[1], m4[2], m4[3]};
         }
       }
-      const float alpha = online_softmax_block<KT, DROP, CAUSAL>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf, dm,
-                                                                 qrow[qt] - kb0 - 4 * g, NEG_MASK);
-      if (!__all(alpha == 1.0f)) {       // (the running maximum rarely moves after the first blocks: skip the rescale then)
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
-      }
+      attn_softmax_rescale<KT, DROP, CAUSAL>(s, qt, kbias, any_masked, g, scale_log2e, m_run, l_run, pf, o, dm, qrow[qt] - kb0 - 4 * g, NEG_MASK);
     }
 
-    // ---- O^T += V^T P^T : contraction over the block's 128 keys in 4 steps of 32
-#pragma unroll
-    for (int ksd = 0; ksd < KT / 2; ++ksd) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        // hardware-transposed read: 16-lane group g, lane 4q+p supplies &V[key][16dt + 4p]
-        const int qq = fr >> 2, pp = fr & 3;
-        const int key0 = 32 * ksd + 4 * g + qq;
-        const int ch = 2 * dt + (pp >> 1);
-        const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-        const int key1 = key0 + 16;
-        const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-        const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vs + off0));
-        const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vs + off1));
-        union { s16x4 s2[2]; bf16x8 v; } u;
-        u.s2[0] = t0;
-        u.s2[1] = t1;
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
-      }
-    }
+    // ---- O^T += V^T P^T
+    attn_pv<KT>(vs, key_row, pf, o, fr, g);
   }
 
   // ---- normalise and store: lane holds O^T[d = 16dt + 4g + r][query fr]
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    float l = l_run[qt];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
+    float l;
+    const float inv = attn_finish(l_run[qt], l);
     // training forwards keep the query's log-sum-exp (log2 domain, as the scores above): the backward recomputes P from it
     if (lse && g == 0 && qrow[qt] < L) lse[(tok0 + qrow[qt]) * heads + h] = m_run[qt] + log2f(l);
-    if (qrow[qt] < L) {
-      __bf16* dst = ctx + (tok0 + qrow[qt]) * H + h * 64 + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv),
-                     (__bf16)(o[dt][qt][3] * inv)};
-        *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
-      }
-    }
+    if (qrow[qt] < L) attn_store_ctx(ctx + (tok0 + qrow[qt]) * H + h * 64 + 4 * g, o, qt, inv);
   }
 }
 

@@ -1,6 +1,19 @@
-// One 64-key block of the online softmax, for one 16-query tile column of a wave (attention.hip and the fused projection +
-// attention kernel of gemm_bf16_kernel.hpp share it: the two must produce the same bits).
+// The forward attention block body, written once: attention_kernel (attention.hip) and the three fused projection + attention branches
+// of gemm_bf16_kernel.hpp (short samples, sample tiles, padded samples / slot bins) are loops over their own geometry -- which LDS row a
+// key is, where the block's bias words lie, how many key blocks there are, where a query row goes -- around the pieces below.  That
+// the fused launches produce the bits of the two-launch form follows from the source: there is one copy of every operation.
 //
+// A wave owns 32 queries (two 16-query tile columns qt) of one head and walks the keys in blocks of 16 KT (KT = 4: 64 keys):
+//   attn_init             o = 0, m_run = -inf, l_run = 0
+//   attn_q_frags          the wave's Q fragments from an LDS image (attention.hip loads them from global memory)
+//   attn_scores           S^T = K Q^T of the block            (A = K rows from the swizzled LDS image, B = Q from registers)
+//   attn_softmax_rescale  online_softmax_block of one tile column + the rescale of its running output
+//   attn_pv               O^T += V^T P^T of the block         (A = V^T by transposed LDS reads, B = P^T: the score accumulators in place)
+//   attn_finish           a query's row sum over its four lanes and the reciprocal
+//   attn_store_ctx        the normalised output row, rounded to bf16
+// Lane (fr, g) = (lane & 15, lane >> 4).  `key_row` maps a key index of the block to its row in the K / V image.
+//
+// online_softmax_block: one 64-key block of the online softmax, for one 16-query tile column of a wave.
 // Scores arrive as the S^T accumulators s[kt][qt] (row = key 16 kt + 4 g + r, column = the lane's query); on return pf holds
 // exp2(score - m_new) rounded to bf16 in the B-operand order of the P V product, m_run / l_run are updated, and the factor the
 // running output must be multiplied by is returned.
@@ -12,6 +25,14 @@
 // degenerates to a uniform average) at three more instructions per score.
 #pragma once
 #include "common.hpp"
+
+// No implicit contraction in any piece of this file: the fused multiply-adds are spelled out.
+#pragma clang fp contract(off)
+
+// One 16-B fragment of a 128-B row of an LDS image whose chunks are swizzled by the row (chunk ^= (row >> 1) & 7)
+__device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk) {
+  return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+}
 
 // A 64-key block whose keys are ALL masked (or beyond L) changes nothing once every query of the wave has seen a live key: its scores
 // are the -3e38 constant (or -inf), so m_new = m_run, alpha = 1, every p = exp2(-3e38 - m_run) = +0 exactly, l and O stay as they are.
@@ -32,7 +53,6 @@ template <int KT, bool DROP = false, bool CAUSAL = false>
 __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const int qt, const float* kbias, const bool any_masked, const int g,
                                                       const float scale_log2e, float& m_run, float& l_run, bf16x8 (&pf)[KT / 2][2],
                                                       const f32x4* dm = nullptr, const int qk = 0, const float causal_neg = 0.0f) {
-#pragma clang fp contract(off)
   float mx = -INFINITY, lsum = 0.0f, m_new, alpha;
   if (any_masked) {
 #pragma unroll
@@ -84,4 +104,101 @@ __device__ __forceinline__ float online_softmax_block(f32x4 (&s)[KT][2], const i
   l_run = __builtin_fmaf(l_run, alpha, lsum);
   m_run = m_new;
   return alpha;
+}
+
+__device__ __forceinline__ void attn_init(f32x4 (&o)[4][2], float (&m_run)[2], float (&l_run)[2]) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) m_run[qt] = -INFINITY, l_run[qt] = 0.f;
+}
+
+// Q fragments (B operand) from the Q image: lane (fr, g) holds Q[query][8g + 32kk .. +7] of query 16 qt + fr, at image row q_row(16 qt + fr)
+template <class QRow>
+__device__ __forceinline__ void attn_q_frags(const char* qimg, QRow q_row, int fr, int g, bf16x8 (&qf)[2][2]) {
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const int row = q_row(qt * 16 + fr);
+    qf[qt][0] = lds_frag(qimg, row, g);
+    qf[qt][1] = lds_frag(qimg, row, g + 4);
+  }
+}
+
+// S^T = K Q^T : KT key tiles x 2 query tiles, contraction over the 64 head columns in two steps of 32 (kk outer, kt inner)
+template <int KT, class KeyRow>
+__device__ __forceinline__ void attn_scores(const char* kimg, KeyRow key_row, const bf16x8 (&qf)[2][2], int fr, int g, f32x4 (&s)[KT][2]) {
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) s[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      const bf16x8 kf = lds_frag(kimg, key_row(kt * 16 + fr), g + 4 * kk);
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], s[kt][qt], 0, 0, 0);
+    }
+}
+
+// The softmax of tile column qt over the block (scores kept in the log2 domain: exp(x) = exp2(x * log2 e)) and the rescale of its
+// running output (the running maximum rarely moves after the first blocks: the rescale is skipped then)
+template <int KT, bool DROP = false, bool CAUSAL = false>
+__device__ __forceinline__ void attn_softmax_rescale(f32x4 (&s)[KT][2], const int qt, const float* kbias, const bool any_masked, const int g,
+                                                     const float scale_log2e, float (&m_run)[2], float (&l_run)[2], bf16x8 (&pf)[KT / 2][2],
+                                                     f32x4 (&o)[4][2], const f32x4* dm = nullptr, const int qk = 0, const float causal_neg = 0.0f) {
+  const float alpha = online_softmax_block<KT, DROP, CAUSAL>(s, qt, kbias, any_masked, g, scale_log2e, m_run[qt], l_run[qt], pf, dm, qk, causal_neg);
+  if (!__all(alpha == 1.0f)) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
+  }
+}
+
+// O^T += V^T P^T : contraction over the block's 16 KT keys in steps of 32 (ksd outer, dt inner).  The V image's rows are 128 B with
+// the transposed-read swizzle (chunk ^= ((row >> 1) & 3) << 1); hardware-transposed read: 16-lane group g, lane 4q+p supplies
+// &V[key][16dt + 4p] of keys 32 ksd + 4 g + q and that + 16
+template <int KT, class KeyRow>
+__device__ __forceinline__ void attn_pv(const char* vimg, KeyRow key_row, const bf16x8 (&pf)[KT / 2][2], f32x4 (&o)[4][2], int fr, int g) {
+#pragma unroll
+  for (int ksd = 0; ksd < KT / 2; ++ksd) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int qq = fr >> 2, pp = fr & 3;
+      const int k0 = 32 * ksd + 4 * g + qq;
+      const int key0 = key_row(k0), key1 = key_row(k0 + 16);
+      const int ch = 2 * dt + (pp >> 1);
+      const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+      const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
+      const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
+      const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
+      union { s16x4 s2[2]; bf16x8 v; } u;
+      u.s2[0] = t0;
+      u.s2[1] = t1;
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
+    }
+  }
+}
+
+// The row sum l of the lane's query (its probabilities live in the lanes fr, fr + 16, fr + 32, fr + 48); returns 1 / l
+__device__ __forceinline__ float attn_finish(const float l_run, float& l) {
+  l = l_run;
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  return 1.0f / l;
+}
+__device__ __forceinline__ float attn_finish(const float l_run) {
+  float l;
+  return attn_finish(l_run, l);
+}
+
+// Normalise and store: the lane holds O^T[d = 16dt + 4g + r][its query]; dst = the query's ctx row at column 64 head + 4 g
+__device__ __forceinline__ void attn_store_ctx(__bf16* dst, const f32x4 (&o)[4][2], const int qt, const float inv) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
+    *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
+  }
 }

@@ -99,15 +99,6 @@ extern "C" int ufnd_gemm_bf16_stat_parts(int M, int N, int K) {
 
 extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
                                       float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
-                                      const ufnd_gemm_ln* ln, const int* m_live, void* stream_);
-extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
-                                 float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
-                                 const ufnd_gemm_ln* ln, void* stream_) {
-  return ufnd_gemm_bf16_ln_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln, nullptr, stream_);
-}
-
-extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
-                                      float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
                                       const ufnd_gemm_ln* ln, const int* m_live, void* stream_) {
   int rc = gemm_bf16_ln_check_args(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln);
   if (rc != UFND_OK) return rc;
@@ -129,24 +120,36 @@ extern "C" int ufnd_gemm_bf16_ln_live(const void* A, const void* W, const float*
   return UFND_OK;
 }
 
+extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias, const float* residual, void* out_bf16,
+                                 float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldo, int ldf, int act,
+                                 const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_gemm_bf16_ln_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln, nullptr, stream_);
+}
+
+// What the three fused Q/K/V projection + attention entries share, after their own shape checks: the operand checks, the
+// projection's arguments (M rows of X against the 3H stacked weight rows), the folded LayerNorm and the attention output.
+// `name` is the entry's name in its messages.
+static int qkv_attention_args(const char* name, GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, void* ctx, int M, int heads, int ldx,
+                              int ldw, const ufnd_gemm_ln* ln) {
+  const int H = heads * 64;
+  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
+               "%s: strides must be multiples of 8 and pointers 16-B aligned", name);
+  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "%s: bias alignment", name);
+  a = GemmArgs{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, M, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
+  if (ln && ln->a_stats) {
+    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "%s: colsum / a_stats alignment", name);
+    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "%s: a_parts=%d width=%d", name, ln->a_parts, ln->width);
+    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
+    a.inv_h = 1.0f / (float)ln->width;
+    a.guard = ln->guard;
+  }
+  a.att_ctx = (__bf16*)ctx;
+  a.att_h = H;
+  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
+  return UFND_OK;
+}
+
 // BertSelfAttention of one layer in ONE launch: fused Q/K/V projection (optionally of LayerNorm(X), folded) + attention.
-extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
-                                              const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
-                                              const ufnd_gemm_ln* ln, void* stream_);
-extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, void* ctx,
-                                       int B, int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
-  return ufnd_qkv_attention_bf16_packed(X, Wqkv, bqkv, key_mask, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
-}
-
-extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
-                                            const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B,
-                                            int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_);
-extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
-                                              const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
-                                              const ufnd_gemm_ln* ln, void* stream_) {
-  return ufnd_qkv_attention_bf16_bins(X, Wqkv, bqkv, key_mask, cu_seqlens, nullptr, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
-}
-
 // bins / nbins (with cu_seqlens; ufnd_text_pack_bins): workgroup row tm runs bin tm's four 32-row slots, tm < *nbins
 extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
                                             const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B,
@@ -156,26 +159,14 @@ extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, con
   UFND_REQUIRE(L == 128 && heads >= 2 && heads % 2 == 0 && heads <= 64 && B >= 1 && B <= 16384,
                "qkv_attention: B=%d L=%d heads=%d (this kernel is built for 128-token samples and an even head count; "
                "use ufnd_gemm_bf16[_ln] + ufnd_attention_bf16 otherwise)", B, L, heads);
-  const int H = heads * 64;
-  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
-               "qkv_attention: strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "qkv_attention: bias alignment");
-  GemmArgs a{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, B * L, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
-  if (ln && ln->a_stats) {
-    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "qkv_attention: colsum / a_stats alignment");
-    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "qkv_attention: a_parts=%d width=%d", ln->a_parts, ln->width);
-    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
-    a.inv_h = 1.0f / (float)ln->width;
-    a.guard = ln->guard;
-  }
+  GemmArgs a;
+  const int rc = qkv_attention_args("qkv_attention", a, X, Wqkv, bqkv, ctx, B * L, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
   a.att_mask = key_mask;
   a.att_cu = cu_seqlens;
   a.att_bins = bins;
   a.att_nbins = nbins;
   a.m_live = cu_seqlens ? cu_seqlens + B : nullptr;      // (the live row count is cu_seqlens[B])
-  a.att_ctx = (__bf16*)ctx;
-  a.att_h = H;
-  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
   a.m_tiles = B;
   a.n_tiles = heads / 2;
   a.xcd_cols = (a.n_tiles % 2 == 0 && a.m_tiles >= 4) ? 2 : 1;
@@ -184,29 +175,28 @@ extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, con
   return UFND_OK;
 }
 
+extern "C" int ufnd_qkv_attention_bf16_packed(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                              const int32_t* cu_seqlens, void* ctx, int B, int L, int heads, int ldx, int ldw,
+                                              const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_qkv_attention_bf16_bins(X, Wqkv, bqkv, key_mask, cu_seqlens, nullptr, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
+}
+
+extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask, void* ctx,
+                                       int B, int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
+  return ufnd_qkv_attention_bf16_packed(X, Wqkv, bqkv, key_mask, nullptr, ctx, B, L, heads, ldx, ldw, ln, stream_);
+}
+
 // The packed form over sample tiles (ufnd_text_pack_tiles): one workgroup per (256-row tile of whole samples, head)
 extern "C" int ufnd_qkv_attention_bf16_tiles(const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles, const int32_t* ntiles,
                                              void* ctx, int cap_tiles, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
   UFND_REQUIRE(X && Wqkv && ctx && tiles && ntiles, "qkv_attention_tiles: null operand");
   UFND_REQUIRE(heads >= 1 && heads <= 64 && cap_tiles >= 1 && cap_tiles <= (UFND_TEXT_TILE_MAX_B + 1) / 2, "qkv_attention_tiles: cap_tiles=%d heads=%d",
                cap_tiles, heads);
-  const int H = heads * 64;
-  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
-               "qkv_attention_tiles: strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "qkv_attention_tiles: bias alignment");
-  GemmArgs a{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, cap_tiles * 256, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
-  if (ln && ln->a_stats) {
-    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "qkv_attention_tiles: colsum / a_stats alignment");
-    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "qkv_attention_tiles: a_parts=%d width=%d", ln->a_parts, ln->width);
-    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
-    a.inv_h = 1.0f / (float)ln->width;
-    a.guard = ln->guard;
-  }
+  GemmArgs a;
+  const int rc = qkv_attention_args("qkv_attention_tiles", a, X, Wqkv, bqkv, ctx, cap_tiles * 256, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
   a.att_bins = tiles;
   a.att_nbins = ntiles;
-  a.att_ctx = (__bf16*)ctx;
-  a.att_h = H;
-  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
   a.m_tiles = cap_tiles;
   a.n_tiles = heads;
   a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a tile share its A rows in one L2
@@ -222,22 +212,10 @@ extern "C" int ufnd_qkv_attention_bf16_vit(const void* X, const void* Wqkv, cons
   UFND_REQUIRE(T >= 1 && T <= 64, "qkv_attention_vit: T=%d (this kernel is built for samples of 1 to 64 rows; use ufnd_gemm_bf16[_ln] + "
                "ufnd_attention_bf16 otherwise)", T);
   UFND_REQUIRE(heads >= 1 && heads <= 64 && N >= 1 && (long long)N * T <= (1 << 24), "qkv_attention_vit: N=%d T=%d heads=%d", N, T, heads);
-  const int H = heads * 64;
-  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
-               "qkv_attention_vit: strides must be multiples of 8 and pointers 16-B aligned");
-  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "qkv_attention_vit: bias alignment");
-  GemmArgs a{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, N * T, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
-  if (ln && ln->a_stats) {
-    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "qkv_attention_vit: colsum / a_stats alignment");
-    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "qkv_attention_vit: a_parts=%d width=%d", ln->a_parts, ln->width);
-    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
-    a.inv_h = 1.0f / (float)ln->width;
-    a.guard = ln->guard;
-  }
-  a.att_ctx = (__bf16*)ctx;
-  a.att_h = H;
+  GemmArgs a;
+  const int rc = qkv_attention_args("qkv_attention_vit", a, X, Wqkv, bqkv, ctx, N * T, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
   a.att_t = T;
-  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
   a.m_tiles = ufnd_cdiv(N, 256 / T);      // 256 / T whole samples per row tile
   a.n_tiles = heads;
   a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a row tile share its A rows in one L2

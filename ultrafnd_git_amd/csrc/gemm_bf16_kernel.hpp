@@ -109,9 +109,7 @@ __device__ __forceinline__ f32x2 opaque_f2(f32x2 x) {
   return x;
 }
 
-__device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-}
+// (lds_frag, the swizzled 16-B fragment read of the operand slots and the attention images: attn_softmax.hpp)
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -142,7 +140,8 @@ template <int V> struct IntC { static constexpr int value = V; };
 //          the head pair (h, h') = (2 pair, 2 pair + 1); grid = samples x heads / 2.  The epilogue rounds the projection
 //          to bf16 exactly as the stand-alone GEMM does, but into LDS images (swizzled like attention.hip's), and the
 //          workgroup then runs attention.hip's per-wave schedule on them (wave w: head w / 4, queries 32 (w % 4) ..):
-//          S^T = K Q^T, online softmax over two 64-key blocks, O^T = V^T P^T.  Same operations in the same order as
+//          S^T = K Q^T, online softmax over two 64-key blocks, O^T = V^T P^T -- the block body both kernels call (attn_softmax.hpp).
+//          Same operations in the same order as
 //          ufnd_gemm_bf16[_ln] + ufnd_attention_bf16: bit-identical ctx, without the (tokens, 3H) round trip through
 //          HBM, the second launch and its three dependent memory round trips.
 //          Slot bins (att_bins, packed rows): the tile's 128 rows are four 32-row slots; a sample of n rows takes ceil(n / 32)
@@ -849,8 +848,9 @@ void gemm_bf16_kernel(const GemmArgs a) {
     stamp[9] = __builtin_amdgcn_s_memrealtime();
   }
   if constexpr (VIT) {
-    // ---- attention of the tile's samples for this head on the LDS images: attention_kernel<64, 2>'s operations per query (one
-    // 64-key block; a key or query at or past T reads the sample's last row, as that kernel's clamped loads do)
+    // ---- attention of the tile's samples for this head on the LDS images, the block body of attn_softmax.hpp in attention_kernel<64, 2>'s
+    // geometry: one 64-key block per sample; a key or query at or past T reads the sample's last row, as that kernel's clamped loads
+    // do, and gets the -inf bias; units of (sample, 32 queries) dealt round-robin to the eight waves
     const int T = a.att_t;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 3 * ATT_IMG);
     if (threadIdx.x < 64) kbias[threadIdx.x] = (int)threadIdx.x < T ? 0.0f : -INFINITY;
@@ -864,80 +864,27 @@ void gemm_bf16_kernel(const GemmArgs a) {
     constexpr int KT = 4;
     for (int u = wave; u < nsamp * nqb; u += NW) {
       const int smp = u / nqb, q0 = (u - smp * nqb) * 32, r0 = smp * T;      // r0: tile row of the sample's row 0
+      const auto row = [&](int k) { return r0 + (k < T ? k : T - 1); };      // tile row of the sample's key (or query) k
       bf16x8 qf[2][2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const int q = q0 + qt * 16 + f16, qc = q < T ? q : T - 1;
-        qf[qt][0] = lds_frag(qimg, r0 + qc, g4);
-        qf[qt][1] = lds_frag(qimg, r0 + qc, g4 + 4);
-      }
-      f32x4 o[4][2];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
-      f32x4 sc[KT][2];
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          const int key = kt * 16 + f16;
-          const bf16x8 kf = lds_frag(kimg, r0 + (key < T ? key : T - 1), g4 + 4 * kk);
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
-        }
+      attn_q_frags(qimg, [&](int q) { return row(q0 + q); }, f16, g4, qf);
+      f32x4 o[4][2], sc[KT][2];
+      float m_run[2], l_run[2];
       bf16x8 pf[KT / 2][2];
+      attn_init(o, m_run, l_run);
+      attn_scores<KT>(kimg, row, qf, f16, g4, sc);
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, kbias, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
+      attn_pv<KT>(vimg, row, pf, o, f16, g4);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        const float alpha = online_softmax_block<KT>(sc, qt, kbias, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
-        }
-      }
-#pragma unroll
-      for (int ksd = 0; ksd < KT / 2; ++ksd) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int qq = f16 >> 2, pp = f16 & 3;
-          const int k0 = 32 * ksd + 4 * g4 + qq, k1 = k0 + 16;
-          const int key0 = r0 + (k0 < T ? k0 : T - 1), key1 = r0 + (k1 < T ? k1 : T - 1);      // tile rows
-          const int ch = 2 * dt + (pp >> 1);
-          const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-          const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-          const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
-          const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
-          union { s16x4 s2[2]; bf16x8 v; } uu;
-          uu.s2[0] = t0;
-          uu.s2[1] = t1;
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uu.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        float l = l_run[qt];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
+        const float inv = attn_finish(l_run[qt]);
         const int q = q0 + qt * 16 + f16;
-        if (q >= T) continue;
-        __bf16* dst = a.att_ctx + (size_t)(arow0 + r0 + q) * a.att_h + tn * 64 + 4 * g4;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
-          *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
-        }
+        if (q < T) attn_store_ctx(a.att_ctx + (size_t)(arow0 + r0 + q) * a.att_h + tn * 64 + 4 * g4, o, qt, inv);
       }
     }
   } else if constexpr (TIL) {
-    // ---- attention of the tile's samples for this head on the LDS images: attention.hip's per-query operation sequence at L = 128 (two
-    // 64-key blocks counted from the sample's row 0).  Key k of a sample of n rows whose row 0 is tile row r0 is tile row r0 + min(k, n - 1):
+    // ---- attention of the tile's samples for this head on the LDS images, the block body of attn_softmax.hpp in attention.hip's geometry at
+    // L = 128 (two 64-key blocks counted from the sample's row 0).  Key k of a sample of n rows whose row 0 is tile row r0 is tile row r0 + min(k, n - 1):
     // a key at or past n reads a finite row of the sample and gets NEG_MASK, what a padding key gets in the padded batch; a live key's bias
     // is its tile row's word (the sample's key-mask row, holes included).  A wave copies the 128 bias words of its unit's sample into a row
     // of its own, so that the block reads are 16-B aligned wherever the sample starts.  Units of (sample, 32 queries) come from the tile's
@@ -969,84 +916,34 @@ void gemm_bf16_kernel(const GemmArgs a) {
         wbias[k] = k < n ? kbias[r0 + k] : NEG_MASK;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      const auto row = [&](int k) { return r0 + (k < n ? k : n - 1); };      // tile row of the sample's key (or query) k
       bf16x8 qf[2][2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const int q = q0 + qt * 16 + f16, qc = q < n ? q : n - 1;
-        qf[qt][0] = lds_frag(qimg, r0 + qc, g4);
-        qf[qt][1] = lds_frag(qimg, r0 + qc, g4 + 4);
-      }
+      attn_q_frags(qimg, [&](int q) { return row(q0 + q); }, f16, g4, qf);
       f32x4 o[4][2];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+      float m_run[2], l_run[2];
+      attn_init(o, m_run, l_run);
 #pragma unroll
       for (int kb0 = 0; kb0 < 128; kb0 += KB) {
         if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
+        const auto key_row = [&](int k) { return row(kb0 + k); };
         f32x4 sc[KT][2];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int kt = 0; kt < KT; ++kt) {
-            const int key = kb0 + kt * 16 + f16;
-            const bf16x8 kf = lds_frag(kimg, r0 + (key < n ? key : n - 1), g4 + 4 * kk);
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
-          }
+        attn_scores<KT>(kimg, key_row, qf, f16, g4, sc);
         const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
         bf16x8 pf[KT / 2][2];
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          const float alpha = online_softmax_block<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
-          if (!__all(alpha == 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
-          }
-        }
-#pragma unroll
-        for (int ksd = 0; ksd < KT / 2; ++ksd) {
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            const int qq = f16 >> 2, pp = f16 & 3;
-            const int k0 = kb0 + 32 * ksd + 4 * g4 + qq, k1 = k0 + 16;
-            const int key0 = r0 + (k0 < n ? k0 : n - 1), key1 = r0 + (k1 < n ? k1 : n - 1);      // tile rows
-            const int ch = 2 * dt + (pp >> 1);
-            const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-            const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-            const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
-            const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
-            union { s16x4 s2[2]; bf16x8 v; } uu;
-            uu.s2[0] = t0;
-            uu.s2[1] = t1;
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uu.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
-          }
-        }
+        for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
+        attn_pv<KT>(vimg, key_row, pf, o, f16, g4);
       }
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        float l = l_run[qt];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
+        const float inv = attn_finish(l_run[qt]);
         const int q = q0 + qt * 16 + f16;
-        if (q >= n) continue;
-        __bf16* dst = a.att_ctx + (size_t)(grow0 + q) * a.att_h + tn * 64 + 4 * g4;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
-          *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
-        }
+        if (q < n) attn_store_ctx(a.att_ctx + (size_t)(grow0 + q) * a.att_h + tn * 64 + 4 * g4, o, qt, inv);
       }
     }
   } else if constexpr (ATT) {
-    // ---- attention of the tile's two heads on the LDS images (attention.hip's per-wave schedule, L = 128 = two key blocks)
+    // ---- attention of the tile's two heads on the LDS images, the block body of attn_softmax.hpp in attention.hip's per-wave geometry
+    // (wave w: head w / 4, queries 32 (w % 4) ..; L = 128 = two key blocks)
     constexpr float NEG_MASK = -3.0e38f;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 6 * 16384);
     if (slots || threadIdx.x < BM) kbias[threadIdx.x] = att_mk != 0 ? 0.0f : NEG_MASK;
@@ -1066,83 +963,34 @@ void gemm_bf16_kernel(const GemmArgs a) {
     const char* kimg = smem + ATT_OFF + (2 + hh) * 16384;
     const char* vimg = smem + ATT_OFF + (4 + hh) * 16384;
     bf16x8 qf[2][2];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      const int q = wq * 32 + qt * 16 + f16;
-      qf[qt][0] = lds_frag(qimg, q, g4);
-      qf[qt][1] = lds_frag(qimg, q, g4 + 4);
-    }
+    attn_q_frags(qimg, [&](int q) { return wq * 32 + q; }, f16, g4, qf);
     f32x4 o[4][2];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    float m_run[2], l_run[2];
+    attn_init(o, m_run, l_run);
     constexpr int KB = 64, KT = KB / 16;
     // (packed rows: a wave whose 32 queries all lie past the sample's length, or whose slot is empty, has nothing to do)
     if (wcnt > 0) {
 #pragma unroll
-    for (int kb0 = 0; kb0 < BM; kb0 += KB) {
-      const int kr0 = koff + kb0;      // tile row of the block's first key (mod 128; koff and kb0 are multiples of 32)
-      if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
-      f32x4 sc[KT][2];
+      for (int kb0 = 0; kb0 < BM; kb0 += KB) {
+        if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
+        // key k of the block is tile row (kr0 + k) mod 128.  koff and kb0 are multiples of 32, so the P V product's key pair
+        // (k, k + 16), k % 32 < 16, lies in one aligned 32-row group: the wrap never splits it
+        const int kr0 = koff + kb0;
+        const auto key_row = [&](int k) { return (kr0 + k) & (BM - 1); };
+        f32x4 sc[KT][2];
+        attn_scores<KT>(kimg, key_row, qf, f16, g4, sc);
+        const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
+        bf16x8 pf[KT / 2][2];
 #pragma unroll
-      for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          const bf16x8 kf = lds_frag(kimg, (kr0 + kt * 16 + f16) & (BM - 1), g4 + 4 * kk);
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][kk], sc[kt][qt], 0, 0, 0);
-        }
-      const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
-      bf16x8 pf[KT / 2][2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const float alpha = online_softmax_block<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run[qt], l_run[qt], pf);
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
-        }
+        for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
+        attn_pv<KT>(vimg, key_row, pf, o, f16, g4);
       }
-#pragma unroll
-      for (int ksd = 0; ksd < KT / 2; ++ksd) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int qq = f16 >> 2, pp = f16 & 3;
-          const int key0 = (kr0 + 32 * ksd + 4 * g4 + qq) & (BM - 1);      // (tile rows; the swizzle only sees key bits 1-2)
-          const int ch = 2 * dt + (pp >> 1);
-          const int off0 = key0 * 128 + ((ch ^ (((key0 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-          const int key1 = key0 + 16;
-          const int off1 = key1 * 128 + ((ch ^ (((key1 >> 1) & 3) << 1)) << 4) + 8 * (pp & 1);
-          const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off0));
-          const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(vimg + off1));
-          union { s16x4 s2[2]; bf16x8 v; } u;
-          u.s2[0] = t0;
-          u.s2[1] = t1;
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf[ksd][qt], o[dt][qt], 0, 0, 0);
-        }
-      }
-    }
     }
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-      float l = l_run[qt];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
-      const float inv = 1.0f / l;
+      const float inv = attn_finish(l_run[qt]);
       const int q = qt * 16 + f16;
-      if (q >= wcnt) continue;
-      __bf16* dst = a.att_ctx + (size_t)(wrow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
-        *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
-      }
+      if (q < wcnt) attn_store_ctx(a.att_ctx + (size_t)(wrow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4, o, qt, inv);
     }
   }
   if constexpr (LNX) {
