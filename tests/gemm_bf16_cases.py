@@ -2,7 +2,8 @@
 encoders -- plain, LayerNorm-folded, residual through a LayerNorm -- and, as the BWD instantiation, the backward input gradient),
 shared by tests/test_gemm_bf16_cases.py (CPU: the table reaches what it claims, read from the library's own host-side checks and
 choice; the bounds accept a float32 restatement of the kernel in two summation orders and reject thirteen wrong kernels) and
-tests/test_gpu_gemm_bf16.py (GPU: every case through the C ABI).  NumPy only.
+tests/test_gpu_gemm_bf16.py (GPU: every case through the C ABI).  NumPy only.  The persistent form of the same arithmetic
+(csrc/gemm_bf16_pp.hpp, tile id 64, K = 768) has its table in tests/gemm_pp_cases.py, built on the functions and bounds of this file.
 
 A case is ONE launch of ufnd_gemm_bf16 ("gemm"), ufnd_gemm_bf16_ex ("ex"), ufnd_gemm_bf16_ln ("ln") or ufnd_gemm_bf16_dgrad ("dgrad").
 Shapes are the smallest that reach an edge: K = 64 .. 320 (nk = K / 64 = 1 .. 5 straddles every ring depth, 2 .. 4), two to four
@@ -93,11 +94,22 @@ LN_TILES = tuple(TILES)            # every product tile has the LayerNorm-aware 
 BWD_TILES = (15, 16, 17, 20, 22)
 A_PARTS = (2, 4, 10, 22, 24)
 R_PARTS = (2, 12, 24)
+# the persistent form (csrc/gemm_bf16_pp.hpp; UFND_GEMM_TILE_PERSISTENT) is not a row of the library's tile table and has no case in
+# CASES: its table is tests/gemm_pp_cases.py, which shares everything below.  Its workgroups walk 256 x 128 tiles (A ring 3, W ring 2,
+# wave tile 64 columns); the grid is G = min(CUs, tiles) & ~7, PP_CUS where nobody names the device's count.
+PP_TILE = 64
+PP_DIMS = (256, 128, 3, 2, 64)
+PP_CUS = 256
+
+
+def tile_dims(tile: int):
+    """(bm, bn, A ring depth, W ring depth, wave-tile columns) of a product tile or of the persistent form"""
+    return PP_DIMS if tile == PP_TILE else TILES[tile]
 
 
 def has_stats_epilogue(tile: int, N: int) -> bool:
-    """stat_parts_for: 32-column groups must not straddle a wave tile (tile 28: 144 columns), N / 32 even and <= 24"""
-    return TILES[tile][4] % 32 == 0 and N % TILES[tile][1] == 0 and (N // 32) % 2 == 0 and N // 32 <= 24
+    """stat_parts_for / pp_stat_parts: 32-column groups must not straddle a wave tile (tile 28: 144 columns), N / 32 even and <= 24"""
+    return tile_dims(tile)[4] % 32 == 0 and N % tile_dims(tile)[1] == 0 and (N // 32) % 2 == 0 and N // 32 <= 24
 
 
 class Case(NamedTuple):
@@ -478,12 +490,30 @@ def row_stats(stats, width, eps):
         return _row_stats(stats, width, eps)
 
 
+BLAS32_FROM = 1 << 32            # multiply-adds from which the exact family's product is formed by an fp32 BLAS call
+BLAS32_ROWS = 64                 # rows of that product that are compared with float64
+
+
+def _product(c: Case, A: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """A W^T in float64.  In the exact family every partial sum of the K <= 768 products, in any order, is a multiple of 1/16 below
+    4 K <= 3,072 (16 x 3,072 < 2^24): an fp32 product IS the float64 one, so the large cases (tests/gemm_pp_cases.py) take it from an
+    fp32 BLAS call and compare a block of rows with float64."""
+    if c.family != "exact" or c.M * c.N * c.K < BLAS32_FROM:
+        return A @ W.T
+    assert c.K <= 768
+    acc = (A.astype(f32) @ W.astype(f32).T).astype(np.float64)
+    r0 = (c.M // 2) // BLAS32_ROWS * BLAS32_ROWS
+    for lo in (0, r0, c.M - BLAS32_ROWS):
+        assert np.array_equal(acc[lo:lo + BLAS32_ROWS], A[lo:lo + BLAS32_ROWS] @ W.T), (c.id, "the fp32 product is not exact", lo)
+    return acc
+
+
 def reference(c: Case, inp: Dict) -> Dict:
     """name -> (reference, bound) over the LIVE region of each output: "of" / "ob" (M, N), "ostats" (M, N / 32, 2), "guard" scalar"""
     M, N, K = c.M, c.N, c.K
     A = bf16_f32(_live(inp["A"], 0, M, K)).astype(np.float64)
     W = bf16_f32(_live(inp["W"], 0, N, K)).astype(np.float64)
-    acc = A @ W.T
+    acc = _product(c, A, W)
     exact = c.family == "exact"       # becomes False at the first operation that is not an exact add
     e = np.zeros_like(acc) if exact else ACC_ULP * K * (np.abs(A) @ np.abs(W).T)
     out: Dict = {}
@@ -579,6 +609,11 @@ def bf16_ratio(got, ref, e) -> float:
     ok = ~rn
     g, r = np.where(ok, got, 0.0), np.where(ok, ref, 0.0)
     same = bf16_round(r.astype(f32)).astype(np.float64) == g
+    sel = ~same & ok                                                        # (only these have a distance: the rest is RNE(ref) itself)
+    if not sel.any():
+        return 0.0
+    e = np.broadcast_to(e, g.shape)
+    g, r, e, ok, same = g[sel], r[sel], e[sel], ok[sel], same[sel]
     mag = np.abs(g)
     ulp = bf16_ulp(mag)                                                     # spacing above |g|
     below = np.where(mag == 2.0 ** np.floor(np.log2(np.where(mag > 0, mag, 1.0))), ulp / 2, ulp)      # spacing below (a power of two: half)
@@ -592,15 +627,16 @@ def bf16_ratio(got, ref, e) -> float:
     return float(np.max(dist[nz] / e[nz])) if nz.any() else 0.0
 
 
-def check(c: Case, inp: Dict, got: Dict, refs: Optional[Dict] = None) -> Dict[str, float]:
+def check(c: Case, inp: Dict, got: Dict, refs: Optional[Dict] = None, cus: Optional[int] = None) -> Dict[str, float]:
     """name -> worst |got - ref| / bound over the live region (inf: a bit differs where the bound is 0, a NaN on one side, or a
-    sentinel was overwritten).  `got` holds whole buffers, laid out as make()'s."""
+    sentinel was overwritten).  `got` holds whole buffers, laid out as make()'s.  `cus`: the device's CU count (the persistent
+    form's grid, i.e. the guard slots its workgroups own)."""
     refs = reference(c, inp) if refs is None else refs
     out = {}
     for name, (ref, bnd) in refs.items():
         if name == "guard":
             g = got["guard"]
-            grid = planned_grid(c)
+            grid = planned_grid(c, cus)
             r = worst_ratio(np.array(float(g.max()) if not np.isnan(g).any() else np.nan), ref, bnd)
             if (g[min(grid, GUARD_SLOTS):] != 0).any() or (g < 0).any():
                 r = math.inf           # a slot no workgroup owns was written
@@ -636,12 +672,15 @@ def is_bit_exact(c: Case) -> bool:
 
 
 def grid_of(tile: int, M: int, N: int):
-    bm, bn = TILES[tile][:2]
+    bm, bn = tile_dims(tile)[:2]
     return (M + bm - 1) // bm, N // bn
 
 
-def planned_grid(c: Case) -> int:
+def planned_grid(c: Case, cus: Optional[int] = None) -> int:
+    """workgroups of the launch (each owns guard slot blockIdx.x % GUARD_SLOTS)"""
     m, n = grid_of(tile_of(c), c.M, c.N)
+    if tile_of(c) == PP_TILE:
+        return min(cus or PP_CUS, m * n) & ~7
     return m * n
 
 
@@ -740,11 +779,12 @@ def emulate(c: Case, inp: Dict, order: int = 0, mutant: Optional[str] = None) ->
                 if "guard" in got:
                     ratio = np.abs(mean) * rstd
                     ratio = np.where(np.isnan(ratio), f32(np.inf), ratio)
-                    bm = TILES[tile_of(c)][0]
+                    bm = tile_dims(tile_of(c))[0]
                     mt, nt = grid_of(tile_of(c), M, N)
+                    slots = min(GUARD_SLOTS, planned_grid(c))      # (the persistent form: G workgroups share the tiles)
                     for b in range(mt * nt):      # (which row tile a workgroup id owns does not matter to the maximum over the slots)
                         tm = b // nt
-                        got["guard"][b % GUARD_SLOTS] = max(got["guard"][b % GUARD_SLOTS], ratio[tm * bm:(tm + 1) * bm].max())
+                        got["guard"][b % slots] = max(got["guard"][b % slots], ratio[tm * bm:(tm + 1) * bm].max())
             if c.bias:
                 v = v + _flat_load(inp["bias"][None, :], 0, 0, 0, 1, N, shift=1 if mutant == "bias_one_column_right" else 0)
             act = c.act
@@ -764,7 +804,7 @@ def emulate(c: Case, inp: Dict, order: int = 0, mutant: Optional[str] = None) ->
     v = v.astype(f32)
     keep = None
     if mutant in ("two_tiles_swapped", "one_tile_computed_twice"):
-        bm, bn = TILES[tile_of(c)][:2]
+        bm, bn = tile_dims(tile_of(c))[:2]
         rows = min(bm, M)
         if mutant == "two_tiles_swapped":
             v = v.copy()

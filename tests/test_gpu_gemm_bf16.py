@@ -36,11 +36,13 @@ def _host(t: torch.Tensor) -> np.ndarray:
     return a.view(np.uint16) if a.dtype == np.int16 else a
 
 
-def launch(c: G.Case, inp: dict):
-    """(return code, error text, {output name: whole buffer after the launch})"""
+def launch(c: G.Case, inp: dict, m_live=None):
+    """(return code, error text, {output name: whole buffer after the launch}).  m_live: a row count that goes to the device and the
+    "ex" / "ln" launch through ufnd_gemm_bf16_live / ufnd_gemm_bf16_ln_live (tests/test_gpu_gemm_pp_cases.py)."""
     L = _lib()
     lib, s = L.lib(), L.stream_ptr(torch.device(DEV))
     t = {k: _dev(v) for k, v in inp.items() if isinstance(v, np.ndarray)}
+    live = None if m_live is None else torch.tensor([m_live], dtype=torch.int32, device=DEV)
 
     def p(name, ld=0):
         if name not in t:
@@ -52,6 +54,9 @@ def launch(c: G.Case, inp: dict):
     M, N, K = c.M, c.N, c.K
     if c.entry == "gemm":
         rc = lib.ufnd_gemm_bf16(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, s)
+    elif c.entry == "ex" and live is not None:
+        rc = lib.ufnd_gemm_bf16_live(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, c.tile,
+                                     live.data_ptr(), s)
     elif c.entry == "ex":
         rc = lib.ufnd_gemm_bf16_ex(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, c.tile, s)
     elif c.entry == "ln":
@@ -59,7 +64,11 @@ def launch(c: G.Case, inp: dict):
                       out_stats=p("ostats", (N // 32) * 2), a_parts=c.parts if c.ln == "fold" else 0, r_parts=c.parts if c.ln == "rln" else 0,
                       a_eps=G.EPS, r_eps=G.EPS, width=K if c.ln == "fold" else N, tile_cfg=c.tile, residual_bf16=p("resb"), ldrb=c.ldrb,
                       guard=p("guard"))
-        rc = lib.ufnd_gemm_bf16_ln(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, C.byref(ln), s)
+        if live is not None:
+            rc = lib.ufnd_gemm_bf16_ln_live(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, C.byref(ln),
+                                            live.data_ptr(), s)
+        else:
+            rc = lib.ufnd_gemm_bf16_ln(p("A"), p("W"), p("bias"), res, ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldo, c.ldf, c.act, C.byref(ln), s)
     else:
         rc = lib.ufnd_gemm_bf16_dgrad(p("A"), p("W"), res, p("aux"), ob, of, M, N, K, c.lda, c.ldw, c.ldr, c.ldaux, c.ldo, c.ldf, c.act, s)
     torch.cuda.synchronize()
@@ -67,18 +76,22 @@ def launch(c: G.Case, inp: dict):
     return rc, err, {k: _host(t[k]) for k in ("of", "ob", "ostats", "guard") if k in t}
 
 
-def measure(c: G.Case):
-    """(worst error / bound, the output it is on, unequal elements or None outside the exact family) of one case on the GPU"""
-    inp = G.make(c)
+def measure(c: G.Case, inp=None, refs=None, cus=None, keep=None):
+    """(worst error / bound, the output it is on, unequal elements or None outside the exact family) of one case on the GPU.  A caller
+    that launches a case more than once passes its inputs and reference (neither is written to) and a dict `keep` that receives the
+    output buffers; cus: the device's CU count (the persistent form's grid, G.check)."""
+    inp = G.make(c) if inp is None else inp
     rc, err, got = launch(c, inp)
+    if keep is not None:
+        keep.update(got)
     if c.refuse:
         assert rc == 1 and c.refuse in err, (c.id, rc, err)
         for k, v in got.items():      # nothing was launched
             assert np.array_equal(v, inp[k], equal_nan=(v.dtype != np.uint16)), (c.id, k)
         return 0.0, "refused", None
     assert rc == 0, (c.id, rc, err)
-    refs = G.reference(c, inp)
-    ratios = G.check(c, inp, got, refs)
+    refs = G.reference(c, inp) if refs is None else refs
+    ratios = G.check(c, inp, got, refs, cus)
     key = max(ratios, key=lambda k: ratios[k])
     return ratios[key], key, (G.unequal(c, got, refs) if G.is_bit_exact(c) else None)
 

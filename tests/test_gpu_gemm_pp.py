@@ -1,7 +1,8 @@
 """GPU: the persistent, software-pipelined bf16 GEMM (csrc/gemm_bf16_pp.hpp, tile id 64) against the one-tile-per-workgroup
 kernels.  The two are held BIT-IDENTICAL: a row's results must not depend on which kernel -- or which batch -- computed it
 (the encoders mix both within one pass), and a race in the persistent kernel's hand-counted vmcnt schedule would show up as a
-mismatch on some launch, so every comparison is repeated on fresh output buffers."""
+mismatch on some launch, so every comparison is repeated on fresh output buffers.
+(Against float64, at edge shapes, strides and partial counts, with poisoned operands: tests/gemm_pp_cases.py, tests/test_gpu_gemm_pp_cases.py.)"""
 import ctypes as C
 
 import pytest

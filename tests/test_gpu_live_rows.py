@@ -299,6 +299,7 @@ PP_CASES = [
 
 @pytest.mark.parametrize("M,N,mode,act", PP_CASES)
 def test_gemm_live_persistent(M, N, mode, act):
+    """(the reference is the same kernel at full capacity; against float64: tests/test_gpu_gemm_pp_cases.py, the LiveCase table of tests/gemm_pp_cases.py)"""
     case = _Gemm(M, N, mode, act, PP, seed=M + N + act, pp=True)
     ref = case.reference()
     extra = [PANEL * p + d for p in range(1, 8) for d in (0, 1, 77)]      # every live panel count, whole and ragged

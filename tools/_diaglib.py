@@ -68,6 +68,8 @@ def diag() -> C.CDLL:
             f.restype = I
         d.ufnd_diag_gemm_bf16_plan.argtypes = [I] + [P] * 7 + [I] * 11 + [C.POINTER(L.GemmLn), IP]
         d.ufnd_diag_gemm_bf16_plan.restype = I
+        d.ufnd_diag_gemm_pp_plan.argtypes = [P] * 6 + [I] * 9 + [C.POINTER(L.GemmLn), I, I, IP]
+        d.ufnd_diag_gemm_pp_plan.restype = I
         d.ufnd_diag_gemm_f32_sizes.argtypes = [IP]
         d.ufnd_diag_gemm_f32_sizes.restype = None
         _d = d
@@ -122,3 +124,21 @@ def gemm_bf16_plan(entry: str, *, A=0, W=0, bias=None, residual=None, aux=None, 
     if rc != 0:
         return rc, None, diag().ufnd_diag_last_error().decode()
     return 0, dict(zip(GEMM_BF16_PLAN_FIELDS, out)), ""
+
+
+GEMM_PP_PLAN_FIELDS = ("mode", "act", "m_tiles", "n_tiles", "pp_rows", "G", "picked", "stat_parts")
+GEMM_PP_MODES = ("plain", "fold", "rln", "res")      # pp::PLAIN, FOLD, RES_LN, RES (csrc/gemm_bf16_pp.hpp)
+
+
+def gemm_pp_plan(*, A=0, W=0, bias=None, residual=None, out_bf16=None, out_f32=None, M=0, N=0, K=0, lda=0, ldw=0, ldr=0, ldo=0, ldf=0,
+                 act=0, ln=None, tile=64, cus=256) -> tuple:
+    """Host-only validation, mode, walk geometry and automatic choice of one call of the persistent bf16 GEMM (csrc/gemm_bf16_pp.hpp)
+    for a device of `cus` compute units: the arguments of ufnd_gemm_bf16_ln (ln: L.GemmLn, whose tile_cfg is not read) or, with
+    ln = None, of ufnd_gemm_bf16_ex; tile = 64 is a forced call, tile < 0 the automatic choice.  Addresses are integers that are never
+    dereferenced (no GPU needed).  Returns (rc, dict of GEMM_PP_PLAN_FIELDS or None, error text)."""
+    out = (C.c_int * len(GEMM_PP_PLAN_FIELDS))()
+    rc = diag().ufnd_diag_gemm_pp_plan(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act,
+                                       C.byref(ln) if ln is not None else None, tile, cus, out)
+    if rc != 0:
+        return rc, None, diag().ufnd_diag_last_error().decode()
+    return 0, dict(zip(GEMM_PP_PLAN_FIELDS, out)), ""

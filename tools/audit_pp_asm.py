@@ -9,7 +9,9 @@ a branch: the register copies in front of the branch read the statistics before 
 failure.  Every retiring wait carries a `; PPRETIRE <registers>` comment naming what it retires.
 
 Also required: no scratch (a spill's reload waits vmcnt(0) and a spill's store changes the hand-counted queue), no packed fp32
-instruction, and no compiler-inserted vmcnt wait inside the K loops.
+instruction, no compiler-inserted vmcnt wait inside the K loops, and no VALU write to the data registers of a 96- / 128-bit store
+within two wait states behind it (the compiler leaves that pair unguarded when the store's offset is in an SGPR; it corrupted the
+output of the stamps build of the diagnostics library, tests/test_gpu_gemm_pp_cases.py).
 
 usage: audit_pp_asm.py [file.s]     (without an argument: compiles csrc/gemm_bf16_pp.hip with -save-temps into a temp dir)"""
 import re
@@ -86,6 +88,26 @@ def audit(asm_path: Path) -> list:
                 while k < len(L) and (not L[k].split(";")[0].strip() or L[k].split(";")[0].strip().startswith(".")):
                     k += 1
                 compiler_waits.append((i, c, L[k].strip() if k < len(L) else ""))
+            m = re.match(r"(buffer|global)_store_dwordx[34]$", op)
+            if m:
+                # store-data hazard: a VALU write to the data registers of a store wider than 64 bits within two wait states reaches
+                # the stored value in part of the lanes, and with the offset in an SGPR the compiler inserts no wait state (seen in
+                # the stamps build: `buffer_store_dwordx4 v[2:5] ..; v_add_f32 v2, ..`).  MFMA results are written passes later.
+                data = set(regs(rest.split(",")[0 if m.group(1) == "buffer" else 1]))
+                ws, k = 0, i + 1
+                while k < len(L) and ws < 2:
+                    nxt = L[k].split(";")[0].strip()
+                    k += 1
+                    if not nxt or nxt.startswith(".") or nxt.endswith(":"):
+                        continue
+                    nop, _, nrest = nxt.partition(" ")
+                    if nop == "s_nop":
+                        ws += int(nrest.strip()) + 1
+                        continue
+                    if nop.startswith("v_") and not nop.startswith("v_mfma") and set(regs(nrest.split(",")[0])) & data:
+                        problems.append((name, i, f"VALU write to a wide store's data registers {ws} wait state(s) behind it: {c} / {nxt}"))
+                        break
+                    ws += 1
             if op.startswith("s_"):
                 continue
             hit = set(regs(rest)) & set(pend)

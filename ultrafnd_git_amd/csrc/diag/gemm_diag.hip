@@ -109,7 +109,8 @@ extern "C" int ufnd_diag_qkv_attention_tiles_stamps(const void* X, const void* W
 //   out   {tile, m_tiles, n_tiles, xcd_cols, out_stats partials per row (0 without out_stats), bm, bn, A ring depth, W ring depth,
 //          ln_aware, part of the product library, has a backward kernel}
 // The persistent form (gemm_bf16_pp.hpp) is not planned here: its automatic choice reads the device's CU count.  A shape it could
-// take (ufnd_diag_pp_shape_ok) is refused for the automatic forward entries, and so is UFND_GEMM_TILE_PERSISTENT.
+// take (ufnd_diag_pp_shape_ok) is refused for the automatic forward entries, and so is UFND_GEMM_TILE_PERSISTENT.  Its own plan
+// entry, which takes the CU count as an argument, is ufnd_diag_gemm_pp_plan (gemm_pp_diag.hip).
 int ufnd_diag_pp_shape_ok(int M, int N, int K);      // gemm_pp_diag.hip
 extern "C" int ufnd_diag_gemm_bf16_plan(int entry, const void* A, const void* W, const float* bias, const float* residual, const void* aux,
                                         const void* out_bf16, const float* out_f32, int M, int N, int K, int lda, int ldw, int ldr, int ldaux,

@@ -10,11 +10,7 @@ __attribute__((visibility("hidden"))) int ufnd_pp_pick(const void* gemm_args) { 
 __attribute__((visibility("hidden"))) int ufnd_pp_stat_parts(int N) { return pp_stat_parts(N); }
 __attribute__((visibility("hidden"))) int ufnd_pp_launch(void* gemm_args, void* stream) {
   GemmArgs& a = *static_cast<GemmArgs*>(gemm_args);
-  if (a.out_stats && (pp_stat_parts(a.N) == 0 || !ufnd_aligned(a.out_stats, 16))) {
-    ufnd_set_error("gemm_bf16 (persistent form): out_stats unsupported for this shape");
-    return UFND_ERR_INVALID;
-  }
-  int rc = launch_pp(a, 0, (hipStream_t)stream);
+  int rc = launch_pp(a, 0, (hipStream_t)stream);      // (every argument check of this form: pp_check_args)
   if (rc != UFND_OK) return rc;
   UFND_CHECK_LAUNCH();
   return UFND_OK;

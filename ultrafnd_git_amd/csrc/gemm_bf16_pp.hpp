@@ -395,8 +395,16 @@ void gemm_pp_kernel(const GemmArgs a) {
     bf16x8 o;
 #pragma unroll
     for (int q = 0; q < 8; ++q) o[q] = (__bf16)v8[q];
+    const u32x4_t ov = __builtin_bit_cast(u32x4_t, o);
     if constexpr (DBG & (4 | 16)) asm volatile("" : : "v"(o));
-    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsOut, vo_out, ((m0p + prow_of(P)) * a.ldo + n0p) * 2, UFND_GEMM_OUT_NT ? 2 : 0);      // (aux bit 1 = nt)
+    else __builtin_amdgcn_raw_buffer_store_b128(ov, rsOut, vo_out, ((m0p + prow_of(P)) * a.ldo + n0p) * 2, UFND_GEMM_OUT_NT ? 2 : 0);      // (aux bit 1 = nt)
+    // Stamps build only (the product instantiations are unchanged): keep the store's data registers alive for two wait states.  A
+    // VALU write to the data registers of a store wider than 64 bits in the very next instruction reaches the stored value in part
+    // of the lanes, and with the offset in an SGPR the compiler inserts no wait state for it: in the stamps build the allocator
+    // reused the first data register as a temporary of the next patch's register phase (`buffer_store_dwordx4 v[2:5] ..; v_add_f32
+    // v2, ..` in the un-overlapped last epilogue) and a few dozen elements of a workgroup's last tile came out wrong, other ones on
+    // every launch.  tools/audit_pp_asm.py now refuses such a pair in the product listing, which has none.
+    if constexpr ((DBG & 1) && !(DBG & (4 | 16))) asm volatile("s_nop 1" : : "v"(ov) : "memory");
   };
   auto slice_rows = [&](auto P_, const f32x4& rres) { slice_rows_a(P_); slice_rows_b(P_, rres); slice_rows_c(P_); };
 
@@ -649,7 +657,9 @@ static int pp_mode_of(const GemmArgs& a) {
   if (a.residual_b) return a.out_stats ? (a.r_stats ? pp::RES_LN : pp::RES) : -1;
   return (a.out_stats || a.r_stats) ? -1 : pp::PLAIN;
 }
-static int pp_cu_count() {
+// the device's CU count; `override` > 0 answers instead of the device (the host-only plan entry of the diagnostics library)
+static int pp_cu_count(int override = 0) {
+  if (override > 0) return override;
   static const int n = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
@@ -657,26 +667,66 @@ static int pp_cu_count() {
   }();
   return n;
 }
-// launch; dbg = 1: the stamps build (diagnostics library only)
-static int launch_pp(GemmArgs& a, int dbg, hipStream_t stream) {
+static int pp_stat_parts(int N) { return ((N / 32) % 2 == 0 && N / 32 <= 24) ? N / 32 : 0; }
+
+// Every host-side condition of the persistent form, in one place: launch_pp (the product entry ufnd_pp_launch and the stamps entry of
+// the diagnostics library), pp_pick (quiet: a call that fails here is not picked) and the host-only plan entry
+// (diag/gemm_pp_diag.hip: ufnd_diag_gemm_pp_plan) call this function, so a check cannot exist in one and be missing in another.
+// Nothing here dereferences an operand or touches the device.
+//
+// Reach: every global address of the kernel is a 32-bit byte offset from the operand's base (sAc, sWc, soff, vo_out, vo_res,
+// vo_stat and the buffer instructions' scalar offsets are int / unsigned; the descriptors carry num_records = 0x7fffffff), so every
+// operand addressed that way must END below 2^31 bytes.  What the hardware does with an offset past that (dropped, wrapped or
+// served) has not been measured and is not to be found out by trying: such a call is refused.  (The statistics operands a_stats /
+// r_stats and the column vectors are addressed through 64-bit pointers.)
+static int pp_check_args(const GemmArgs& a, bool quiet = false) {
+#define UFND_PP_REFUSE(...)                       \
+  do {                                            \
+    if (!quiet) ufnd_set_error(__VA_ARGS__);      \
+    return UFND_ERR_INVALID;                      \
+  } while (0)
   const int mode = pp_mode_of(a);
-  if (mode < 0 || !pp_shape_ok(a.M, a.N, a.K)) {
-    ufnd_set_error("gemm_bf16 (persistent form): unsupported call (M=%d N=%d K=%d: needs K = 768, M %% 256 == 0, N %% 128 == 0, bf16 output only, "
+  if (mode < 0 || !pp_shape_ok(a.M, a.N, a.K))
+    UFND_PP_REFUSE("gemm_bf16 (persistent form): unsupported call (M=%d N=%d K=%d: needs K = 768, M %% 256 == 0, N %% 128 == 0, bf16 output only, "
                    "bf16 residual stream with out_stats)", a.M, a.N, a.K);
-    return UFND_ERR_INVALID;
-  }
-  if (mode != pp::FOLD && mode != pp::PLAIN && a.act != UFND_ACT_NONE) {
-    ufnd_set_error("gemm_bf16 (persistent form): a residual call carries no activation");
-    return UFND_ERR_INVALID;
-  }
+  if (mode != pp::FOLD && mode != pp::PLAIN && a.act != UFND_ACT_NONE)
+    UFND_PP_REFUSE("gemm_bf16 (persistent form): a residual call carries no activation");
+  if (a.out_stats && (pp_stat_parts(a.N) == 0 || !ufnd_aligned(a.out_stats, 16)))
+    UFND_PP_REFUSE("gemm_bf16 (persistent form): out_stats unsupported for this shape");
+  const long long T = (long long)(a.M / pp::BM) * (a.N / pp::BN);
+  if (T < 8) UFND_PP_REFUSE("gemm_bf16 (persistent form): %d tiles are too few", (int)T);      // (G = min(CUs, T) & ~7 with at least 8 CUs)
+  const long long lim = 1ll << 31, M = a.M, N = a.N, K = a.K;
+  const struct { const char* name; bool present; long long bytes; } reach[] = {
+      // (the narrowest rows first: out_stats can only pass the limit together with A and out_bf16, and is the one named then)
+      {"out_stats", a.out_stats != nullptr, M * (N / 32) * 8},
+      {"residual_bf16", a.residual_b != nullptr, ((M - 1) * a.ldrb + N) * 2},
+      {"out_bf16", true, ((M - 1) * a.ldo + N) * 2},
+      {"W", true, ((N - 1) * a.ldw + K) * 2},
+      {"A", true, ((M - 1) * a.lda + K) * 2},
+  };
+  for (const auto& r : reach)
+    if (r.present && r.bytes >= lim)
+      UFND_PP_REFUSE("gemm_bf16 (persistent form): %s reaches %lld bytes: the kernel's 32-bit byte offsets need every operand to end below 2^31 bytes",
+                     r.name, r.bytes);
+#undef UFND_PP_REFUSE
+  return UFND_OK;
+}
+// the walk's geometry for `cus` compute units, into the arguments; returns the grid G (after pp_check_args: G >= 8)
+static int pp_geometry(GemmArgs& a, int cus) {
   a.m_tiles = a.M / pp::BM;
   a.n_tiles = a.N / pp::BN;
   a.pp_rows = 4;
   const int T = a.m_tiles * a.n_tiles;
-  int G = pp_cu_count();
-  G = (G < T ? G : T) & ~7;
+  return (cus < T ? cus : T) & ~7;
+}
+// launch; dbg = 1: the stamps build (diagnostics library only)
+static int launch_pp(GemmArgs& a, int dbg, hipStream_t stream) {
+  int rc = pp_check_args(a);
+  if (rc != UFND_OK) return rc;
+  const int mode = pp_mode_of(a);
+  const int G = pp_geometry(a, pp_cu_count());
   if (G < 8) {
-    ufnd_set_error("gemm_bf16 (persistent form): %d tiles are too few", T);
+    ufnd_set_error("gemm_bf16 (persistent form): %d tiles are too few", a.m_tiles * a.n_tiles);
     return UFND_ERR_INVALID;
   }
   const dim3 grid(G), block(512);
@@ -717,7 +767,6 @@ static int launch_pp(GemmArgs& a, int dbg, hipStream_t stream) {
   return UFND_OK;
 }
 
-static int pp_stat_parts(int N) { return ((N / 32) % 2 == 0 && N / 32 <= 24) ? N / 32 : 0; }
 // Automatic choice of the persistent form (measured on MI355X, tools/gemm_pp_bench.py, interleaved rounds, cold operands;
 // profiles/r04_gemm_pp_*): it wins where the one-tile kernels' epilogue is long -- a folded LayerNorm + GELU / quick-GELU
 // (FFN1: 16,384 x 3072 106 -> 101 us, 65,536 x 3072 436 -> 393 us, ViT 6,400 x 3072 46.1 -> 42.9 us) -- and a workgroup gets at
@@ -727,13 +776,14 @@ static int pp_stat_parts(int N) { return ((N / 32) % 2 == 0 && N / 32 <= 24) ? N
 // and every mode wins (profiles/r04_gemm_pp_bench.txt, last blocks): 65,536 rows Q/K/V 293 -> 268 us, LayerNorm-residual out-projection
 // 145 -> 114 us; 32,768 x 768 (exactly 3 tiles per workgroup) 66.6 -> 55.0 us; 24,576 x 2304 (6.75) 109.6 -> 97.1 us -- while 16,384 x 2304
 // (4.5 tiles per workgroup: a fifth round that is half empty) loses, 66.7 -> 70.1 us.  So: at least three tiles per workgroup AND at
-// least 93 % of the last round filled.
-static bool pp_pick(const GemmArgs& a) {
+// least 93 % of the last round filled.  A call pp_check_args refuses (an operand that reaches 2^31 bytes among them) is never
+// picked: the automatic choice falls back to a one-tile kernel.
+static bool pp_pick(const GemmArgs& a, int cus = 0) {
+  if (pp_check_args(a, true) != UFND_OK) return false;
   const int mode = pp_mode_of(a);
-  if (mode < 0 || !pp_shape_ok(a.M, a.N, a.K) || (mode != pp::FOLD && mode != pp::PLAIN && a.act != UFND_ACT_NONE)) return false;
   const long long tiles = (long long)(a.M / pp::BM) * (a.N / pp::BN);
   if (mode == pp::FOLD && a.act != UFND_ACT_NONE && tiles >= pp::MIN_TILES) return true;
-  const long long G = pp_cu_count() & ~7, rounds = (tiles + G - 1) / G;
+  const long long G = pp_cu_count(cus) & ~7, rounds = (tiles + G - 1) / G;
   return G > 0 && tiles >= 3 * G && tiles * 100 >= rounds * G * 93;
 }
 
