@@ -1053,7 +1053,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
   X(26, 256, 192, 4, 2, 2, 2, 32, 0, 0)  /* 32x32x16 MFMA form (measured 2-4 % slower than 16x16x32 on every shape) */ \
   X(27, 128, 128, 4, 2, 3, 3, 32, 0, 0)                                                                    \
   X(28, 256, 144, 8, 1, 2, 2, 16, 1, 1)  /* 100 KiB: N=2304 -> 16 x 16 = 256 tiles (wave tile 32x144; W pieces dealt unevenly) */ \
-  X(29, 128, 128, 4, 2, 2, 2, 16, 1, 0)  /*  64 KiB, 8 waves (wave tile 32x64, 110 registers): 2 blocks/CU (measured: no gain) */
+  X(29, 128, 128, 4, 2, 2, 2, 16, 1, 0)  /*  64 KiB, 8 waves (wave tile 32x64, 110 registers): 2 blocks/CU (measured: no gain) */ \
+  X(30, 256, 128, 4, 2, 3, 2, 16, 1, 0)  /* 128 KiB: tile 2 with the W ring one K-step ahead, the persistent form's rings (measured on the packed text pass's N = 768 launches: FFN2 61 us against tile 2's 50, auto_cfg) */
 
 #ifdef UFND_DIAG
 #define UFND_TILE_BUILT(PROD_) 1
@@ -1177,6 +1178,14 @@ static int auto_cfg(int M, int N, int K) {
   // ... and where it fills ONE round (ViT QKV at 6,400 rows: 225 tiles instead of 300 of 256x192 in 1.17 rounds: 40 -> 29.5 us
   // per launch, step +0.8 % in two interleaved pairs)
   if (N % 256 == 0 && N >= 2048 && tiles(15) >= 190 && tiles(15) <= 256) return 15;
+  // (N = 768 at 16,384 rows lands here too: 64 x 4 = 256 tiles, right when every row is computed.  The packed text pass launches these
+  //  shapes through the live-row entries, where 34 to 40 of the 64 row panels are live: 136 to 160 workgroups of 256x192, each carrying
+  //  the full tile.  This function sees (M, N, K) at the capacity, never the live count, so it keeps returning 22; the pass itself names
+  //  tile 2 (256x128: 204 to 240 live workgroups, still one round) for its out-projection and FFN2 -- BertTextEncoder.text_narrow_tile.
+  //  Measured inside the encoder pass: FFN2 74.2 -> 50.3 us, out-projection 28.6 -> 21.3 us per launch.  Not kept: tile 30, the same
+  //  tile with a 2-slot W ring (61.0 / 23.2 us); 128x192 and 128x128 give these live counts 272 to 480 workgroups, a second round.
+  //  With every row live tile 2 is 384 workgroups, a round and a half, and 2.8 % of the step lost; the crossover is the round boundary, 42 live panels
+  //  (the bf16 GEMM section).  Step: 1.0737 -> 1.0512 ms, medians of three interleaved pairs, profiles/text_narrow_tile_summary.md.)
   if (N % 192 == 0 && tiles(22) >= 160) return 22;
   if (N >= 2048) {                                     // wide N, fewer rows (ViT QKV / FFN1): 32-row wave tiles
     if (N % 192 == 0 && N >= 3072) return 17;          //   128x192

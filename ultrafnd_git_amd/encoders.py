@@ -145,6 +145,8 @@ class _EncoderBase(nn.Module):
         # GEMM tile per Linear ("qkv", "out", "ffn1", "ffn2"): -1 = the library's own choice for the shape.  Set by the
         # trainer when the encoder runs on a compute-unit partition (a launch wants about one tile per CU it may use).
         self.tiles: Dict[str, int] = {}
+        # ... and the tiles a pass chose for its own live-row launches (BertTextEncoder.live_tiles), which `tiles` overrides
+        self._live_tiles: Dict[str, int] = {}
         self._guard: Optional[torch.Tensor] = None      # device float: largest |mean| / std any folded LayerNorm has seen
         self._w: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         self._packed: Optional[dict] = None
@@ -251,7 +253,14 @@ class _EncoderBase(nn.Module):
     # ---- thin wrappers over the C ABI
     # m_live (BertTextEncoder's packed pass): the device address of an int holding how many of the operands' rows are live.  With it a
     # Linear / LayerNorm computes the first *m_live rows of its capacity-sized operands only (include/ultrafnd_hip.h,
-    # ufnd_gemm_bf16_live): same launches, same shapes, same tiles.  None: every row.
+    # ufnd_gemm_bf16_live): same launches, same shapes (the tile: _tile_for).  None: every row.
+    def _tile_for(self, which, m_live) -> int:
+        """The GEMM tile of a Linear's launch: the `tiles` entry, else (a live-row launch) the running pass's own choice, else -1."""
+        t = self.tiles.get(which)
+        if t is None and m_live is not None:
+            t = self._live_tiles.get(which)
+        return -1 if t is None else t
+
     def _gemm(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, which=None, m_live=None):
         M = A.shape[0]
         N, K = W.shape
@@ -259,7 +268,7 @@ class _EncoderBase(nn.Module):
                                             L.ptr(out_f32), M, N, K, A.stride(0), W.stride(0),
                                             residual.stride(0) if residual is not None else 0,
                                             out_bf16.stride(0) if out_bf16 is not None else 0,
-                                            out_f32.stride(0) if out_f32 is not None else 0, act, self.tiles.get(which, -1),
+                                            out_f32.stride(0) if out_f32 is not None else 0, act, self._tile_for(which, m_live),
                                             m_live, L.stream_ptr(A.device)), "ufnd_gemm_bf16_live")
 
     def _gemm_ln(self, A, W, bias, out_bf16=None, out_f32=None, residual=None, act=ACT_NONE, a_stats=None, colsum=None,
@@ -275,7 +284,7 @@ class _EncoderBase(nn.Module):
         ln.r_parts = r_stats.shape[1] if r_stats is not None else 0
         ln.a_eps = ln.r_eps = eps
         ln.width = self.hidden
-        ln.tile_cfg = self.tiles.get(which, -1)
+        ln.tile_cfg = self._tile_for(which, m_live)
         if residual_bf16 is not None:
             ln.residual_bf16, ln.ldrb = residual_bf16.data_ptr(), residual_bf16.stride(0)
         if a_stats is not None:      # fold guard: the launch reports the largest |mean| / std among the rows it folds
@@ -456,6 +465,15 @@ class BertTextEncoder(_EncoderBase):
         # a batch whose slot bins get a compute unit each (256: one round either way) stays on them -- measured at B = 32, 12 heads:
         # the tile workgroup is the longer one, the step 1 % slower (profiles/text_tile_pack_summary.md).
         self.text_tile_min_grid = 257
+        # the packed L = 128 pass's out-projection and FFN2 (N = 768, residual + row statistics) from text_narrow_min_rows capacity rows on:
+        # the 256x128 tile (2) instead of the library's choice for the capacity, 256x192 (22).  The library sizes 64 x 4 = 256 workgroups
+        # for 16,384 rows; the 34 to 40 live row panels of a batch of 16- to 128-token samples give 136 to 160 of them, 204 to 240 of
+        # 256x128 -- one round either way, each workgroup a third shorter (FFN2 74 -> 50 us, out-projection 29 -> 21 us per launch).
+        # Above 42 live panels (66 % of the capacity) the 256x128 launch spills into a second round; measured crossover and the
+        # full-length batch (+2.8 % there): DESIGN.md's bf16 GEMM section, profiles/text_narrow_tile_summary.md.  22 restores the library's choice; a
+        # `tiles` entry for the op wins over this.  Bit-identical rows either way: a row does not depend on the tile that computed it.
+        self.text_narrow_tile = 2
+        self.text_narrow_min_rows = 8192
         self.layers, self.inter, self.vocab, self.eps = layers, intermediate, vocab_size, eps
         self.max_position = max_position
         w, init = self._w, self._seeded_init()
@@ -522,6 +540,13 @@ class BertTextEncoder(_EncoderBase):
         if Lq > self.max_position:
             raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
 
+    def live_tiles(self, packed: bool, B: int, Lq: int) -> Dict[str, int]:
+        """The tiles a (B, L) pass names for its own live-row launches (text_narrow_tile, above): fixed by the pass's form and shape
+        alone, so a captured pass never reads the live row count back.  N = 768 only: the width the choice was measured at."""
+        if packed and Lq == 128 and B * Lq >= self.text_narrow_min_rows and self.hidden == 768:
+            return {"out": self.text_narrow_tile, "ffn2": self.text_narrow_tile}
+        return {}
+
     def _pass(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, packed: bool, n_layers: Optional[int] = None, pool: bool = True,
               tail=None) -> dict:
         """One pass over a (B, L) batch: embeddings, the first n_layers layers (all by default) and, with pool, the pooled features.
@@ -540,6 +565,7 @@ class BertTextEncoder(_EncoderBase):
         fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0      # a layer's Q/K/V projection + attention as one launch
         cu = b["cu"] if packed else None                 # packed rows: sample b's are cu[b] .. cu[b+1] ...
         live = _live_ptr(cu) if packed else None         # ... and cu[B], their count, stays on the device: the pack kernel writes it
+        self._live_tiles = self.live_tiles(packed, B, Lq)
         tiled = packed and fuse and self.text_sample_tiles and "tiles" in b and B * (self.heads // 2) >= self.text_tile_min_grid
         self._pack_embed(ids, mask, b, B, Lq, packed, fuse, tiled, live)
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
