@@ -11,6 +11,8 @@
 //   attn_pv               O^T += V^T P^T of the block         (A = V^T by transposed LDS reads, B = P^T: the score accumulators in place)
 //   attn_finish           a query's row sum over its four lanes and the reciprocal
 //   attn_store_ctx        the normalised output row, rounded to bf16
+//   attn_unit             the loop of the fused kernels around all of these: one unit of 32 queries against the key blocks of its sample,
+//                         all operands in LDS images (attention.hip stages K / V through LDS block by block and keeps its own loop)
 // Lane (fr, g) = (lane & 15, lane >> 4).  `key_row` maps a key index of the block to its row in the K / V image.
 //
 // online_softmax_block: one 64-key block of the online softmax, for one 16-query tile column of a wave.
@@ -200,5 +202,41 @@ __device__ __forceinline__ void attn_store_ctx(__bf16* dst, const f32x4 (&o)[4][
   for (int dt = 0; dt < 4; ++dt) {
     bf16x4 ov = {(__bf16)(o[dt][qt][0] * inv), (__bf16)(o[dt][qt][1] * inv), (__bf16)(o[dt][qt][2] * inv), (__bf16)(o[dt][qt][3] * inv)};
     *reinterpret_cast<bf16x4*>(dst + dt * 16) = ov;
+  }
+}
+
+// One unit of the fused projection + attention kernels: a wave's 32 queries of one head against the NKB 64-key blocks of their sample,
+// all three operands in LDS images.  q_row maps a query of the unit (0..31), key_row a key of the sample (0 .. 64 NKB - 1) to its image
+// row; kbias holds the sample's 64 NKB key-bias words (16-B aligned); SKIP: the masked-block skip of attention.hip runs.  The first nq
+// queries are live: query q's normalised output goes to ctx + q * ldc (ctx = the unit's first query at its head's first column).
+template <int NKB, bool SKIP, class QRow, class KeyRow>
+__device__ __forceinline__ void attn_unit(const char* qimg, const char* kimg, const char* vimg, QRow q_row, KeyRow key_row, const float* kbias,
+                                          const float scale_log2e, const int lane, __bf16* ctx, const int ldc, const int nq) {
+  constexpr int KB = 64, KT = KB / 16;
+  const int g = lane >> 4, fr = lane & 15;
+  bf16x8 qf[2][2];
+  attn_q_frags(qimg, q_row, fr, g, qf);
+  f32x4 o[4][2];
+  float m_run[2], l_run[2];
+  attn_init(o, m_run, l_run);
+#pragma unroll
+  for (int kb0 = 0; kb0 < NKB * KB; kb0 += KB) {
+    if constexpr (SKIP) {
+      if (masked_block_is_noop(kbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see above)
+    }
+    const auto blk_row = [&](int k) { return key_row(kb0 + k); };
+    f32x4 sc[KT][2];
+    attn_scores<KT>(kimg, blk_row, qf, fr, g, sc);
+    const bool any_masked = __any(kbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
+    bf16x8 pf[KT / 2][2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, kbias + kb0, any_masked, g, scale_log2e, m_run, l_run, pf, o);
+    attn_pv<KT>(vimg, blk_row, pf, o, fr, g);
+  }
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const float inv = attn_finish(l_run[qt]);
+    const int q = qt * 16 + fr;
+    if (q < nq) attn_store_ctx(ctx + (size_t)q * ldc + 4 * g, o, qt, inv);
   }
 }

@@ -126,51 +126,16 @@ extern "C" int ufnd_gemm_bf16_ln(const void* A, const void* W, const float* bias
   return ufnd_gemm_bf16_ln_live(A, W, bias, residual, out_bf16, out_f32, M, N, K, lda, ldw, ldr, ldo, ldf, act, ln, nullptr, stream_);
 }
 
-// What the three fused Q/K/V projection + attention entries share, after their own shape checks: the operand checks, the
-// projection's arguments (M rows of X against the 3H stacked weight rows), the folded LayerNorm and the attention output.
-// `name` is the entry's name in its messages.
-static int qkv_attention_args(const char* name, GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, void* ctx, int M, int heads, int ldx,
-                              int ldw, const ufnd_gemm_ln* ln) {
-  const int H = heads * 64;
-  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
-               "%s: strides must be multiples of 8 and pointers 16-B aligned", name);
-  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "%s: bias alignment", name);
-  a = GemmArgs{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, M, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
-  if (ln && ln->a_stats) {
-    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "%s: colsum / a_stats alignment", name);
-    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "%s: a_parts=%d width=%d", name, ln->a_parts, ln->width);
-    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
-    a.inv_h = 1.0f / (float)ln->width;
-    a.guard = ln->guard;
-  }
-  a.att_ctx = (__bf16*)ctx;
-  a.att_h = H;
-  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
-  return UFND_OK;
-}
-
 // BertSelfAttention of one layer in ONE launch: fused Q/K/V projection (optionally of LayerNorm(X), folded) + attention.
 // bins / nbins (with cu_seqlens; ufnd_text_pack_bins): workgroup row tm runs bin tm's four 32-row slots, tm < *nbins
+// (checks and launch arguments of the three geometries: gemm_bf16_checks.hpp)
 extern "C" int ufnd_qkv_attention_bf16_bins(const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
                                             const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B,
                                             int L, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
-  UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention: null operand");
-  UFND_REQUIRE(!bins == !nbins && (!bins || cu_seqlens), "qkv_attention: slot bins need cu_seqlens, bins and nbins");
-  UFND_REQUIRE(L == 128 && heads >= 2 && heads % 2 == 0 && heads <= 64 && B >= 1 && B <= 16384,
-               "qkv_attention: B=%d L=%d heads=%d (this kernel is built for 128-token samples and an even head count; "
-               "use ufnd_gemm_bf16[_ln] + ufnd_attention_bf16 otherwise)", B, L, heads);
   GemmArgs a;
-  const int rc = qkv_attention_args("qkv_attention", a, X, Wqkv, bqkv, ctx, B * L, heads, ldx, ldw, ln);
+  const int rc = qkv_attention_pair_setup(a, X, Wqkv, bqkv, key_mask, cu_seqlens, bins, nbins, ctx, B, L, heads, ldx, ldw, ln);
   if (rc != UFND_OK) return rc;
-  a.att_mask = key_mask;
-  a.att_cu = cu_seqlens;
-  a.att_bins = bins;
-  a.att_nbins = nbins;
-  a.m_live = cu_seqlens ? cu_seqlens + B : nullptr;      // (the live row count is cu_seqlens[B])
-  a.m_tiles = B;
-  a.n_tiles = heads / 2;
-  a.xcd_cols = (a.n_tiles % 2 == 0 && a.m_tiles >= 4) ? 2 : 1;
-  hipLaunchKernelGGL((gemm_bf16_kernel<128, 384, 2, 4, 3, 2, 16, 0, 0, 1, 1>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
+  qkv_attention_launch<128, 384, 2, 4, 1, 0>(a, (hipStream_t)stream_);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -189,18 +154,10 @@ extern "C" int ufnd_qkv_attention_bf16(const void* X, const void* Wqkv, const fl
 // The packed form over sample tiles (ufnd_text_pack_tiles): one workgroup per (256-row tile of whole samples, head)
 extern "C" int ufnd_qkv_attention_bf16_tiles(const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles, const int32_t* ntiles,
                                              void* ctx, int cap_tiles, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln, void* stream_) {
-  UFND_REQUIRE(X && Wqkv && ctx && tiles && ntiles, "qkv_attention_tiles: null operand");
-  UFND_REQUIRE(heads >= 1 && heads <= 64 && cap_tiles >= 1 && cap_tiles <= (UFND_TEXT_TILE_MAX_B + 1) / 2, "qkv_attention_tiles: cap_tiles=%d heads=%d",
-               cap_tiles, heads);
   GemmArgs a;
-  const int rc = qkv_attention_args("qkv_attention_tiles", a, X, Wqkv, bqkv, ctx, cap_tiles * 256, heads, ldx, ldw, ln);
+  const int rc = qkv_attention_tiles_setup(a, X, Wqkv, bqkv, tiles, ntiles, ctx, cap_tiles, heads, ldx, ldw, ln);
   if (rc != UFND_OK) return rc;
-  a.att_bins = tiles;
-  a.att_nbins = ntiles;
-  a.m_tiles = cap_tiles;
-  a.n_tiles = heads;
-  a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a tile share its A rows in one L2
-  hipLaunchKernelGGL((gemm_bf16_kernel<256, 192, 4, 2, 3, 2, 16, 0, 0, 1, 2>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
+  qkv_attention_launch<256, 192, 4, 2, 2, 0>(a, (hipStream_t)stream_);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }
@@ -208,18 +165,10 @@ extern "C" int ufnd_qkv_attention_bf16_tiles(const void* X, const void* Wqkv, co
 // The same for samples of T <= 64 rows (CLIPAttention of a ViT layer: T = 50): one workgroup per (256 / T whole samples, head).
 extern "C" int ufnd_qkv_attention_bf16_vit(const void* X, const void* Wqkv, const float* bqkv, void* ctx, int N, int T, int heads, int ldx,
                                            int ldw, const ufnd_gemm_ln* ln, void* stream_) {
-  UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention_vit: null operand");
-  UFND_REQUIRE(T >= 1 && T <= 64, "qkv_attention_vit: T=%d (this kernel is built for samples of 1 to 64 rows; use ufnd_gemm_bf16[_ln] + "
-               "ufnd_attention_bf16 otherwise)", T);
-  UFND_REQUIRE(heads >= 1 && heads <= 64 && N >= 1 && (long long)N * T <= (1 << 24), "qkv_attention_vit: N=%d T=%d heads=%d", N, T, heads);
   GemmArgs a;
-  const int rc = qkv_attention_args("qkv_attention_vit", a, X, Wqkv, bqkv, ctx, N * T, heads, ldx, ldw, ln);
+  const int rc = qkv_attention_vit_setup(a, X, Wqkv, bqkv, ctx, N, T, heads, ldx, ldw, ln);
   if (rc != UFND_OK) return rc;
-  a.att_t = T;
-  a.m_tiles = ufnd_cdiv(N, 256 / T);      // 256 / T whole samples per row tile
-  a.n_tiles = heads;
-  a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a row tile share its A rows in one L2
-  hipLaunchKernelGGL((gemm_bf16_kernel<256, 192, 4, 2, 3, 2, 16, 0, 0, 1, 1>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, (hipStream_t)stream_, a);
+  qkv_attention_launch<256, 192, 4, 2, 1, 0>(a, (hipStream_t)stream_);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

@@ -1,5 +1,5 @@
 // Host-side argument checks of the one-tile bf16 GEMM entries (ufnd_gemm_bf16[_ex|_live], ufnd_gemm_bf16_ln[_live],
-// ufnd_gemm_bf16_dgrad), in one place: the product entries (gemm_bf16.hip, gemm_bf16_bwd.hip) and the host-only plan entry of the
+// ufnd_gemm_bf16_dgrad) and the launch setup of the fused Q/K/V + attention entries (at the end), in one place: the product entries (gemm_bf16.hip, gemm_bf16_bwd.hip) and the host-only plan entry of the
 // diagnostics library (diag/gemm_diag.hip: ufnd_diag_gemm_bf16_plan, which tests/test_gemm_bf16_cases.py reads the tile, the grid
 // and every refusal from) call the same functions, so a check cannot exist in one and be missing in the other.  Nothing here
 // dereferences an operand or touches the device.  Include after gemm_bf16_kernel.hpp.
@@ -92,4 +92,85 @@ static inline int gemm_bf16_dgrad_check_tile(int cfg, int N) {
   UFND_REQUIRE(N % kTiles[cfg].bn == 0, "gemm_bf16_dgrad: tile %d needs N %% %d == 0", cfg, kTiles[cfg].bn);
   UFND_REQUIRE(gemm_bwd_tile(cfg), "gemm_bf16 backward: tile %d has no backward kernel", cfg);
   return UFND_OK;
+}
+
+// ---- The fused Q/K/V projection + attention launches (ATT kernels): checks, arguments and grid of the three geometries, for the product
+// entries (gemm_bf16.hip) and the stamps entries of the diagnostics library (diag/gemm_diag.hip: the same setup, then a.stamps and
+// the DBG instantiation).
+// What the three share, after their own shape checks: the operand checks, the projection's arguments (M rows of X against the 3H
+// stacked weight rows), the folded LayerNorm and the attention output.  `name` is the entry's name in its messages.
+static inline int qkv_attention_args(const char* name, GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, void* ctx, int M, int heads,
+                                     int ldx, int ldw, const ufnd_gemm_ln* ln) {
+  const int H = heads * 64;
+  UFND_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= H && ldw >= H && ufnd_aligned(X, 16) && ufnd_aligned(Wqkv, 16) && ufnd_aligned(ctx, 16),
+               "%s: strides must be multiples of 8 and pointers 16-B aligned", name);
+  UFND_REQUIRE(!bqkv || ufnd_aligned(bqkv, 16), "%s: bias alignment", name);
+  a = GemmArgs{(const __bf16*)X, (const __bf16*)Wqkv, bqkv, nullptr, nullptr, nullptr, M, 3 * H, H, ldx, ldw, 0, 0, 0, UFND_ACT_NONE, 0, 0, nullptr};
+  if (ln && ln->a_stats) {
+    UFND_REQUIRE(ln->colsum && ufnd_aligned(ln->colsum, 16) && ufnd_aligned(ln->a_stats, 16), "%s: colsum / a_stats alignment", name);
+    UFND_REQUIRE(ln->a_parts >= 2 && ln->a_parts <= 24 && ln->a_parts % 2 == 0 && ln->width > 0, "%s: a_parts=%d width=%d", name, ln->a_parts, ln->width);
+    a.a_stats = ln->a_stats; a.colsum = ln->colsum; a.a_parts = ln->a_parts; a.a_eps = ln->a_eps;
+    a.inv_h = 1.0f / (float)ln->width;
+    a.guard = ln->guard;
+  }
+  a.att_ctx = (__bf16*)ctx;
+  a.att_h = H;
+  a.att_scale_log2e = 0.125f * 1.44269504088896340736f;      // 1 / sqrt(64) * log2(e)
+  return UFND_OK;
+}
+// 128-token samples, one workgroup per (sample or slot bin, head pair): padded (cu_seqlens NULL), packed rows, slot bins
+static inline int qkv_attention_pair_setup(GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, const int32_t* key_mask,
+                                           const int32_t* cu_seqlens, const int32_t* bins, const int32_t* nbins, void* ctx, int B, int L, int heads,
+                                           int ldx, int ldw, const ufnd_gemm_ln* ln) {
+  UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention: null operand");
+  UFND_REQUIRE(!bins == !nbins && (!bins || cu_seqlens), "qkv_attention: slot bins need cu_seqlens, bins and nbins");
+  UFND_REQUIRE(L == 128 && heads >= 2 && heads % 2 == 0 && heads <= 64 && B >= 1 && B <= 16384,
+               "qkv_attention: B=%d L=%d heads=%d (this kernel is built for 128-token samples and an even head count; "
+               "use ufnd_gemm_bf16[_ln] + ufnd_attention_bf16 otherwise)", B, L, heads);
+  const int rc = qkv_attention_args("qkv_attention", a, X, Wqkv, bqkv, ctx, B * L, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
+  a.att_mask = key_mask;
+  a.att_cu = cu_seqlens;
+  a.att_bins = bins;
+  a.att_nbins = nbins;
+  a.m_live = cu_seqlens ? cu_seqlens + B : nullptr;      // (the live row count is cu_seqlens[B])
+  a.m_tiles = B;
+  a.n_tiles = heads / 2;
+  a.xcd_cols = (a.n_tiles % 2 == 0 && a.m_tiles >= 4) ? 2 : 1;
+  return UFND_OK;
+}
+// sample tiles (ufnd_text_pack_tiles): one workgroup per (256-row tile of whole samples, head)
+static inline int qkv_attention_tiles_setup(GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, const int32_t* tiles,
+                                            const int32_t* ntiles, void* ctx, int cap_tiles, int heads, int ldx, int ldw, const ufnd_gemm_ln* ln) {
+  UFND_REQUIRE(X && Wqkv && ctx && tiles && ntiles, "qkv_attention_tiles: null operand");
+  UFND_REQUIRE(heads >= 1 && heads <= 64 && cap_tiles >= 1 && cap_tiles <= (UFND_TEXT_TILE_MAX_B + 1) / 2, "qkv_attention_tiles: cap_tiles=%d heads=%d",
+               cap_tiles, heads);
+  const int rc = qkv_attention_args("qkv_attention_tiles", a, X, Wqkv, bqkv, ctx, cap_tiles * 256, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
+  a.att_bins = tiles;
+  a.att_nbins = ntiles;
+  a.m_tiles = cap_tiles;
+  a.n_tiles = heads;
+  a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a tile share its A rows in one L2
+  return UFND_OK;
+}
+// samples of T <= 64 rows (a ViT layer: T = 50): one workgroup per (256 / T whole samples, head)
+static inline int qkv_attention_vit_setup(GemmArgs& a, const void* X, const void* Wqkv, const float* bqkv, void* ctx, int N, int T, int heads, int ldx,
+                                          int ldw, const ufnd_gemm_ln* ln) {
+  UFND_REQUIRE(X && Wqkv && ctx, "qkv_attention_vit: null operand");
+  UFND_REQUIRE(T >= 1 && T <= 64, "qkv_attention_vit: T=%d (this kernel is built for samples of 1 to 64 rows; use ufnd_gemm_bf16[_ln] + "
+               "ufnd_attention_bf16 otherwise)", T);
+  UFND_REQUIRE(heads >= 1 && heads <= 64 && N >= 1 && (long long)N * T <= (1 << 24), "qkv_attention_vit: N=%d T=%d heads=%d", N, T, heads);
+  const int rc = qkv_attention_args("qkv_attention_vit", a, X, Wqkv, bqkv, ctx, N * T, heads, ldx, ldw, ln);
+  if (rc != UFND_OK) return rc;
+  a.att_t = T;
+  a.m_tiles = ufnd_cdiv(N, 256 / T);      // 256 / T whole samples per row tile
+  a.n_tiles = heads;
+  a.xcd_cols = 1;                         // an XCD takes whole row tiles: the `heads` workgroups of a row tile share its A rows in one L2
+  return UFND_OK;
+}
+// the launch of an ATT kernel after its setup (rings 3 / 2, eight waves; DBG = 1: the stamps build, a.stamps set)
+template <int BM, int BN, int WM, int WN, int ATT, int DBG>
+static inline void qkv_attention_launch(const GemmArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, 3, 2, 16, 0, DBG, 1, ATT>), dim3(a.m_tiles * a.n_tiles), dim3(512), 0, stream, a);
 }

@@ -16,14 +16,7 @@
 // Grid: one block per tile, XCD-aware (bijective) remap so that the blocks sharing an A
 // row-panel land on the same XCD's L2.
 #pragma once
-// Experiment switch (python -m ultrafnd_git_amd.build --defs=UFND_GEMM_OUT_NT=1): forward bf16 outputs with the non-temporal hint, so that a
-// streaming output does not evict the operand panels an XCD's workgroups are about to re-read.  Measured in round 4 (one box, A/B/A,
-// profiles/r04_nt_stores.txt): alone, FFN1 gains 5-9 % (104.5 -> 95.0 us on 256x256 tiles, 98.1 -> 92.2 persistent); inside the encoder
-// pass nothing gains and the fused QKV + attention launch, whose input is the previous layer's nt-stored output, loses 5 us (84.8 -> 89.5):
-// step 1.3746 -> 1.387-1.402 ms.  Off.
-#ifndef UFND_GEMM_OUT_NT
-#define UFND_GEMM_OUT_NT 0
-#endif
+// (Non-temporal bf16 output stores were measured and rejected: DESIGN.md, "Non-temporal output stores"; profiles/r04_nt_stores.txt.)
 
 #include <type_traits>
 
@@ -33,10 +26,6 @@
 // No implicit contraction in this file: the epilogues spell every fused multiply-add out (fmaf), so that
 // all tile shapes emit the same floating-point operation sequence (rows are batch-invariant, bit for bit).
 #pragma clang fp contract(off)
-
-#ifndef UFND_GEMM_ILV
-#define UFND_GEMM_ILV 1      // 1: fragment reads interleaved with the leading MFMAs of a k-half (0: issued as one burst)
-#endif
 
 namespace {
 
@@ -107,6 +96,67 @@ __device__ __forceinline__ float opaque_f(float x) {
 __device__ __forceinline__ f32x2 opaque_f2(f32x2 x) {
   asm volatile("" : "+v"(x));
   return x;
+}
+
+// ---- The epilogue arithmetic, written once: gemm_bf16_kernel and the persistent gemm_pp_kernel (gemm_bf16_pp.hpp) call these, each
+// from its own schedule (loads, counted waits, LDS addressing and interleave counts stay with the kernel).  A row's bits therefore do
+// not depend on which kernel, tile shape or batch computed it.
+
+// Row totals {sum, sumsq} -> {mean, variance}, then rstd.  Two functions: the one-tile kernel picks eps by a select that stays behind the
+// variance, where it was before the arithmetic moved here (as an argument of one function it moved ahead and changed the schedule).
+// (The canonical summation of the partial chunks in front of this -- chunk c to group c % 4, chunks ascending, (g0 + g1) + (g2 + g3) --
+//  stays written out in both kernels, beside the loads it consumes: as a function, in every form tried -- chunks by value or by
+//  reference, sums as vectors or scalars -- it changed the register allocation or the schedule of every LayerNorm-aware instantiation;
+//  profiles/gemm_epilogue_refactor_resources.md.)
+__device__ __forceinline__ f32x2 ln_mean_var(const float sm, const float sq, const float inv_h) {
+  const float mean = __fmul_rn(sm, inv_h);
+  const float var = fmaxf(__fmaf_rn(-mean, mean, __fmul_rn(sq, inv_h)), 0.f);
+  return f32x2{mean, var};
+}
+__device__ __forceinline__ float ln_rstd(const float var, const float eps) {
+  return __builtin_amdgcn_rsqf(__fadd_rn(var, eps));   // v_rsq_f32 (1 ulp, the same instruction in every tile shape)
+}
+// fold guard: |mean| / std of a folded row (a NaN statistic must trip the guard: fmaxf would drop it)
+__device__ __forceinline__ float ln_guard_ratio(const float mean, const float rstd) {
+  const float ratio = __fmul_rn(fabsf(mean), rstd);
+  return ratio == ratio ? ratio : INFINITY;
+}
+// [folded LayerNorm of the A operand,] bias, activation on two rows of an accumulator column:
+// LayerNorm(A) W'^T = rstd (A W'^T - mean colsum(W')), explicit roundings.  (opaque: the product must not be re-fused with the bias
+// add below -- the backend did so for a few elements of some tile shapes even with contraction switched off in the source)
+template <bool FOLD, int ACT>
+__device__ __forceinline__ f32x2 epi_fold_bias_act(f32x2 v, const f32x2 mean2, const f32x2 rstd2, const float cs, const float b) {
+  if constexpr (FOLD) v = opaque_f2(rstd2 * __builtin_elementwise_fma(-mean2, f32x2{cs, cs}, v));
+  v = v + f32x2{b, b};
+  if constexpr (ACT == UFND_ACT_GELU) v = gelu_fast_f2(v);
+  else if constexpr (ACT == UFND_ACT_QUICK_GELU) v = quick_gelu_fast_f2(v);
+  return v;
+}
+// the residual stream is LayerNorm(residual) * gamma + beta, never materialised (ms = the row's {mean, rstd})
+__device__ __forceinline__ void epi_residual_ln(float (&r)[8], const f32x2 ms, const float (&g8)[8], const float (&b8)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) r[q] = __fmaf_rn(__fmul_rn(__fsub_rn(r[q], ms[0]), ms[1]), g8[q], b8[q]);
+}
+__device__ __forceinline__ void epi_add8(float (&v)[8], const float (&r)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(v[q], r[q]);
+}
+// partial {sum, sumsq} of an fp32 output row over an aligned 32-column group: the lane's 8 columns, then its quad's
+__device__ __forceinline__ f32x2 epi_row_partial(const float (&v)[8]) {
+  float sm = 0.f, sq = 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { sm = __fadd_rn(sm, v[q]); sq = __fmaf_rn(v[q], v[q], sq); }
+  sm += quad_xor1(sm);
+  sq += quad_xor1(sq);
+  sm += quad_xor2(sm);
+  sq += quad_xor2(sq);
+  return f32x2{sm, sq};
+}
+__device__ __forceinline__ bf16x8 epi_round_bf16x8(const float (&v)[8]) {
+  bf16x8 o;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) o[q] = (__bf16)v[q];
+  return o;
 }
 
 // (lds_frag, the swizzled 16-B fragment read of the operand slots and the attention images: attn_softmax.hpp)
@@ -489,13 +539,11 @@ void gemm_bf16_kernel(const GemmArgs a) {
         sm = s01 + s23;
         sq = q01 + q23;
       }
-      const float mean = __fmul_rn(sm, a.inv_h);
-      const float var = fmaxf(__fmaf_rn(-mean, mean, __fmul_rn(sq, a.inv_h)), 0.f);
-      const float rstd = __builtin_amdgcn_rsqf(__fadd_rn(var, a.a_stats ? a.a_eps : a.r_eps));   // v_rsq_f32 (1 ulp, the same instruction in every tile shape)
-      if (threadIdx.x % TPR == 0) st_lds[threadIdx.x / TPR] = f32x2{mean, rstd};
+      const f32x2 mv = ln_mean_var(sm, sq, a.inv_h);
+      const f32x2 ms = {mv[0], ln_rstd(mv[1], a.a_stats ? a.a_eps : a.r_eps)};
+      if (threadIdx.x % TPR == 0) st_lds[threadIdx.x / TPR] = ms;
       if (a.guard && a.a_stats) {      // fold guard: the largest |mean| / std among the rows this workgroup folds (reported at the kernel's end)
-        float ratio = __fmul_rn(fabsf(mean), rstd);
-        ratio = ratio == ratio ? ratio : INFINITY;      // (a NaN statistic must trip the guard: fmaxf would drop it)
+        const float ratio = ln_guard_ratio(ms[0], ms[1]);
         const float worst = wave_max(threadIdx.x % TPR == 0 && tile_row_live((int)threadIdx.x / TPR) ? ratio : 0.0f);      // (live rows only)
         if (lane == 0) reinterpret_cast<float*>(smem + STAT_OFF + BM * 8)[wave] = worst;
       }
@@ -537,25 +585,20 @@ void gemm_bf16_kernel(const GemmArgs a) {
   // half a step of queued matrix work on either side.  One MFMA leads each half so that the wait the
   // compiler places in front of it covers only reads issued half a step earlier.
   constexpr int NMF = KQ * MT * NT, NRD = KQ * (MT + NT);
-  constexpr bool ILV = UFND_GEMM_ILV != 0;
   auto body = [&](int t, auto ia_, auto ib_, auto next_) {
     constexpr bool IA = decltype(ia_)::value != 0, IB = decltype(ib_)::value != 0, NEXT = decltype(next_)::value != 0;
     if constexpr (ABL != 1) {
       read_half(t, IntC<1>{}, af1, bf1);
       mma_half(af0, bf0);
-      if constexpr (ILV) {            // one fragment read behind each of the first MFMAs: the matrix pipe is never left
-#pragma unroll                        // waiting behind a burst of NRD LDS instructions of both waves of the SIMD
-        for (int q = 0; q < (NRD < NMF ? NRD : NMF - 1); ++q) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, NRD - (NRD < NMF ? NRD : NMF - 1), 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - (NRD < NMF ? NRD : NMF - 1), 0);
-      } else {
+      // one fragment read behind each of the first MFMAs: the matrix pipe is never left waiting behind a burst of NRD LDS
+      // instructions of both waves of the SIMD
+#pragma unroll
+      for (int q = 0; q < (NRD < NMF ? NRD : NMF - 1); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NRD, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
+      __builtin_amdgcn_sched_group_barrier(0x100, NRD - (NRD < NMF ? NRD : NMF - 1), 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - (NRD < NMF ? NRD : NMF - 1), 0);
     }
     if constexpr (NEXT) {
       __builtin_amdgcn_sched_barrier(0);
@@ -576,7 +619,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
       mma_half(af1, bf1);
       constexpr int PW = (ABL == 2 || !NEXT) ? 0 : (IA ? PWA : 0) + (IB ? PWB : 0);
       constexpr int GRP = (NMF - 1) / (PW + 1) > 0 ? (NMF - 1) / (PW + 1) : 1;
-      if constexpr (ILV && NEXT && NRD + PW < NMF) {
+      if constexpr (NEXT && NRD + PW < NMF) {
 #pragma unroll
         for (int q = 0; q < NRD; ++q) {           // {MFMA, fragment read} x NRD
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -736,15 +779,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          f32x2 v = {acc[i][j][r], acc[i][j][r + 1]};
-          // LayerNorm(A) W'^T = rstd (A W'^T - mean colsum(W')); explicit roundings: every tile shape must
-          // emit the same operation sequence (rows stay batch-invariant)
-          // (opaque(): the product must not be re-fused with the bias add below -- the backend did so
-          //  for a few elements of some tile shapes even with contraction switched off in the source)
-          if constexpr (FOLD) v = opaque_f2(rstd2 * __builtin_elementwise_fma(-mean2, f32x2{csj[j], csj[j]}, v));
-          v = v + f32x2{bj[j], bj[j]};
-          if constexpr (ACT == UFND_ACT_GELU) v = gelu_fast_f2(v);
-          else if constexpr (ACT == UFND_ACT_QUICK_GELU) v = quick_gelu_fast_f2(v);
+          const f32x2 v = epi_fold_bias_act<FOLD, ACT>(f32x2{acc[i][j][r], acc[i][j][r + 1]}, mean2, rstd2, csj[j], bj[j]);
           cst[prow_ * CP + j * MI + fr] = v.x;
           cst[(prow_ + 1) * CP + j * MI + fr] = v.y;
         }
@@ -780,33 +815,22 @@ void gemm_bf16_kernel(const GemmArgs a) {
               ld8(a.r_gamma + col, g8);
               ld8(a.r_beta + col, b8);
             }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) rr8[it][q] = __fmaf_rn(__fmul_rn(__fsub_rn(rr8[it][q], ms[0]), ms[1]), g8[q], b8[q]);
+            epi_residual_ln(rr8[it], ms, g8, b8);
           }
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(v[q], rr8[it][q]);
+          epi_add8(v, rr8[it]);
         }
         if constexpr (LNX && RES) {
           if (a.out_stats) {      // partial {sum, sumsq} of the fp32 output row over each aligned 32-column group
             if constexpr (CPR % 4 == 0) {   // (canonical: the partial of columns [32p, 32p+32) never depends on the tile shape)
-              float sm = 0.f, sq = 0.f;
-#pragma unroll
-              for (int q = 0; q < 8; ++q) { sm = __fadd_rn(sm, v[q]); sq = __fmaf_rn(v[q], v[q], sq); }
-              sm += quad_xor1(sm);
-              sq += quad_xor1(sq);
-              sm += quad_xor2(sm);
-              sq += quad_xor2(sq);
-              if (live && (id & 3) == 0)
-                *reinterpret_cast<f32x2*>(a.out_stats + ((size_t)row * (a.N >> 5) + (col >> 5)) * 2) = f32x2{sm, sq};
+              const f32x2 part = epi_row_partial(v);
+              if (live && (id & 3) == 0) *reinterpret_cast<f32x2*>(a.out_stats + ((size_t)row * (a.N >> 5) + (col >> 5)) * 2) = part;
             }
           }
         }
         if constexpr (ATT) {        // bf16 rounding of the projection (as the stand-alone GEMM stores it) into the LDS image of
           const int ct = wn * TN + cl;                     // its (q|k|v, head): 128-B rows, 16-B chunks swizzled as attention.hip reads them
           const int trow = wm * TM + i * MI + rr, img = ct >> 6, ch = (ct & 63) >> 3;
-          bf16x8 o;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) o[q] = (__bf16)v[q];
+          const bf16x8 o = epi_round_bf16x8(v);
           const int sw = img >= (ONEH ? 2 : 4) ? (ch ^ (((trow >> 1) & 3) << 1)) : (ch ^ ((trow >> 1) & 7));      // V images: the transposed-read swizzle
           *reinterpret_cast<bf16x8*>(smem + ATT_OFF + img * ATT_IMG + trow * 128 + (sw << 4)) = o;
           continue;
@@ -817,13 +841,7 @@ void gemm_bf16_kernel(const GemmArgs a) {
           *reinterpret_cast<f32x4*>(op) = f32x4{v[0], v[1], v[2], v[3]};
           *reinterpret_cast<f32x4*>(op + 4) = f32x4{v[4], v[5], v[6], v[7]};
         }
-        if (a.out_bf16) {
-          bf16x8 o;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) o[q] = (__bf16)v[q];
-          if constexpr (UFND_GEMM_OUT_NT && !BWD) __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(a.out_bf16 + (size_t)row * a.ldo + col));
-          else *reinterpret_cast<bf16x8*>(a.out_bf16 + (size_t)row * a.ldo + col) = o;
-        }
+        if (a.out_bf16) *reinterpret_cast<bf16x8*>(a.out_bf16 + (size_t)row * a.ldo + col) = epi_round_bf16x8(v);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // patch reads done before the next row-tile overwrites it
     }
@@ -847,60 +865,35 @@ void gemm_bf16_kernel(const GemmArgs a) {
     stamp[8] = __builtin_amdgcn_s_memtime();       // projection epilogue done (images written), attention starts
     stamp[9] = __builtin_amdgcn_s_memrealtime();
   }
+  // ---- attention on the LDS images: every geometry deals units of (sample, head, 32 queries) to its waves and runs attn_unit
+  // (attn_softmax.hpp) on them; what differs is the bias row, the row maps and where a query's output goes
   if constexpr (VIT) {
-    // ---- attention of the tile's samples for this head on the LDS images, the block body of attn_softmax.hpp in attention_kernel<64, 2>'s
-    // geometry: one 64-key block per sample; a key or query at or past T reads the sample's last row, as that kernel's clamped loads
-    // do, and gets the -inf bias; units of (sample, 32 queries) dealt round-robin to the eight waves
+    // attention_kernel<64, 2>'s geometry: one 64-key block per sample, no block skip; a key or query at or past T reads the sample's
+    // last row, as that kernel's clamped loads do, and gets the -inf bias; units dealt round-robin to the eight waves
     const int T = a.att_t;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 3 * ATT_IMG);
     if (threadIdx.x < 64) kbias[threadIdx.x] = (int)threadIdx.x < T ? 0.0f : -INFINITY;
     __syncthreads();
-    const int g4 = lane >> 4, f16 = lane & 15;
-    const char* qimg = smem + ATT_OFF;
-    const char* kimg = smem + ATT_OFF + ATT_IMG;
-    const char* vimg = smem + ATT_OFF + 2 * ATT_IMG;
     const int nqb = (T + 31) >> 5, nsamp = alen > 0 ? alen / T : 0;      // (alen is a whole number of samples: M = samples x T)
-    const bool any_masked = __any(kbias[lane] != 0.0f);                  // (wave-uniform; false only at T = 64)
-    constexpr int KT = 4;
     for (int u = wave; u < nsamp * nqb; u += NW) {
       const int smp = u / nqb, q0 = (u - smp * nqb) * 32, r0 = smp * T;      // r0: tile row of the sample's row 0
       const auto row = [&](int k) { return r0 + (k < T ? k : T - 1); };      // tile row of the sample's key (or query) k
-      bf16x8 qf[2][2];
-      attn_q_frags(qimg, [&](int q) { return row(q0 + q); }, f16, g4, qf);
-      f32x4 o[4][2], sc[KT][2];
-      float m_run[2], l_run[2];
-      bf16x8 pf[KT / 2][2];
-      attn_init(o, m_run, l_run);
-      attn_scores<KT>(kimg, row, qf, f16, g4, sc);
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, kbias, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
-      attn_pv<KT>(vimg, row, pf, o, f16, g4);
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const float inv = attn_finish(l_run[qt]);
-        const int q = q0 + qt * 16 + f16;
-        if (q < T) attn_store_ctx(a.att_ctx + (size_t)(arow0 + r0 + q) * a.att_h + tn * 64 + 4 * g4, o, qt, inv);
-      }
+      attn_unit<1, false>(smem + ATT_OFF, smem + ATT_OFF + ATT_IMG, smem + ATT_OFF + 2 * ATT_IMG, [&](int q) { return row(q0 + q); }, row, kbias,
+                          a.att_scale_log2e, lane, a.att_ctx + (size_t)(arow0 + r0 + q0) * a.att_h + tn * 64, a.att_h, T - q0);
     }
   } else if constexpr (TIL) {
-    // ---- attention of the tile's samples for this head on the LDS images, the block body of attn_softmax.hpp in attention.hip's geometry at
-    // L = 128 (two 64-key blocks counted from the sample's row 0).  Key k of a sample of n rows whose row 0 is tile row r0 is tile row r0 + min(k, n - 1):
-    // a key at or past n reads a finite row of the sample and gets NEG_MASK, what a padding key gets in the padded batch; a live key's bias
-    // is its tile row's word (the sample's key-mask row, holes included).  A wave copies the 128 bias words of its unit's sample into a row
-    // of its own, so that the block reads are 16-B aligned wherever the sample starts.  Units of (sample, 32 queries) come from the tile's
-    // unit list -- samples in descending length, so the two-block units lead -- and are dealt round-robin to the eight waves.
+    // attention.hip's geometry at L = 128 (two 64-key blocks counted from the sample's row 0).  Key k of a sample of n rows whose row 0 is tile row
+    // r0 is tile row r0 + min(k, n - 1): a key at or past n reads a finite row of the sample and gets NEG_MASK, what a padding key gets in the padded
+    // batch; a live key's bias is its tile row's word (the sample's key-mask row, holes included).  A wave copies the 128 bias words of its unit's
+    // sample into a row of its own, so that the block reads are 16-B aligned wherever the sample starts.  Units come from the tile's unit list --
+    // samples in descending length, so the two-block units lead -- and are dealt round-robin to the eight waves.
     constexpr float NEG_MASK = -3.0e38f;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 3 * ATT_IMG);
     float* wbias = kbias + BM + wave * 128;
     if (threadIdx.x < BM) kbias[threadIdx.x] = til_kb;
     __syncthreads();
-    const int g4 = lane >> 4, f16 = lane & 15;
-    const char* qimg = smem + ATT_OFF;
-    const char* kimg = smem + ATT_OFF + ATT_IMG;
-    const char* vimg = smem + ATT_OFF + 2 * ATT_IMG;
     int nunits = __builtin_amdgcn_readfirstlane(til[2]);
     nunits = nunits < UFND_TEXT_TILE_UNITS ? nunits : UFND_TEXT_TILE_UNITS;
-    constexpr int KB = 64, KT = KB / 16;
     for (int u = wave; u < nunits; u += NW) {
       const int unit = __builtin_amdgcn_readfirstlane(til[UFND_TEXT_TILE_UNIT0 + u]);
       const int sj = unit & (UFND_TEXT_TILE_SAMPLES - 1), q0 = ((unit >> 8) & 3) * 32;
@@ -917,38 +910,16 @@ void gemm_bf16_kernel(const GemmArgs a) {
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const auto row = [&](int k) { return r0 + (k < n ? k : n - 1); };      // tile row of the sample's key (or query) k
-      bf16x8 qf[2][2];
-      attn_q_frags(qimg, [&](int q) { return row(q0 + q); }, f16, g4, qf);
-      f32x4 o[4][2];
-      float m_run[2], l_run[2];
-      attn_init(o, m_run, l_run);
-#pragma unroll
-      for (int kb0 = 0; kb0 < 128; kb0 += KB) {
-        if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
-        const auto key_row = [&](int k) { return row(kb0 + k); };
-        f32x4 sc[KT][2];
-        attn_scores<KT>(kimg, key_row, qf, f16, g4, sc);
-        const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
-        bf16x8 pf[KT / 2][2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
-        attn_pv<KT>(vimg, key_row, pf, o, f16, g4);
-      }
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        const float inv = attn_finish(l_run[qt]);
-        const int q = q0 + qt * 16 + f16;
-        if (q < n) attn_store_ctx(a.att_ctx + (size_t)(grow0 + q) * a.att_h + tn * 64 + 4 * g4, o, qt, inv);
-      }
+      attn_unit<2, true>(smem + ATT_OFF, smem + ATT_OFF + ATT_IMG, smem + ATT_OFF + 2 * ATT_IMG, [&](int q) { return row(q0 + q); }, row, wbias,
+                         a.att_scale_log2e, lane, a.att_ctx + (size_t)(grow0 + q0) * a.att_h + tn * 64, a.att_h, n - q0);
     }
   } else if constexpr (ATT) {
-    // ---- attention of the tile's two heads on the LDS images, the block body of attn_softmax.hpp in attention.hip's per-wave geometry
-    // (wave w: head w / 4, queries 32 (w % 4) ..; L = 128 = two key blocks)
+    // the tile's two heads in attention.hip's per-wave geometry: one unit per wave (wave w: head w / 4, queries 32 (w % 4) ..; L = 128 = two key blocks)
     constexpr float NEG_MASK = -3.0e38f;
     float* kbias = reinterpret_cast<float*>(smem + ATT_OFF + 6 * 16384);
     if (slots || threadIdx.x < BM) kbias[threadIdx.x] = att_mk != 0 ? 0.0f : NEG_MASK;
     __syncthreads();
-    const int hh = wave >> 2, wq = wave & 3, g4 = lane >> 4, f16 = lane & 15;
+    const int hh = wave >> 2, wq = wave & 3;
     // my 32 queries are rows wrow0 .. wrow0 + wcnt of the sample whose row 0 is tile row koff (its keys: tile rows koff + k, mod 128)
     int wrow0 = arow0 + 32 * wq, wcnt = alen - 32 * wq, koff = 0;
     const float* wbias = kbias;
@@ -959,39 +930,13 @@ void gemm_bf16_kernel(const GemmArgs a) {
       koff = 32 * (wq - ((mt >> 8) & 3));
       wbias = kbias + wq * BM;
     }
-    const char* qimg = smem + ATT_OFF + hh * 16384;
-    const char* kimg = smem + ATT_OFF + (2 + hh) * 16384;
-    const char* vimg = smem + ATT_OFF + (4 + hh) * 16384;
-    bf16x8 qf[2][2];
-    attn_q_frags(qimg, [&](int q) { return wq * 32 + q; }, f16, g4, qf);
-    f32x4 o[4][2];
-    float m_run[2], l_run[2];
-    attn_init(o, m_run, l_run);
-    constexpr int KB = 64, KT = KB / 16;
     // (packed rows: a wave whose 32 queries all lie past the sample's length, or whose slot is empty, has nothing to do)
-    if (wcnt > 0) {
-#pragma unroll
-      for (int kb0 = 0; kb0 < BM; kb0 += KB) {
-        if (masked_block_is_noop(wbias + kb0, lane, m_run)) continue;      // (as attention.hip: bit-identical, see attn_softmax.hpp)
-        // key k of the block is tile row (kr0 + k) mod 128.  koff and kb0 are multiples of 32, so the P V product's key pair
-        // (k, k + 16), k % 32 < 16, lies in one aligned 32-row group: the wrap never splits it
-        const int kr0 = koff + kb0;
-        const auto key_row = [&](int k) { return (kr0 + k) & (BM - 1); };
-        f32x4 sc[KT][2];
-        attn_scores<KT>(kimg, key_row, qf, f16, g4, sc);
-        const bool any_masked = __any(wbias[kb0 + lane] != 0.0f);      // (64 bias words of this key block: one per lane; wave-uniform)
-        bf16x8 pf[KT / 2][2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) attn_softmax_rescale<KT>(sc, qt, wbias + kb0, any_masked, g4, a.att_scale_log2e, m_run, l_run, pf, o);
-        attn_pv<KT>(vimg, key_row, pf, o, f16, g4);
-      }
-    }
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      const float inv = attn_finish(l_run[qt]);
-      const int q = qt * 16 + f16;
-      if (q < wcnt) attn_store_ctx(a.att_ctx + (size_t)(wrow0 + q) * a.att_h + (tn * 2 + hh) * 64 + 4 * g4, o, qt, inv);
-    }
+    // key k of the sample is tile row (koff + k) mod 128.  koff and the block starts are multiples of 32, so the P V product's key pair
+    // (k, k + 16), k % 32 < 16, lies in one aligned 32-row group: the wrap never splits it
+    if (wcnt > 0)
+      attn_unit<2, true>(smem + ATT_OFF + hh * 16384, smem + ATT_OFF + (2 + hh) * 16384, smem + ATT_OFF + (4 + hh) * 16384, [&](int q) { return wq * 32 + q; },
+                         [&](int k) { return (koff + k) & (BM - 1); }, wbias, a.att_scale_log2e, lane,
+                         a.att_ctx + (size_t)wrow0 * a.att_h + (tn * 2 + hh) * 64, a.att_h, wcnt);
   }
   if constexpr (LNX) {
     if (a.guard && a.a_stats && threadIdx.x == 0) {      // (the waves' maxima were written in front of the K loop's first barrier)

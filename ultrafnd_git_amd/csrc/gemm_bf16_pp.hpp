@@ -20,8 +20,10 @@
 // (s_waitcnt vmcnt(0)) in front of their first use (cdna_hip_programming.md section 5, trap (b)).
 //
 // Arithmetic: the same operations in the same order as gemm_bf16_kernel (k ascending in steps of 32 per MFMA; the epilogue
-// code is the same expression sequence), so a row's results do not depend on which kernel -- or which batch -- computed it:
-// tests/test_gpu_gemm_pp.py holds the two kernels bit-identical.
+// arithmetic is the same functions -- ln_mean_var, ln_rstd, ln_guard_ratio, epi_fold_bias_act, epi_residual_ln, epi_add8, epi_row_partial,
+// epi_round_bf16x8 in gemm_bf16_kernel.hpp; only the canonical sum of the statistics' partial chunks is written out in both, see there),
+// so a row's results do not depend on which kernel -- or which batch -- computed it: tests/test_gpu_gemm_pp.py holds the two kernels
+// bit-identical.
 #pragma once
 #include "gemm_bf16_kernel.hpp"
 
@@ -290,14 +292,11 @@ void gemm_pp_kernel(const GemmArgs a) {
       }
       const float s01 = gs[0] + quad_xor1(gs[0]), s23 = gs[1] + quad_xor1(gs[1]);
       const float q01 = gq[0] + quad_xor1(gq[0]), q23 = gq[1] + quad_xor1(gq[1]);
-      const float sm = s01 + s23, sq = q01 + q23;
-      const float mean = __fmul_rn(sm, a.inv_h);
-      const float var = fmaxf(__fmaf_rn(-mean, mean, __fmul_rn(sq, a.inv_h)), 0.f);
-      const float rstd = __builtin_amdgcn_rsqf(__fadd_rn(var, stat_eps));
-      if (sub == 0) st_lds[tid >> 1] = f32x2{mean, rstd};
+      const f32x2 mv = ln_mean_var(s01 + s23, q01 + q23, a.inv_h);
+      const f32x2 ms = {mv[0], ln_rstd(mv[1], stat_eps)};
+      if (sub == 0) st_lds[tid >> 1] = ms;
       if constexpr (MODE == FOLD) {
-        float ratio = __fmul_rn(fabsf(mean), rstd);
-        ratio = ratio == ratio ? ratio : INFINITY;      // (a NaN statistic must trip the guard: fmaxf would drop it)
+        const float ratio = ln_guard_ratio(ms[0], ms[1]);
         guard_max = fmaxf(guard_max, sub == 0 && m0c + (tid >> 1) < mlive ? ratio : 0.0f);      // (live rows only)
       }
     }
@@ -336,12 +335,7 @@ void gemm_pp_kernel(const GemmArgs a) {
   };
   auto slice_regs_j = [&](acc_t& prv, auto P_, auto j_) {
     constexpr int P = decltype(P_)::value, i = P >> 1, r0 = 2 * (P & 1), j = decltype(j_)::value;
-    f32x2 v = {prv[i][j][r0], prv[i][j][r0 + 1]};
-    const float bj = bjv[j], csj = csjv[j];
-    if constexpr (MODE == FOLD) v = opaque_f2(rstd2 * __builtin_elementwise_fma(-mean2, f32x2{csj, csj}, v));
-    v = v + f32x2{bj, bj};
-    if constexpr (ACT == UFND_ACT_GELU) v = gelu_fast_f2(v);
-    else if constexpr (ACT == UFND_ACT_QUICK_GELU) v = quick_gelu_fast_f2(v);
+    const f32x2 v = epi_fold_bias_act<MODE == FOLD, ACT>(f32x2{prv[i][j][r0], prv[i][j][r0 + 1]}, mean2, rstd2, csjv[j], bjv[j]);
     if constexpr (DBG & 8) { asm volatile("" : : "v"(v.x), "v"(v.y)); return; }      // (timing-only: no patch writes)
     *(lds_w1)(size_t)(cw_a + (unsigned)(j * 64)) = v.x;
     *(lds_w1)(size_t)(cw_a + (unsigned)(CP * 4 + j * 64)) = v.y;
@@ -371,33 +365,23 @@ void gemm_pp_kernel(const GemmArgs a) {
         const f32x4 b0 = *(lds_f4)(size_t)(gb_a + (unsigned)(BN * 4)), b1 = *(lds_f4)(size_t)(gb_a + (unsigned)(BN * 4 + 16));
         const float g8[8] = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
         const float b8[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) r8[q] = __fmaf_rn(__fmul_rn(__fsub_rn(r8[q], ms[0]), ms[1]), g8[q], b8[q]);
+        epi_residual_ln(r8, ms, g8, b8);
       }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v8[q] = __fadd_rn(v8[q], r8[q]);
-      float sm = 0.f, sq = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { sm = __fadd_rn(sm, v8[q]); sq = __fmaf_rn(v8[q], v8[q], sq); }
-      sm += quad_xor1(sm);
-      sq += quad_xor1(sq);
-      sm += quad_xor2(sm);
-      sq += quad_xor2(sq);
+      epi_add8(v8, r8);
+      const f32x2 part = epi_row_partial(v8);
       // (every lane stores: the four lanes of a 32-column group hold the same pair and write the same 8 bytes -- an
       //  unpredicated instruction keeps the vmcnt schedule exact)
-      if constexpr (DBG & 4) asm volatile("" : : "v"(sm), "v"(sq));
-      else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, f32x2{sm, sq}), rsStat, vo_stat,
+      if constexpr (DBG & 4) asm volatile("" : : "v"(part.x), "v"(part.y));
+      else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, part), rsStat, vo_stat,
                                                  ((m0p + prow_of(P)) * (a.N >> 5) + (n0p >> 5)) * 8, 0);
     }
   };
   auto slice_rows_c = [&](auto P_) {
     constexpr int P = decltype(P_)::value;
-    bf16x8 o;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) o[q] = (__bf16)v8[q];
+    const bf16x8 o = epi_round_bf16x8(v8);
     const u32x4_t ov = __builtin_bit_cast(u32x4_t, o);
     if constexpr (DBG & (4 | 16)) asm volatile("" : : "v"(o));
-    else __builtin_amdgcn_raw_buffer_store_b128(ov, rsOut, vo_out, ((m0p + prow_of(P)) * a.ldo + n0p) * 2, UFND_GEMM_OUT_NT ? 2 : 0);      // (aux bit 1 = nt)
+    else __builtin_amdgcn_raw_buffer_store_b128(ov, rsOut, vo_out, ((m0p + prow_of(P)) * a.ldo + n0p) * 2, 0);
     // Stamps build only (the product instantiations are unchanged): keep the store's data registers alive for two wait states.  A
     // VALU write to the data registers of a store wider than 64 bits in the very next instruction reaches the stored value in part
     // of the lanes, and with the offset in an SGPR the compiler inserts no wait state for it: in the stamps build the allocator
