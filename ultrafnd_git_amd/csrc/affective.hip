@@ -237,10 +237,7 @@ extern "C" int ufnd_emotion_head(const float* x, const float* wd, const float* b
                "emotion_head: probs, text_intensity, intensity and valence go together, with the group table");
   UFND_REQUIRE(B >= 1 && B <= 65535 && H >= 32 && H % 32 == 0 && H <= HEAD_MAX_H && C >= 1 && C <= HEAD_MAX_C,
                "emotion_head: B=%d H=%d C=%d (B <= 65535, H a multiple of 32 up to %d, C <= %d)", B, H, C, HEAD_MAX_H, HEAD_MAX_C);
-  NtProb p{};
-  p.X = x; p.W = wd; p.bias = bd; p.Y = workspace;
-  p.M = B; p.N = H; p.K = H; p.ldx = H; p.ldw = H; p.ldy = H;
-  p.ksplit = 1;
+  const NtProb p = nt_linear(x, H, wd, H, bd, workspace, H, B, H, H);
   const int rc = launch_nt(&p, 1, nullptr, (hipStream_t)stream_);      // (the exact-fp32 skinny GEMM: ufnd_linear_f32's kernels)
   if (rc != UFND_OK) return rc;
   hipLaunchKernelGGL(emotion_head_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, (const float*)workspace, bd, wo, bo, group, text_valid, arousal,

@@ -293,9 +293,6 @@ extern "C" int ufnd_w2v2_frames(const int32_t* lengths, int32_t* frames, int32_t
 
 extern "C" int ufnd_linear_f32(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, void* stream_) {
   UFND_REQUIRE(X && W && Y && M >= 1 && N >= 32 && K >= 4 && K % 4 == 0, "linear_f32: M=%d N=%d K=%d", M, N, K);
-  NtProb p{};
-  p.X = X; p.W = W; p.bias = bias; p.Y = Y;
-  p.M = M; p.N = N; p.K = K; p.ldx = K; p.ldw = K; p.ldy = N;
-  p.ksplit = 1;
+  const NtProb p = nt_linear(X, K, W, K, bias, Y, N, M, N, K);
   return launch_nt(&p, 1, nullptr, (hipStream_t)stream_);
 }

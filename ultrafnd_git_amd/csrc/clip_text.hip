@@ -185,15 +185,7 @@ extern "C" int ufnd_semantic_head(const float* text, const float* image, const f
   UFND_REQUIRE(text && image && wt && bt && wi && bi && workspace && out_text && out_image && out_gap, "semantic_head: null argument");
   UFND_REQUIRE(B >= 1 && B <= 65535 && D >= 32 && D % 32 == 0 && K >= 4 && K % 4 == 0 && (long long)B * D < (1ll << 30), "semantic_head: B=%d D=%d K=%d", B,
                D, K);
-  NtProb p[2] = {};
-  const float* X[2] = {text, image};
-  const float* W[2] = {wt, wi};
-  const float* bias[2] = {bt, bi};
-  for (int i = 0; i < 2; ++i) {
-    p[i].X = X[i]; p[i].W = W[i]; p[i].bias = bias[i]; p[i].Y = workspace + (size_t)i * B * D;
-    p[i].M = B; p[i].N = D; p[i].K = K; p[i].ldx = K; p[i].ldw = K; p[i].ldy = D;
-    p[i].ksplit = 1;
-  }
+  const NtProb p[2] = {nt_linear(text, K, wt, K, bt, workspace, D, B, D, K), nt_linear(image, K, wi, K, bi, workspace + (size_t)B * D, D, B, D, K)};
   const int rc = launch_nt(p, 2, nullptr, (hipStream_t)stream_);      // (the exact-fp32 skinny GEMM: both products in one launch)
   if (rc != UFND_OK) return rc;
   hipLaunchKernelGGL(semantic_head_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream_, (const float*)workspace, out_text, out_image, out_gap, B, D);

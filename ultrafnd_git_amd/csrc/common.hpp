@@ -47,6 +47,34 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
   return cdf + x * pdf;
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
+// VEC (4, 2 or 1) consecutive floats as ONE 16 / 8 / 4-byte access (p aligned to it), to and from a lane's registers
+template <int VEC>
+__device__ __forceinline__ void ld_vec(const float* p, float (&v)[VEC]) {
+  static_assert(VEC == 4 || VEC == 2 || VEC == 1, "16-, 8- or 4-byte accesses");
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const vec_t t = *reinterpret_cast<const vec_t*>(p);
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) v[q] = t[q];
+}
+template <int VEC>
+__device__ __forceinline__ void st_vec(float* p, const float (&v)[VEC]) {
+  static_assert(VEC == 4 || VEC == 2 || VEC == 1, "16-, 8- or 4-byte accesses");
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  vec_t t;
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) t[q] = v[q];
+  *reinterpret_cast<vec_t*>(p) = t;
+}
+// the same load where `ok`, zeros elsewhere (p is not dereferenced then)
+template <int VEC>
+__device__ __forceinline__ void ld_vec_or_zero(const float* p, bool ok, float (&v)[VEC]) {
+  if (ok) {
+    ld_vec<VEC>(p, v);
+  } else {
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) v[q] = 0.0f;
+  }
+}
 // XCD-aware block order (bijective): hardware block id n lands on XCD n % 8 (observed round-robin placement: speed only, never
 // correctness); the logical id returned gives every XCD a CONTIGUOUS range of the grid, so that workgroups with neighbouring
 // logical ids -- the query blocks of one (sample, head), which walk the same K / V rows -- share one XCD's L2 instead of fetching

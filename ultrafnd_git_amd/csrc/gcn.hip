@@ -298,20 +298,20 @@ int gcn_forward_ws(const float* x, const float* adj, int ld_adj, const ufnd_gcn_
   UFND_CHECK_LAUNCH();
   hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(((size_t)Np * F + 255) / 256)), dim3(256), 0, stream, x, F, N, Np, F, w.xp);
   UFND_CHECK_LAUNCH();
-  NnProb ax{w.an, w.xp, w.P, nullptr, nullptr, N, Np, F, Np, F, F, 0, 0, 0.0f, 0, 0, 1};                 // P = A_norm X
+  const NnProb ax = nn_dgrad(w.an, Np, w.xp, F, w.P, F, N, Np, F);                                        // P = A_norm X
   int rc = launch_nn(&ax, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
-  NtProb l1{w.P, p->w1, p->b1, w.H, w.U1, N, hid, F, F, F, hid, hid, 1, drop_p, LAYER_GCN, 1};            // H = drop(gelu(P W1^T + b1))
+  const NtProb l1 = nt_linear(w.P, F, p->w1, F, p->b1, w.H, hid, N, hid, F).gelu(w.U1, hid).dropout(drop_p, LAYER_GCN);      // H = drop(gelu(P W1^T + b1))
   rc = launch_nt(&l1, 1, st, stream);
   if (rc != UFND_OK) return rc;
   if (Np > N) {
     hipError_t e = hipMemsetAsync(w.H + (size_t)N * hid, 0, (size_t)(Np - N) * hid * sizeof(float), stream);
     if (e != hipSuccess) { ufnd_set_error("gcn: memset failed: %s", hipGetErrorString(e)); return UFND_ERR_LAUNCH; }
   }
-  NnProb ah{w.an, w.H, w.Q, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};            // Q = A_norm H
+  const NnProb ah = nn_dgrad(w.an, Np, w.H, hid, w.Q, hid, N, Np, hid);                                   // Q = A_norm H
   rc = launch_nn(&ah, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
-  NtProb l2{w.Q, p->w2, p->b2, z, nullptr, N, out, hid, hid, hid, out, 0, 0, 0.0f, 0, 1};                 // Z = Q W2^T + b2
+  const NtProb l2 = nt_linear(w.Q, hid, p->w2, hid, p->b2, z, out, N, out, hid);                          // Z = Q W2^T + b2
   return launch_nt(&l2, 1, nullptr, stream);
 }
 
@@ -367,10 +367,10 @@ extern "C" int ufnd_gcn_pretrain_step(const float* x, const float* adj, int ld_a
   float* gb1 = gw1 + n1;
   float* gw2 = gb1 + hid;
   float* gb2 = gw2 + n2;
-  TnProb t2{w.dZ, w.Q, gw2, gb2, N, out_dim, hid, out_dim, hid, hid};                                      // dW2 = dZ^T Q, db2
+  const TnProb t2 = tn_wgrad(w.dZ, out_dim, w.Q, hid, gw2, hid, gb2, N, out_dim, hid);                     // dW2 = dZ^T Q, db2
   rc = launch_tn(&t2, 1, stream);
   if (rc != UFND_OK) return rc;
-  NnProb dq{w.dZ, p->w2, w.dQ, nullptr, nullptr, N, out_dim, hid, out_dim, hid, hid, 0, 0, 0.0f, 0, 0, 1};    // dQ = dZ W2
+  const NnProb dq = nn_dgrad(w.dZ, out_dim, p->w2, hid, w.dQ, hid, N, out_dim, hid);                       // dQ = dZ W2
   rc = launch_nn(&dq, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
   if (w.Np > N) {
@@ -380,10 +380,10 @@ extern "C" int ufnd_gcn_pretrain_step(const float* x, const float* adj, int ld_a
   hipLaunchKernelGGL(gcn_norm_adj_t_kernel, dim3(w.Np / 32, ufnd_cdiv(N, 32)), dim3(256), 0, stream, adj, ld_adj, w.dinv, N, w.Np, w.ant);
   UFND_CHECK_LAUNCH();
   // dU1 = (A_norm^T dQ) * gelu'(U1) * dropout mask
-  NnProb du{w.ant, w.dQ, w.dU1, w.U1, nullptr, N, w.Np, hid, w.Np, hid, hid, hid, 0, dropout_p, LAYER_GCN, hid, 1};
+  const NnProb du = nn_dgrad(w.ant, w.Np, w.dQ, hid, w.dU1, hid, N, w.Np, hid).act_bwd(w.U1, hid, dropout_p, LAYER_GCN, hid);
   rc = launch_nn(&du, 1, state, stream);
   if (rc != UFND_OK) return rc;
-  TnProb t1{w.dU1, w.P, gw1, gb1, N, hid, in_dim, hid, in_dim, in_dim};                                    // dW1 = dU1^T P, db1
+  const TnProb t1 = tn_wgrad(w.dU1, hid, w.P, in_dim, gw1, in_dim, gb1, N, hid, in_dim);                   // dW1 = dU1^T P, db1
   rc = launch_tn(&t1, 1, stream);
   if (rc != UFND_OK) return rc;
   const float b1 = 0.9f, b2 = 0.999f;
@@ -447,21 +447,21 @@ extern "C" int ufnd_gnn_forward(const float* x, const float* adj, int ld_adj, co
     }
     return UFND_OK;
   };
-  NtProb l1{x, p->w1, p->b1, w.Y1, nullptr, N, hid, in_dim, in_dim, in_dim, hid, 0, 0, 0.0f, 0, 1};            // Y1 = X W1^T + b1
+  const NtProb l1 = nt_linear(x, in_dim, p->w1, in_dim, p->b1, w.Y1, hid, N, hid, in_dim);                     // Y1 = X W1^T + b1
   rc = launch_nt(&l1, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
   if ((rc = zero_pad(w.Y1)) != UFND_OK) return rc;
-  NnProb a1{w.an, w.Y1, w.U, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                  // U = A_norm Y1
+  const NnProb a1 = nn_dgrad(w.an, Np, w.Y1, hid, w.U, hid, N, Np, hid);                                        // U = A_norm Y1
   rc = launch_nn(&a1, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
   const size_t n = (size_t)N * hid;
   hipLaunchKernelGGL(relu_drop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)w.U, w.H, n, dropout_p, state);
   UFND_CHECK_LAUNCH();
   if ((rc = zero_pad(w.H)) != UFND_OK) return rc;
-  NnProb a2{w.an, w.H, w.G, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                   // G = A_norm H
+  const NnProb a2 = nn_dgrad(w.an, Np, w.H, hid, w.G, hid, N, Np, hid);                                         // G = A_norm H
   rc = launch_nn(&a2, 1, nullptr, stream);
   if (rc != UFND_OK) return rc;
-  NtProb l2{w.G, p->w2, p->b2, z, nullptr, N, out_dim, hid, hid, hid, out_dim, 0, 0, 0.0f, 0, 1};               // Z = G W2^T + b2
+  const NtProb l2 = nt_linear(w.G, hid, p->w2, hid, p->b2, z, out_dim, N, out_dim, hid);                        // Z = G W2^T + b2
   return launch_nt(&l2, 1, nullptr, stream);
 }
 
@@ -485,20 +485,20 @@ extern "C" int ufnd_gnn_backward(const float* x, const ufnd_gcn_params* p, float
     return UFND_OK;
   };
   int rc;
-  TnProb t2{d_z, w.G, g_w2, g_b2, N, out_dim, hid, out_dim, hid, hid};                                              // dW2 = dZ^T G, db2
+  const TnProb t2 = tn_wgrad(d_z, out_dim, w.G, hid, g_w2, hid, g_b2, N, out_dim, hid);                             // dW2 = dZ^T G, db2
   if ((rc = launch_tn(&t2, 1, stream)) != UFND_OK) return rc;
-  NnProb dg{d_z, p->w2, w.dG, nullptr, nullptr, N, out_dim, hid, out_dim, hid, hid, 0, 0, 0.0f, 0, 0, 1};           // dG = dZ W2
+  const NnProb dg = nn_dgrad(d_z, out_dim, p->w2, hid, w.dG, hid, N, out_dim, hid);                                 // dG = dZ W2
   if ((rc = launch_nn(&dg, 1, nullptr, stream)) != UFND_OK) return rc;
   if ((rc = zero_pad(w.dG)) != UFND_OK) return rc;
-  NnProb dh{w.ant, w.dG, w.dH, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                    // dH = A_norm^T dG
+  const NnProb dh = nn_dgrad(w.ant, Np, w.dG, hid, w.dH, hid, N, Np, hid);                                          // dH = A_norm^T dG
   if ((rc = launch_nn(&dh, 1, nullptr, stream)) != UFND_OK) return rc;
   const size_t n = (size_t)N * hid;
   hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)w.dH, (const float*)w.U,
                      w.dU, n, dropout_p, state);
   UFND_CHECK_LAUNCH();
   if ((rc = zero_pad(w.dU)) != UFND_OK) return rc;
-  NnProb dy{w.ant, w.dU, w.dY1, nullptr, nullptr, N, Np, hid, Np, hid, hid, 0, 0, 0.0f, 0, 0, 1};                   // dY1 = A_norm^T dU
+  const NnProb dy = nn_dgrad(w.ant, Np, w.dU, hid, w.dY1, hid, N, Np, hid);                                         // dY1 = A_norm^T dU
   if ((rc = launch_nn(&dy, 1, nullptr, stream)) != UFND_OK) return rc;
-  TnProb t1{w.dY1, x, g_w1, g_b1, N, hid, in_dim, hid, in_dim, in_dim};                                             // dW1 = dY1^T X, db1
+  const TnProb t1 = tn_wgrad(w.dY1, hid, x, in_dim, g_w1, in_dim, g_b1, N, hid, in_dim);                            // dW1 = dY1^T X, db1
   return launch_tn(&t1, 1, stream);
 }

@@ -6,7 +6,7 @@
 
 #define UFND_GEMM_MAX_PROB 16
 
-// The 20 kernel instantiations the three launchers choose between (gemm_f32.hip: choose_nt / choose_nn / choose_tn validate a
+// The 20 kernel instantiations the three launchers choose between (gemm_f32.hip: the three overloads of choose() validate a
 // launch and name its form on the host; the diagnostics library reports the choice to the op-level tests).
 enum GemmF32Form {
   GEMM_F32_NT16_W4 = 0,         // nt16_kernel<4>: 16x16 tiles, 16-B weight loads
@@ -32,19 +32,36 @@ enum GemmF32Form {
   GEMM_F32_FORMS
 };
 
+// The three problem structures are filled through the builders below them (host only): every leading dimension sits next to
+// its pointer and every optional feature is one named call.  The kernels and the ctypes mirrors read the plain members.
+
 // Y[m][n] = act(sum_k X[m][k] W[n][k] + bias[n])            (nn.Linear forward)
 struct NtProb {
-  const float* X;     // (M, K) row stride ldx (ldx % 4 == 0, 16-B aligned)
-  const float* W;     // (N, K) row stride ldw
-  const float* bias;  // (N) or null
-  float* Y;           // (M, N) row stride ldy; when ksplit > 1: partials [ksplit][M][N]
-  float* Z;           // optional pre-activation copy (M, N) row stride ldz
+  const float* X;
+  const float* W;
+  const float* bias;
+  float* Y;
+  float* Z;
   int M, N, K, ldx, ldw, ldy, ldz;
   int act;            // 0 none, 1 exact GELU
-  float drop_p;       // dropout on the output (train), 0 = off
+  float drop_p;
   uint32_t drop_layer;
-  int ksplit;         // grid-level split of K (1 => epilogue in-kernel)
+  int ksplit;
+
+  // Y = gelu(.), exact; Z: optional copy of the pre-activation (M, N), row stride ldz (16-B aligned, ldz % 4 == 0)
+  NtProb& gelu(float* Z_, int ldz_) { Z = Z_; ldz = ldz_; act = 1; return *this; }
+  // dropout on the output (train), p == 0 = off; the mask's element index is m * N + n in the stream `layer`
+  NtProb& dropout(float p, uint32_t layer) { drop_p = p; drop_layer = layer; return *this; }
+  // grid-level split of K: Y receives bare partials [n][M][N] and neither bias, Z, activation nor mask is applied
+  NtProb& split_k(int n) { ksplit = n; return *this; }
 };
+// X: (M, K) row stride ldx (16-B aligned, ldx % 4 == 0); W: (N, K) row stride ldw; bias: (N) or null; Y: (M, N) row stride ldy
+inline NtProb nt_linear(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K) {
+  NtProb p{};
+  p.X = X; p.ldx = ldx; p.W = W; p.ldw = ldw; p.bias = bias; p.Y = Y; p.ldy = ldy;
+  p.M = M; p.N = N; p.K = K; p.ksplit = 1;
+  return p;
+}
 int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream);
 
 // dX[m][k] = (sum_n dY[m][n] W[n][k]) * [gelu'(actZ[m][k]) * dropmask] + add[m][k]
@@ -52,28 +69,56 @@ int launch_nt(const NtProb* probs, int nprob, const ufnd_step_state* st, hipStre
 // forward (element index m * drop_ld + k), so drop_p > 0 without actZ is refused.  With nsplit > 1 the kernels write bare partial
 // sums and apply neither the bracket nor add.
 struct NnProb {
-  const float* dY;    // (M, N) row stride lddy (lddy % 4 == 0)
-  const float* W;     // (N, K) row stride ldw
-  float* out;         // (M, K) row stride ldo; when nsplit > 1: partials [nsplit][M] rows of stride ldo
-  const float* actZ;  // optional (M, K) row stride ldz
-  const float* add;   // optional (M, K) row stride ldadd
+  const float* dY;
+  const float* W;
+  float* out;
+  const float* actZ;
+  const float* add;
   int M, N, K, lddy, ldw, ldo, ldz, ldadd;
-  float drop_p;       // needs actZ
+  float drop_p;
   uint32_t drop_layer;
-  int drop_ld;        // logical row stride used for the dropout element index (with drop_p > 0: >= K, M * drop_ld < 2^31)
+  int drop_ld;
   int nsplit;
+
+  // the activation backward: Z (M, K) row stride ldz, the forward's pre-activation; p, layer: the dropout that followed the
+  // activation; drop_ld: the logical row stride of the mask's element index (with p > 0: >= K, M * drop_ld < 2^31)
+  NnProb& act_bwd(const float* Z, int ldz_, float p, uint32_t layer, int drop_ld_) {
+    actZ = Z; ldz = ldz_; drop_p = p; drop_layer = layer; drop_ld = drop_ld_;
+    return *this;
+  }
+  // out += add: (M, K) row stride ldadd
+  NnProb& plus(const float* add_, int ldadd_) { add = add_; ldadd = ldadd_; return *this; }
+  // grid-level split of N: out receives partials [n][M] rows of stride ldo
+  NnProb& split_n(int n) { nsplit = n; return *this; }
 };
+// dY: (M, N) row stride lddy (lddy % 4 == 0); W: (N, K) row stride ldw; out: (M, K) row stride ldo
+inline NnProb nn_dgrad(const float* dY, int lddy, const float* W, int ldw, float* out, int ldo, int M, int N, int K) {
+  NnProb p{};
+  p.dY = dY; p.lddy = lddy; p.W = W; p.ldw = ldw; p.out = out; p.ldo = ldo;
+  p.M = M; p.N = N; p.K = K; p.nsplit = 1;
+  return p;
+}
 int launch_nn(const NnProb* probs, int nprob, const ufnd_step_state* st, hipStream_t stream);
 
 // dW[n][k] = sum_m dY[m][n] X[m][k];  db[n] = sum_m dY[m][n]
 struct TnProb {
-  const float* dY;    // (M, N) row stride lddy
-  const float* X;     // (M, K) row stride ldx
-  float* dW;          // (N, K) row stride ldw
-  float* db;          // (N) or null
+  const float* dY;
+  const float* X;
+  float* dW;
+  float* db;
   int M, N, K, lddy, ldx, ldw;
-  // Batch rows in SEGMENTS (gathered data-parallel factors: rank r's rows live at dY + r * seg_dy, X + r * seg_x, seg_rows rows
-  // each, M = ranks x seg_rows); seg_rows == 0: one contiguous panel.
   int seg_rows, seg_dy, seg_x;
+
+  // Batch rows in SEGMENTS (gathered data-parallel factors: rank r's rows live at dY + r * seg_dy, X + r * seg_x, `rows` rows
+  // each, M = ranks x rows); rows == 0: one contiguous panel.
+  TnProb& segments(int rows, int seg_dy_, int seg_x_) { seg_rows = rows; seg_dy = seg_dy_; seg_x = seg_x_; return *this; }
 };
+// dY: (M, N) row stride lddy; X: (M, K) row stride ldx; dW: (N, K) row stride ldw; db: (N) or null
+inline TnProb tn_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int ldw, float* db, int M, int N, int K) {
+  TnProb p{};
+  p.dY = dY; p.lddy = lddy; p.X = X; p.ldx = ldx; p.dW = dW; p.ldw = ldw; p.db = db;
+  p.M = M; p.N = N; p.K = K;
+  return p;
+}
 int launch_tn(const TnProb* probs, int nprob, hipStream_t stream);
+

@@ -175,7 +175,7 @@ extern "C" int ufnd_tcn_forward(const float* text_seq, int text_dim, const float
       hipLaunchKernelGGL(tcn_unfold_kernel, dim3((unsigned)M), dim3(256), 0, stream, text_seq, text_dim, vis_seq, vis_dim, T, kernel,
                          dil, left, cols, ldc);
     UFND_CHECK_LAUNCH();
-    NtProb conv{cols, l.w, l.b, y, nullptr, (int)M, hid, kernel * ch, ldc, ldc, hid, 0, 0, 0.0f, 0, 1};
+    const NtProb conv = nt_linear(cols, ldc, l.w, ldc, l.b, y, hid, (int)M, hid, kernel * ch);
     int rc = launch_nt(&conv, 1, nullptr, stream);
     if (rc != UFND_OK) return rc;
     const float *mean = l.running_mean, *var = l.running_var;
@@ -196,6 +196,6 @@ extern "C" int ufnd_tcn_forward(const float* text_seq, int text_dim, const float
   }
   hipLaunchKernelGGL(tcn_pool_kernel, dim3(ufnd_cdiv(hid, 256), B), dim3(256), 0, stream, h, T, hid, pooled);
   UFND_CHECK_LAUNCH();
-  NtProb head{pooled, head_w, head_b, out, nullptr, B, out_dim, 2 * hid, 2 * hid, 2 * hid, out_dim, 0, 0, 0.0f, 0, 1};
+  const NtProb head = nt_linear(pooled, 2 * hid, head_w, 2 * hid, head_b, out, out_dim, B, out_dim, 2 * hid);
   return launch_nt(&head, 1, nullptr, stream);
 }

@@ -60,9 +60,9 @@ extern "C" int ufnd_temporal_align(const float* text, const float* visual, const
   UFND_CHECK_LAUNCH();
   // note: visual rows are read with their own stride vis_dim; columns >= in_dim are ignored (truncate)
   constexpr uint32_t LAYER_ALIGN = 21;       // dropout stream tag (mask keyed by state->{seed, step})
-  NtProb p0{feat, w0, b0, h, nullptr, B, hidden, 4 * in_dim + 1, ldf, ldf, hidden, 0, 1, dropout_p, LAYER_ALIGN, 1};
+  const NtProb p0 = nt_linear(feat, ldf, w0, ldf, b0, h, hidden, B, hidden, 4 * in_dim + 1).gelu(nullptr, 0).dropout(dropout_p, LAYER_ALIGN);
   int rc = launch_nt(&p0, 1, dropout_p > 0.0f ? state : nullptr, stream);
   if (rc != UFND_OK) return rc;
-  NtProb p1{h, w3, b3, out, nullptr, B, out_dim, hidden, hidden, hidden, out_dim, 0, 0, 0.0f, 0, 1};
+  const NtProb p1 = nt_linear(h, hidden, w3, hidden, b3, out, out_dim, B, out_dim, hidden);
   return launch_nt(&p1, 1, nullptr, stream);
 }

@@ -1041,20 +1041,6 @@ __global__ __launch_bounds__(256) void smoothgrad_points_kernel(const float* x0,
   }
 }
 
-template <int VEC>
-__device__ __forceinline__ void ld_strip(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const f32x4 t = ld4(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void st_strip(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, f32x4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
 // smooth-grad: out[b, j] = (acc + sum_i |G[i B + b, j]|) / divisor, the steps added in order.  One thread per (row, VEC columns).
 // SIGNED: the same without the absolute value (the mean gradient along an integration path).
 template <int VEC, bool SIGNED = false>
@@ -1067,10 +1053,10 @@ __global__ __launch_bounds__(256) void attr_smooth_kernel(const float* G, int ld
   float acc[VEC];
 #pragma unroll
   for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
-  if (accumulate) ld_strip<VEC>(out + (size_t)b * ldo + col, acc);
+  if (accumulate) ld_vec<VEC>(out + (size_t)b * ldo + col, acc);
   for (int i = 0; i < steps; ++i) {
     float g[VEC];
-    ld_strip<VEC>(G + ((size_t)i * B + b) * ldg + col, g);
+    ld_vec<VEC>(G + ((size_t)i * B + b) * ldg + col, g);
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] += SIGNED ? g[q] : fabsf(g[q]);
   }
@@ -1079,7 +1065,7 @@ __global__ __launch_bounds__(256) void attr_smooth_kernel(const float* G, int ld
     if (divisor > 0) acc[q] /= (float)divisor;
     if (col + q >= W) acc[q] = 0.0f;
   }
-  st_strip<VEC>(out + (size_t)b * ldo + col, acc);
+  st_vec<VEC>(out + (size_t)b * ldo + col, acc);
 }
 // grad x input: out = |G * X|; block (x, s) also sums its slice of ATTR_SLICE_ROWS rows into part[s][W] (when asked), which
 // attr_mean_finish_kernel adds in ascending slice order -- the row-slice form of node_param_kernel / node_param_finish_kernel.
@@ -1095,14 +1081,14 @@ __global__ __launch_bounds__(64) void attr_gxi_kernel(const float* G, int ldg, c
   for (int q = 0; q < VEC; ++q) sum[q] = 0.0f;
   for (int r = r0; r < r1; ++r) {
     float g[VEC], x[VEC], v[VEC];
-    ld_strip<VEC>(G + (size_t)r * ldg + col, g);
-    ld_strip<VEC>(X + (size_t)r * ldx + col, x);
+    ld_vec<VEC>(G + (size_t)r * ldg + col, g);
+    ld_vec<VEC>(X + (size_t)r * ldx + col, x);
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
       v[q] = col + q < W ? fabsf(g[q] * x[q]) : 0.0f;
       sum[q] += v[q];
     }
-    st_strip<VEC>(out + (size_t)r * ldo + col, v);
+    st_vec<VEC>(out + (size_t)r * ldo + col, v);
   }
   if (part) {
 #pragma unroll
@@ -1217,8 +1203,7 @@ int fusion_forward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const f
     const int slot[5] = {0, 1, 2, 3, 15};
     NtProb pr[5];
     for (int i = 0; i < NPROJ; ++i)
-      pr[i] = NtProb{xs[i], ws_[i], bs[i], w.cat + (size_t)slot[i] * H, nullptr, B, H, ks[i], ks[i], ks[i], 16 * H, 0,
-                     0, 0.0f, 0, 1};
+      pr[i] = nt_linear(xs[i], ks[i], ws_[i], ks[i], bs[i], w.cat + (size_t)slot[i] * H, 16 * H, B, H, ks[i]);
     TRY(launch_nt(pr, NPROJ, state, stream));
   }
   // 2. stacked q/k/v projections: t -> [q_tv q_ta], v -> [k_tv v_tv q_vu], a -> [k_ta v_ta], u -> [k_vu v_vu]
@@ -1226,8 +1211,8 @@ int fusion_forward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const f
     const int src_slot[4] = {0, 2, 1, 3}, row0[4] = {0, 2, 5, 7}, nrows[4] = {2, 3, 2, 2};
     NtProb pr[4];
     for (int i = 0; i < 4; ++i)
-      pr[i] = NtProb{w.cat + (size_t)src_slot[i] * H, p->qkv_w + (size_t)row0[i] * H * H, p->qkv_b + (size_t)row0[i] * H,
-                     w.qkv + (size_t)row0[i] * H, nullptr, B, nrows[i] * H, H, 16 * H, H, 9 * H, 0, 0, 0.0f, 0, 1};
+      pr[i] = nt_linear(w.cat + (size_t)src_slot[i] * H, 16 * H, p->qkv_w + (size_t)row0[i] * H * H, H, p->qkv_b + (size_t)row0[i] * H,
+                        w.qkv + (size_t)row0[i] * H, 9 * H, B, nrows[i] * H, H);
     TRY(launch_nt(pr, 4, state, stream));
   }
   // 3. evidence scalars + the three evidence gates (:153-164,48), co-attention combine + pairwise features -> CAT slots
@@ -1243,8 +1228,7 @@ int fusion_forward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const f
   UFND_CHECK_LAUNCH();
   // 4. fuse_mlp.0: (B,16H) x (2H,16H)^T, split-K then bias+GELU(+dropout)             (:122-124)
   {
-    NtProb pr{w.cat, p->fuse0_w, nullptr, w.part1, nullptr, B, 2 * H, CW, 16 * H, CW, 2 * H, 0, 0, 0.0f, 0,
-              KSPLIT_FUSE0};
+    const NtProb pr = nt_linear(w.cat, 16 * H, p->fuse0_w, CW, nullptr, w.part1, 2 * H, B, 2 * H, CW).split_k(KSPLIT_FUSE0);
     TRY(launch_nt(&pr, 1, state, stream));
     const int n4 = B * 2 * H / 4;
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(ufnd_cdiv(n4, 256)), blk, 0, stream, (const float*)w.part1,
@@ -1253,7 +1237,7 @@ int fusion_forward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const f
   }
   // 5. fuse_mlp.3 + GELU(+dropout) -> fused                                           (:125-127)
   {
-    NtProb pr{w.h1, p->fuse3_w, p->fuse3_b, fused, w.z2, B, H, 2 * H, 2 * H, 2 * H, ld_fused, H, 1, drop, LAYER_FUSE3, 1};
+    const NtProb pr = nt_linear(w.h1, 2 * H, p->fuse3_w, 2 * H, p->fuse3_b, fused, ld_fused, B, H, 2 * H).gelu(w.z2, H).dropout(drop, LAYER_FUSE3);
     TRY(launch_nt(&pr, 1, state, stream));
   }
   // 6. aux head (unused by the trainer's loss, :198)
@@ -1291,14 +1275,11 @@ FusionFactors fusion_factors(const FusionWs& w, size_t B, size_t H, const float*
   return FusionFactors{w.dz2, w.h1, w.dz1, w.cat, w.dqkv, {w.dtavu, w.dtavu + B * H, w.dtavu + 2 * B * H, w.dtavu + 3 * B * H, w.dg},
                        {text, audio, visual, temporal, gnn}};
 }
-inline TnProb tn_prob(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, int lddy, int ldx, int ldw, Seg sg) {
-  return TnProb{dY, X, dW, db, M, N, K, lddy, ldx, ldw, sg.rows, sg.stride, sg.stride};
-}
 // fuse_mlp.3 and fuse_mlp.0 (the 33.5 MB gradient): 2 problems
 int fusion_tn_fuse(const ufnd_dims& d, const FusionFactors& f, const ufnd_fusion_params* g, int M, TnProb* tn, Seg sg = Seg{0, 0}) {
   const int H = d.hidden, CW = (d.gnn_dim > 0 ? 16 : 15) * H;      // (use_gnn: false: 15 slots; CAT keeps its 16H row stride)
-  tn[0] = tn_prob(f.dz2, f.h1, g->fuse3_w, g->fuse3_b, M, H, 2 * H, H, 2 * H, 2 * H, sg);
-  tn[1] = tn_prob(f.dz1, f.cat, g->fuse0_w, g->fuse0_b, M, 2 * H, CW, 2 * H, 16 * H, CW, sg);
+  tn[0] = tn_wgrad(f.dz2, H, f.h1, 2 * H, g->fuse3_w, 2 * H, g->fuse3_b, M, H, 2 * H).segments(sg.rows, sg.stride, sg.stride);
+  tn[1] = tn_wgrad(f.dz1, 2 * H, f.cat, 16 * H, g->fuse0_w, CW, g->fuse0_b, M, 2 * H, CW).segments(sg.rows, sg.stride, sg.stride);
   return 2;
 }
 // stacked q/k/v (t -> [q_tv q_ta], v -> [k_tv v_tv q_vu], a -> [k_ta v_ta], u -> [k_vu v_vu]) and the projections: 4 + (5 | 4) problems
@@ -1307,20 +1288,21 @@ int fusion_tn_rest(const ufnd_dims& d, const FusionFactors& f, const ufnd_fusion
   const int src_slot[4] = {0, 2, 1, 3}, row0[4] = {0, 2, 5, 7}, nrows[4] = {2, 3, 2, 2};
   int n = 0;
   for (int i = 0; i < 4; ++i)
-    tn[n++] = tn_prob(f.dqkv + (size_t)row0[i] * H, f.cat + (size_t)src_slot[i] * H, g->qkv_w + (size_t)row0[i] * H * H,
-                      g->qkv_b + (size_t)row0[i] * H, M, nrows[i] * H, H, 9 * H, 16 * H, H, sg);
+    tn[n++] = tn_wgrad(f.dqkv + (size_t)row0[i] * H, 9 * H, f.cat + (size_t)src_slot[i] * H, 16 * H, g->qkv_w + (size_t)row0[i] * H * H, H,
+                       g->qkv_b + (size_t)row0[i] * H, M, nrows[i] * H, H).segments(sg.rows, sg.stride, sg.stride);
   float* gw[5] = {g->text_w, g->audio_w, g->visual_w, g->temporal_w, g->gnn_w};
   float* gb[5] = {g->text_b, g->audio_b, g->visual_b, g->temporal_b, g->gnn_b};
   const int ks[5] = {d.text_dim, d.audio_dim, d.visual_dim, d.temporal_dim, d.gnn_dim};
-  for (int i = 0; i < (d.gnn_dim > 0 ? 5 : 4); ++i) tn[n++] = tn_prob(f.dproj[i], f.x[i], gw[i], gb[i], M, H, ks[i], H, ks[i], ks[i], sg);
+  for (int i = 0; i < (d.gnn_dim > 0 ? 5 : 4); ++i)
+    tn[n++] = tn_wgrad(f.dproj[i], H, f.x[i], ks[i], gw[i], ks[i], gb[i], M, H, ks[i]).segments(sg.rows, sg.stride, sg.stride);
   return n;
 }
 // classifier pre.3 and pre.0 (over the full (hidden + aux) width): 2 problems
 struct ClfFactors { const float *dz4, *h3, *dz3, *xin; int ldx; };
 int clf_tn(const ufnd_dims& d, const ClfFactors& f, const ufnd_clf_params* g, int M, TnProb* tn, Seg sg = Seg{0, 0}) {
   const int H = d.hidden;
-  tn[0] = tn_prob(f.dz4, f.h3, g->pre3_w, g->pre3_b, M, H, H, H, H, H, sg);
-  tn[1] = tn_prob(f.dz3, f.xin, g->pre0_w, g->pre0_b, M, H, H + d.aux_dim, H, f.ldx, H + d.aux_dim, sg);
+  tn[0] = tn_wgrad(f.dz4, H, f.h3, H, g->pre3_w, H, g->pre3_b, M, H, H).segments(sg.rows, sg.stride, sg.stride);
+  tn[1] = tn_wgrad(f.dz3, H, f.xin, f.ldx, g->pre0_w, H + d.aux_dim, g->pre0_b, M, H, H + d.aux_dim).segments(sg.rows, sg.stride, sg.stride);
   return 2;
 }
 }  // namespace
@@ -1381,15 +1363,14 @@ int fusion_backward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const 
   UFND_CHECK_LAUNCH();
   // fuse_mlp.3: dW, db; dH1 -> dZ1 (epilogue applies gelu'(Z1) * mask)
   {
-    NnProb n{w.dz2, p->fuse3_w, w.dz1, w.z1, nullptr, B, H, 2 * H, H, 2 * H, 2 * H, 2 * H, 0, drop, LAYER_FUSE0, 2 * H, 1};
+    const NnProb n = nn_dgrad(w.dz2, H, p->fuse3_w, 2 * H, w.dz1, 2 * H, B, H, 2 * H).act_bwd(w.z1, 2 * H, drop, LAYER_FUSE0, 2 * H);
     TRY(launch_nn(&n, 1, state, stream));
   }
   // fuse_mlp.0: dW (the 33.5 MB gradient), db; dCAT partials
   {
     const int CW = (d->gnn_dim > 0 ? 16 : 15) * H;      // (use_gnn: false: 15 slots; CAT / dCAT keep their 16H row stride)
     ntn += fusion_tn_fuse(*d, fusion_factors(w, B, H, text, audio, visual, temporal, gnn), g, B, tn + ntn);
-    NnProb n{w.dz1, p->fuse0_w, w.dcatp, nullptr, nullptr, B, 2 * H, CW, 2 * H, CW, 16 * H, 0, 0, 0.0f, 0, 0,
-             NSPLIT_FUSE0};
+    const NnProb n = nn_dgrad(w.dz1, 2 * H, p->fuse0_w, CW, w.dcatp, 16 * H, B, 2 * H, CW).split_n(NSPLIT_FUSE0);
     if (phase == UFND_BWD_FUSE_MLP && linear) {
       // bucketed gradient exchange: the two fuse_mlp weight gradients (67 % of all gradient bytes) are written NOW,
       // ahead of the dCAT product, so that the caller can start reducing them while the rest of backward runs
@@ -1446,8 +1427,7 @@ int fusion_backward_impl(const ufnd_dims* d, const ufnd_fusion_params* p, const 
     NnProb n[4];
     for (int i = 0; i < 4; ++i) {
       float* dst = w.dtavu + (size_t)src_slot[i] * B * H;  // dtavu order is [t a v u]
-      n[i] = NnProb{w.dqkv + (size_t)row0[i] * H, p->qkv_w + (size_t)row0[i] * H * H, dst, nullptr, dst, B, nrows[i] * H,
-                    H, 9 * H, H, H, 0, H, 0.0f, 0, 0, 1};
+      n[i] = nn_dgrad(w.dqkv + (size_t)row0[i] * H, 9 * H, p->qkv_w + (size_t)row0[i] * H * H, H, dst, H, B, nrows[i] * H, H).plus(dst, H);
     }
     TRY(launch_nn(n, 4, state, stream));
     fj.fork(3);   // every dY of the module is ready
@@ -1502,7 +1482,7 @@ int fusion_input_grads_impl(const ufnd_dims* d, const ufnd_fusion_params* p, flo
   for (int i = 0; i < 5; ++i) {
     if (!dx[i]) continue;
     UFND_REQUIRE(ufnd_aligned(dx[i], 16), "%s: output %d is not 16-byte aligned", who, i);
-    n[k++] = NnProb{f.dproj[i], pw[i], dx[i], nullptr, nullptr, B, H, ks[i], H, ks[i], ks[i], 0, 0, 0.0f, 0, 0, 1};
+    n[k++] = nn_dgrad(f.dproj[i], H, pw[i], ks[i], dx[i], ks[i], B, H, ks[i]);
   }
   return launch_nn(n, k, state, (hipStream_t)stream_);
 }
@@ -1555,9 +1535,9 @@ int classifier_forward_impl(const ufnd_dims* d, const ufnd_clf_params* p, const 
     UFND_CHECK_LAUNCH();
   }
   {  // pre.0 / pre.3 + GELU(+dropout)                                    deep_truth_classifier.py:121-128
-    NtProb a{w.xin, p->pre0_w, p->pre0_b, w.h3, w.z3, B, H, H + d->aux_dim, w.ldx, H + d->aux_dim, H, H, 1, drop, LAYER_PRE0, 1};
+    const NtProb a = nt_linear(w.xin, w.ldx, p->pre0_w, H + d->aux_dim, p->pre0_b, w.h3, H, B, H, H + d->aux_dim).gelu(w.z3, H).dropout(drop, LAYER_PRE0);
     TRY(launch_nt(&a, 1, state, stream));
-    NtProb b{w.h3, p->pre3_w, p->pre3_b, w.hh, w.z4, B, H, H, H, H, H, H, 1, drop, LAYER_PRE3, 1};
+    const NtProb b = nt_linear(w.h3, H, p->pre3_w, H, p->pre3_b, w.hh, H, B, H, H).gelu(w.z4, H).dropout(drop, LAYER_PRE3);
     TRY(launch_nt(&b, 1, state, stream));
   }
   NI_DISPATCH(H, node_head_kernel, dim3(B), blk, stream, (const float*)w.hh, (const float*)w.alpha, (const float*)p->thresh,
@@ -1619,7 +1599,7 @@ int classifier_backward_impl(const ufnd_dims* d, const ufnd_clf_params* p, const
     }
   }
   {  // pre.3: dX -> dz3 (epilogue applies gelu'(z3) * mask)
-    NnProb n{w.dz4, p->pre3_w, w.dz3, w.z3, nullptr, B, H, H, H, H, H, H, 0, drop, LAYER_PRE0, H, 1};
+    const NnProb n = nn_dgrad(w.dz4, H, p->pre3_w, H, w.dz3, H, B, H, H).act_bwd(w.z3, H, drop, LAYER_PRE0, H);
     TRY(launch_nn(&n, 1, state, stream));
   }
   {  // both dW products of the module in one grouped launch (pre.0 over the full (hidden + aux) width), then pre.0's dX
@@ -1628,14 +1608,9 @@ int classifier_backward_impl(const ufnd_dims* d, const ufnd_clf_params* p, const
     TnProb t[2];
     clf_tn(*d, ClfFactors{w.dz4, w.h3, w.dz3, w.xin, w.ldx}, g, B, t);
     if (!(flags & UFND_BWD_NO_LINEAR_GRADS) && !(fo && fo->defer_tn)) TRY(launch_tn(t, 2, fj.dw()));
-    NnProb n{w.dz3, p->pre0_w, d_fused, nullptr, nullptr, B, H, H, H, H + d->aux_dim, ld_dfused, 0, 0, 0.0f, 0, 0, 1};
-    if (fo && fo->next_z) {      // dZ2 = d_fused gelu'(Z2) mask, the expression of act_bwd_kernel, in this product's epilogue
-      n.actZ = fo->next_z;
-      n.ldz = H;
-      n.drop_p = fo->next_drop;
-      n.drop_layer = LAYER_FUSE3;
-      n.drop_ld = H;
-    }
+    NnProb n = nn_dgrad(w.dz3, H, p->pre0_w, H + d->aux_dim, d_fused, ld_dfused, B, H, H);
+    // dZ2 = d_fused gelu'(Z2) mask, the expression of act_bwd_kernel, in this product's epilogue
+    if (fo && fo->next_z) n.act_bwd(fo->next_z, H, fo->next_drop, LAYER_FUSE3, H);
     TRY(launch_nn(&n, 1, state, stream));
   }
   if (join) fj.join(7);
@@ -1692,11 +1667,11 @@ extern "C" int ufnd_classifier_input_grad(const ufnd_dims* d, const ufnd_clf_par
               d->depth, ndrop, drop, state, w.df, w.dz4, (const float*)nullptr, (ufnd_step_state*)nullptr);
   UFND_CHECK_LAUNCH();
   {  // pre.3: dX -> dz3 (epilogue applies gelu'(z3) * mask)
-    NnProb n{w.dz4, p->pre3_w, w.dz3, w.z3, nullptr, B, H, H, H, H, H, H, 0, drop, LAYER_PRE0, H, 1};
+    const NnProb n = nn_dgrad(w.dz4, H, p->pre3_w, H, w.dz3, H, B, H, H).act_bwd(w.z3, H, drop, LAYER_PRE0, H);
     TRY(launch_nn(&n, 1, state, stream));
   }
   {  // pre.0: dX over the whole input row, aux columns included (the training backward stops at the fused columns)
-    NnProb n{w.dz3, p->pre0_w, d_x, nullptr, nullptr, B, H, H + d->aux_dim, H, H + d->aux_dim, ld_dx, 0, 0, 0.0f, 0, 0, 1};
+    const NnProb n = nn_dgrad(w.dz3, H, p->pre0_w, H + d->aux_dim, d_x, ld_dx, B, H, H + d->aux_dim);
     TRY(launch_nn(&n, 1, state, stream));
   }
   return UFND_OK;
