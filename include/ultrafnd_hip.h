@@ -1075,6 +1075,48 @@ int ufnd_emotion_head(const float* x, const float* wd, const float* bd, const fl
                       float* text_intensity, float* intensity, float* valence, int B, int H, int C, void* stream);
 int ufnd_audio_arousal(const float* waves, const int32_t* lengths, float* arousal, int B, int T, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * Video motion forensics: OpticalFlow3DCNN.extract (src/core_blocks/visual_blocks.py:129-258) and ChronosGuard
+ * (src/models/chronos_guard.py), batched, on the branches the reference takes without OpenCV (csrc/motion.hip).  A clip is T uint8 RGB
+ * frames of H x W; every frame becomes a 256 x 256 uint8 luma plane (nearest neighbour: source pixel ((y H) >> 8, (x W) >> 8); luma
+ * (0.2989 r + 0.587 g + 0.114 b) in double, operation by operation, truncated).  Pair t is frames (t, t + 1); d = g[t+1] - g[t].
+ * `lengths` (B int32, NULL: T; clamped to [0, T]): clip b uses frames 0 .. lengths[b] - 1 and its results are the bits of that clip alone.
+ * Nothing allocates or synchronises; no global atomics, fixed reduction orders; every entry can be captured into a hipGraph.
+ *
+ *   ufnd_motion_workspace_bytes   bytes of the workspace all four stages share for (B, T) (0 for a refused shape).  It starts with the
+ *                         gray planes, (B, T, 256, 256) uint8; the rest is per-slab histogram counts and per-tile partials.
+ *                         Alignment: 256 bytes.
+ *   ufnd_motion_gray      frames: device pointer to uint8; element (b, t, c, y, x) lies at frames + b stride_b + t stride_t +
+ *                         c stride_c + y stride_h + x stride_w (64-bit offsets: any layout, no copy; 3 channels).  Writes the gray
+ *                         planes and each frame's 32-bin counts (value v in bin min(31, 32 v / 255): np.histogram(bins=32, range=(0,
+ *                         255))).  Only the sampled source pixels are read; frames past a clip's length are not touched.
+ *   ufnd_motion_pairs     over the gray planes: pair_sums != 0 -> per pair the integer sum of |d| over the plane (ChronosGuard's flow
+ *                         magnitude); levels == 3 -> per pixel and chunk of the 1-2-4 temporal pyramid (chunk p of a level with
+ *                         `parts` parts is pairs [p seg, (p + 1) seg), seg = max(1, pairs / parts), the last one runs to the end)
+ *                         m = fl32(sum |d| / n) and a = fl32(0.25 (2n + sum sign d) / n), correctly rounded, and per chunk the sum and
+ *                         centred second moment of m in double, max m and the counts of a in 8 bins (min(7, floor(8 a))).  levels 0:
+ *                         no pyramid.
+ *   ufnd_motion_chronos_finish   cut_scores, flow_mags (B, T - 1) fp32 (entries past a clip's last pair: 0; T == 1: may be NULL):
+ *                         cut = sum_k |c0_k / w / N - c1_k / w / N| in double over the 32 bins (w = 7.96875, N = 65536), flow = sum |d|
+ *                         / 65536 (exact); stats (B, 7) = mean, std, max of the cut scores, of the flow magnitudes, and their
+ *                         correlation (0 up to 3 pairs; NaN when a series has no variance), evaluated in double; features (B,
+ *                         feat_dim) = the seven tiled to feat_dim and divided by (norm + 1e-9); tamper_score (B) = clip(0.6
+ *                         norm01(mean cut, 0.05, 0.5) + 0.4 norm01(|std flow - mean flow|, 0, 0.5), 0, 1).  Fewer than 2 frames:
+ *                         zeros.  Needs ufnd_motion_gray and ufnd_motion_pairs (pair_sums) before it.
+ *   ufnd_motion_flow_finish   pooled (B, 77, optional) = per chunk [mean m, std m, max m, 8 counts], in double from the partials;
+ *                         features (B, dim) = pooled tiled (or cut) to dim and divided by (norm + 1e-9).  Fewer than 2 frames: zeros;
+ *                         2 to 4 frames: a pyramid chunk is empty, its mean, std and max are NaN and so is every feature, as in the
+ *                         reference.  levels must be 3.  Needs ufnd_motion_gray and ufnd_motion_pairs (levels 3) before it.
+ * B >= 1, T >= 1, B T <= 2^24, 1 <= H, W <= 2^20. */
+size_t ufnd_motion_workspace_bytes(int B, int T);
+int ufnd_motion_gray(const void* frames, long long stride_b, long long stride_t, long long stride_c, long long stride_h, long long stride_w,
+                     const int32_t* lengths, void* workspace, int B, int T, int H, int W, void* stream);
+int ufnd_motion_pairs(const int32_t* lengths, void* workspace, int B, int T, int pair_sums, int levels, void* stream);
+int ufnd_motion_chronos_finish(const int32_t* lengths, const void* workspace, float* cut_scores, float* flow_mags, float* stats, float* features,
+                               float* tamper_score, int B, int T, int feat_dim, void* stream);
+int ufnd_motion_flow_finish(const int32_t* lengths, const void* workspace, float* pooled, float* features, int B, int T, int dim, int levels,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,15 @@ def _declare_encoders(lib: C.CDLL) -> None:
         "ufnd_emotion_head": [P] * 15 + [I, I, I, P],
         "ufnd_audio_arousal": [P, P, P, I, I, P],
     })
+    LL = C.c_longlong
+    sigs.update({      # video motion forensics: OpticalFlow3DCNN and ChronosGuard (csrc/motion.hip)
+        "ufnd_motion_gray": [P, LL, LL, LL, LL, LL, P, P, I, I, I, I, P],
+        "ufnd_motion_pairs": [P, P, I, I, I, I, P],
+        "ufnd_motion_chronos_finish": [P, P, P, P, P, P, P, I, I, I, P],
+        "ufnd_motion_flow_finish": [P, P, P, P, I, I, I, I, P],
+    })
+    lib.ufnd_motion_workspace_bytes.argtypes = [I, I]
+    lib.ufnd_motion_workspace_bytes.restype = S
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

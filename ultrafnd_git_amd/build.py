@@ -57,7 +57,8 @@ def _digest(extra: str) -> str:
 # per-file switches.  The persistent GEMM is built without packed fp32 instructions (csrc/gemm_bf16_pp.hip says why); the feature
 # switch reaches the host pass of hipcc too, which answers "not a recognized feature for this target (ignoring feature)".
 FILE_FLAGS = {"gemm_bf16_pp": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "gemm_pp_diag": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "gemm_pp_diag": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "motion": ["-ffp-contract=off"]}      # the float64 luma is bit-exact only with every operation rounded on its own (csrc/motion.hip)
 
 
 def _compile(src: Path, tag: str, flags: list, verbose: bool) -> Path:

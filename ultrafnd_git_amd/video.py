@@ -1,0 +1,250 @@
+"""Batched video motion forensics on the GPU: OpticalFlow3DCNN (src/core_blocks/visual_blocks.py:129-258) and ChronosGuard
+(src/models/chronos_guard.py) of the reference, on the branches the reference itself takes on a host without OpenCV: nearest-neighbour
+resize to 256 x 256, a float64 luma truncated to uint8, 32-bin frame histograms, |frame difference| as the flow, a 1-2-4 temporal
+pyramid of per-pixel means with an 8-bin orientation histogram (csrc/motion.hip).  TV-L1 and Farneback flow are not built.
+
+Frames: (B, T, H, W, 3) or (B, T, 3, H, W) on a HIP device, read through their strides (any view, no copy).  A frame is CHW by the
+reference's rule -- shape[0] in (1, 3) and shape[2] != 3 -- unless layout= says otherwise; exactly 3 channels.  uint8 is the native
+format; float frames are converted on the device by the reference's per-frame rule (a frame whose max is <= 1 + 1e-6 is scaled by 255;
+then clip to 0..255 and truncate).  lengths: (B,) int32 on the device, clip b uses frames 0 .. lengths[b] - 1 and its results are the
+bits of that clip alone; per-pair outputs are zero past a clip's last pair.
+
+Degenerate clips give exactly what the reference gives, NaN included:
+  fewer than 2 frames       zero vectors, score 0
+  OpticalFlow3DCNN, 2-4 frames   the pyramid's finest level has four parts of max(1, pairs // 4) pairs; with fewer than 4 pairs one of
+                            them is empty, its mean is NaN and normalisation spreads it: the whole vector is NaN (5 frames are finite)
+  ChronosGuard.features     with more than 3 pairs the seventh statistic is np.corrcoef of the two per-pair series; a series without
+                            variance (a static clip) makes it 0 / 0 = NaN and so the vector.  tamper_score does not use it and stays finite.
+There is no CPU fallback: CPU tensors or a missing library raise.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+SIDE = 256             # the reference's working size
+POOLED = 77            # 7 pyramid chunks x (mean, std, max, 8 orientation counts)
+
+
+def _as_clips(frames, device=None) -> torch.Tensor:
+    """A (T, ...) or (B, T, ...) stack -> 5-D device tensor.  Host arrays and lists are moved to `device` (the single-clip methods take
+    what the reference's take); a CPU tensor is refused like everywhere in the package."""
+    if isinstance(frames, str):
+        raise TypeError("a str input is the reference's salted-hash() text proxy, which is not reproduced: pass frames")
+    if not isinstance(frames, torch.Tensor):
+        if device is None:
+            raise L.UltrafndHipError("frames must be a tensor on a HIP device (no CPU fallback)")
+        frames = torch.from_numpy(np.ascontiguousarray(np.asarray(frames))).to(device)
+    L.require_hip(frames)
+    return frames
+
+
+def frame_layout(frame_shape) -> str:
+    """The reference's rule for one frame (_as_numpy_frame): CHW if shape[0] in (1, 3) and shape[2] != 3, else HWC."""
+    return "CHW" if frame_shape[0] in (1, 3) and frame_shape[2] != 3 else "HWC"
+
+
+def frames_to_uint8(frames: torch.Tensor) -> torch.Tensor:
+    """The reference's per-frame conversion of non-uint8 frames, with torch ops on the device and no host synchronisation: a frame whose
+    max is <= 1 + 1e-6 is scaled by 255; then clip to 0..255 and truncate.  uint8 frames pass through untouched."""
+    if frames.dtype == torch.uint8:
+        return frames
+    if not frames.dtype.is_floating_point:
+        frames = frames.float()
+    peak = frames.amax(dim=(-3, -2, -1), keepdim=True)
+    scale = torch.where(peak <= 1.0 + 1e-6, 255.0, 1.0).to(frames.dtype)
+    return (frames * scale).clamp_(0, 255).to(torch.uint8)
+
+
+class _Plan:
+    """The strides of one call: (B, T, H, W) and element strides (b, t, c, y, x) of a 5-D uint8 tensor."""
+
+    def __init__(self, frames: torch.Tensor, layout: Optional[str]):
+        if frames.dim() != 5:
+            raise ValueError(f"frames {tuple(frames.shape)}: expected (B, T, H, W, 3) or (B, T, 3, H, W)")
+        lay = (layout or frame_layout(tuple(frames.shape[2:]))).upper()
+        if lay not in ("HWC", "CHW"):
+            raise ValueError(f"layout={layout!r}: 'HWC' or 'CHW'")
+        s = frames.stride()
+        B, T = frames.shape[:2]
+        if lay == "CHW":
+            Cn, H, W = frames.shape[2:]
+            sc, sh, sw = s[2], s[3], s[4]
+        else:
+            H, W, Cn = frames.shape[2:]
+            sh, sw, sc = s[2], s[3], s[4]
+        if Cn != 3:
+            raise ValueError(f"frames {tuple(frames.shape)} read as {lay}: {Cn} channels, exactly 3 (RGB) are supported")
+        if B < 1 or T < 1 or H < 1 or W < 1:
+            raise ValueError(f"frames {tuple(frames.shape)}: empty")
+        self.B, self.T, self.H, self.W = int(B), int(T), int(H), int(W)
+        self.strides = tuple(int(x) for x in (s[0], s[1], sc, sh, sw))
+
+
+def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
+    if lengths is None:
+        return None
+    lens = lengths.to(dev, torch.int32).contiguous() if isinstance(lengths, torch.Tensor) else torch.tensor(list(lengths), dtype=torch.int32, device=dev)
+    if lens.numel() != B:
+        raise ValueError(f"lengths holds {lens.numel()} entries for {B} clips")
+    return lens
+
+
+class MotionStages:
+    """The three stages over one batch, sharing one workspace: gray -> pairs (+ pyramid) -> the two finishes.  Both classes below
+    run on it; motion_features() runs everything once for callers that want both."""
+
+    def __init__(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None):
+        frames = frames_to_uint8(frames)
+        self.dev = L.require_hip(frames)
+        self.frames = frames                      # (kept alive until the launches are enqueued)
+        self.plan = p = _Plan(frames, layout)
+        self.lens = _lengths(lengths, p.B, self.dev)
+        nbytes = L.lib().ufnd_motion_workspace_bytes(p.B, p.T)
+        if nbytes == 0:
+            raise L.UltrafndHipError(f"motion: B={p.B} T={p.T} is refused (B T <= 2^24)")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self._stream = L.stream_ptr(self.dev)
+
+    def gray(self) -> torch.Tensor:
+        p = self.plan
+        L.check(L.lib().ufnd_motion_gray(self.frames.data_ptr(), *p.strides, L.ptr(self.lens), self.workspace.data_ptr(), p.B, p.T, p.H, p.W,
+                                         self._stream), "ufnd_motion_gray")
+        return self.workspace[:p.B * p.T * SIDE * SIDE].view(p.B, p.T, SIDE, SIDE)
+
+    def pairs(self, pair_sums: bool, levels: int) -> None:
+        p = self.plan
+        L.check(L.lib().ufnd_motion_pairs(L.ptr(self.lens), self.workspace.data_ptr(), p.B, p.T, int(pair_sums), levels, self._stream), "ufnd_motion_pairs")
+
+    def chronos(self, feat_dim: int) -> Dict[str, torch.Tensor]:
+        p, dev = self.plan, self.dev
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"features": torch.empty(p.B, feat_dim, **f32), "tamper_score": torch.empty(p.B, **f32), "cut_scores": torch.empty(p.B, p.T - 1, **f32),
+               "flow_mags": torch.empty(p.B, p.T - 1, **f32), "stats": torch.empty(p.B, 7, **f32)}
+        L.check(L.lib().ufnd_motion_chronos_finish(L.ptr(self.lens), self.workspace.data_ptr(), out["cut_scores"].data_ptr() if p.T > 1 else None,
+                                                   out["flow_mags"].data_ptr() if p.T > 1 else None, out["stats"].data_ptr(), out["features"].data_ptr(),
+                                                   out["tamper_score"].data_ptr(), p.B, p.T, feat_dim, self._stream), "ufnd_motion_chronos_finish")
+        return out
+
+    def flow(self, dim: int, levels: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+        p, dev = self.plan, self.dev
+        pooled = torch.empty(p.B, POOLED, dtype=torch.float32, device=dev)
+        feats = torch.empty(p.B, dim, dtype=torch.float32, device=dev)
+        L.check(L.lib().ufnd_motion_flow_finish(L.ptr(self.lens), self.workspace.data_ptr(), pooled.data_ptr(), feats.data_ptr(), p.B, p.T, dim, levels,
+                                                self._stream), "ufnd_motion_flow_finish")
+        return feats, pooled
+
+
+@torch.no_grad()
+def motion_features(frames: torch.Tensor, lengths=None, feat_dim: int = 128, dim: int = 256, layout: Optional[str] = None) -> Dict[str, torch.Tensor]:
+    """ChronosGuard.analyze_batch and OpticalFlow3DCNN.extract_batch over one gray pass and one walk through time: the dict of
+    analyze_batch plus `flow` (B, dim) and `pooled` (B, 77)."""
+    st = MotionStages(frames, lengths, layout)
+    st.gray()
+    st.pairs(True, 3)
+    out = st.chronos(feat_dim)
+    out["flow"], out["pooled"] = st.flow(dim)
+    return out
+
+
+class OpticalFlow3DCNN:
+    """OpticalFlow3DCNN of the reference with its frame-difference flow: per pyramid chunk the mean, std and max of the per-pixel mean
+    |d| and the 8-bin histogram of the per-pixel mean angle (77 values), tiled to `dim` and L2-normalised.
+
+    n_pyramid_levels: 3 only.  use_tvl1 is accepted for signature compatibility and has no effect: neither TV-L1 nor Farneback is built,
+    the flow is always the reference's frame-difference branch."""
+
+    def __init__(self, dim: int = 256, n_pyramid_levels: int = 3, use_tvl1: bool = True, device="cuda"):
+        if int(n_pyramid_levels) != 3:
+            raise ValueError(f"n_pyramid_levels={n_pyramid_levels}: only the reference's default of 3 levels (1-2-4 parts) is built")
+        if int(dim) < 1:
+            raise ValueError(f"dim={dim}: at least 1")
+        self.dim, self.n_pyr, self.use_tvl1 = int(dim), 3, False
+        self.device = torch.device(device)
+
+    @torch.no_grad()
+    def extract_batch(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None, return_pooled: bool = False):
+        """(B, dim) fp32 on the frames' device; with return_pooled also the (B, 77) values before tiling and normalisation."""
+        st = MotionStages(_as_clips(frames), lengths, layout)
+        st.gray()
+        st.pairs(False, 3)
+        feats, pooled = st.flow(self.dim)
+        return (feats, pooled) if return_pooled else feats
+
+    def extract(self, frames) -> np.ndarray:
+        """One clip (T, H, W, 3) or (T, 3, H, W): a device tensor, or a host array / list of frames -> np.ndarray[dim]."""
+        clip = _as_clips(frames, self.device)
+        if clip.dim() != 4:
+            raise ValueError(f"frames {tuple(clip.shape)}: one clip is (T, H, W, 3) or (T, 3, H, W)")
+        return self.extract_batch(clip[None])[0].cpu().numpy()
+
+
+class ChronosGuard:
+    """ChronosGuard of the reference: per pair of frames a cut score (L1 distance of the two 32-bin density histograms) and a flow
+    magnitude (mean |d|), seven statistics of the two series tiled to feat_dim and L2-normalised, and the heuristic tamper score."""
+
+    def __init__(self, feat_dim: int = 128, device="cuda"):
+        if int(feat_dim) < 1:
+            raise ValueError(f"feat_dim={feat_dim}: at least 1")
+        self.feat_dim = int(feat_dim)
+        self.device = torch.device(device)
+
+    @torch.no_grad()
+    def analyze_batch(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None) -> Dict[str, torch.Tensor]:
+        """features (B, feat_dim), tamper_score (B,), cut_scores and flow_mags (B, T - 1), stats (B, 7) = mean, std, max of the cut
+        scores, mean, std, max of the flow magnitudes, their correlation: all fp32 on the frames' device."""
+        st = MotionStages(_as_clips(frames), lengths, layout)
+        st.gray()
+        st.pairs(True, 0)
+        return st.chronos(self.feat_dim)
+
+    @torch.no_grad()
+    def gray_frames(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None) -> torch.Tensor:
+        """The intermediate luma planes (B, T, 256, 256) uint8 (planes past a clip's length are not written)."""
+        return MotionStages(_as_clips(frames), lengths, layout).gray()
+
+    def _one(self, frames) -> Dict[str, torch.Tensor]:
+        clip = _as_clips(frames, self.device)
+        if clip.dim() != 4:
+            raise ValueError(f"frames {tuple(clip.shape)}: one clip is (T, H, W, 3) or (T, 3, H, W)")
+        return self.analyze_batch(clip[None])
+
+    def extract_features(self, frames) -> np.ndarray:
+        return self._one(frames)["features"][0].cpu().numpy()
+
+    def temporal_tamper_score(self, frames, audio=None) -> float:
+        """The score in [0, 1] (fp32 on the device).  `audio` is accepted and unused, as in the reference."""
+        return float(self._one(frames)["tamper_score"][0].cpu())
+
+    @staticmethod
+    def estimate_av_lag(audio_env, mouth_open, sr: float = 16000.0, fps: float = 25.0, max_lag_s: float = 0.5) -> float:
+        """Host-side NumPy.  The lag (seconds) at the peak of the cross-correlation of the two standardised envelopes, searched within
+        +-max_lag_s: both cut to the shorter length n, correlated through a zero-padded FFT of the first power of two >= 2n, lags
+        ordered -(n-1) .. n-1.  Fewer than 4 samples: 0.0.  (`fps` is unused, as in the reference.)"""
+        a, m = np.asarray(audio_env), np.asarray(mouth_open)
+        n = min(len(a), len(m))
+        if n < 4:
+            return 0.0
+        a, m = a[:n], m[:n]
+        a = (a - np.mean(a)) / (np.std(a) + 1e-9)
+        m = (m - np.mean(m)) / (np.std(m) + 1e-9)
+        nfft = 1
+        while nfft < 2 * n:
+            nfft *= 2
+        xc = np.fft.irfft(np.fft.rfft(a, nfft) * np.conj(np.fft.rfft(m, nfft)), nfft)
+        lags = np.concatenate([xc[nfft - (n - 1):], xc[:n]])
+        mid, half = lags.size // 2, int(max_lag_s * sr)
+        lo, hi = max(0, mid - half), min(lags.size, mid + half + 1)
+        return float((lo + int(np.argmax(lags[lo:hi])) - mid) / sr)
+
+
+@torch.no_grad()
+def cache_visual(frames: torch.Tensor, lengths=None, visual_dim: int = 512, layout: Optional[str] = None) -> torch.Tensor:
+    """The `visual` row of the reference's cache builder: l2n(concat(flow(dim=visual_dim), ela)[:visual_dim]) with l2n(x) = x / (||x|| +
+    1e-9).  The flow vector already fills visual_dim, so the ELA part never enters: (B, visual_dim) fp32."""
+    x = OpticalFlow3DCNN(dim=visual_dim).extract_batch(frames, lengths, layout)
+    return x / (torch.linalg.vector_norm(x, dim=1, keepdim=True) + 1e-9)
