@@ -1117,6 +1117,43 @@ int ufnd_motion_chronos_finish(const int32_t* lengths, const void* workspace, fl
 int ufnd_motion_flow_finish(const int32_t* lengths, const void* workspace, float* pooled, float* features, int B, int T, int dim, int levels,
                             void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * STFT audio forensics: the branches of src/core_blocks/audio_blocks.py that the reference takes without librosa and without a
+ * wav2vec2 checkpoint (csrc/spectral.hip): SpectralForensics._torch_stft_fallback, MelSpectrogramGenerator.generate's torch branch,
+ * VoiceCloneDetector.score's energy proxy.  Geometry: torch.stft(n_fft=400, hop_length=160, window=None, center=True,
+ * pad_mode="reflect"), one-sided: 201 bins.  waves (B, n_max) fp32; lengths (B int32 on the device, NULL: n_max; clamped to
+ * [0, n_max]).  Clip b of len_b samples has T_b = 1 + len_b / 160 frames, frame t being samples 160 t .. 160 t + 399 of the clip
+ * reflect-padded by 200 on both sides (x_pad[i] = x[200 - i], ..., x[2 (len_b - 1) - (i - 200)]); the padding is index arithmetic,
+ * nothing at or past waves[b][len_b] is read.  A clip of fewer than 201 samples (torch.stft refuses it) has T_b = 0: all its outputs
+ * are zeros.  T_max = 1 + n_max / 160.  Nothing allocates or synchronises; no atomics, fixed reduction orders; a clip's outputs are
+ * the same bits alone, in any batch and with any set of outputs; every entry can be captured into a hipGraph.
+ *
+ *   ufnd_spectral_workspace_bytes   bytes of the per-tile statistics partials for (B, n_max) (0 for a refused shape): 32 per tile of
+ *                         UFND_STFT_FRAME_TILE frames.  Alignment: 8 bytes.
+ *   ufnd_stft_forensics   basis: (402, 400) fp32, row k < 201 = cos(2 pi k n / 400), row 201 + k = -sin(2 pi k n / 400), each the
+ *                         float64 value rounded once; 16-B aligned.  re and im of a (frame, bin) are each one chain of 400 fmaf from
+ *                         zero on the exact-fp32 MFMA, taps in the order 8u + e, 8u + 4 + e (u = 0 .. 49, e = 0 .. 3);
+ *                         |S| = sqrtf(fmaf(re, re, im im)).  Outputs, each optional (NULL), at least one:
+ *                           magnitude (B, 201, T_max)  |S|, zeros from frame T_b on
+ *                           mel_like  (B, 64, T_max)   ((|S|[3m] + |S|[3m+1]) + |S|[3m+2]) / 3 in fp32 (bins 192 .. 200 dropped), zeros
+ *                                                      from frame T_b on
+ *                           stats     (B, 4)           mean, population std, max, min of the clip's 201 T_b magnitudes: sum and centred
+ *                                                      second moment in double (per tile, then the tiles in order by Chan's update),
+ *                                                      rounded to fp32 once
+ *                           features  (B, dim)         stats tiled to dim, divided by (norm + 1e-9) in fp32 (the norm in double,
+ *                                                      rounded once); an all-zero clip gives exactly 0
+ *                         stats or features need the workspace; neither writes the spectrogram anywhere.
+ *   ufnd_wave_energy      energy (B, optional) = e = mean(x^2) over the clip's len_b samples in fp32 (thread t of 256 chains samples
+ *                         t, t + 256, ... by fmaf, then a fixed tree; len_b = 0 gives 0); score (B, optional) = clip(e / (e + 1), 0, 1)
+ *                         divided in double and rounded once.  Any len_b >= 0.
+ * 1 <= B <= 65535, 1 <= n_max <= 2^30; offsets are 64-bit. */
+#define UFND_STFT_FRAME_TILE 64         /* frames of a workgroup's tile, counted from the clip's first frame */
+#define UFND_STFT_MIN_SAMPLES 201       /* shorter clips have no frames */
+size_t ufnd_spectral_workspace_bytes(int B, int n_max);
+int ufnd_stft_forensics(const float* waves, const int32_t* lengths, const float* basis, void* workspace, float* magnitude, float* mel_like,
+                        float* stats, float* features, int B, int n_max, int dim, void* stream);
+int ufnd_wave_energy(const float* waves, const int32_t* lengths, float* energy, float* score, int B, int n_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,7 @@ KNN_MAX_K = 64                              # ufnd_cosine_knn: neighbours per ro
 ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 AUDIO_MIN_SAMPLES, WAVE_CHUNK, CONV0_CHUNK = 400, 4096, 256      # UFND_AUDIO_MIN_SAMPLES, UFND_WAVE_CHUNK, UFND_CONV0_CHUNK
+STFT_FRAME_TILE, STFT_MIN_SAMPLES = 64, 201      # UFND_STFT_FRAME_TILE, UFND_STFT_MIN_SAMPLES
 
 _lib: Optional[C.CDLL] = None
 
@@ -267,6 +268,12 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_motion_workspace_bytes.argtypes = [I, I]
     lib.ufnd_motion_workspace_bytes.restype = S
+    sigs.update({      # STFT audio forensics (csrc/spectral.hip)
+        "ufnd_stft_forensics": [P] * 8 + [I, I, I, P],
+        "ufnd_wave_energy": [P, P, P, P, I, I, P],
+    })
+    lib.ufnd_spectral_workspace_bytes.argtypes = [I, I]
+    lib.ufnd_spectral_workspace_bytes.restype = S
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

@@ -4,7 +4,11 @@
                         normalisation (Wav2Vec2FeatureExtractor do_normalize) -> Wav2Vec2Model (wav2vec2-base geometry)
                         .last_hidden_state -> mean over time -> Linear(768, 128); batched over clips instead of one record at a
                         time on the CPU.
-  SpectralForensics     the reference's class name and extract(audio, sr), bound to the encoder above.
+  SpectralForensics     the reference's class name and extract(audio, sr), bound to the encoder above (branch="w2v2", the default)
+                        or to the STFT statistics (branch="stft").
+  stft_forensics, MelSpectrogramGenerator, VoiceCloneDetector, cache_audio, wave_energy
+                        the branches the reference takes without a checkpoint and without librosa (second half of this file,
+                        csrc/spectral.hip): torch.stft(n_fft=400, hop_length=160) magnitudes -> statistics, 64 bands; the energy proxy.
 
 Weights keep HF's `Wav2Vec2Model` state_dict names (plus proj.weight / proj.bias), so real checkpoints load unchanged.
 
@@ -292,47 +296,247 @@ class Wav2Vec2AudioEncoder(_EncoderBase):
         return self._run(waves, lengths)[0]["feat"]
 
 
-class SpectralForensics:
-    """The reference's audio feature extractor (src/core_blocks/audio_blocks.py), its wav2vec2 branch, on the GPU."""
+# ---------------------------------------------------------------------------------------------------------------------------
+# The STFT branches (csrc/spectral.hip): what the reference computes on a host without librosa and without a wav2vec2 checkpoint.
+N_FFT, HOP, N_BINS, N_BANDS = 400, 160, 201, 64
+STFT_MIN_SAMPLES = L.STFT_MIN_SAMPLES      # torch.stft's reflect padding of 200 needs 201 samples
+STFT_OUTPUTS = ("features", "stats", "mel_like", "magnitude", "frames")
+_basis_cache: dict = {}
 
-    def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32):
-        self.dim = int(dim)
+
+def dft_basis() -> np.ndarray:
+    """(402, 400) float32: row k < 201 = cos(2 pi k n / 400), row 201 + k = -sin(2 pi k n / 400); the angle is reduced exactly
+    (k n mod 400) and evaluated in float64, then rounded once."""
+    kn = (np.arange(N_BINS, dtype=np.int64)[:, None] * np.arange(N_FFT, dtype=np.int64)[None, :]) % N_FFT
+    ang = 2.0 * np.pi * kn.astype(np.float64) / N_FFT
+    return np.concatenate([np.cos(ang), -np.sin(ang)]).astype(np.float32)
+
+
+def _basis(dev: torch.device) -> torch.Tensor:
+    """The basis on `dev`: built on the host once, uploaded once per device."""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _basis_cache:
+        _basis_cache[key] = torch.from_numpy(dft_basis()).to(dev)
+    return _basis_cache[key]
+
+
+def stft_frame_count(n: int) -> int:
+    """T_b of a clip of n samples: 1 + n // 160, and 0 below 201 samples (torch.stft refuses those)."""
+    return 1 + int(n) // HOP if int(n) >= STFT_MIN_SAMPLES else 0
+
+
+def _device_waves(waves, lengths):
+    """(B, n_max) or (B, C, n_max) on a HIP device -> ((B, n_max) fp32 contiguous, (B,) int32 lengths or None); channels are averaged
+    on the device as the reference's _ensure_mono_16k does on the host."""
+    if isinstance(waves, str):
+        raise TypeError("a str (text proxy) is not supported: the reference's proxies use Python's salted hash(), so their values are not "
+                        "reproducible from run to run")
+    if not torch.is_tensor(waves):
+        raise L.UltrafndHipError("waves must be a tensor on a HIP device (no CPU fallback)")
+    dev = L.require_hip(waves)
+    if waves.dim() == 3:
+        waves = waves.float().mean(dim=1)
+    if waves.dim() != 2 or waves.shape[0] < 1 or waves.shape[1] < 1:
+        raise ValueError(f"waves: expected (B, n_max) or (B, C, n_max), got {tuple(waves.shape)}")
+    B = waves.shape[0]
+    lens = None
+    if lengths is not None:
+        lens = lengths.to(dev, torch.int32).contiguous() if torch.is_tensor(lengths) else torch.tensor(list(lengths), dtype=torch.int32, device=dev)
+        if lens.numel() != B:
+            raise ValueError(f"lengths holds {lens.numel()} entries for {B} clips")
+    return L.f32c(waves), lens
+
+
+@torch.no_grad()
+def stft_forensics(waves: torch.Tensor, lengths=None, dim: int = 128, want: Sequence[str] = ("features",)) -> dict:
+    """torch.stft(n_fft=400, hop_length=160).abs() of every clip and what the reference derives from it, in one launch plus a finish:
+      features (B, dim)           SpectralForensics._torch_stft_fallback: [mean, std, max, min] tiled to dim, L2-normalised
+      stats (B, 4)                mean, population std, max, min of |S|
+      mel_like (B, 64, T_max)     MelSpectrogramGenerator's 3-bin pooling, [band, time], zeros past a clip's frames
+      magnitude (B, 201, T_max)   |S| itself, zeros past a clip's frames
+      frames (B,) int32           T_b = 1 + len_b // 160 (0 for a clip under 201 samples, whose outputs are all zeros)
+    waves: (B, n_max) fp32 on a HIP device, or (B, C, n_max), averaged to mono; lengths: (B,) samples per clip (a device tensor is not
+    read on the host: nothing here synchronises).  features and stats never write the spectrogram."""
+    want = tuple(want)
+    for name in want:
+        if name not in STFT_OUTPUTS:
+            raise ValueError(f"want={name!r}: one of {STFT_OUTPUTS}")
+    if not want:
+        raise ValueError(f"want is empty: some of {STFT_OUTPUTS}")
+    if int(dim) < 1:
+        raise ValueError(f"dim={dim}: at least 1")
+    x, lens = _device_waves(waves, lengths)
+    dev, (B, n_max) = x.device, x.shape
+    T_max = 1 + n_max // HOP
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {}
+    if "features" in want:
+        out["features"] = torch.empty(B, int(dim), **f32)
+    if "stats" in want:
+        out["stats"] = torch.empty(B, 4, **f32)
+    if "mel_like" in want:
+        out["mel_like"] = torch.empty(B, N_BANDS, T_max, **f32)
+    if "magnitude" in want:
+        out["magnitude"] = torch.empty(B, N_BINS, T_max, **f32)
+    if out:
+        ws = None
+        if "features" in out or "stats" in out:
+            nbytes = L.lib().ufnd_spectral_workspace_bytes(B, n_max)
+            if nbytes == 0:
+                raise L.UltrafndHipError(f"stft_forensics: B={B} n_max={n_max} is refused (B <= 65535, n_max <= 2^30)")
+            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        L.check(L.lib().ufnd_stft_forensics(x.data_ptr(), L.ptr(lens), _basis(dev).data_ptr(), L.ptr(ws), L.ptr(out.get("magnitude")),
+                                            L.ptr(out.get("mel_like")), L.ptr(out.get("stats")), L.ptr(out.get("features")), B, n_max, int(dim),
+                                            L.stream_ptr(dev)), "ufnd_stft_forensics")
+    if "frames" in want:
+        n = torch.full((B,), n_max, dtype=torch.int32, device=dev) if lens is None else lens.clamp(0, n_max)
+        out["frames"] = torch.where(n >= STFT_MIN_SAMPLES, 1 + torch.div(n, HOP, rounding_mode="floor"), torch.zeros_like(n)).to(torch.int32)
+    return out
+
+
+@torch.no_grad()
+def wave_energy(waves: torch.Tensor, lengths=None) -> dict:
+    """energy (B,) = mean(x^2) and score (B,) = clip(e / (e + 1), 0, 1): VoiceCloneDetector's energy proxy, batched."""
+    x, lens = _device_waves(waves, lengths)
+    B, n_max = x.shape
+    out = {"energy": torch.empty(B, dtype=torch.float32, device=x.device), "score": torch.empty(B, dtype=torch.float32, device=x.device)}
+    L.check(L.lib().ufnd_wave_energy(x.data_ptr(), L.ptr(lens), out["energy"].data_ptr(), out["score"].data_ptr(), B, n_max, L.stream_ptr(x.device)),
+            "ufnd_wave_energy")
+    return out
+
+
+def _mono_16k(audio, sr: int, who: str) -> np.ndarray:
+    """One clip as the reference's _ensure_mono_16k leaves it: host float32 (T,), channels averaged."""
+    if isinstance(audio, str):
+        raise TypeError(f"{who}: a str (text proxy) is not supported: the reference's _hash_embed uses Python's salted "
+                        "hash(), so its vectors are not reproducible from run to run")
+    if int(sr) != 16000:
+        raise ValueError(f"sr={sr}: {who} takes 16 kHz audio (the reference resamples with librosa, which is not part of this package)")
+    wav = audio.detach().cpu().numpy() if torch.is_tensor(audio) else np.asarray(audio)
+    wav = wav.astype(np.float32)
+    if wav.ndim == 2:      # (C, T) -> mono, as _ensure_mono_16k
+        wav = wav.mean(axis=0)
+    if wav.ndim != 1:
+        raise ValueError(f"audio: expected (T,) or (C, T), got {wav.shape}")
+    return wav
+
+
+def _length_groups(wavs: List[np.ndarray], max_batch: int):
+    """Clips sorted by length, in groups of at most max_batch neighbours (bounded padding): (indices, (n, n_max) zero-padded host
+    batch, lengths) per group."""
+    order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
+    for s0 in range(0, len(order), max_batch):
+        idx = order[s0:s0 + max_batch]
+        batch = torch.zeros(len(idx), max(len(wavs[i]) for i in idx))
+        for r, i in enumerate(idx):
+            batch[r, :len(wavs[i])] = torch.from_numpy(wavs[i])
+        yield idx, batch, [len(wavs[i]) for i in idx]
+
+
+def _require_stft_lengths(wavs: List[np.ndarray]) -> None:
+    for w in wavs:
+        if len(w) < STFT_MIN_SAMPLES:
+            raise ValueError(f"clip length {len(w)}: the STFT branch needs at least {STFT_MIN_SAMPLES} samples (torch.stft's reflect padding of 200)")
+
+
+class SpectralForensics:
+    """The reference's audio feature extractor (src/core_blocks/audio_blocks.py) on the GPU.
+      branch="w2v2"  (default) its wav2vec2 branch: the encoder above.
+      branch="stft"  its _torch_stft_fallback, the branch it takes without a checkpoint and without librosa: no encoder is built."""
+
+    def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32, branch: str = "w2v2"):
+        if branch not in ("w2v2", "stft"):
+            raise ValueError(f"branch={branch!r}: 'w2v2' or 'stft'")
+        self.dim, self.branch = int(dim), branch
+        if self.dim < 1:
+            raise ValueError(f"dim={dim}: at least 1")
+        self.max_batch = int(max_batch)
+        self.device = torch.device(device)
+        if branch == "stft":
+            if encoder is not None:
+                raise ValueError("branch='stft' runs no encoder: pass encoder=None")
+            self.encoder = None
+            return
         self.encoder = encoder if encoder is not None else Wav2Vec2AudioEncoder(out_dim=self.dim).to(device)
         if self.encoder.out_dim != self.dim:
             raise ValueError(f"dim={self.dim} but the encoder projects to {self.encoder.out_dim}")
-        self.max_batch = int(max_batch)
 
     @staticmethod
     def _mono_16k(audio, sr: int) -> np.ndarray:
-        if isinstance(audio, str):
-            raise TypeError("SpectralForensics.extract: a str (text proxy) is not supported: the reference's _hash_embed uses Python's salted "
-                            "hash(), so its vectors are not reproducible from run to run")
-        if int(sr) != 16000:
-            raise ValueError(f"sr={sr}: SpectralForensics takes 16 kHz audio (the reference resamples with librosa, which is not part of this package)")
-        wav = audio.detach().cpu().numpy() if torch.is_tensor(audio) else np.asarray(audio)
-        wav = wav.astype(np.float32)
-        if wav.ndim == 2:      # (C, T) -> mono, as _ensure_mono_16k
-            wav = wav.mean(axis=0)
-        if wav.ndim != 1:
-            raise ValueError(f"audio: expected (T,) or (C, T), got {wav.shape}")
-        return wav
+        return _mono_16k(audio, sr, "SpectralForensics")
 
     def extract(self, audio_or_text, sr: int = 16000) -> np.ndarray:
         """One clip -> (dim,) float32."""
         wav = self._mono_16k(audio_or_text, sr)
+        if self.branch == "stft":
+            _require_stft_lengths([wav])
+            return stft_forensics(torch.from_numpy(wav)[None].to(self.device), None, self.dim)["features"].cpu().numpy()[0]
         return self.encoder(torch.from_numpy(wav)[None]).cpu().numpy()[0]
 
     def extract_batch(self, waves, sr: int = 16000) -> np.ndarray:
         """A list of clips -> (N, dim) float32: the batched entry of a cache builder.  Clips are sorted by length and run in groups
         of at most max_batch neighbours, which bounds the padding; every row equals extract() of its clip bit for bit."""
         wavs = [self._mono_16k(a, sr) for a in waves]
+        if self.branch == "stft":
+            _require_stft_lengths(wavs)
         out = np.zeros((len(wavs), self.dim), dtype=np.float32)
-        order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
-        for s0 in range(0, len(order), self.max_batch):
-            idx = order[s0:s0 + self.max_batch]
-            n_max = max(len(wavs[i]) for i in idx)
-            batch = torch.zeros(len(idx), n_max)
-            for r, i in enumerate(idx):
-                batch[r, :len(wavs[i])] = torch.from_numpy(wavs[i])
-            out[idx] = self.encoder(batch, [len(wavs[i]) for i in idx]).cpu().numpy()
+        for idx, batch, lens in _length_groups(wavs, self.max_batch):
+            if self.branch == "stft":
+                out[idx] = stft_forensics(batch.to(self.device), lens, self.dim)["features"].cpu().numpy()
+            else:
+                out[idx] = self.encoder(batch, lens).cpu().numpy()
         return out
+
+
+class MelSpectrogramGenerator:
+    """MelSpectrogramGenerator of the reference on its torch branch: the STFT magnitudes' bins 3m, 3m + 1, 3m + 2 averaged into 64
+    bands ([band, time]; bins 192 .. 200 are dropped).  The reference's geometry only; anything else is refused by name."""
+
+    def __init__(self, sr: int = 16000, n_mels: int = N_BANDS, n_fft: int = N_FFT, hop_length: int = HOP, device="cuda", max_batch: int = 32):
+        for name, got, want in (("sr", sr, 16000), ("n_mels", n_mels, N_BANDS), ("n_fft", n_fft, N_FFT), ("hop_length", hop_length, HOP)):
+            if int(got) != want:
+                raise ValueError(f"{name}={got!r}: MelSpectrogramGenerator is built for the reference's defaults ({name}={want})")
+        self.sr, self.n_mels, self.n_fft, self.hop = 16000, N_BANDS, N_FFT, HOP
+        self.device, self.max_batch = torch.device(device), int(max_batch)
+
+    def generate_batch(self, waves, sr: int = 16000, flatten: bool = True) -> List[np.ndarray]:
+        """A list of clips -> per clip the (64, T_b) float32 matrix, or its flattening."""
+        wavs = [_mono_16k(a, sr, "MelSpectrogramGenerator") for a in waves]
+        _require_stft_lengths(wavs)
+        out: List[Optional[np.ndarray]] = [None] * len(wavs)
+        for idx, batch, lens in _length_groups(wavs, self.max_batch):
+            mel = stft_forensics(batch.to(self.device), lens, want=("mel_like",))["mel_like"].cpu().numpy()
+            for r, i in enumerate(idx):
+                m = np.ascontiguousarray(mel[r, :, :stft_frame_count(lens[r])])
+                out[i] = m.flatten() if flatten else m
+        return out
+
+    def generate(self, wave, sr: int = 16000, flatten: bool = True) -> np.ndarray:
+        return self.generate_batch([wave], sr, flatten)[0]
+
+
+class VoiceCloneDetector:
+    """VoiceCloneDetector of the reference on its energy branch: e = mean(x^2), score = clip(e / (e + 1), 0, 1)."""
+
+    def __init__(self, device="cuda", max_batch: int = 32):
+        self.device, self.max_batch = torch.device(device), int(max_batch)
+
+    def score_batch(self, waves, sr: int = 16000) -> np.ndarray:
+        """A list of clips -> (N,) float32 scores; every entry equals score() of its clip bit for bit."""
+        wavs = [_mono_16k(a, sr, "VoiceCloneDetector") for a in waves]
+        out = np.zeros(len(wavs), dtype=np.float32)
+        for idx, batch, lens in _length_groups(wavs, self.max_batch):
+            if batch.shape[1] == 0:      # (empty clips only: the mean of nothing; the reference returns NaN there, this returns 0)
+                continue
+            out[idx] = wave_energy(batch.to(self.device), lens)["score"].cpu().numpy()
+        return out
+
+    def score(self, audio_or_text, sr: int = 16000) -> float:
+        return float(self.score_batch([audio_or_text], sr)[0])
+
+
+@torch.no_grad()
+def cache_audio(waves: torch.Tensor, lengths=None, audio_dim: int = 128) -> torch.Tensor:
+    """The `audio` row of the reference's cache builder on real waveforms, on the branch the reference takes without a checkpoint:
+    SpectralForensics(dim=audio_dim).extract of every clip, (B, audio_dim) fp32 on the waves' device (a vector of unit norm already)."""
+    return stft_forensics(waves, lengths, audio_dim)["features"]

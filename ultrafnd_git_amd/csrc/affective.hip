@@ -151,13 +151,7 @@ __global__ __launch_bounds__(256) void audio_arousal_kernel(const float* x, cons
   const int b = blockIdx.x;
   int n = lengths ? lengths[b] : T;
   n = n < 0 ? 0 : (n > T ? T : n);
-  const float* row = x + (size_t)b * T;
-  float q = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const float v = row[i];
-    q = fmaf(v, v, q);
-  }
-  const float tot = block_sum4(q, red);
+  const float tot = block_square_sum(x + (size_t)b * T, n, red);
   if (threadIdx.x == 0) {
     const float en = n > 0 ? tot / (float)n : 0.0f;
     out[b] = clip01(1.0f / (1.0f + expf(-5.0f * en)));

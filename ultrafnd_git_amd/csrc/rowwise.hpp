@@ -72,6 +72,17 @@ __device__ __forceinline__ float block_sum4(float v, float* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// sum of x[i]^2 over a clip's first n samples by a 256-thread workgroup: thread t adds the squares of samples t, t + 256, ... in
+// order (one fmaf each), then block_sum4's tree (ufnd_audio_arousal, ufnd_wave_energy)
+__device__ __forceinline__ float block_square_sum(const float* row, int n, float* red) {
+  float q = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float v = row[i];
+    q = fmaf(v, v, q);
+  }
+  return block_sum4(q, red);
+}
+
 // The pack kernels (ufnd_text_pack, ufnd_clip_text_pack): ONE workgroup of PACK_THREADS threads over up to PACK_MAX_B samples.
 // In: lens[b] = n_b, the rows sample b keeps, written by all threads and not yet synchronised.  Out: cu = the exclusive prefix
 // sum of n_b in a fixed order (cu[B] = the live row count, which is returned), lens[b] = cu[b], and
