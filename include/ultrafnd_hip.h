@@ -1154,6 +1154,59 @@ int ufnd_stft_forensics(const float* waves, const int32_t* lengths, const float*
                         float* stats, float* features, int B, int n_max, int dim, void* stream);
 int ufnd_wave_energy(const float* waves, const int32_t* lengths, float* energy, float* score, int B, int n_max, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * Image-forgery evidence: DeepForgeryDetector.ela_lbp and FaceWarpAnalyzer.score (src/core_blocks/visual_blocks.py:265-406), batched
+ * (csrc/forgery.hip).  Frames as for ufnd_motion_gray: uint8, (b, t, c, y, x) at frames + b stride_b + t stride_t + c stride_c +
+ * y stride_h + x stride_w, 3 channels; a batch of single images is T = 1.  `lengths` (B int32 on the device, NULL: T; clamped to
+ * [0, T]).  Clip b contributes ONE frame, index len_b / 2 (the reference's frames[len(frames) // 2]), resized to 256 x 256 by the
+ * nearest-neighbour rule (source pixel ((y H) >> 8, (x W) >> 8)).  A clip of length 0 has no frame: nothing of it is read, its stats,
+ * histogram, vector and gradient are zeros and its score is 0.0 (the reference's `img is None` result); its planes and maps are not
+ * written.  The error level (ELA) map is |rgb - rec| with rec the image after a JPEG round trip, which is integer arithmetic from end to
+ * end (baseline libjpeg, 4:2:0, the "islow" DCTs, fancy upsampling; entropy coding is lossless and left out): rec equals what
+ * libjpeg decodes in every byte.  Nothing allocates or synchronises; no global atomics, fixed reduction orders: a clip's results are the
+ * same bits alone, in any batch and from run to run; every entry can be captured into a hipGraph.
+ *
+ *   ufnd_forgery_workspace_bytes   bytes of the workspace all stages share for B clips (0 for a refused B).  It starts with rgb
+ *                         (B, 256, 256, 3) uint8, then rec slot 0 and rec slot 1 of the same shape; the rest is the decoded Y / Cb /
+ *                         Cr planes and per-slab partials.  Alignment: 256 bytes.
+ *   ufnd_forgery_resize   writes rgb.  Only the sampled pixels of the one frame per clip are read.
+ *   ufnd_forgery_roundtrip   rgb -> rec[slot].  jpeg_mode 1: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G +
+ *                         32768 B + (128 << 16) + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16; chroma
+ *                         2 x 2 downsampled, (sum + bias) >> 2 with bias 1 on even and 2 on odd output columns; per 8 x 8 block of
+ *                         sample - 128 jfdctint (rows, then columns; the result is scaled by 8), |c| -> (|c| + (8 q >> 1)) / (8 q) with
+ *                         the sign restored, times q, jidctint (columns DESCALE 11, rows DESCALE 18), + 128, clamped; fancy h2v2
+ *                         upsampling (3/4 nearer + 1/4 farther row, then column, edges replicated, rounding 8 / 7 on even / odd
+ *                         columns); R = Y + ((91881 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16), G = Y + ((-22554 Cb' +
+ *                         32768 - 46802 Cr') >> 16) with C' = C - 128, clamped.  qtables: HOST pointer to 128 quantisers (1 .. 255),
+ *                         luma then chroma, natural order; they travel as kernel arguments.  jpeg_mode 0: rec[slot] = rgb, the
+ *                         reference's branch on a host without OpenCV (qtables may be NULL).  Needs ufnd_forgery_resize before it.
+ *   ufnd_forgery_maps     over rgb and rec[slot]: ela = uint8(trunc(clip(fl32(|rgb - rec|) ela_scale, 0, 255))), the product in fp32;
+ *                         per 16-row slab the integer sum, sum of squares, max and min over the three channels.  want_lbp: the luma of
+ *                         the ELA map (the float64 luma of ufnd_motion_gray) and, for the centres (y, x), y and x in 1, 3, ..., 253,
+ *                         the number of the 8 neighbours strictly greater than the centre: counts per code 0 .. 8.  want_grad: of the
+ *                         luma g of rgb (not of the map) gx = g(y, x) - g(y, x - 1), gy = g(y, x) - g(y - 1, x), zero in column 0 /
+ *                         row 0; the sum of sqrt(gx^2 + gy^2) in double and of gx^2 + gy^2 as an integer (slot 0 only: the gradient does
+ *                         not depend on rec).  ela_map (B, 256, 256, 3) and ela_gray (B, 256, 256) uint8, each optional (NULL), 4-B aligned.
+ *   ufnd_forgery_finish   every output optional (NULL), at least one.  From slot 0's partials: stats (B, 4) = mean (the exact integer
+ *                         sum divided once in double), population std (sqrt((N Q - S^2) / N^2) from the exact integer numerator),
+ *                         max, min over the N = 196608 values; lbp (B, 10) = count / 1.0 / 16129 in double, as np.histogram(bins=10,
+ *                         range=(0, 10), density=True): code k in bin k, the tenth bin is always 0; features (B, dim) = the 14 values
+ *                         tiled (or cut) to dim and divided by (norm + 1e-9), the finish of ufnd_motion_flow_finish.  Needs maps on
+ *                         slot 0 with want_lbp.  grad (B, 2) = mean and population std of sqrt(gx^2 + gy^2) over the 65536 pixels in
+ *                         double; score (B) = clip(0.5 tanh(g_std / (g_mean + 1e-6)) + 0.5 mean_ela / 255, 0, 1) in double, rounded
+ *                         once, mean_ela being the map mean of rec[score_slot] (the reference scores with a quality-85, scale-1
+ *                         map whatever the detector's own settings are: callers put that map in a slot).  Needs maps on slot 0 with
+ *                         want_grad, and maps on score_slot.
+ * 1 <= B <= 65536, T >= 1, 1 <= H, W <= 2^20. */
+size_t ufnd_forgery_workspace_bytes(int B);
+int ufnd_forgery_resize(const void* frames, long long stride_b, long long stride_t, long long stride_c, long long stride_h, long long stride_w,
+                        const int32_t* lengths, void* workspace, int B, int T, int H, int W, void* stream);
+int ufnd_forgery_roundtrip(const int32_t* lengths, void* workspace, const unsigned char* qtables, int B, int T, int jpeg_mode, int slot, void* stream);
+int ufnd_forgery_maps(const int32_t* lengths, void* workspace, float ela_scale, void* ela_map, void* ela_gray, int B, int T, int slot, int want_lbp,
+                      int want_grad, void* stream);
+int ufnd_forgery_finish(const int32_t* lengths, const void* workspace, float* stats, float* lbp, float* features, float* grad, float* score, int B, int T,
+                        int dim, int score_slot, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,6 +268,14 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_motion_workspace_bytes.argtypes = [I, I]
     lib.ufnd_motion_workspace_bytes.restype = S
+    sigs.update({      # image-forgery evidence: DeepForgeryDetector and FaceWarpAnalyzer (csrc/forgery.hip)
+        "ufnd_forgery_resize": [P, LL, LL, LL, LL, LL, P, P, I, I, I, I, P],
+        "ufnd_forgery_roundtrip": [P, P, C.c_char_p, I, I, I, I, P],
+        "ufnd_forgery_maps": [P, P, C.c_float, P, P, I, I, I, I, I, P],
+        "ufnd_forgery_finish": [P, P, P, P, P, P, P, I, I, I, I, P],
+    })
+    lib.ufnd_forgery_workspace_bytes.argtypes = [I]
+    lib.ufnd_forgery_workspace_bytes.restype = S
     sigs.update({      # STFT audio forensics (csrc/spectral.hip)
         "ufnd_stft_forensics": [P] * 8 + [I, I, I, P],
         "ufnd_wave_energy": [P, P, P, P, I, I, P],

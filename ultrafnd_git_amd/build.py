@@ -58,7 +58,8 @@ def _digest(extra: str) -> str:
 # switch reaches the host pass of hipcc too, which answers "not a recognized feature for this target (ignoring feature)".
 FILE_FLAGS = {"gemm_bf16_pp": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "gemm_pp_diag": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "motion": ["-ffp-contract=off"]}      # the float64 luma is bit-exact only with every operation rounded on its own (csrc/motion.hip)
+              "motion": ["-ffp-contract=off"],      # the float64 luma is bit-exact only with every operation rounded on its own (csrc/frames.hpp)
+              "forgery": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, tag: str, flags: list, verbose: bool) -> Path:

@@ -13,6 +13,7 @@
 // are the same bits alone, in any batch and from run to run.  Degenerate clips give what the reference gives, NaN included: an empty
 // pyramid chunk (fewer than 4 pairs) is a NaN mean, a zero-variance series is a NaN correlation.
 #include "common.hpp"
+#include "frames.hpp"
 
 namespace {
 
@@ -44,42 +45,6 @@ inline Workspace carve(void* base, long long B, long long T) {
   w.bins = (int32_t*)take((size_t)B * CHUNKS * TILES * 8 * sizeof(int32_t));
   w.bytes = off;
   return w;
-}
-
-__device__ __forceinline__ int clip_len(const int32_t* lengths, int b, int T) {
-  const int n = lengths ? lengths[b] : T;
-  return n < 0 ? 0 : (n > T ? T : n);
-}
-
-// wave-wide integer sum by DPP, the association order of wave_sum (common.hpp); integer adds are order-independent anyway
-#define MOTION_DPP_I(v, ctrl, rmask) __builtin_amdgcn_update_dpp(0, (v), ctrl, rmask, 0xF, false)
-__device__ __forceinline__ int wave_sum_i(int v) {
-  v += MOTION_DPP_I(v, 0xB1, 0xF);
-  v += MOTION_DPP_I(v, 0x4E, 0xF);
-  v += MOTION_DPP_I(v, 0x141, 0xF);
-  v += MOTION_DPP_I(v, 0x140, 0xF);
-  v += MOTION_DPP_I(v, 0x142, 0xA);
-  v += MOTION_DPP_I(v, 0x143, 0xC);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// wave-wide double sum: the xor butterfly, every lane ends with the same bits
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// (0.2989 r + 0.587 g + 0.114 b) in double, each operation rounded on its own, truncated.  A fused multiply-add changes 224 of the 2^24
-// triples.  HIP's __dmul_rn / __dadd_rn are plain operators compiled with the header's contraction setting and were fused here; plain
-// operators under the pragma are not (and build.py compiles this file with -ffp-contract=off).
-__device__ __forceinline__ uint32_t luma_u8(uint32_t r, uint32_t g, uint32_t b) {
-#pragma clang fp contract(off)
-  const double pr = 0.2989 * (double)r;
-  const double pg = 0.587 * (double)g;
-  const double pb = 0.114 * (double)b;
-  const double rg = pr + pg;
-  const double y = rg + pb;
-  return (uint32_t)(int)y;
 }
 
 // ---- gray: grid B T 16, 256 threads; a thread packs 4 neighbouring outputs into one 32-bit store, 4 times
@@ -236,18 +201,6 @@ __global__ __launch_bounds__(256) void motion_pairs_kernel(const uint8_t* gray, 
     }
   }
   if (tid < CHUNKS * 8) binsg[(part + (size_t)(tid >> 3) * TILES) * 8 + (tid & 7)] = bins[tid >> 3][tid & 7];
-}
-
-// tile v (nv values, in LDS) to `dim` entries and divide by fl32(||.||) + 1e-9 (fp32, as np.linalg.norm(v) + 1e-9 is under NumPy 2)
-__device__ __forceinline__ void tile_normalise(const float* v, int nv, float* out, int dim, float* nrm_slot) {
-  if (threadIdx.x == 0) {
-    double q = 0.0;
-    for (int k = 0; k < nv && k < dim; ++k) q += (double)((dim - k + nv - 1) / nv) * ((double)v[k] * (double)v[k]);      // entry k occurs ceil((dim - k) / nv) times
-    *nrm_slot = (float)sqrt(q) + 1e-9f;
-  }
-  __syncthreads();
-  const float nrm = *nrm_slot;
-  for (int j = threadIdx.x; j < dim; j += blockDim.x) out[j] = __fdiv_rn(v[j % nv], nrm);
 }
 
 // ---- ChronosGuard finish: grid B, 256 threads.  A wave per pair: lanes 0..31 hold the bins of frame t, lanes 32..63 those of t + 1.

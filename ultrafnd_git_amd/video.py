@@ -16,6 +16,14 @@ Degenerate clips give exactly what the reference gives, NaN included:
   ChronosGuard.features     with more than 3 pairs the seventh statistic is np.corrcoef of the two per-pair series; a series without
                             variance (a static clip) makes it 0 / 0 = NaN and so the vector.  tamper_score does not use it and stays finite.
 There is no CPU fallback: CPU tensors or a missing library raise.
+
+Image-forgery evidence (csrc/forgery.hip): DeepForgeryDetector (:265-351) and FaceWarpAnalyzer (:358-406) of the same file.  Each clip
+contributes one frame, index len // 2, resized to 256 x 256; a (B, H, W, 3) / (B, 3, H, W) image batch is a batch of one-frame clips.
+The error level (ELA) map is |rgb - rec| with rec the frame after a JPEG round trip at `ela_quality`.  The reference makes that trip
+through OpenCV; here it is baseline libjpeg's integer arithmetic on the device (4:2:0, standard tables, the islow DCTs, fancy
+upsampling), equal to what libjpeg decodes in every byte -- jpeg="libjpeg".  jpeg="none" is the reference on a host without OpenCV:
+rec = rgb, the map is zero and the vector a constant.  The LBP histogram is the reference's branch without scikit-image, the
+gradient its forward differences.  A clip of length 0 gives a zero vector and score 0.0.
 """
 from __future__ import annotations
 
@@ -31,8 +39,9 @@ POOLED = 77            # 7 pyramid chunks x (mean, std, max, 8 orientation count
 
 
 def _as_clips(frames, device=None) -> torch.Tensor:
-    """A (T, ...) or (B, T, ...) stack -> 5-D device tensor.  Host arrays and lists are moved to `device` (the single-clip methods take
-    what the reference's take); a CPU tensor is refused like everywhere in the package."""
+    """Frames of any rank -> the same frames as a device tensor; the callers check the rank (MotionStages: 5-D clips; ForgeryStages: 5-D
+    clips or a 4-D image batch).  Host arrays and lists are moved to `device` (the single-input methods take what the reference's
+    take); a CPU tensor is refused like everywhere in the package; a str raises."""
     if isinstance(frames, str):
         raise TypeError("a str input is the reference's salted-hash() text proxy, which is not reproduced: pass frames")
     if not isinstance(frames, torch.Tensor):
@@ -242,9 +251,192 @@ class ChronosGuard:
         return float((lo + int(np.argmax(lags[lo:hi])) - mid) / sr)
 
 
+# ISO/IEC 10918-1 Annex K, tables K.1 (luminance) and K.2 (chrominance), natural (row-major) order
+JPEG_K1 = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+JPEG_K2 = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+SCORE_QUALITY = 85     # FaceWarpAnalyzer scores with DeepForgeryDetector(dim=16)'s map: quality 85, scale 1, whatever the caller's detector uses
+
+
+def jpeg_qtables(quality: int) -> bytes:
+    """libjpeg's quality rule over the two Annex-K tables -> 128 quantisers, luma then chroma, natural order."""
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"ela_quality={quality}: 1 .. 100")
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return bytes(min(255, max(1, (base * scale + 50) // 100)) for base in JPEG_K1 + JPEG_K2)
+
+
+def _jpeg_mode(jpeg: str) -> int:
+    if jpeg not in ("libjpeg", "none"):
+        raise ValueError(f"jpeg={jpeg!r}: 'libjpeg' (the round trip) or 'none' (the reference without OpenCV: rec = rgb)")
+    return int(jpeg == "libjpeg")
+
+
+class ForgeryStages:
+    """The stages over one batch, sharing one workspace: resize -> roundtrip -> maps -> finish.  Two slots hold a round-tripped image
+    and its map partials each: slot 0 feeds the vector, `score_slot` the score's ELA term."""
+
+    def __init__(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None):
+        frames = frames_to_uint8(frames)
+        if frames.dim() == 4:                     # an image batch: clips of one frame
+            frames = frames.unsqueeze(1)
+        self.dev = L.require_hip(frames)
+        self.frames = frames                      # (kept alive until the launches are enqueued)
+        self.plan = p = _Plan(frames, layout)
+        self.lens = _lengths(lengths, p.B, self.dev)
+        nbytes = L.lib().ufnd_forgery_workspace_bytes(p.B)
+        if nbytes == 0:
+            raise L.UltrafndHipError(f"forgery: B={p.B} is refused (B <= 65536)")
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self._stream = L.stream_ptr(self.dev)
+
+    def _image(self, k: int) -> torch.Tensor:
+        n = self.plan.B * SIDE * SIDE * 3
+        return self.workspace[k * n:(k + 1) * n].view(self.plan.B, SIDE, SIDE, 3)
+
+    def resize(self) -> torch.Tensor:
+        """The middle frames at the working size: (B, 256, 256, 3) uint8, a view of the workspace."""
+        p = self.plan
+        L.check(L.lib().ufnd_forgery_resize(self.frames.data_ptr(), *p.strides, L.ptr(self.lens), self.workspace.data_ptr(), p.B, p.T, p.H, p.W,
+                                            self._stream), "ufnd_forgery_resize")
+        return self._image(0)
+
+    def roundtrip(self, quality: int, jpeg_mode: int = 1, slot: int = 0) -> torch.Tensor:
+        """rec[slot] (B, 256, 256, 3) uint8, a view of the workspace."""
+        p = self.plan
+        tables = jpeg_qtables(quality) if jpeg_mode else None
+        L.check(L.lib().ufnd_forgery_roundtrip(L.ptr(self.lens), self.workspace.data_ptr(), tables, p.B, p.T, jpeg_mode, slot, self._stream),
+                "ufnd_forgery_roundtrip")
+        return self._image(1 + slot)
+
+    def maps(self, scale: float, slot: int = 0, lbp: bool = True, grad: bool = False, ela_map: bool = False, ela_gray: bool = False) -> Dict[str, torch.Tensor]:
+        p = self.plan
+        new = torch.empty if self.lens is None else torch.zeros      # an empty clip's map is not written: zeros
+        out = {}
+        if ela_map:
+            out["ela_map"] = new(p.B, SIDE, SIDE, 3, dtype=torch.uint8, device=self.dev)
+        if ela_gray:
+            out["ela_gray"] = new(p.B, SIDE, SIDE, dtype=torch.uint8, device=self.dev)
+        L.check(L.lib().ufnd_forgery_maps(L.ptr(self.lens), self.workspace.data_ptr(), float(scale), L.ptr(out.get("ela_map")), L.ptr(out.get("ela_gray")), p.B, p.T,
+                                          slot, int(lbp), int(grad), self._stream), "ufnd_forgery_maps")
+        return out
+
+    def finish(self, dim: Optional[int] = None, grad: bool = False, score_slot: int = 0) -> Dict[str, torch.Tensor]:
+        """dim: stats (B, 4), lbp (B, 10), features (B, dim); grad: grad (B, 2), score (B,)."""
+        p = self.plan
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {}
+        if dim is not None:
+            out.update(stats=torch.empty(p.B, 4, **f32), lbp=torch.empty(p.B, 10, **f32), features=torch.empty(p.B, int(dim), **f32))
+        if grad:
+            out.update(grad=torch.empty(p.B, 2, **f32), score=torch.empty(p.B, **f32))
+        L.check(L.lib().ufnd_forgery_finish(L.ptr(self.lens), self.workspace.data_ptr(), L.ptr(out.get("stats")), L.ptr(out.get("lbp")), L.ptr(out.get("features")),
+                                            L.ptr(out.get("grad")), L.ptr(out.get("score")), p.B, p.T, int(dim or 1), score_slot, self._stream),
+                "ufnd_forgery_finish")
+        return out
+
+
+@torch.no_grad()
+def forgery_features(frames: torch.Tensor, lengths=None, dim: int = 256, ela_quality: int = 85, ela_scale: float = 1.0, jpeg: str = "libjpeg",
+                     layout: Optional[str] = None, ela_map: bool = False) -> Dict[str, torch.Tensor]:
+    """DeepForgeryDetector.ela_lbp_batch and FaceWarpAnalyzer.score_batch over one resize and, when the detector's settings are the
+    score's (quality 85, scale 1), one round trip and one map: features (B, dim), stats (B, 4), lbp (B, 10), grad (B, 2), score (B,);
+    with ela_map also the detector's map (B, 256, 256, 3) uint8."""
+    mode = _jpeg_mode(jpeg)
+    jpeg_qtables(ela_quality)
+    st = ForgeryStages(_as_clips(frames), lengths, layout)
+    st.resize()
+    st.roundtrip(ela_quality, mode, 0)
+    out = st.maps(ela_scale, 0, lbp=True, grad=True, ela_map=ela_map)
+    score_slot = 0
+    if mode and (int(ela_quality) != SCORE_QUALITY or float(ela_scale) != 1.0):
+        score_slot = 1
+        st.roundtrip(SCORE_QUALITY, mode, 1)
+        st.maps(1.0, 1, lbp=False, grad=False)
+    out.update(st.finish(dim, grad=True, score_slot=score_slot))
+    return out
+
+
+def _one_image(x, device) -> torch.Tensor:
+    """What the reference's single-input methods take -> a batch of one clip: an image (H, W, 3) / (3, H, W), a stack of frames
+    (T, H, W, 3) / (T, 3, H, W), or a list of frames."""
+    if isinstance(x, (list, tuple)) and x and isinstance(x[0], torch.Tensor):
+        x = torch.stack(list(x))
+    clip = _as_clips(x, device)
+    if clip.dim() == 3:
+        clip = clip[None]
+    if clip.dim() != 4:
+        raise ValueError(f"input {tuple(clip.shape)}: one image (H, W, 3) or one stack of frames (T, H, W, 3), channels first or last")
+    return clip[None]
+
+
+class DeepForgeryDetector:
+    """DeepForgeryDetector of the reference: [mean, std, max, min] of the ELA map and the 10-bin histogram of its luma's 3 x 3
+    greater-neighbour counts, tiled to `dim` and L2-normalised.  lbp_radius and lbp_points are accepted and unused, as in the
+    reference's branch without scikit-image."""
+
+    def __init__(self, dim: int = 256, ela_quality: int = 85, ela_scale: float = 1.0, lbp_radius: int = 1, lbp_points: int = 8, jpeg: str = "libjpeg",
+                 device="cuda"):
+        if int(dim) < 1:
+            raise ValueError(f"dim={dim}: at least 1")
+        jpeg_qtables(ela_quality)
+        if not np.isfinite(float(ela_scale)):
+            raise ValueError(f"ela_scale={ela_scale}: finite")
+        self.dim, self.ela_quality, self.ela_scale = int(dim), int(ela_quality), float(ela_scale)
+        self.lbp_radius, self.lbp_points = int(lbp_radius), int(lbp_points)
+        self.jpeg, self._mode = jpeg, _jpeg_mode(jpeg)
+        self.device = torch.device(device)
+
+    def _stages(self, frames, lengths, layout, **maps) -> Tuple[ForgeryStages, Dict[str, torch.Tensor]]:
+        st = ForgeryStages(_as_clips(frames), lengths, layout)
+        st.resize()
+        st.roundtrip(self.ela_quality, self._mode, 0)
+        return st, st.maps(self.ela_scale, 0, lbp=True, grad=False, **maps)
+
+    @torch.no_grad()
+    def ela_lbp_batch(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None, return_parts: bool = False):
+        """(B, dim) fp32 on the frames' device; with return_parts also stats (B, 4) and lbp (B, 10)."""
+        st, _ = self._stages(frames, lengths, layout)
+        out = st.finish(self.dim)
+        return (out["features"], out["stats"], out["lbp"]) if return_parts else out["features"]
+
+    @torch.no_grad()
+    def ela_map_batch(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None) -> torch.Tensor:
+        """The ELA map itself, (B, 256, 256, 3) uint8 (zeros for a clip of length 0)."""
+        return self._stages(frames, lengths, layout, ela_map=True)[1]["ela_map"]
+
+    def ela_lbp(self, image_or_frames) -> np.ndarray:
+        """One image or one stack of frames (its middle frame): a device tensor, or a host array / list -> np.ndarray[dim]."""
+        return self.ela_lbp_batch(_one_image(image_or_frames, self.device))[0].cpu().numpy()
+
+
+class FaceWarpAnalyzer:
+    """FaceWarpAnalyzer of the reference: clip(0.5 tanh(g_std / (g_mean + 1e-6)) + 0.5 mean(ELA) / 255, 0, 1) with g the forward-difference
+    gradient magnitude of the resized frame's luma and the ELA map that of a quality-85 round trip (zero with jpeg="none")."""
+
+    def __init__(self, jpeg: str = "libjpeg", device="cuda"):
+        self.jpeg, self._mode = jpeg, _jpeg_mode(jpeg)
+        self.device = torch.device(device)
+
+    @torch.no_grad()
+    def score_batch(self, frames: torch.Tensor, lengths=None, layout: Optional[str] = None, return_parts: bool = False):
+        """(B,) fp32 on the frames' device; with return_parts also grad (B, 2) = [g_mean, g_std]."""
+        st = ForgeryStages(_as_clips(frames), lengths, layout)
+        st.resize()
+        st.roundtrip(SCORE_QUALITY, self._mode, 0)
+        st.maps(1.0, 0, lbp=False, grad=True)
+        out = st.finish(None, grad=True)
+        return (out["score"], out["grad"]) if return_parts else out["score"]
+
+    def score(self, image_or_frames) -> float:
+        return float(self.score_batch(_one_image(image_or_frames, self.device))[0].cpu())
+
+
 @torch.no_grad()
 def cache_visual(frames: torch.Tensor, lengths=None, visual_dim: int = 512, layout: Optional[str] = None) -> torch.Tensor:
     """The `visual` row of the reference's cache builder: l2n(concat(flow(dim=visual_dim), ela)[:visual_dim]) with l2n(x) = x / (||x|| +
-    1e-9).  The flow vector already fills visual_dim, so the ELA part never enters: (B, visual_dim) fp32."""
+    1e-9).  The flow vector already fills visual_dim, so the ELA part (DeepForgeryDetector(dim=visual_dim)) is cut off whole and is
+    not computed: (B, visual_dim) fp32."""
     x = OpticalFlow3DCNN(dim=visual_dim).extract_batch(frames, lengths, layout)
     return x / (torch.linalg.vector_norm(x, dim=1, keepdim=True) + 1e-9)
