@@ -1155,6 +1155,47 @@ int ufnd_stft_forensics(const float* waves, const int32_t* lengths, const float*
 int ufnd_wave_energy(const float* waves, const int32_t* lengths, float* energy, float* score, int B, int n_max, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * Sample-rate conversion (csrc/resample.hip): the device form of the reference's _ensure_mono_16k
+ * (src/core_blocks/audio_blocks.py:34-45: channel mean, then librosa.resample, one clip at a time on the host).  Band-limited
+ * windowed-sinc interpolation in polyphase form.  With g = gcd(orig_sr, new_sr), o = orig_sr / g, n = new_sr / g and a quality
+ * (lpw, rolloff, window):  base = min(o, n) rolloff,  width = ceil(lpw o / base),  K = 2 width + o,  and for phase p < n, tap k < K
+ *     t = ((k - width) n - p o) / (o n) base;   h[p][k] = (base / o) sinc(pi t) w(t) for |t| < lpw, else 0
+ * (hann: w = cos^2(pi t / (2 lpw)); kaiser: w = I0(beta sqrt(1 - (t / lpw)^2)) / I0(beta)), evaluated in float64 on the host and
+ * rounded once.  Output:  y[q n + p] = sum_k h[p][k] xz[q o + k - width],  xz the clip, zero outside [0, len_b);  clip b has
+ * m_b = ceil(n len_b / o) outputs (64-bit arithmetic), m_max = ceil(n n_max / o).  o = n = 1 with the table h = [[1]] (width 0) copies.
+ *
+ *   waves     element (b, c, s) at waves + b stride_b + c stride_c + s stride_s ELEMENTS (64-bit offsets: channel-first, channel-last
+ *             or mono, no copy); dtype UFND_RESAMPLE_F32 or UFND_RESAMPLE_I16.  The mix happens while staging: float(v) per channel,
+ *             summed in channel order in fp32, divided once by C, multiplied once by `scale` (NumPy's
+ *             astype(float32).mean(axis=0) bit for bit; 1 / 32768 for PCM).  lengths: (B) int32 on the device, NULL: n_max; clamped
+ *             to [0, n_max].  Nothing at or past sample len_b of a clip is read.
+ *   the table is built by the host for a super-stride of G strides (o' = G o, n' = G n; phase g n + p of the super-stride is phase
+ *             p with its taps shifted by g o), in GROUPS of 4 neighbouring phases:
+ *               groups (ngroups, 3) int32 = first tap, tap count, row offset into `taps`; ngroups = ceil(n' / 4); first and count
+ *                      are multiples of 8 and cover the bands of the group's phases
+ *               taps   (tap_rows, 4) fp32, 16-B aligned: row (offset + k - first) = the taps k of phases 4 g .. 4 g + 3, zero where a
+ *                      phase has none (and for the phases past n')
+ *             A group whose entry is inconsistent (negative, not a multiple of 8, past tap_rows) computes zeros; the device never
+ *             reads outside the two tables.
+ *   a workgroup owns qt (<= UFND_RESAMPLE_OUT_TILE) super-strides of one clip, that is qt G n consecutive outputs counted from the
+ *             clip's first, and walks the filter in nchunks chunks of kc taps (kc a multiple of 8, nchunks kc >= the largest
+ *             first + count, (qt - 1) G o + kc <= UFND_RESAMPLE_LDS_FLOATS; a filter that fits has nchunks = 1).
+ *   out (B, m_max) fp32, zeros from m_b on;  out_lengths (B) int32 = m_b, written on the device.
+ * One value, one arithmetic: output (q, p) is ONE chain acc = fmaf(h[p][k], xz[q o + k - width], acc) from +0 over the stored band
+ * of phase p in ASCENDING k, whatever G, the group, the tile, the chunking, the batch and the row; the zero taps the group table
+ * adds leave it unchanged for finite samples (a non-finite sample inside a clip also poisons the outputs whose group band covers it,
+ * a few taps beyond its true support).  Nothing allocates or synchronises; no atomics, no scratch; hipGraph-capturable.
+ * 1 <= B <= 65535, 1 <= C <= 64, 1 <= n_max <= 2^30, 1 <= o, n <= UFND_RESAMPLE_MAX_RATIO_TERM, m_max <= 2^31 - 1. */
+#define UFND_RESAMPLE_OUT_TILE 64          /* super-strides (rows of G n outputs) of a workgroup's tile: one per lane */
+#define UFND_RESAMPLE_LDS_FLOATS 40000     /* staged samples of a workgroup */
+#define UFND_RESAMPLE_MAX_RATIO_TERM 1024  /* the reduced o and n */
+#define UFND_RESAMPLE_F32 0
+#define UFND_RESAMPLE_I16 1
+int ufnd_resample(const void* waves, int dtype, long long stride_b, long long stride_c, long long stride_s, const int32_t* lengths,
+                  const float* taps, const int32_t* groups, float* out, int32_t* out_lengths, int B, int C, int n_max, int o, int n, int G,
+                  int width, int ngroups, int tap_rows, int qt, int kc, int nchunks, float scale, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * Image-forgery evidence: DeepForgeryDetector.ela_lbp and FaceWarpAnalyzer.score (src/core_blocks/visual_blocks.py:265-406), batched
  * (csrc/forgery.hip).  Frames as for ufnd_motion_gray: uint8, (b, t, c, y, x) at frames + b stride_b + t stride_t + c stride_c +
  * y stride_h + x stride_w, 3 channels; a batch of single images is T = 1.  `lengths` (B int32 on the device, NULL: T; clamped to

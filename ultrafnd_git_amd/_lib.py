@@ -116,6 +116,8 @@ ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 AUDIO_MIN_SAMPLES, WAVE_CHUNK, CONV0_CHUNK = 400, 4096, 256      # UFND_AUDIO_MIN_SAMPLES, UFND_WAVE_CHUNK, UFND_CONV0_CHUNK
 STFT_FRAME_TILE, STFT_MIN_SAMPLES = 64, 201      # UFND_STFT_FRAME_TILE, UFND_STFT_MIN_SAMPLES
+RESAMPLE_OUT_TILE, RESAMPLE_LDS_FLOATS, RESAMPLE_MAX_RATIO_TERM = 64, 40000, 1024      # UFND_RESAMPLE_OUT_TILE, _LDS_FLOATS, _MAX_RATIO_TERM
+RESAMPLE_F32, RESAMPLE_I16 = 0, 1
 
 _lib: Optional[C.CDLL] = None
 
@@ -279,6 +281,9 @@ def _declare_encoders(lib: C.CDLL) -> None:
     sigs.update({      # STFT audio forensics (csrc/spectral.hip)
         "ufnd_stft_forensics": [P] * 8 + [I, I, I, P],
         "ufnd_wave_energy": [P, P, P, P, I, I, P],
+    })
+    sigs.update({      # sample-rate conversion (csrc/resample.hip)
+        "ufnd_resample": [P, I, LL, LL, LL, P, P, P, P, P] + [I] * 12 + [F, P],
     })
     lib.ufnd_spectral_workspace_bytes.argtypes = [I, I]
     lib.ufnd_spectral_workspace_bytes.restype = S

@@ -9,6 +9,10 @@
   stft_forensics, MelSpectrogramGenerator, VoiceCloneDetector, cache_audio, wave_energy
                         the branches the reference takes without a checkpoint and without librosa (second half of this file,
                         csrc/spectral.hip): torch.stft(n_fft=400, hop_length=160) magnitudes -> statistics, 64 bands; the energy proxy.
+  resample, resampled_length, resample_taps
+                        the reference's _ensure_mono_16k (:34-45: channel mean + librosa.resample on the host) as a batched device
+                        stage (csrc/resample.hip): polyphase windowed-sinc interpolation to 16 kHz.  Opt-in: the classes and
+                        cache_audio take other rates only when given a `resample` quality.
 
 Weights keep HF's `Wav2Vec2Model` state_dict names (plus proj.weight / proj.bias), so real checkpoints load unchanged.
 
@@ -405,6 +409,209 @@ def wave_energy(waves: torch.Tensor, lengths=None) -> dict:
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Sample-rate conversion (csrc/resample.hip): the stage between a decoded waveform and the 16 kHz entries of this file.
+RESAMPLE_QUALITIES = {      # name: (lowpass_filter_width, rolloff, kaiser beta or None for the Hann window)
+    "kaiser_best": (64, 0.9475937167399596, 14.769656459379492),      # the set published as equivalent to resampy's kaiser_best
+    "kaiser_fast": (16, 0.85, 8.555504641634386),
+    "hann": (6, 0.99, None)}
+RESAMPLE_MAX_TABLE_FLOATS = 1 << 22      # the device table of one (rate pair, quality): fewer strides are folded above this
+_taps_cache: dict = {}
+_taps_dev_cache: dict = {}
+
+
+def _rate_ratio(orig_sr, new_sr):
+    """(o, n): the reduced ratio orig_sr / new_sr; refuses by name what the resampler does not take."""
+    for name, v in (("orig_sr", orig_sr), ("new_sr", new_sr)):
+        ok = not isinstance(v, bool) and (isinstance(v, (int, np.integer)) or (isinstance(v, (float, np.floating)) and float(v).is_integer()))
+        if not ok or int(v) <= 0:
+            raise ValueError(f"{name}={v!r}: a sample rate is a positive integer (Hz)")
+    g = int(np.gcd(int(orig_sr), int(new_sr)))
+    o, n = int(orig_sr) // g, int(new_sr) // g
+    if o > L.RESAMPLE_MAX_RATIO_TERM or n > L.RESAMPLE_MAX_RATIO_TERM:
+        raise ValueError(f"orig_sr={int(orig_sr)} -> new_sr={int(new_sr)}: the reduced ratio {o}/{n} has a term above {L.RESAMPLE_MAX_RATIO_TERM} "
+                         "(the limit that bounds the tap table)")
+    return o, n
+
+
+def _quality(quality):
+    if not isinstance(quality, str) or quality not in RESAMPLE_QUALITIES:
+        raise ValueError(f"quality={quality!r}: one of {tuple(RESAMPLE_QUALITIES)}")
+    return RESAMPLE_QUALITIES[quality]
+
+
+def resampled_length(n: int, orig_sr: int, new_sr: int = 16000) -> int:
+    """Samples a clip of n samples has after resampling: ceil(new n / orig) on the reduced ratio, the device's formula."""
+    o, m = _rate_ratio(orig_sr, new_sr)
+    if int(n) < 0:
+        raise ValueError(f"n={n}: a clip length is at least 0")
+    return (m * int(n) + o - 1) // o
+
+
+def _device_table(h: np.ndarray, first: np.ndarray, count: np.ndarray, o: int, n: int, K: int) -> dict:
+    """The tables ufnd_resample reads (include/ultrafnd_hip.h): G strides folded into one super-stride, groups of 4 phases."""
+    lds, qt_max = L.RESAMPLE_LDS_FLOATS, L.RESAMPLE_OUT_TILE
+    G = max(1, 64 // n)
+    G -= 1 - G % 2      # odd: o' = G o stays odd when o is, and the lanes' LDS reads spread over all banks
+    while G > 1 and (G * n * (K + (G - 1) * o) > RESAMPLE_MAX_TABLE_FLOATS or (qt_max - 1) * G * o + 1024 > lds):
+        G -= 2
+    np_, op = G * n, G * o
+    sfirst = np.concatenate([first + g * o for g in range(G)])      # phase g n + p of the super-stride: phase p shifted by g o taps
+    scount = np.tile(count, G)
+    ngroups = -(-np_ // 4)
+    groups = np.zeros((ngroups, 3), dtype=np.int32)
+    rows = 0
+    for g in range(ngroups):
+        ph = slice(4 * g, min(4 * g + 4, np_))
+        lo = int(sfirst[ph].min()) // 8 * 8
+        hi = -(-int((sfirst[ph] + scount[ph]).max()) // 8) * 8
+        groups[g] = (lo, hi - lo, rows)
+        rows += hi - lo
+    table = np.zeros((rows, 4), dtype=np.float32)
+    for j in range(np_):
+        p, (lo, _, off) = j % n, groups[j // 4]
+        a = off + int(sfirst[j]) - lo
+        table[a:a + int(scount[j]), j % 4] = h[p, first[p]:first[p] + count[p]]
+    k_pad = int((groups[:, 0] + groups[:, 1]).max())
+    qt = max(1, min(qt_max, (lds - min(k_pad, 1024)) // op + 1))
+    kc = min(k_pad, (lds - (qt - 1) * op) // 8 * 8)
+    return {"G": G, "groups": groups, "table": table, "qt": qt, "kc": kc, "nchunks": -(-k_pad // kc), "out_tile": qt * np_}
+
+
+def resample_taps(orig_sr: int, new_sr: int = 16000, quality: str = "kaiser_best") -> dict:
+    """The filter of a rate pair and quality, built once on the host in float64 and rounded once (as dft_basis()):
+      o, n, width, K      the reduced ratio, the half width in input samples, taps per phase
+      h (n, K) float32    h[p][k] = (base / o) sinc(pi t) w(t), t = ((k - width) n - p o) / (o n) base, 0 where |t| >= lpw
+      first, count (n,)   each phase's stored band: the taps with |t| < lpw
+      G, groups, table, qt, kc, nchunks      the device form (include/ultrafnd_hip.h)
+      out_tile            outputs of a workgroup's tile: L.RESAMPLE_OUT_TILE (or fewer, qt) rows of G n
+    orig_sr == new_sr is the one-tap filter h = [[1]]."""
+    o, n = _rate_ratio(orig_sr, new_sr)
+    lpw, rolloff, beta = _quality(quality)
+    key = (o, n, quality)
+    if key in _taps_cache:
+        return _taps_cache[key]
+    if o == 1 and n == 1:
+        width, K = 0, 1
+        h = np.ones((1, 1), dtype=np.float32)
+        first, count = np.zeros(1, dtype=np.int64), np.ones(1, dtype=np.int64)
+    else:
+        base = min(o, n) * rolloff
+        width = int(np.ceil(lpw * o / base))
+        K = 2 * width + o
+        num = (np.arange(K, dtype=np.int64)[None, :] - width) * n - np.arange(n, dtype=np.int64)[:, None] * o      # exact
+        t = num.astype(np.float64) / float(o * n) * base
+        inside = np.abs(t) < lpw
+        tc = np.where(inside, t, 0.0)
+        if beta is None:
+            win = np.cos(np.pi * tc / (2.0 * lpw)) ** 2
+        else:
+            win = np.i0(beta * np.sqrt(1.0 - (tc / lpw) ** 2)) / np.i0(beta)
+        h = np.where(inside, (base / o) * np.sinc(tc) * win, 0.0).astype(np.float32)      # (np.sinc(x) = sin(pi x) / (pi x))
+        first = inside.argmax(axis=1).astype(np.int64)
+        count = inside.sum(axis=1).astype(np.int64)
+    taps = {"orig_sr": int(orig_sr), "new_sr": int(new_sr), "quality": quality, "o": o, "n": n, "width": width, "K": K, "h": h, "first": first,
+            "count": count}
+    taps.update(_device_table(h, first, count, o, n, K))
+    _taps_cache[key] = taps
+    return taps
+
+
+def _taps_on(dev: torch.device, taps: dict):
+    """The device tables of a filter on `dev`: uploaded once per device."""
+    key = (taps["o"], taps["n"], taps["quality"], dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _taps_dev_cache:
+        _taps_dev_cache[key] = (torch.from_numpy(taps["table"]).to(dev), torch.from_numpy(taps["groups"]).to(dev))
+    return _taps_dev_cache[key]
+
+
+@torch.no_grad()
+def resample(waves: torch.Tensor, lengths=None, orig_sr: Optional[int] = None, new_sr: int = 16000, quality: str = "kaiser_best",
+             scale: float = 1.0) -> dict:
+    """Mono mix and sample-rate conversion of a batch, in one launch: {"waves": (B, m_max) fp32, zeros from a clip's own length on,
+    "lengths": (B,) int32 = resampled_length(len_b), written on the device}, m_max = resampled_length(n_max).
+    waves: (B, n_max) or (B, C, n_max) on a HIP device, fp32 or int16, ANY strides (a channel-last decoder buffer viewed as
+    (B, C, n_max) is read in place).  Channels are converted to fp32, summed in index order, divided by C, multiplied by `scale`
+    (1 / 32768 for PCM): NumPy's astype(float32).mean(axis=0), bit for bit.  lengths: (B,) samples per clip (a device tensor is
+    not read on the host: nothing here synchronises); nothing at or past a clip's length is read.
+    Every output is one fmaf chain from zero over its phase's taps in ascending tap order: the same bits alone, in any batch, in any
+    row and from run to run.  A non-finite sample INSIDE a clip may poison outputs a few taps beyond its true support (the
+    device table pads bands with zero taps); finite samples are unaffected."""
+    if orig_sr is None:
+        raise ValueError("orig_sr is required: the rate of `waves` in Hz")
+    taps = resample_taps(orig_sr, new_sr, quality)
+    if isinstance(waves, str) or not torch.is_tensor(waves):
+        raise L.UltrafndHipError("waves must be a tensor on a HIP device (no CPU fallback)")
+    dev = L.require_hip(waves)
+    if waves.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"waves: dtype {waves.dtype} (fp32 or int16)")
+    if waves.dim() not in (2, 3) or min(waves.shape) < 1:
+        raise ValueError(f"waves: expected (B, n_max) or (B, C, n_max), got {tuple(waves.shape)}")
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f"scale={scale}: a finite factor")
+    B, n_max = waves.shape[0], waves.shape[-1]
+    C, sc = (waves.shape[1], waves.stride(1)) if waves.dim() == 3 else (1, 0)
+    lens = None
+    if lengths is not None:
+        lens = lengths.to(dev, torch.int32).contiguous() if torch.is_tensor(lengths) else torch.tensor(list(lengths), dtype=torch.int32, device=dev)
+        if lens.numel() != B:
+            raise ValueError(f"lengths holds {lens.numel()} entries for {B} clips")
+    m_max = resampled_length(n_max, orig_sr, new_sr)
+    out = {"waves": torch.empty(B, m_max, dtype=torch.float32, device=dev), "lengths": torch.empty(B, dtype=torch.int32, device=dev)}
+    table, groups = _taps_on(dev, taps)
+    L.check(L.lib().ufnd_resample(waves.data_ptr(), L.RESAMPLE_I16 if waves.dtype == torch.int16 else L.RESAMPLE_F32, waves.stride(0), sc,
+                                  waves.stride(-1), L.ptr(lens), table.data_ptr(), groups.data_ptr(), out["waves"].data_ptr(), out["lengths"].data_ptr(),
+                                  B, C, n_max, taps["o"], taps["n"], taps["G"], taps["width"], groups.shape[0], table.shape[0], taps["qt"], taps["kc"],
+                                  taps["nchunks"], scale, L.stream_ptr(dev)), "ufnd_resample")
+    return out
+
+
+_resample_batch = resample      # (cache_audio and the classes take a keyword named `resample`)
+
+
+def _check_resample_keyword(resample, who: str):
+    if resample is not None:
+        try:
+            _quality(resample)
+        except ValueError:
+            raise ValueError(f"resample={resample!r}: {who} takes None (16 kHz audio only) or one of {tuple(RESAMPLE_QUALITIES)}") from None
+    return resample
+
+
+def _to_16k(wavs: List[np.ndarray], rates: List[int], quality: str, device, max_batch: int) -> List[np.ndarray]:
+    """Host mono clips at their own rates -> the same clips at 16 kHz: the clips of every other rate are grouped by rate and by
+    length and resampled on the device."""
+    out = list(wavs)
+    for rate in sorted(set(rates)):
+        if rate == 16000:
+            continue
+        idx = [i for i, r in enumerate(rates) if r == rate]
+        for sub, batch, lens in _length_groups([wavs[i] for i in idx], max_batch):
+            if batch.shape[1] == 0:
+                continue
+            r = _resample_batch(batch.to(device), lens, orig_sr=rate, quality=quality)
+            y, m = r["waves"].cpu().numpy(), r["lengths"].cpu().numpy()
+            for row, j in enumerate(sub):
+                out[idx[j]] = np.ascontiguousarray(y[row, :m[row]])
+    return out
+
+
+def _clips_16k(waves, sr, who: str, quality, device, max_batch: int) -> List[np.ndarray]:
+    """A list of clips -> host mono float32 at 16 kHz.  quality None: every clip must be 16 kHz already (refused by name).
+    sr: one rate for all clips, or one per clip."""
+    waves = list(waves)
+    rates = [int(r) for r in sr] if isinstance(sr, (list, tuple, np.ndarray)) else [sr] * len(waves)
+    if len(rates) != len(waves):
+        raise ValueError(f"sr holds {len(rates)} rates for {len(waves)} clips")
+    if quality is None:
+        return [_mono_16k(a, r, who) for a, r in zip(waves, rates)]
+    for r in rates:
+        _rate_ratio(r, 16000)
+    rates = [int(r) for r in rates]
+    return _to_16k([_mono_16k(a, 16000, who) for a in waves], rates, quality, device, max_batch)
+
+
 def _mono_16k(audio, sr: int, who: str) -> np.ndarray:
     """One clip as the reference's _ensure_mono_16k leaves it: host float32 (T,), channels averaged."""
     if isinstance(audio, str):
@@ -442,11 +649,15 @@ def _require_stft_lengths(wavs: List[np.ndarray]) -> None:
 class SpectralForensics:
     """The reference's audio feature extractor (src/core_blocks/audio_blocks.py) on the GPU.
       branch="w2v2"  (default) its wav2vec2 branch: the encoder above.
-      branch="stft"  its _torch_stft_fallback, the branch it takes without a checkpoint and without librosa: no encoder is built."""
+      branch="stft"  its _torch_stft_fallback, the branch it takes without a checkpoint and without librosa: no encoder is built.
+    resample=None refuses anything but 16 kHz audio; a quality name ("kaiser_best", ...) resamples other rates on the device first
+    (audio.resample), and the minimum-length checks then apply to the resampled clip."""
 
-    def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32, branch: str = "w2v2"):
+    def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32, branch: str = "w2v2",
+                 resample: Optional[str] = None):
         if branch not in ("w2v2", "stft"):
             raise ValueError(f"branch={branch!r}: 'w2v2' or 'stft'")
+        self.resample = _check_resample_keyword(resample, "SpectralForensics")
         self.dim, self.branch = int(dim), branch
         if self.dim < 1:
             raise ValueError(f"dim={dim}: at least 1")
@@ -467,7 +678,7 @@ class SpectralForensics:
 
     def extract(self, audio_or_text, sr: int = 16000) -> np.ndarray:
         """One clip -> (dim,) float32."""
-        wav = self._mono_16k(audio_or_text, sr)
+        wav = _clips_16k([audio_or_text], sr, "SpectralForensics", self.resample, self.device, self.max_batch)[0]
         if self.branch == "stft":
             _require_stft_lengths([wav])
             return stft_forensics(torch.from_numpy(wav)[None].to(self.device), None, self.dim)["features"].cpu().numpy()[0]
@@ -475,8 +686,9 @@ class SpectralForensics:
 
     def extract_batch(self, waves, sr: int = 16000) -> np.ndarray:
         """A list of clips -> (N, dim) float32: the batched entry of a cache builder.  Clips are sorted by length and run in groups
-        of at most max_batch neighbours, which bounds the padding; every row equals extract() of its clip bit for bit."""
-        wavs = [self._mono_16k(a, sr) for a in waves]
+        of at most max_batch neighbours, which bounds the padding; every row equals extract() of its clip bit for bit.
+        sr: one rate for all clips, or one per clip (with resample set)."""
+        wavs = _clips_16k(waves, sr, "SpectralForensics", self.resample, self.device, self.max_batch)
         if self.branch == "stft":
             _require_stft_lengths(wavs)
         out = np.zeros((len(wavs), self.dim), dtype=np.float32)
@@ -492,7 +704,9 @@ class MelSpectrogramGenerator:
     """MelSpectrogramGenerator of the reference on its torch branch: the STFT magnitudes' bins 3m, 3m + 1, 3m + 2 averaged into 64
     bands ([band, time]; bins 192 .. 200 are dropped).  The reference's geometry only; anything else is refused by name."""
 
-    def __init__(self, sr: int = 16000, n_mels: int = N_BANDS, n_fft: int = N_FFT, hop_length: int = HOP, device="cuda", max_batch: int = 32):
+    def __init__(self, sr: int = 16000, n_mels: int = N_BANDS, n_fft: int = N_FFT, hop_length: int = HOP, device="cuda", max_batch: int = 32,
+                 resample: Optional[str] = None):
+        self.resample = _check_resample_keyword(resample, "MelSpectrogramGenerator")
         for name, got, want in (("sr", sr, 16000), ("n_mels", n_mels, N_BANDS), ("n_fft", n_fft, N_FFT), ("hop_length", hop_length, HOP)):
             if int(got) != want:
                 raise ValueError(f"{name}={got!r}: MelSpectrogramGenerator is built for the reference's defaults ({name}={want})")
@@ -501,7 +715,7 @@ class MelSpectrogramGenerator:
 
     def generate_batch(self, waves, sr: int = 16000, flatten: bool = True) -> List[np.ndarray]:
         """A list of clips -> per clip the (64, T_b) float32 matrix, or its flattening."""
-        wavs = [_mono_16k(a, sr, "MelSpectrogramGenerator") for a in waves]
+        wavs = _clips_16k(waves, sr, "MelSpectrogramGenerator", self.resample, self.device, self.max_batch)
         _require_stft_lengths(wavs)
         out: List[Optional[np.ndarray]] = [None] * len(wavs)
         for idx, batch, lens in _length_groups(wavs, self.max_batch):
@@ -518,12 +732,13 @@ class MelSpectrogramGenerator:
 class VoiceCloneDetector:
     """VoiceCloneDetector of the reference on its energy branch: e = mean(x^2), score = clip(e / (e + 1), 0, 1)."""
 
-    def __init__(self, device="cuda", max_batch: int = 32):
+    def __init__(self, device="cuda", max_batch: int = 32, resample: Optional[str] = None):
         self.device, self.max_batch = torch.device(device), int(max_batch)
+        self.resample = _check_resample_keyword(resample, "VoiceCloneDetector")
 
     def score_batch(self, waves, sr: int = 16000) -> np.ndarray:
         """A list of clips -> (N,) float32 scores; every entry equals score() of its clip bit for bit."""
-        wavs = [_mono_16k(a, sr, "VoiceCloneDetector") for a in waves]
+        wavs = _clips_16k(waves, sr, "VoiceCloneDetector", self.resample, self.device, self.max_batch)
         out = np.zeros(len(wavs), dtype=np.float32)
         for idx, batch, lens in _length_groups(wavs, self.max_batch):
             if batch.shape[1] == 0:      # (empty clips only: the mean of nothing; the reference returns NaN there, this returns 0)
@@ -536,7 +751,14 @@ class VoiceCloneDetector:
 
 
 @torch.no_grad()
-def cache_audio(waves: torch.Tensor, lengths=None, audio_dim: int = 128) -> torch.Tensor:
+def cache_audio(waves: torch.Tensor, lengths=None, audio_dim: int = 128, sr: int = 16000, resample: str = "kaiser_best") -> torch.Tensor:
     """The `audio` row of the reference's cache builder on real waveforms, on the branch the reference takes without a checkpoint:
-    SpectralForensics(dim=audio_dim).extract of every clip, (B, audio_dim) fp32 on the waves' device (a vector of unit norm already)."""
-    return stft_forensics(waves, lengths, audio_dim)["features"]
+    SpectralForensics(dim=audio_dim).extract of every clip, (B, audio_dim) fp32 on the waves' device (a vector of unit norm already).
+    sr != 16000: the clips are mixed to mono and resampled on the device first (audio.resample at quality `resample`, fp32 or int16
+    input, any strides); sr == 16000 is the direct path."""
+    _rate_ratio(sr, 16000)
+    if int(sr) == 16000:
+        return stft_forensics(waves, lengths, audio_dim)["features"]
+    _quality(resample)
+    r = _resample_batch(waves, lengths, orig_sr=sr, quality=resample)
+    return stft_forensics(r["waves"], r["lengths"], audio_dim)["features"]

@@ -59,7 +59,8 @@ def _digest(extra: str) -> str:
 FILE_FLAGS = {"gemm_bf16_pp": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "gemm_pp_diag": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "motion": ["-ffp-contract=off"],      # the float64 luma is bit-exact only with every operation rounded on its own (csrc/frames.hpp)
-              "forgery": ["-ffp-contract=off"]}
+              "forgery": ["-ffp-contract=off"],
+              "resample": ["-ffp-contract=off"]}      # the channel mix rounds every operation on its own (the chain is explicit fmaf)
 
 
 def _compile(src: Path, tag: str, flags: list, verbose: bool) -> Path:
