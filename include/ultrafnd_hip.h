@@ -1155,6 +1155,56 @@ int ufnd_stft_forensics(const float* waves, const int32_t* lengths, const float*
 int ufnd_wave_energy(const float* waves, const int32_t* lengths, float* energy, float* score, int B, int n_max, void* stream);
 
 /* -------------------------------------------------------------------------------------
+ * The librosa branches of src/core_blocks/audio_blocks.py (csrc/spectral_desc.hip): SpectralForensics._librosa_spectral (:141-176)
+ * and VoiceCloneDetector.score's descriptor mix (:244-254), batched over 16 kHz clips.  The arithmetic below is RESTATED from
+ * librosa's documented algorithms (0.10 defaults) and is not verified against librosa itself.  waves, lengths as for
+ * ufnd_stft_forensics.  A clip of len_b >= 1 samples has T_A = 1 + len_b / 160 and T_B = 1 + len_b / 512 frames; len_b = 0 has none
+ * and all its outputs are zeros.  TA_max = 1 + n_max / 160, TB_max = 1 + n_max / 512.
+ *
+ *   STFT A   n_fft 400, hop 160, periodic Hann window w[n] = 0.5 - 0.5 cos(2 pi n / 400), center=True with ZERO padding of 200
+ *            (pad_mode="constant", librosa >= 0.10; "reflect" is not built), 201 bins 40 Hz apart, S = |.|.
+ *            basis_a (402, 400) fp32: row k < 201 = w[n] cos(2 pi k n / 400), row 201 + k = -w[n] sin(2 pi k n / 400), each the
+ *            float64 product rounded once.  re, im: one chain of 400 fmaf each, in the tap order of ufnd_stft_forensics.
+ *   stats    mean, population std, max, min of the clip's 201 T_A magnitudes (double per tile, tiles in order by Chan's update).
+ *   contrast (7, T_A): spectral_contrast(S, sr=16000), n_bands 6, fmin 200, quantile 0.02.  Band k uses the bin rows
+ *            0..4, 4..9, 9..19, 19..39, 39..79, 79..159, 159..200; valley = the smallest row value of the frame, peak = the
+ *            largest (band 5: the mean of the two smallest / two largest, (a + b) 0.5 in fp32).  dB(v) = 10 log10(max(1e-10, v)) in
+ *            double; each of the two (7, T_A) dB arrays is clipped from below at its own maximum - 80; contrast = dB(peak) -
+ *            dB(valley).  Descriptors: its mean and population std (double, two passes).
+ *   flatness (T_A): P = max(1e-10, S^2); exp(mean_bins log P) / mean_bins P over the 201 bins in ascending order, in double.
+ *            Descriptors: its mean and population std.
+ *   STFT B   n_fft 2048, hop 512, the same window rule, ZERO padding of 1024, 1025 bins 7.8125 Hz apart.  basis_b (2050, 2048) as
+ *            basis_a.  re, im: one chain of 2048 fmaf each, taps 8u + e, 8u + 4 + e (u = 0 .. 255, e = 0 .. 3).
+ *   centroid   (T_B): 7.8125 sum_k k S_k / sum_k S_k, 0 where sum S < FLT_MIN.  rolloff (T_B): 7.8125 times the first bin whose
+ *            running sum of S over ascending bins is >= 0.85 sum S (bin 0 for a silent frame).  flatness_y (T_B): as flatness, over
+ *            the 1025 bins.  All in double: a lane of the frame's wave owns 17 consecutive bins in ascending order and the 64 lane
+ *            sums are added in lane order; the running sum of a lane starts from the sum of the lanes below it.
+ *   zcr      (T_B): frame t = samples 512 t - 1024 .. 512 t + 1023 of the clip EDGE-padded; a sample with |x| <= 1e-10f counts as
+ *            +0; crossings = number of i in 1 .. 2047 whose sign bit differs from sample i - 1's; value = crossings / 2048 (exact).
+ *   descriptors (B, 11) = stats (4), contrast mean, std, flatness mean, std, mean centroid, mean rolloff, mean zcr, each a double
+ *            rounded to fp32 once.  features (B, dim) = descriptors tiled to dim, divided by (norm + 1e-9) in fp32 (the norm in
+ *            double, rounded once).  clone_score (B) = clip(0.4 mean(flatness_y) + 0.3 mean(zcr) + 0.3 tanh(mean(centroid) / 3000),
+ *            0, 1) from the fp32 means, in double, rounded once.
+ *
+ *   ufnd_spectral_desc_workspace_bytes   bytes of the workspace for (B, n_max) (0 for a refused shape): the per-frame values above
+ *            and the frame-major magnitudes of STFT B, 4224 bytes per frame of 32-frame tiles.  Alignment: 16 bytes.
+ *   ufnd_spectral_descriptors   every member of `out` is optional (NULL), at least one is needed; only what the asked outputs need
+ *            is launched, and an output's bits do not depend on which others are asked for.  Per-frame outputs hold zeros from the
+ *            clip's own frame count on: contrast (B, 7, TA_max), flatness (B, TA_max), magnitude (B, 201, TA_max), centroid /
+ *            rolloff / flatness_y / zcr (B, TB_max), magnitude_y (B, 1025, TB_max).
+ * Nothing allocates or synchronises; no atomics, no scratch, fixed reduction orders: a clip's outputs are the same bits alone, in
+ * any batch and from run to run; hipGraph-capturable.  1 <= B <= 65535, 1 <= n_max <= 2^30; offsets are 64-bit.
+ * Not built: the mel-dB filterbank, pyin, pad_mode="reflect", an FFT form of STFT B, other n_fft / hop, the str hash proxies. */
+#define UFND_DESC_FRAME_TILE_A 64       /* frames of a workgroup's tile in STFT A */
+#define UFND_DESC_FRAME_TILE_B 32       /* ... in STFT B */
+typedef struct ufnd_spectral_desc_out {
+  float *features, *descriptors, *contrast, *flatness, *centroid, *rolloff, *flatness_y, *zcr, *clone_score, *magnitude, *magnitude_y;
+} ufnd_spectral_desc_out;
+size_t ufnd_spectral_desc_workspace_bytes(int B, int n_max);
+int ufnd_spectral_descriptors(const float* waves, const int32_t* lengths, const float* basis_a, const float* basis_b, void* workspace,
+                              const ufnd_spectral_desc_out* out, int B, int n_max, int dim, void* stream);
+
+/* -------------------------------------------------------------------------------------
  * Sample-rate conversion (csrc/resample.hip): the device form of the reference's _ensure_mono_16k
  * (src/core_blocks/audio_blocks.py:34-45: channel mean, then librosa.resample, one clip at a time on the host).  Band-limited
  * windowed-sinc interpolation in polyphase form.  With g = gcd(orig_sr, new_sr), o = orig_sr / g, n = new_sr / g and a quality

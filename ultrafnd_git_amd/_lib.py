@@ -85,6 +85,12 @@ class Dropout(C.Structure):
     _fields_ = [("state", C.c_void_p), ("p", C.c_float), ("tag", C.c_uint32)]
 
 
+class SpectralDescOut(C.Structure):
+    """ufnd_spectral_desc_out: the optional outputs of ufnd_spectral_descriptors."""
+    _fields_ = [(n, C.c_void_p) for n in ("features", "descriptors", "contrast", "flatness", "centroid", "rolloff", "flatness_y", "zcr", "clone_score",
+                                           "magnitude", "magnitude_y")]
+
+
 PARTIALS_DEFER = 2
 LN_BWD_DROP_DXB, LN_BWD_DROP_DY = 1, 2
 WGRAD_ALL, WGRAD_TRANSPOSE, WGRAD_PRODUCT = 0, 1, 2
@@ -116,6 +122,7 @@ ABI_VERSION = 6
 FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 AUDIO_MIN_SAMPLES, WAVE_CHUNK, CONV0_CHUNK = 400, 4096, 256      # UFND_AUDIO_MIN_SAMPLES, UFND_WAVE_CHUNK, UFND_CONV0_CHUNK
 STFT_FRAME_TILE, STFT_MIN_SAMPLES = 64, 201      # UFND_STFT_FRAME_TILE, UFND_STFT_MIN_SAMPLES
+DESC_FRAME_TILE_A, DESC_FRAME_TILE_B = 64, 32      # UFND_DESC_FRAME_TILE_A, UFND_DESC_FRAME_TILE_B
 RESAMPLE_OUT_TILE, RESAMPLE_LDS_FLOATS, RESAMPLE_MAX_RATIO_TERM = 64, 40000, 1024      # UFND_RESAMPLE_OUT_TILE, _LDS_FLOATS, _MAX_RATIO_TERM
 RESAMPLE_F32, RESAMPLE_I16 = 0, 1
 
@@ -287,6 +294,11 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_spectral_workspace_bytes.argtypes = [I, I]
     lib.ufnd_spectral_workspace_bytes.restype = S
+    sigs.update({      # the librosa-branch spectral descriptors (csrc/spectral_desc.hip)
+        "ufnd_spectral_descriptors": [P, P, P, P, P, C.POINTER(SpectralDescOut), I, I, I, P],
+    })
+    lib.ufnd_spectral_desc_workspace_bytes.argtypes = [I, I]
+    lib.ufnd_spectral_desc_workspace_bytes.restype = S
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

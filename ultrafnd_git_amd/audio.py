@@ -5,7 +5,12 @@
                         .last_hidden_state -> mean over time -> Linear(768, 128); batched over clips instead of one record at a
                         time on the CPU.
   SpectralForensics     the reference's class name and extract(audio, sr), bound to the encoder above (branch="w2v2", the default)
-                        or to the STFT statistics (branch="stft").
+                        to the STFT statistics (branch="stft") or to the librosa descriptors (branch="librosa").
+  spectral_descriptors, spectral_basis
+                        the reference's librosa branches (_librosa_spectral's 11 descriptors, VoiceCloneDetector's descriptor mix) as
+                        batched device kernels (csrc/spectral_desc.hip); restated from librosa's documented algorithms, not verified
+                        against librosa.  SpectralForensics(branch="librosa"), VoiceCloneDetector(branch="librosa"),
+                        cache_audio(branch="librosa").
   stft_forensics, MelSpectrogramGenerator, VoiceCloneDetector, cache_audio, wave_energy
                         the branches the reference takes without a checkpoint and without librosa (second half of this file,
                         csrc/spectral.hip): torch.stft(n_fft=400, hop_length=160) magnitudes -> statistics, 64 bands; the energy proxy.
@@ -410,6 +415,83 @@ def wave_energy(waves: torch.Tensor, lengths=None) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The librosa branches (csrc/spectral_desc.hip): what the reference computes on a host WITH librosa and without a checkpoint.
+# Restated from librosa's documented algorithms (0.10 defaults), not verified against librosa itself (include/ultrafnd_hip.h).
+DESC_GEOMETRY = {400: 160, 2048: 512}      # n_fft: hop of the two STFTs of _librosa_spectral
+N_DESCRIPTORS, N_CONTRAST_BANDS = 11, 7
+DESC_OUTPUTS = ("features", "descriptors", "contrast", "flatness", "centroid", "rolloff", "flatness_y", "zcr", "clone_score", "magnitude",
+                "magnitude_y")
+_desc_basis_cache: dict = {}
+
+
+def spectral_basis(n_fft: int) -> np.ndarray:
+    """(2 (n_fft / 2 + 1), n_fft) float32, n_fft 400 or 2048: row k = w[n] cos(2 pi k n / n_fft), row n_fft / 2 + 1 + k =
+    -w[n] sin(2 pi k n / n_fft) with the periodic Hann window w[n] = 0.5 - 0.5 cos(2 pi n / n_fft); the angle is reduced exactly
+    (k n mod n_fft), everything is evaluated in float64 and the product is rounded once."""
+    if n_fft not in DESC_GEOMETRY:
+        raise ValueError(f"n_fft={n_fft!r}: spectral_basis is built for {tuple(DESC_GEOMETRY)} (other n_fft / hop are not built)")
+    n = np.arange(n_fft, dtype=np.int64)
+    kn = (np.arange(n_fft // 2 + 1, dtype=np.int64)[:, None] * n[None, :]) % n_fft
+    ang = 2.0 * np.pi * kn.astype(np.float64) / n_fft
+    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * n.astype(np.float64) / n_fft)
+    return np.concatenate([np.cos(ang) * win, -np.sin(ang) * win]).astype(np.float32)
+
+
+def _desc_basis(dev: torch.device, n_fft: int) -> torch.Tensor:
+    key = (n_fft, dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _desc_basis_cache:
+        _desc_basis_cache[key] = torch.from_numpy(spectral_basis(n_fft)).to(dev)
+    return _desc_basis_cache[key]
+
+
+def desc_frame_counts(n: int):
+    """(T_A, T_B) of a clip of n samples: 1 + n // 160 and 1 + n // 512 (zero padding: any n >= 1 has frames), (0, 0) for n = 0."""
+    return (1 + int(n) // 160, 1 + int(n) // 512) if int(n) >= 1 else (0, 0)
+
+
+@torch.no_grad()
+def spectral_descriptors(waves: torch.Tensor, lengths=None, dim: int = 128, want: Sequence[str] = ("features",), pad_mode: str = "constant") -> dict:
+    """SpectralForensics._librosa_spectral and VoiceCloneDetector's librosa score of every 16 kHz clip, batched:
+      features (B, dim)             the 11 descriptors tiled to dim, L2-normalised
+      descriptors (B, 11)           |S| mean, std, max, min; contrast mean, std; flatness mean, std; mean centroid, rolloff, zcr
+      contrast (B, 7, T_A_max)      spectral_contrast(S, sr=16000)            } of librosa.stft(n_fft=400, hop_length=160),
+      flatness (B, T_A_max)         spectral_flatness(S)                      } T_A = 1 + len // 160
+      magnitude (B, 201, T_A_max)   S itself                                  }
+      centroid, rolloff, flatness_y, zcr (B, T_B_max)     the y= forms: n_fft 2048, hop 512, T_B = 1 + len // 512
+      magnitude_y (B, 1025, T_B_max)                      their magnitudes
+      clone_score (B,)              clip(0.4 mean(flatness_y) + 0.3 mean(zcr) + 0.3 tanh(mean(centroid) / 3000), 0, 1)
+    Per-frame outputs hold zeros from a clip's own frame count on; a clip of length 0 gives zeros everywhere.
+    waves, lengths: as stft_forensics (a device `lengths` is not read on the host: nothing here synchronises).  Outputs that are not
+    asked for are not stored, and what is asked for does not change any value's bits.  pad_mode: librosa >= 0.10's "constant" (zero
+    padding) only."""
+    if pad_mode != "constant":
+        raise ValueError(f"pad_mode={pad_mode!r}: only 'constant' (zero padding, librosa >= 0.10's default) is built; 'reflect' is not")
+    want = tuple(want)
+    for name in want:
+        if name not in DESC_OUTPUTS:
+            raise ValueError(f"want={name!r}: one of {DESC_OUTPUTS}")
+    if not want:
+        raise ValueError(f"want is empty: some of {DESC_OUTPUTS}")
+    if int(dim) < 1:
+        raise ValueError(f"dim={dim}: at least 1")
+    x, lens = _device_waves(waves, lengths)
+    dev, (B, n_max) = x.device, x.shape
+    TA, TB = 1 + n_max // 160, 1 + n_max // 512
+    shapes = {"features": (B, int(dim)), "descriptors": (B, N_DESCRIPTORS), "contrast": (B, N_CONTRAST_BANDS, TA), "flatness": (B, TA),
+              "centroid": (B, TB), "rolloff": (B, TB), "flatness_y": (B, TB), "zcr": (B, TB), "clone_score": (B,), "magnitude": (B, 201, TA),
+              "magnitude_y": (B, 1025, TB)}
+    out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in DESC_OUTPUTS if name in want}
+    nbytes = L.lib().ufnd_spectral_desc_workspace_bytes(B, n_max)
+    if nbytes == 0:
+        raise L.UltrafndHipError(f"spectral_descriptors: B={B} n_max={n_max} is refused (B <= 65535, n_max <= 2^30)")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    io = L.SpectralDescOut(**{name: t.data_ptr() for name, t in out.items()})
+    L.check(L.lib().ufnd_spectral_descriptors(x.data_ptr(), L.ptr(lens), _desc_basis(dev, 400).data_ptr(), _desc_basis(dev, 2048).data_ptr(),
+                                              ws.data_ptr(), io, B, n_max, int(dim), L.stream_ptr(dev)), "ufnd_spectral_descriptors")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Sample-rate conversion (csrc/resample.hip): the stage between a decoded waveform and the 16 kHz entries of this file.
 RESAMPLE_QUALITIES = {      # name: (lowpass_filter_width, rolloff, kaiser beta or None for the Hann window)
     "kaiser_best": (64, 0.9475937167399596, 14.769656459379492),      # the set published as equivalent to resampy's kaiser_best
@@ -646,26 +728,34 @@ def _require_stft_lengths(wavs: List[np.ndarray]) -> None:
             raise ValueError(f"clip length {len(w)}: the STFT branch needs at least {STFT_MIN_SAMPLES} samples (torch.stft's reflect padding of 200)")
 
 
+def _require_samples(wavs: List[np.ndarray]) -> None:
+    for w in wavs:
+        if len(w) < 1:
+            raise ValueError("clip length 0: the librosa branch needs at least one sample")
+
+
 class SpectralForensics:
     """The reference's audio feature extractor (src/core_blocks/audio_blocks.py) on the GPU.
       branch="w2v2"  (default) its wav2vec2 branch: the encoder above.
       branch="stft"  its _torch_stft_fallback, the branch it takes without a checkpoint and without librosa: no encoder is built.
+      branch="librosa"  its _librosa_spectral, the branch it takes without a checkpoint WITH librosa (spectral_descriptors: zero
+                     padding, any clip of at least one sample): no encoder is built.
     resample=None refuses anything but 16 kHz audio; a quality name ("kaiser_best", ...) resamples other rates on the device first
     (audio.resample), and the minimum-length checks then apply to the resampled clip."""
 
     def __init__(self, dim: int = 128, encoder: Optional[Wav2Vec2AudioEncoder] = None, device="cuda", max_batch: int = 32, branch: str = "w2v2",
                  resample: Optional[str] = None):
-        if branch not in ("w2v2", "stft"):
-            raise ValueError(f"branch={branch!r}: 'w2v2' or 'stft'")
+        if branch not in ("w2v2", "stft", "librosa"):
+            raise ValueError(f"branch={branch!r}: 'w2v2', 'stft' or 'librosa'")
         self.resample = _check_resample_keyword(resample, "SpectralForensics")
         self.dim, self.branch = int(dim), branch
         if self.dim < 1:
             raise ValueError(f"dim={dim}: at least 1")
         self.max_batch = int(max_batch)
         self.device = torch.device(device)
-        if branch == "stft":
+        if branch != "w2v2":
             if encoder is not None:
-                raise ValueError("branch='stft' runs no encoder: pass encoder=None")
+                raise ValueError(f"branch={branch!r} runs no encoder: pass encoder=None")
             self.encoder = None
             return
         self.encoder = encoder if encoder is not None else Wav2Vec2AudioEncoder(out_dim=self.dim).to(device)
@@ -682,6 +772,9 @@ class SpectralForensics:
         if self.branch == "stft":
             _require_stft_lengths([wav])
             return stft_forensics(torch.from_numpy(wav)[None].to(self.device), None, self.dim)["features"].cpu().numpy()[0]
+        if self.branch == "librosa":
+            _require_samples([wav])
+            return spectral_descriptors(torch.from_numpy(wav)[None].to(self.device), None, self.dim)["features"].cpu().numpy()[0]
         return self.encoder(torch.from_numpy(wav)[None]).cpu().numpy()[0]
 
     def extract_batch(self, waves, sr: int = 16000) -> np.ndarray:
@@ -691,10 +784,14 @@ class SpectralForensics:
         wavs = _clips_16k(waves, sr, "SpectralForensics", self.resample, self.device, self.max_batch)
         if self.branch == "stft":
             _require_stft_lengths(wavs)
+        if self.branch == "librosa":
+            _require_samples(wavs)
         out = np.zeros((len(wavs), self.dim), dtype=np.float32)
         for idx, batch, lens in _length_groups(wavs, self.max_batch):
             if self.branch == "stft":
                 out[idx] = stft_forensics(batch.to(self.device), lens, self.dim)["features"].cpu().numpy()
+            elif self.branch == "librosa":
+                out[idx] = spectral_descriptors(batch.to(self.device), lens, self.dim)["features"].cpu().numpy()
             else:
                 out[idx] = self.encoder(batch, lens).cpu().numpy()
         return out
@@ -730,9 +827,14 @@ class MelSpectrogramGenerator:
 
 
 class VoiceCloneDetector:
-    """VoiceCloneDetector of the reference on its energy branch: e = mean(x^2), score = clip(e / (e + 1), 0, 1)."""
+    """VoiceCloneDetector of the reference.
+      branch="energy"   (default) its energy branch: e = mean(x^2), score = clip(e / (e + 1), 0, 1).
+      branch="librosa"  its librosa descriptor mix (spectral_descriptors' clone_score)."""
 
-    def __init__(self, device="cuda", max_batch: int = 32, resample: Optional[str] = None):
+    def __init__(self, device="cuda", max_batch: int = 32, resample: Optional[str] = None, branch: str = "energy"):
+        if branch not in ("energy", "librosa"):
+            raise ValueError(f"branch={branch!r}: 'energy' or 'librosa'")
+        self.branch = branch
         self.device, self.max_batch = torch.device(device), int(max_batch)
         self.resample = _check_resample_keyword(resample, "VoiceCloneDetector")
 
@@ -743,6 +845,9 @@ class VoiceCloneDetector:
         for idx, batch, lens in _length_groups(wavs, self.max_batch):
             if batch.shape[1] == 0:      # (empty clips only: the mean of nothing; the reference returns NaN there, this returns 0)
                 continue
+            if self.branch == "librosa":
+                out[idx] = spectral_descriptors(batch.to(self.device), lens, want=("clone_score",))["clone_score"].cpu().numpy()
+                continue
             out[idx] = wave_energy(batch.to(self.device), lens)["score"].cpu().numpy()
         return out
 
@@ -751,14 +856,19 @@ class VoiceCloneDetector:
 
 
 @torch.no_grad()
-def cache_audio(waves: torch.Tensor, lengths=None, audio_dim: int = 128, sr: int = 16000, resample: str = "kaiser_best") -> torch.Tensor:
-    """The `audio` row of the reference's cache builder on real waveforms, on the branch the reference takes without a checkpoint:
+def cache_audio(waves: torch.Tensor, lengths=None, audio_dim: int = 128, sr: int = 16000, resample: str = "kaiser_best",
+                branch: str = "stft") -> torch.Tensor:
+    """The `audio` row of the reference's cache builder on real waveforms, on a branch the reference takes without a checkpoint:
     SpectralForensics(dim=audio_dim).extract of every clip, (B, audio_dim) fp32 on the waves' device (a vector of unit norm already).
+    branch="stft" (default): the branch of a host without librosa; branch="librosa": the 11-descriptor branch of a host with it.
     sr != 16000: the clips are mixed to mono and resampled on the device first (audio.resample at quality `resample`, fp32 or int16
     input, any strides); sr == 16000 is the direct path."""
+    if branch not in ("stft", "librosa"):
+        raise ValueError(f"branch={branch!r}: 'stft' or 'librosa'")
+    entry = stft_forensics if branch == "stft" else spectral_descriptors
     _rate_ratio(sr, 16000)
     if int(sr) == 16000:
-        return stft_forensics(waves, lengths, audio_dim)["features"]
+        return entry(waves, lengths, audio_dim)["features"]
     _quality(resample)
     r = _resample_batch(waves, lengths, orig_sr=sr, quality=resample)
-    return stft_forensics(r["waves"], r["lengths"], audio_dim)["features"]
+    return entry(r["waves"], r["lengths"], audio_dim)["features"]
