@@ -1194,7 +1194,7 @@ int ufnd_wave_energy(const float* waves, const int32_t* lengths, float* energy, 
  *            rolloff / flatness_y / zcr (B, TB_max), magnitude_y (B, 1025, TB_max).
  * Nothing allocates or synchronises; no atomics, no scratch, fixed reduction orders: a clip's outputs are the same bits alone, in
  * any batch and from run to run; hipGraph-capturable.  1 <= B <= 65535, 1 <= n_max <= 2^30; offsets are 64-bit.
- * Not built: the mel-dB filterbank, pyin, pad_mode="reflect", an FFT form of STFT B, other n_fft / hop, the str hash proxies. */
+ * Not built: pyin, pad_mode="reflect", an FFT form of STFT B, other n_fft / hop, the HTK mel scale, the str hash proxies. */
 #define UFND_DESC_FRAME_TILE_A 64       /* frames of a workgroup's tile in STFT A */
 #define UFND_DESC_FRAME_TILE_B 32       /* ... in STFT B */
 typedef struct ufnd_spectral_desc_out {
@@ -1203,6 +1203,51 @@ typedef struct ufnd_spectral_desc_out {
 size_t ufnd_spectral_desc_workspace_bytes(int B, int n_max);
 int ufnd_spectral_descriptors(const float* waves, const int32_t* lengths, const float* basis_a, const float* basis_b, void* workspace,
                               const ufnd_spectral_desc_out* out, int B, int n_max, int dim, void* stream);
+
+/* -------------------------------------------------------------------------------------
+ * The mel spectrogram in dB of the librosa branch (csrc/mel_db.hip): MelSpectrogramGenerator.generate of
+ * src/core_blocks/audio_blocks.py (:71-78) on a host with librosa,
+ *     S_db = power_to_db(melspectrogram(y, sr=16000, n_fft=400, hop_length=160, n_mels=64, power=2.0), ref=np.max)
+ * batched over 16 kHz clips.  Like the descriptors above, the arithmetic is RESTATED from librosa's documented algorithms (0.10
+ * defaults) and is not verified against librosa itself; the filterbank alone has an independent check (tests/test_mel_ref.py:
+ * transformers.audio_utils.mel_filter_bank).  Fixed geometry: sr 16000, n_fft 400, hop 160, 64 mels, fmin 0, fmax 8000, the Slaney
+ * scale (htk=False), norm="slaney".  waves, lengths as for ufnd_stft_forensics.
+ *
+ *   frames     T = 1 + len_b / 160 for len_b >= 1, none for len_b = 0; center=True with ZERO padding of 200 (pad_mode="constant");
+ *              T_max = 1 + n_max / 160.  basis_a: the (402, 400) window-folded basis of STFT A above.
+ *   magnitude  S[k, t]: STFT A, the same bits as ufnd_spectral_descriptors' `magnitude` (one value, one arithmetic: the tap order
+ *              8u + e, 8u + 4 + e and sqrtf(fmaf(re, re, im im))).
+ *   power      P = S S, one fp32 multiply (librosa's np.abs(D) ** 2).
+ *   filterbank W (64, 201), evaluated in float64 on the host and rounded to fp32 once: mel(f) = 3 f / 200 below 1000 Hz and
+ *              15 + 27 ln(f / 1000) / ln 6.4 from 1000 Hz on; 66 points equally spaced in mel over [mel(0), mel(8000)], mapped back
+ *              to Hz as m[0 .. 65] (m[1] = 46.4057851 Hz; m[22] is the first at or above 1000 Hz); bin k is at 40 k Hz;
+ *              W[i, k] = max(0, min((40 k - m[i]) / (m[i+1] - m[i]), (m[i+2] - 40 k) / (m[i+2] - m[i+1]))) 2 / (m[i+2] - m[i]).
+ *              Every row's support is contiguous: 2 to 18 bins, 388 nonzeros in all; bins 0 and 200 carry no weight; row 0 covers
+ *              bins 1..2, row 63 bins 182..199.  The device gets fb_weights (388: the nonzeros, row after row), fb_first (64) and
+ *              fb_count (64); whatever those arrays hold, a support is clamped to the 201 bins and to the 388 weights.
+ *   mel power  M[i, t] = one chain from zero over the row's support in ascending bins, M = fmaf(W[i, k], P[k, t], M).  Nothing
+ *              outside the support is touched (an exact zero weight times a stray Inf would be NaN).
+ *   dB         power_to_db(M, ref=np.max) is  L = 10 log10(max(1e-10, M)) - 10 log10(max(1e-10, Mmax)),  Mmax the maximum of the
+ *              clip's own 64 T values, then  max(L, max(L) - top_db)  with top_db = 80.  log10 and max are monotone, so the largest
+ *              L belongs to the entry that IS Mmax and is exactly 0: the floor is the constant -80,  D = max(L, -80).  Evaluated in
+ *              double and rounded to fp32 once (as the contrast dB above).  An all-zero clip has D = 0 on all its frames.
+ *
+ *   mel_db (B, 64, T_max), mel_power (B, 64, T_max), mel_max (B): each optional (NULL), at least one is needed; which of them are
+ *              asked for changes no bit of any.  Per-frame outputs hold zeros from the clip's own T on -- 0 is ALSO a legitimate dB
+ *              value (the clip's loudest entry), so read a clip's frames by its own T.  A clip of length 0 gives zeros everywhere.
+ *   ufnd_mel_workspace_bytes   bytes of the workspace for (B, n_max), 0 for a refused shape: the mel powers (B 64 T_max floats) and
+ *              one maximum per 64-frame tile, each rounded up to 16 bytes.  Alignment: 16 bytes.
+ * Two launches (tile kernel: STFT tile + filterbank + tile maximum; dB kernel: every workgroup folds its clip's tile maxima, then
+ * converts its own tile).  Nothing allocates or synchronises; no atomics, no scratch: a clip's outputs are the same bits alone, in
+ * any batch and from run to run; hipGraph-capturable.  1 <= B <= 65535, 1 <= n_max <= 2^30; offsets are 64-bit.
+ * Not built: pad_mode="reflect", other geometries (sr, n_fft, hop, n_mels, fmin, fmax), the HTK scale, norm other than "slaney". */
+#define UFND_MEL_FRAME_TILE 64          /* frames of a workgroup's tile */
+#define UFND_MEL_FILTERS 64             /* mel filters */
+#define UFND_MEL_NNZ 388                /* nonzero weights of the (64, 201) filterbank */
+size_t ufnd_mel_workspace_bytes(int B, int n_max);
+int ufnd_mel_spectrogram(const float* waves, const int32_t* lengths, const float* basis_a, const float* fb_weights, const int32_t* fb_first,
+                         const int32_t* fb_count, void* workspace, float* mel_db, float* mel_power, float* mel_max, int B, int n_max,
+                         void* stream);
 
 /* -------------------------------------------------------------------------------------
  * Sample-rate conversion (csrc/resample.hip): the device form of the reference's _ensure_mono_16k

@@ -123,6 +123,7 @@ FOLD_GUARD_SLOTS = 1024      # UFND_FOLD_GUARD_SLOTS
 AUDIO_MIN_SAMPLES, WAVE_CHUNK, CONV0_CHUNK = 400, 4096, 256      # UFND_AUDIO_MIN_SAMPLES, UFND_WAVE_CHUNK, UFND_CONV0_CHUNK
 STFT_FRAME_TILE, STFT_MIN_SAMPLES = 64, 201      # UFND_STFT_FRAME_TILE, UFND_STFT_MIN_SAMPLES
 DESC_FRAME_TILE_A, DESC_FRAME_TILE_B = 64, 32      # UFND_DESC_FRAME_TILE_A, UFND_DESC_FRAME_TILE_B
+MEL_FRAME_TILE, MEL_FILTERS, MEL_NNZ = 64, 64, 388      # UFND_MEL_FRAME_TILE, UFND_MEL_FILTERS, UFND_MEL_NNZ
 RESAMPLE_OUT_TILE, RESAMPLE_LDS_FLOATS, RESAMPLE_MAX_RATIO_TERM = 64, 40000, 1024      # UFND_RESAMPLE_OUT_TILE, _LDS_FLOATS, _MAX_RATIO_TERM
 RESAMPLE_F32, RESAMPLE_I16 = 0, 1
 
@@ -299,6 +300,11 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_spectral_desc_workspace_bytes.argtypes = [I, I]
     lib.ufnd_spectral_desc_workspace_bytes.restype = S
+    sigs.update({      # the librosa-branch mel spectrogram in dB (csrc/mel_db.hip)
+        "ufnd_mel_spectrogram": [P, P, P, P, P, P, P, P, P, P, I, I, P],
+    })
+    lib.ufnd_mel_workspace_bytes.argtypes = [I, I]
+    lib.ufnd_mel_workspace_bytes.restype = S
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

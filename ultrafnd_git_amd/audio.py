@@ -11,6 +11,10 @@
                         batched device kernels (csrc/spectral_desc.hip); restated from librosa's documented algorithms, not verified
                         against librosa.  SpectralForensics(branch="librosa"), VoiceCloneDetector(branch="librosa"),
                         cache_audio(branch="librosa").
+  mel_spectrogram, mel_filterbank, mel_frame_count
+                        the librosa branch of MelSpectrogramGenerator.generate: the 64-band mel spectrogram in dB (Slaney filterbank,
+                        ref = the clip's maximum, floor -80) on the same STFT tile (csrc/mel_db.hip); restated, not verified against
+                        librosa.  MelSpectrogramGenerator(branch="librosa").
   stft_forensics, MelSpectrogramGenerator, VoiceCloneDetector, cache_audio, wave_energy
                         the branches the reference takes without a checkpoint and without librosa (second half of this file,
                         csrc/spectral.hip): torch.stft(n_fft=400, hop_length=160) magnitudes -> statistics, 64 bands; the energy proxy.
@@ -492,6 +496,104 @@ def spectral_descriptors(waves: torch.Tensor, lengths=None, dim: int = 128, want
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The librosa branch of MelSpectrogramGenerator (csrc/mel_db.hip): power_to_db(melspectrogram(y, sr=16000, n_fft=400, hop_length=160,
+# n_mels=64), ref=np.max).  Restated from librosa's documented algorithms (0.10 defaults), not verified against librosa itself
+# (include/ultrafnd_hip.h); the filterbank alone is checked against an independent implementation (tests/test_mel_ref.py).
+MEL_OUTPUTS = ("mel_db", "mel_power", "mel_max")
+MEL_FMIN, MEL_FMAX = 0.0, 8000.0
+_mel_fb_host: dict = {}
+_mel_fb_cache: dict = {}
+
+
+def _slaney_mel(f):
+    """Hz -> mel on the Slaney scale (htk=False): 3 f / 200 below 1000 Hz, 15 + 27 ln(f / 1000) / ln 6.4 from 1000 Hz on."""
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) * (27.0 / np.log(6.4)), 3.0 * f / 200.0)
+
+
+def _slaney_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (np.maximum(m, 15.0) - 15.0)), 200.0 * m / 3.0)
+
+
+def mel_points() -> np.ndarray:
+    """m[0 .. 65] in Hz (float64): 66 points equally spaced in mel over [mel(0), mel(8000)]."""
+    return _slaney_hz(np.linspace(float(_slaney_mel(MEL_FMIN)), float(_slaney_mel(MEL_FMAX)), N_BANDS + 2))
+
+
+def mel_filterbank() -> dict:
+    """librosa.filters.mel(sr=16000, n_fft=400, n_mels=64) (fmin 0, fmax 8000, htk=False, norm="slaney"), restated:
+      weights (64, 201) float32   W[i, k] = max(0, min((40 k - m[i]) / (m[i+1] - m[i]), (m[i+2] - 40 k) / (m[i+2] - m[i+1])))
+                                  2 / (m[i+2] - m[i]), evaluated in float64 and rounded once
+      first, count (64,) int32    every row's support is contiguous: bins first .. first + count - 1
+      packed (388,) float32       the nonzeros, row after row: what the device reads
+    Built once; the same (read-only) arrays are returned on every call."""
+    if not _mel_fb_host:
+        m = mel_points()
+        freq = np.linspace(0.0, 8000.0, N_BINS)      # 40 k Hz, exact
+        diff = np.diff(m)
+        slopes = m[None, :] - freq[:, None]      # (201, 66)
+        down, up = -slopes[:, :-2] / diff[:-1], slopes[:, 2:] / diff[1:]
+        w64 = np.maximum(0.0, np.minimum(down, up)) * (2.0 / (m[2:] - m[:-2]))
+        w = np.ascontiguousarray(w64.T.astype(np.float32))
+        first = np.array([np.flatnonzero(r)[0] for r in w], dtype=np.int32)
+        count = np.array([np.count_nonzero(r) for r in w], dtype=np.int32)
+        packed = np.concatenate([w[i, first[i]:first[i] + count[i]] for i in range(N_BANDS)])
+        if len(packed) != L.MEL_NNZ or np.count_nonzero(packed) != L.MEL_NNZ:
+            raise L.UltrafndHipError(f"mel_filterbank: {np.count_nonzero(packed)} nonzeros in contiguous supports, the kernel is built for {L.MEL_NNZ}")
+        for a in (w, first, count, packed):
+            a.setflags(write=False)
+        _mel_fb_host.update(weights=w, first=first, count=count, packed=packed)
+    return dict(_mel_fb_host)
+
+
+def _mel_fb(dev: torch.device):
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _mel_fb_cache:
+        fb = mel_filterbank()
+        _mel_fb_cache[key] = tuple(torch.from_numpy(fb[k].copy()).to(dev) for k in ("packed", "first", "count"))
+    return _mel_fb_cache[key]
+
+
+def mel_frame_count(n: int) -> int:
+    """T of a clip of n samples: 1 + n // 160 (zero padding: any n >= 1 has frames), 0 for n = 0."""
+    return 1 + int(n) // HOP if int(n) >= 1 else 0
+
+
+@torch.no_grad()
+def mel_spectrogram(waves: torch.Tensor, lengths=None, want: Sequence[str] = ("mel_db",)) -> dict:
+    """MelSpectrogramGenerator.generate's librosa branch of every 16 kHz clip, batched (T = 1 + len // 160, T_max = 1 + n_max // 160):
+      mel_db (B, 64, T_max)      power_to_db(melspectrogram(y, sr=16000, n_fft=400, hop_length=160, n_mels=64, power=2.0), ref=np.max):
+                                 10 log10(max(1e-10, M)) - 10 log10(max(1e-10, max M)), floored at -80; the maximum is the clip's own
+      mel_power (B, 64, T_max)   M = W S^2, S the magnitudes of spectral_descriptors (the same bits)
+      mel_max (B,)               the clip's largest M
+    Per-frame outputs hold zeros from a clip's own T on -- 0 is also a legitimate dB value (the clip's loudest entry), so cut a clip
+    by mel_frame_count; a clip of length 0 gives zeros everywhere, an all-zero clip 0 dB on its frames.  waves, lengths: as
+    spectral_descriptors (a device `lengths` is not read on the host: nothing here synchronises).  What is asked for changes no
+    value's bits."""
+    want = tuple(want)
+    for name in want:
+        if name not in MEL_OUTPUTS:
+            raise ValueError(f"want={name!r}: one of {MEL_OUTPUTS}")
+    if not want:
+        raise ValueError(f"want is empty: some of {MEL_OUTPUTS}")
+    x, lens = _device_waves(waves, lengths)
+    dev, (B, n_max) = x.device, x.shape
+    T_max = 1 + n_max // HOP
+    shapes = {"mel_db": (B, N_BANDS, T_max), "mel_power": (B, N_BANDS, T_max), "mel_max": (B,)}
+    out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in MEL_OUTPUTS if name in want}
+    nbytes = L.lib().ufnd_mel_workspace_bytes(B, n_max)
+    if nbytes == 0:
+        raise L.UltrafndHipError(f"mel_spectrogram: B={B} n_max={n_max} is refused (B <= 65535, n_max <= 2^30)")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    packed, first, count = _mel_fb(dev)
+    L.check(L.lib().ufnd_mel_spectrogram(x.data_ptr(), L.ptr(lens), _desc_basis(dev, 400).data_ptr(), packed.data_ptr(), first.data_ptr(),
+                                         count.data_ptr(), ws.data_ptr(), L.ptr(out.get("mel_db")), L.ptr(out.get("mel_power")),
+                                         L.ptr(out.get("mel_max")), B, n_max, L.stream_ptr(dev)), "ufnd_mel_spectrogram")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Sample-rate conversion (csrc/resample.hip): the stage between a decoded waveform and the 16 kHz entries of this file.
 RESAMPLE_QUALITIES = {      # name: (lowpass_filter_width, rolloff, kaiser beta or None for the Hann window)
     "kaiser_best": (64, 0.9475937167399596, 14.769656459379492),      # the set published as equivalent to resampy's kaiser_best
@@ -798,27 +900,45 @@ class SpectralForensics:
 
 
 class MelSpectrogramGenerator:
-    """MelSpectrogramGenerator of the reference on its torch branch: the STFT magnitudes' bins 3m, 3m + 1, 3m + 2 averaged into 64
-    bands ([band, time]; bins 192 .. 200 are dropped).  The reference's geometry only; anything else is refused by name."""
+    """MelSpectrogramGenerator of the reference.
+      branch="torch"    (default) its branch without librosa: the STFT magnitudes' bins 3m, 3m + 1, 3m + 2 averaged into 64 bands
+                        ([band, time]; bins 192 .. 200 are dropped); clips of at least 201 samples.
+      branch="librosa"  its branch with librosa: the (64, T) mel spectrogram in dB (mel_spectrogram: zero padding, Slaney scale and
+                        norm, ref = the clip's maximum, floor -80; T = 1 + len // 160); any clip of at least one sample.  htk, norm
+                        and pad_mode name what that branch is built for; any other value is refused.
+    The reference's geometry only; anything else is refused by name."""
 
     def __init__(self, sr: int = 16000, n_mels: int = N_BANDS, n_fft: int = N_FFT, hop_length: int = HOP, device="cuda", max_batch: int = 32,
-                 resample: Optional[str] = None):
+                 resample: Optional[str] = None, branch: str = "torch", htk: bool = False, norm: Optional[str] = "slaney",
+                 pad_mode: str = "constant"):
         self.resample = _check_resample_keyword(resample, "MelSpectrogramGenerator")
         for name, got, want in (("sr", sr, 16000), ("n_mels", n_mels, N_BANDS), ("n_fft", n_fft, N_FFT), ("hop_length", hop_length, HOP)):
             if int(got) != want:
                 raise ValueError(f"{name}={got!r}: MelSpectrogramGenerator is built for the reference's defaults ({name}={want})")
-        self.sr, self.n_mels, self.n_fft, self.hop = 16000, N_BANDS, N_FFT, HOP
+        if branch not in ("torch", "librosa"):
+            raise ValueError(f"branch={branch!r}: 'torch' or 'librosa'")
+        for name, got, want in (("htk", htk, False), ("norm", norm, "slaney"), ("pad_mode", pad_mode, "constant")):
+            if got != want or type(got) is not type(want):
+                raise ValueError(f"{name}={got!r}: only {name}={want!r} is built (the librosa branch's Slaney scale and norm, zero padding; "
+                                 "branch='torch' takes none of the three)")
+        self.sr, self.n_mels, self.n_fft, self.hop, self.branch = 16000, N_BANDS, N_FFT, HOP, branch
         self.device, self.max_batch = torch.device(device), int(max_batch)
 
     def generate_batch(self, waves, sr: int = 16000, flatten: bool = True) -> List[np.ndarray]:
         """A list of clips -> per clip the (64, T_b) float32 matrix, or its flattening."""
         wavs = _clips_16k(waves, sr, "MelSpectrogramGenerator", self.resample, self.device, self.max_batch)
-        _require_stft_lengths(wavs)
+        if self.branch == "librosa":
+            _require_samples(wavs)
+        else:
+            _require_stft_lengths(wavs)
         out: List[Optional[np.ndarray]] = [None] * len(wavs)
         for idx, batch, lens in _length_groups(wavs, self.max_batch):
-            mel = stft_forensics(batch.to(self.device), lens, want=("mel_like",))["mel_like"].cpu().numpy()
+            if self.branch == "librosa":
+                mel, frames = mel_spectrogram(batch.to(self.device), lens)["mel_db"].cpu().numpy(), mel_frame_count
+            else:
+                mel, frames = stft_forensics(batch.to(self.device), lens, want=("mel_like",))["mel_like"].cpu().numpy(), stft_frame_count
             for r, i in enumerate(idx):
-                m = np.ascontiguousarray(mel[r, :, :stft_frame_count(lens[r])])
+                m = np.ascontiguousarray(mel[r, :, :frames(lens[r])])
                 out[i] = m.flatten() if flatten else m
         return out
 
