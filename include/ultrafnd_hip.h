@@ -1343,6 +1343,51 @@ int ufnd_forgery_maps(const int32_t* lengths, void* workspace, float ela_scale, 
 int ufnd_forgery_finish(const int32_t* lengths, const void* workspace, float* stats, float* lbp, float* features, float* grad, float* score, int B, int T,
                         int dim, int score_slot, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * A/V lag estimation (csrc/av_lag.hip): the reference's estimate_av_lag (TemporalSyncNet, src/core_blocks/temporal_blocks.py:176-223,
+ * and ChronosGuard, src/models/chronos_guard.py:175-196), batched on the device as a DIRECT windowed cross-correlation (the
+ * reference reads the same window out of three zero-padded FFTs).  Pair b is a = a[b, :len_a[b]] and m = m[b, :len_m[b]]:
+ *
+ *   n          min(len_a, len_m) (each clamped to [0, row width] on the device; NULL: the row width).  n < 4: lag 0, peak 0, the
+ *              xcorr row -inf, the a_std / m_std rows zero (the reference returns 0.0 before it standardises).
+ *   statistics sum of x and, with the mean in double, sum of (x - mean)^2, both in double: thread t of 1024 adds x[t], x[t + 1024],
+ *              ... in ascending order, the 1024 partials fold by halves (red[t] += red[t + o], o = 512 .. 1); mean = sum / n and
+ *              std = sqrt(sumsq / n) (population, ddof 0) in double, each rounded to fp32 once.
+ *   xhat       (x - mean) / (std + 1e-9f), three fp32 operations (the reference's float32 NumPy expression; its mean and std are
+ *              NumPy's pairwise fp32 sums, so the two differ within rounding).  A constant row whose mean is exact gives zeros.
+ *   window     K = max_lag (the host's int(max_lag_s * sr)), Kc = min(K, n - 1):  c[k] = sum_i ahat[i + k] mhat[i] over the i with
+ *              0 <= i < n and 0 <= i + k < n, k = -Kc .. Kc; a[i + s] = m[i] gives lag +s.  (The reference's lo / hi / center
+ *              arithmetic on its 2 n - 1 lags is this window, for K < n - 1 and for K >= n - 1.)
+ *   c[k]       segments of UFND_AVLAG_SEGMENT = 2048 samples i: P[s][k] = ONE chain acc = fmaf(ahat[i + k], mhat[i], acc) from +0
+ *              over the i of segment s in ASCENDING i (terms with i + k outside the pair multiply a zero: the value is that of the
+ *              chain over the valid i);  c[k] = ((P[0][k] + P[1][k]) + ...) + P[S - 1][k] + 0.0f, S = ceil(n / 2048), fp32 additions
+ *              in ascending s; the closing + 0.0f makes every zero +0.  The order depends on (n, k) alone.
+ *   lag        argmax_k c[k], ties to the LOWEST k (np.argmax's first index): an all-zero a gives -Kc, as in the reference.
+ *              lag_seconds = lag_samples / sr is left to the caller (an IEEE double division equals the reference's float).
+ *
+ *   a, m       fp32, row b at a + b a_row_stride, m + b m_row_stride ELEMENTS (64-bit, >= 0), unit inner stride, na_max / nm_max wide.
+ *   lag_samples (B) int32;  peak_corr (B) fp32 = c[lag] / n, one fp32 division (an addition to the reference: a correlation
+ *              coefficient);  xcorr (B, 2 K + 1) fp32, column j is lag j - K, -inf outside the pair's window;  a_std, m_std
+ *              (B, min(na_max, nm_max)) fp32, zero from n on.  Each optional (NULL), at least one; what is asked for changes no bit.
+ *   ufnd_av_lag_workspace_bytes(B, n_max, max_lag)   n_max = min(na_max, nm_max).  The two standardised rows (each B rows of n_max
+ *              rounded up to 8 floats) and the partials (B ceil(n_max / 2048) (2 max_lag + 1) floats), each rounded up to 16 bytes.
+ *              0 for a refused shape: B outside 1 .. UFND_AVLAG_MAX_B, n_max outside 1 .. UFND_AVLAG_MAX_N, max_lag < 0 or above
+ *              UFND_AVLAG_MAX_LAG, or more partials than UFND_AVLAG_MAX_PARTIAL_FLOATS.  Alignment: 16 bytes.
+ * Three launches (standardise; correlate: a workgroup per (UFND_AVLAG_LAG_BLOCK lags, segment, pair), a lane per 8 consecutive lags
+ * sliding a register window over LDS; finish).  Nothing allocates or synchronises; no atomics, no scratch; lengths are never read on
+ * the host; nothing at or past a row's length is read; a pair's outputs are the same bits alone, in any batch and from run to run;
+ * hipGraph-capturable.  Not built: an FFT form, producers of the two envelopes, non-finite samples (outside the contract). */
+#define UFND_AVLAG_SEGMENT 2048                        /* samples of one partial chain */
+#define UFND_AVLAG_LAG_BLOCK 1024                      /* lags of a workgroup */
+#define UFND_AVLAG_MAX_B 65535
+#define UFND_AVLAG_MAX_N (1 << 26)
+#define UFND_AVLAG_MAX_LAG (1 << 26)
+#define UFND_AVLAG_MAX_PARTIAL_FLOATS 2147483648LL     /* 8 GiB of partials */
+size_t ufnd_av_lag_workspace_bytes(int B, int n_max, int max_lag);
+int ufnd_av_lag(const float* a, int64_t a_row_stride, const float* m, int64_t m_row_stride, const int32_t* len_a, const int32_t* len_m,
+                void* workspace, int32_t* lag_samples, float* peak_corr, float* xcorr, float* a_std, float* m_std, int B, int na_max, int nm_max,
+                int max_lag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,8 @@ DESC_FRAME_TILE_A, DESC_FRAME_TILE_B = 64, 32      # UFND_DESC_FRAME_TILE_A, UFN
 MEL_FRAME_TILE, MEL_FILTERS, MEL_NNZ = 64, 64, 388      # UFND_MEL_FRAME_TILE, UFND_MEL_FILTERS, UFND_MEL_NNZ
 RESAMPLE_OUT_TILE, RESAMPLE_LDS_FLOATS, RESAMPLE_MAX_RATIO_TERM = 64, 40000, 1024      # UFND_RESAMPLE_OUT_TILE, _LDS_FLOATS, _MAX_RATIO_TERM
 RESAMPLE_F32, RESAMPLE_I16 = 0, 1
+AVLAG_SEGMENT, AVLAG_LAG_BLOCK = 2048, 1024      # UFND_AVLAG_SEGMENT, UFND_AVLAG_LAG_BLOCK
+AVLAG_MAX_B, AVLAG_MAX_N, AVLAG_MAX_LAG, AVLAG_MAX_PARTIAL_FLOATS = 65535, 1 << 26, 1 << 26, 1 << 31      # UFND_AVLAG_MAX_*
 
 _lib: Optional[C.CDLL] = None
 
@@ -305,6 +307,11 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_mel_workspace_bytes.argtypes = [I, I]
     lib.ufnd_mel_workspace_bytes.restype = S
+    sigs.update({      # A/V lag estimation (csrc/av_lag.hip)
+        "ufnd_av_lag": [P, C.c_int64, P, C.c_int64, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    })
+    lib.ufnd_av_lag_workspace_bytes.argtypes = [I, I, I]
+    lib.ufnd_av_lag_workspace_bytes.restype = S
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

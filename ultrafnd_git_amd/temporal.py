@@ -13,10 +13,12 @@ Conv1d -> BatchNorm1d -> GELU -> dropout blocks with residuals, mean+max pooling
 `ufnd_tcn_forward` (frames stay rows, every conv is an unfold + fp32 MFMA GEMM).  Same sub-module names and
 `state_dict` keys (`tcn.convs.i.*`, `tcn.norms.i.*`, `head.*`) and, under the same torch seed, the same initial
 weights.  Forward only, like everything else in this module.  `delay_score` / `estimate_av_lag` (:162-226) are the
-reference's host-side helpers, restated in numpy."""
+reference's host-side helpers, restated in numpy; `av_lag` / `estimate_av_lag_batch` are the batched device form of the
+latter (csrc/av_lag.hip: a direct windowed cross-correlation, no FFT)."""
 from __future__ import annotations
 
-from typing import Dict, Union
+import math
+from typing import Dict, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -24,6 +26,97 @@ import torch.nn as nn
 
 from . import _lib as L
 from .state import StepStateBuffer
+
+
+AV_LAG_OUTPUTS = ("lag_samples", "lag_seconds", "peak_corr", "xcorr", "a_std", "m_std")
+
+
+def _pair_lengths(lengths, B: int, dev, name: str) -> Optional[torch.Tensor]:
+    if lengths is None:
+        return None
+    lens = lengths.to(dev, torch.int32).contiguous() if isinstance(lengths, torch.Tensor) else torch.tensor(list(lengths), dtype=torch.int32, device=dev)
+    if lens.numel() != B:
+        raise ValueError(f"{name} holds {lens.numel()} entries for {B} pairs")
+    return lens
+
+
+def _rows(x, name: str) -> torch.Tensor:
+    """(B, n) fp32 device rows with unit inner stride, read through their row stride (no copy of a strided row view)."""
+    if not isinstance(x, torch.Tensor):
+        raise L.UltrafndHipError(f"{name}: a {type(x).__name__}; av_lag runs on a HIP device only and takes device tensors (no CPU fallback; "
+                                 "the host form is estimate_av_lag)")
+    L.require_hip(x)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{name} {tuple(x.shape)}: (B, n) rows, or one row (n,), with B >= 1 and n >= 1")
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(1) != 1 or x.stride(0) < 0:
+        x = x.contiguous()
+    return x
+
+
+@torch.no_grad()
+def av_lag(audio_env: torch.Tensor, mouth_open: torch.Tensor, len_a=None, len_m=None, sr: float = 16000.0, fps: float = 25.0,
+           max_lag_s: float = 0.5, want: Sequence[str] = ("lag_seconds",)) -> dict:
+    """The reference's estimate_av_lag of every pair of a batch, on the device.  Pair b is audio_env[b, :len_a[b]] and
+    mouth_open[b, :len_m[b]] (`len_*`: (B,) int32 device tensors or sequences, None: the full row; never read on the host); both are
+    cut to the shorter length n, standardised (population std) and correlated directly over the lags k = -Kc .. Kc with
+    K = int(max_lag_s * sr), Kc = min(K, n - 1):  c[k] = sum_i a[i + k] m[i];  a[i + s] = m[i] gives lag +s.  `want` selects
+      lag_samples (B,) int32       argmax_k c[k], ties to the lowest k
+      lag_seconds (B,) float64     lag_samples / sr: the reference's float, bit for bit
+      peak_corr (B,) fp32          c[lag] / n, a correlation coefficient -- an addition, the reference does not return it
+      xcorr (B, 2 K + 1) fp32      column j is lag j - K; -inf outside a pair's window
+      a_std, m_std (B, min(na_max, nm_max)) fp32      the standardised signals, zero from n on
+    Pairs with n < 4 give lag 0, 0.0 seconds, peak 0, an xcorr row of -inf and zero a_std / m_std rows.  `fps` is accepted and
+    unused, as in the reference.  Nothing here synchronises; the call can be captured in a graph.  What is asked for changes no bit.
+    Not covered: non-finite samples, and the reference's rounding noise on a constant row whose fp32 mean is inexact (+-tiny there,
+    exactly zero here)."""
+    want = tuple(want)
+    for name in want:
+        if name not in AV_LAG_OUTPUTS:
+            raise ValueError(f"want={name!r}: one of {AV_LAG_OUTPUTS}")
+    if not want:
+        raise ValueError(f"want is empty: some of {AV_LAG_OUTPUTS}")
+    sr, max_lag_s = float(sr), float(max_lag_s)
+    if not (sr > 0.0) or not math.isfinite(sr):
+        raise ValueError(f"sr={sr!r}: a positive finite sample rate (the reference divides by it)")
+    span = max_lag_s * sr
+    if not (span >= 0.0) or not math.isfinite(span):
+        raise ValueError(f"max_lag_s={max_lag_s!r} with sr={sr!r}: max_lag_s * sr must be finite and >= 0 (the reference searches an empty window)")
+    K = int(span)
+    a, m = _rows(audio_env, "audio_env"), _rows(mouth_open, "mouth_open")
+    dev = L.require_hip(a, m)
+    B, na_max = a.shape
+    if m.shape[0] != B:
+        raise ValueError(f"audio_env holds {B} rows, mouth_open {m.shape[0]}")
+    nm_max = m.shape[1]
+    la, lm = _pair_lengths(len_a, B, dev, "len_a"), _pair_lengths(len_m, B, dev, "len_m")
+    nw = min(na_max, nm_max)
+    nbytes = L.lib().ufnd_av_lag_workspace_bytes(B, nw, K) if K <= L.AVLAG_MAX_LAG else 0
+    if nbytes == 0:
+        raise L.UltrafndHipError(f"av_lag: B={B} n_max={nw} max_lag={K} is refused (B <= {L.AVLAG_MAX_B}, n_max <= 2^26, max_lag <= 2^26, "
+                                 f"B ceil(n_max / {L.AVLAG_SEGMENT}) (2 max_lag + 1) <= 2^31 partial sums)")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    need_lag = "lag_samples" in want or "lag_seconds" in want
+    bufs = {}
+    if need_lag:
+        bufs["lag_samples"] = torch.empty(B, dtype=torch.int32, device=dev)
+    if "peak_corr" in want:
+        bufs["peak_corr"] = torch.empty(B, dtype=torch.float32, device=dev)
+    if "xcorr" in want:
+        bufs["xcorr"] = torch.empty(B, 2 * K + 1, dtype=torch.float32, device=dev)
+    for name in ("a_std", "m_std"):
+        if name in want:
+            bufs[name] = torch.empty(B, nw, dtype=torch.float32, device=dev)
+    L.check(L.lib().ufnd_av_lag(a.data_ptr(), a.stride(0), m.data_ptr(), m.stride(0), L.ptr(la), L.ptr(lm), ws.data_ptr(), L.ptr(bufs.get("lag_samples")),
+                                L.ptr(bufs.get("peak_corr")), L.ptr(bufs.get("xcorr")), L.ptr(bufs.get("a_std")), L.ptr(bufs.get("m_std")), B, na_max,
+                                nm_max, K, L.stream_ptr(dev)), "ufnd_av_lag")
+    if "lag_seconds" in want:
+        # a tensor divisor: a true IEEE division (a Python scalar divisor is applied as a multiplication by its reciprocal)
+        bufs["lag_seconds"] = bufs["lag_samples"].double() / torch.full((B,), sr, dtype=torch.float64, device=dev)
+    return {name: bufs[name] for name in AV_LAG_OUTPUTS if name in want}
 
 
 class _TinyTCN(nn.Module):
@@ -227,3 +320,9 @@ class TemporalSyncNet(nn.Module):
         half = int(max_lag_s * sr)
         lo, hi = max(0, mid - half), min(lags.size, mid + half + 1)
         return float((lo + int(np.argmax(lags[lo:hi])) - mid) / sr)
+
+    @staticmethod
+    def estimate_av_lag_batch(audio_env, mouth_open, len_a=None, len_m=None, sr: float = 16000.0, fps: float = 25.0, max_lag_s: float = 0.5,
+                              want: Sequence[str] = ("lag_seconds",)) -> dict:
+        """estimate_av_lag of a batch of pairs on the device: `av_lag` of this module (device tensors in, device tensors out)."""
+        return av_lag(audio_env, mouth_open, len_a, len_m, sr, fps, max_lag_s, want)

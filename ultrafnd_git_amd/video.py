@@ -250,6 +250,13 @@ class ChronosGuard:
         lo, hi = max(0, mid - half), min(lags.size, mid + half + 1)
         return float((lo + int(np.argmax(lags[lo:hi])) - mid) / sr)
 
+    @staticmethod
+    def estimate_av_lag_batch(audio_env, mouth_open, len_a=None, len_m=None, sr: float = 16000.0, fps: float = 25.0, max_lag_s: float = 0.5,
+                              want=("lag_seconds",)) -> dict:
+        """estimate_av_lag of a batch of pairs on the device: temporal.av_lag (device tensors in, device tensors out)."""
+        from .temporal import av_lag
+        return av_lag(audio_env, mouth_open, len_a, len_m, sr, fps, max_lag_s, want)
+
 
 # ISO/IEC 10918-1 Annex K, tables K.1 (luminance) and K.2 (chrominance), natural (row-major) order
 JPEG_K1 = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
