@@ -1388,6 +1388,66 @@ int ufnd_av_lag(const float* a, int64_t a_row_stride, const float* m, int64_t m_
                 void* workspace, int32_t* lag_samples, float* peak_corr, float* xcorr, float* a_std, float* m_std, int B, int na_max, int nm_max,
                 int max_lag, void* stream);
 
+/* -------------------------------------------------------------------------------------
+ * CLIP image preprocessing (csrc/clip_preprocess.hip): what the checkpoint's CLIPImageProcessor does on its Pillow backend (the one
+ * the reference instantiates, src/models/semantic_forgery.py:54-61) -- shortest-edge bicubic resize, centre crop, rescale,
+ * normalise -- on decoded uint8 frames, batched and ragged on the device, equal to Pillow and the processor in every byte and bit.
+ * Frames as for ufnd_motion_gray: uint8, (b, t, c, y, x) at frames + b stride_b + t stride_t + c stride_c + y stride_h + x stride_w
+ * (elements, 64-bit, >= 0), 3 channels; a batch of single images is T = 1.  `lengths` (B int32 on the device, NULL: T; clamped to
+ * [0, T]).  With S the output edge (the encoder's `image`):
+ *
+ *   size       short, long = the source's shorter and longer edge; the resized image has short edge S and long edge
+ *              int(S * long / short) (truncated); W <= H makes the width the short edge.
+ *   one pass   in -> out samples along an axis: scale = in / out, fs = max(scale, 1), support = 2 fs.  Output xx: c = (xx + 0.5) scale,
+ *              xmin = max(int(c - support + 0.5), 0), xmax = min(int(c + support + 0.5), in), n = xmax - xmin taps
+ *              w[x] = bicubic((x + xmin - c + 0.5) (1 / fs)), a = -0.5: ((a + 2)|t| - (a + 3)) t^2 + 1 for |t| < 1,
+ *              (((|t| - 5)|t| + 8)|t| - 4) a for |t| < 2, else 0; summed in index order in double, each divided by a non-zero sum;
+ *              k = (int)(w 2^22 + 0.5) for w >= 0, (int)(w 2^22 - 0.5) for w < 0 (the cast truncates);
+ *              pixel = clip((2^21 + sum_x k[x] p[xmin + x]) >> 22, 0, 255), an arithmetic shift of a signed 32-bit sum.
+ *   order      horizontal, then vertical; the image between them is uint8 (rounded and clipped as above).  A pass with in == out is
+ *              skipped: its table is the identity, one tap of 2^22.
+ *   crop       S x S at top = (h' - S) / 2, left = (w' - S) / 2 (floor) of the resized h' x w' image; only the crop's rows and columns
+ *              are computed, and of the source only the rows and columns their taps reach.
+ *   value map  channel c, byte v:  r = fl32(double(v) 0.00392156862745098);  (r - fl32(mean[c])) / fl32(std[c]), both in fp32, the
+ *              division correctly rounded: 768 values, evaluated on the host and passed as value_map (3, 256) fp32 on the device.
+ *
+ *   tables     int32 on the device, built on the host in double by the formulas above (video.clip_resize_tables) for the S crop
+ *              columns and the S crop rows:  hfirst[S], hcount[S], vfirst[S], vcount[S], hk[S][taps_h], vk[S][taps_v]  in this
+ *              order; taps_h / taps_v = the largest count of the pass; |k| < 2^23 (a normalised weight stays below 2: the kernel's
+ *              products are 24-bit multiplies).  x_lo, x_span: the source columns the horizontal taps reach,
+ *              [x_lo, x_lo + x_span).  tile_rows: output rows of a workgroup; lds_rows: the most intermediate rows one tile's taps
+ *              reach.  The kernel clamps every table entry into the source and into its tile, so a wrong table gives wrong pixels,
+ *              never an access outside the frames or the tile.
+ *   outputs    pixel_values (B, T, 3, S, S) fp32 and rgb (B, T, S, S, 3) uint8 (the cropped resized image), contiguous, each optional
+ *              (NULL), at least one.  Frame t >= len_b holds the bits of frame len_b - 1 (the reference's padding,
+ *              src/training/run_train_eval.py:329-333); a clip of length 0 holds the image of an all-zero frame (:325).  Source
+ *              frames at or past a clip's length are never read.
+ * One launch: a workgroup per (frame, tile of tile_rows output rows).  It runs the horizontal pass over the intermediate rows its
+ * tile needs, source rows staged through LDS in 16-byte reads when the pixels are dense (stride_c = 1 and stride_w = 3, or
+ * stride_w = 1; any other view is gathered byte by byte), keeps the uint8 intermediate in LDS, and runs the vertical pass from
+ * there: the intermediate never travels through memory.  Intermediates up to UFND_CLIP_PRE_INTER_BYTES run in a 64 KiB workgroup
+ * (two per CU), larger ones up to UFND_CLIP_PRE_INTER_BYTES_LARGE in a 156 KiB one.  Each output depends on its source frame and
+ * (H, W, S) alone: the same bits alone, in any batch, for any tile_rows, from run to run.  Nothing allocates or synchronises; no
+ * atomics, no scratch, no workspace; hipGraph-capturable.
+ * Refused by name: B, T, H, W < 1; H, W > UFND_CLIP_PRE_MAX_EDGE; B T > UFND_CLIP_PRE_MAX_FRAMES or more than 2^31 - 1
+ * workgroups; S outside UFND_CLIP_PRE_MIN_SIZE .. UFND_CLIP_PRE_MAX_SIZE; taps_h, taps_v outside 1 .. UFND_CLIP_PRE_MAX_TAPS (41 taps
+ * resize 2160 x 3840 to 224); x_span outside 1 .. UFND_CLIP_PRE_MAX_SPAN or a span outside the row; tile_rows outside
+ * 1 .. UFND_CLIP_PRE_MAX_TILE_ROWS; lds_rows < 1, > H or more than UFND_CLIP_PRE_INTER_BYTES_LARGE of intermediate (rows of
+ * 3 S bytes rounded up to 4). */
+#define UFND_CLIP_PRE_MIN_SIZE 16
+#define UFND_CLIP_PRE_MAX_SIZE 448
+#define UFND_CLIP_PRE_MAX_TAPS 64
+#define UFND_CLIP_PRE_MAX_SPAN 7000                  /* source columns a row's horizontal taps reach */
+#define UFND_CLIP_PRE_MAX_TILE_ROWS 16
+#define UFND_CLIP_PRE_INTER_BYTES 40960              /* the intermediate of a tile in the 64 KiB workgroup */
+#define UFND_CLIP_PRE_INTER_BYTES_LARGE 135168       /* ... and in the 156 KiB one */
+#define UFND_CLIP_PRE_STAGE_BYTES 21376              /* staged source rows of a workgroup */
+#define UFND_CLIP_PRE_MAX_EDGE 65536
+#define UFND_CLIP_PRE_MAX_FRAMES (1 << 24)
+int ufnd_clip_preprocess(const void* frames, long long stride_b, long long stride_t, long long stride_c, long long stride_h, long long stride_w,
+                         const int32_t* lengths, const int32_t* tables, const float* value_map, float* pixel_values, void* rgb, int B, int T, int H,
+                         int W, int S, int taps_h, int taps_v, int x_lo, int x_span, int tile_rows, int lds_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

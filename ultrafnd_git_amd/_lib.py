@@ -128,6 +128,9 @@ RESAMPLE_OUT_TILE, RESAMPLE_LDS_FLOATS, RESAMPLE_MAX_RATIO_TERM = 64, 40000, 102
 RESAMPLE_F32, RESAMPLE_I16 = 0, 1
 AVLAG_SEGMENT, AVLAG_LAG_BLOCK = 2048, 1024      # UFND_AVLAG_SEGMENT, UFND_AVLAG_LAG_BLOCK
 AVLAG_MAX_B, AVLAG_MAX_N, AVLAG_MAX_LAG, AVLAG_MAX_PARTIAL_FLOATS = 65535, 1 << 26, 1 << 26, 1 << 31      # UFND_AVLAG_MAX_*
+CLIP_PRE_MIN_SIZE, CLIP_PRE_MAX_SIZE, CLIP_PRE_MAX_TAPS, CLIP_PRE_MAX_SPAN, CLIP_PRE_MAX_TILE_ROWS = 16, 448, 64, 7000, 16      # UFND_CLIP_PRE_*
+CLIP_PRE_INTER_BYTES, CLIP_PRE_INTER_BYTES_LARGE, CLIP_PRE_STAGE_BYTES = 40960, 135168, 21376
+CLIP_PRE_MAX_EDGE, CLIP_PRE_MAX_FRAMES = 65536, 1 << 24
 
 _lib: Optional[C.CDLL] = None
 
@@ -312,6 +315,9 @@ def _declare_encoders(lib: C.CDLL) -> None:
     })
     lib.ufnd_av_lag_workspace_bytes.argtypes = [I, I, I]
     lib.ufnd_av_lag_workspace_bytes.restype = S
+    sigs.update({      # CLIP image preprocessing (csrc/clip_preprocess.hip)
+        "ufnd_clip_preprocess": [P, LL, LL, LL, LL, LL, P, P, P, P, P] + [I] * 11 + [P],
+    })
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

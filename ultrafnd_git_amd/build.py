@@ -61,7 +61,8 @@ FILE_FLAGS = {"gemm_bf16_pp": ["-Xclang", "-target-feature", "-Xclang", "-packed
               "motion": ["-ffp-contract=off"],      # the float64 luma is bit-exact only with every operation rounded on its own (csrc/frames.hpp)
               "forgery": ["-ffp-contract=off"],
               "resample": ["-ffp-contract=off"],      # the channel mix rounds every operation on its own (the chain is explicit fmaf)
-              "av_lag": ["-ffp-contract=off"]}      # the double statistics round every operation on their own (the chain is explicit fmaf)
+              "av_lag": ["-ffp-contract=off"],      # the double statistics round every operation on their own (the chain is explicit fmaf)
+              "clip_preprocess": ["-ffp-contract=off"]}      # shares csrc/frames.hpp (its own arithmetic is integer; the value map is a host-built table)
 
 
 def _compile(src: Path, tag: str, flags: list, verbose: bool) -> Path:

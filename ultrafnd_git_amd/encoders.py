@@ -895,3 +895,11 @@ class ClipVisualEncoder(_EncoderBase):
         L.check(L.lib().ufnd_l2norm_frames(e.data_ptr(), b["feat"].data_ptr(), B, Fr, self.proj, L.stream_ptr(self.device)),
                 "ufnd_l2norm_frames")
         return b["feat"]
+
+    @torch.no_grad()
+    def encode_frames(self, frames_u8: torch.Tensor, lengths=None, layout: Optional[str] = None) -> torch.Tensor:
+        """Decoded uint8 frames (B,F,H,W,3) / (B,F,3,H,W), or a 4-D image batch, on the device -> (B,512) features: the checkpoint's
+        image preprocessing at this encoder's `image` size (video.clip_preprocess, bit-exact to CLIPImageProcessor's Pillow backend),
+        then forward().  lengths: frames at or past a clip's length repeat its last valid frame."""
+        from .video import clip_preprocess
+        return self.forward(clip_preprocess(frames_u8, lengths, layout, image_size=self.image)["pixel_values"])

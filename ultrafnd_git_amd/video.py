@@ -24,6 +24,11 @@ through OpenCV; here it is baseline libjpeg's integer arithmetic on the device (
 upsampling), equal to what libjpeg decodes in every byte -- jpeg="libjpeg".  jpeg="none" is the reference on a host without OpenCV:
 rec = rgb, the map is zero and the vector a constant.  The LBP histogram is the reference's branch without scikit-image, the
 gradient its forward differences.  A clip of length 0 gives a zero vector and score 0.0.
+
+CLIP image preprocessing (csrc/clip_preprocess.hip): clip_preprocess() turns decoded uint8 frames into the (B, T, 3, 224, 224) float32
+tensor ClipVisualEncoder takes, as the checkpoint's CLIPImageProcessor does on its Pillow backend (shortest-edge bicubic resize, centre
+crop, rescale, normalise), equal to Pillow and the processor in every byte and float32 bit; clip_resize_tables() builds its
+fixed-point coefficient tables on the host.
 """
 from __future__ import annotations
 
@@ -447,3 +452,172 @@ def cache_visual(frames: torch.Tensor, lengths=None, visual_dim: int = 512, layo
     not computed: (B, visual_dim) fp32."""
     x = OpticalFlow3DCNN(dim=visual_dim).extract_batch(frames, lengths, layout)
     return x / (torch.linalg.vector_norm(x, dim=1, keepdim=True) + 1e-9)
+
+
+# ------------------------------------------------------------------ CLIP image preprocessing (csrc/clip_preprocess.hip)
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # the processor's image_mean / image_std (OPENAI_CLIP_MEAN / _STD)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+CLIP_RESCALE = 0.00392156862745098                    # its rescale_factor: 1 / 255 as a double
+_COEF_BITS = 22                                       # fractional bits of Pillow's fixed-point coefficients
+_clip_tables_cache: dict = {}
+_clip_tables_dev_cache: dict = {}
+_clip_map_dev_cache: dict = {}
+
+
+def _bicubic_weight(t: float) -> float:
+    """Pillow's bicubic kernel, a = -0.5."""
+    a = -0.5
+    t = -t if t < 0.0 else t
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    if t < 2.0:
+        return (((t - 5) * t + 8) * t - 4) * a
+    return 0.0
+
+
+def _pass_tables(n_in: int, n_out: int, lo: int, n: int) -> Dict[str, np.ndarray]:
+    """Outputs lo .. lo + n - 1 of one resampling pass n_in -> n_out: first, count (n,) and k (n, taps) int32, built in float64 by
+    Pillow's rule (include/ultrafnd_hip.h states it).  A pass with n_in == n_out is skipped by Pillow: the identity table."""
+    if n_in == n_out:
+        return {"first": np.arange(lo, lo + n, dtype=np.int32), "count": np.ones(n, np.int32), "k": np.full((n, 1), 1 << _COEF_BITS, np.int32), "skipped": True}
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support, inv = 2.0 * fs, 1.0 / fs
+    first, count, rows = np.zeros(n, np.int32), np.zeros(n, np.int32), []
+    for i in range(n):
+        c = (lo + i + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        xmax = max(min(int(c + support + 0.5), n_in), xmin)
+        w = [_bicubic_weight((x + xmin - c + 0.5) * inv) for x in range(xmax - xmin)]
+        total = 0.0
+        for v in w:
+            total += v
+        if total != 0.0:
+            w = [v / total for v in w]
+        rows.append([int(v * (1 << _COEF_BITS) + 0.5) if v >= 0 else int(v * (1 << _COEF_BITS) - 0.5) for v in w])      # (int() truncates)
+        first[i], count[i] = xmin, xmax - xmin
+    k = np.zeros((n, max(1, int(count.max()))), np.int32)
+    for i, r in enumerate(rows):
+        k[i, :len(r)] = r
+    assert int(np.abs(k).max()) < 1 << 23, "a normalised bicubic weight stays below 2: the kernel multiplies in 24 bits"
+    return {"first": first, "count": count, "k": k, "skipped": False}
+
+
+def clip_resize_tables(H: int, W: int, image_size: int = 224) -> dict:
+    """Host only: the tables of CLIPImageProcessor's resize (shortest edge -> image_size, Pillow's bicubic) and centre crop for H x W
+    sources, for the crop's rows and columns alone.
+      resized (h', w'), top, left     the resized size and the crop's offsets in it
+      h, v                            per pass (horizontal: W -> w', vertical: H -> h'): first, count (S,) int32, k (S, taps) int32
+                                      (22 fractional bits), skipped (the pass has in == out: the identity table)
+      x_lo, x_span                    the source columns the crop's horizontal taps reach
+      tile_rows, lds_rows             output rows of a workgroup and the most intermediate rows one tile reaches: the largest tile of
+                                      at most L.CLIP_PRE_MAX_TILE_ROWS rows whose intermediate fits L.CLIP_PRE_INTER_BYTES if that is at
+                                      least 8 rows, else the largest that fits L.CLIP_PRE_INTER_BYTES_LARGE
+      table                           the device form: hfirst, hcount, vfirst, vcount, hk, vk in one int32 array
+    Cached per (H, W, image_size)."""
+    H, W, S = int(H), int(W), int(image_size)
+    if H < 1 or W < 1 or H > L.CLIP_PRE_MAX_EDGE or W > L.CLIP_PRE_MAX_EDGE:
+        raise ValueError(f"clip_resize_tables: H={H} W={W} (1 .. {L.CLIP_PRE_MAX_EDGE} each)")
+    if not L.CLIP_PRE_MIN_SIZE <= S <= L.CLIP_PRE_MAX_SIZE:
+        raise ValueError(f"clip_resize_tables: image_size={S} ({L.CLIP_PRE_MIN_SIZE} .. {L.CLIP_PRE_MAX_SIZE})")
+    key = (H, W, S)
+    if key in _clip_tables_cache:
+        return _clip_tables_cache[key]
+    short, long_ = (W, H) if W <= H else (H, W)
+    new_long = int(S * long_ / short)
+    h2, w2 = (new_long, S) if W <= H else (S, new_long)
+    top, left = (h2 - S) // 2, (w2 - S) // 2
+    for name, n_in, n_out in (("horizontal", W, w2), ("vertical", H, h2)):
+        taps = 2 * int(np.ceil(2.0 * max(n_in / n_out, 1.0))) + 1
+        if n_in != n_out and taps > L.CLIP_PRE_MAX_TAPS:
+            raise ValueError(f"clip_resize_tables: {H}x{W} -> {S}: the {name} pass has {taps} taps (at most {L.CLIP_PRE_MAX_TAPS}: the source is too large)")
+    h, v = _pass_tables(W, w2, left, S), _pass_tables(H, h2, top, S)
+    x_lo = int(h["first"].min())
+    x_span = int((h["first"] + h["count"]).max()) - x_lo
+    if x_span > L.CLIP_PRE_MAX_SPAN:
+        raise ValueError(f"clip_resize_tables: {H}x{W} -> {S}: a row's taps reach {x_span} source columns (at most {L.CLIP_PRE_MAX_SPAN})")
+    pitch = (3 * S + 3) // 4 * 4
+    end = v["first"] + v["count"]
+
+    def reach(tr):      # the most intermediate rows a tile of tr output rows needs
+        return max(int(end[min(y0 + tr, S) - 1] - v["first"][y0]) for y0 in range(0, S, tr))
+
+    fits = lambda limit: next((tr for tr in range(L.CLIP_PRE_MAX_TILE_ROWS, 0, -1) if reach(tr) * pitch <= limit), 0)
+    tile_rows = fits(L.CLIP_PRE_INTER_BYTES)
+    if tile_rows < 8:
+        tile_rows = fits(L.CLIP_PRE_INTER_BYTES_LARGE)
+    if tile_rows < 1:
+        raise ValueError(f"clip_resize_tables: {H}x{W} -> {S}: one output row reaches {reach(1)} intermediate rows of {pitch} bytes "
+                         f"(at most {L.CLIP_PRE_INTER_BYTES_LARGE} bytes)")
+    table = np.concatenate([h["first"], h["count"], v["first"], v["count"], h["k"].ravel(), v["k"].ravel()]).astype(np.int32)
+    out = {"H": H, "W": W, "image_size": S, "resized": (h2, w2), "top": top, "left": left, "h": h, "v": v, "x_lo": x_lo, "x_span": x_span,
+           "tile_rows": tile_rows, "lds_rows": reach(tile_rows), "table": table}
+    _clip_tables_cache[key] = out
+    return out
+
+
+def clip_value_map(mean=CLIP_MEAN, std=CLIP_STD) -> np.ndarray:
+    """(3, 256) float32: what the processor's rescale + normalise make of byte v in channel c -- r = fl32(double(v) / 255-as-a-double
+    product), then (r - fl32(mean)) / fl32(std) in fp32."""
+    mean, std = np.asarray(mean, np.float64).ravel(), np.asarray(std, np.float64).ravel()
+    if mean.size != 3 or std.size != 3 or not (np.isfinite(mean).all() and np.isfinite(std).all()) or (std.astype(np.float32) == 0).any():
+        raise ValueError(f"clip_value_map: mean={tuple(mean)} std={tuple(std)} (3 finite values each, std non-zero)")
+    r = (np.arange(256, dtype=np.float64) * CLIP_RESCALE).astype(np.float32)
+    return ((r[None, :] - mean.astype(np.float32)[:, None]) / std.astype(np.float32)[:, None]).astype(np.float32)
+
+
+def _dev_key(dev: torch.device):
+    return (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+@torch.no_grad()
+def clip_preprocess(frames: torch.Tensor, lengths=None, layout: Optional[str] = None, image_size: int = 224, mean=CLIP_MEAN, std=CLIP_STD,
+                    want=("pixel_values",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """The checkpoint's CLIPImageProcessor (Pillow backend: shortest-edge bicubic resize, centre crop, rescale, normalise) on decoded
+    uint8 frames, in one launch, bit for bit: {"pixel_values": (B, T, 3, S, S) fp32 -- what ClipVisualEncoder takes -- and / or
+    "rgb": (B, T, S, S, 3) uint8, the cropped resized image}, as `want` names them.
+    frames: (B, T, H, W, 3) or (B, T, 3, H, W) uint8 on a HIP device, read through their strides (frames[:, ::k] subsamples for free);
+    a 4-D image batch is a batch of one-frame clips.  lengths: (B,) frames per clip, never read on the host: a frame at or past its
+    clip's length holds the bits of the clip's last valid frame, a clip of length 0 the image of an all-zero frame, and source frames
+    at or past a length are not read.  out: {"pixel_values": ..., "rgb": ...} contiguous tensors of those shapes to write in place."""
+    if isinstance(frames, str) or not torch.is_tensor(frames):
+        raise L.UltrafndHipError("frames must be a tensor on a HIP device (no CPU fallback)")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"frames: dtype {frames.dtype} (uint8 only: the processor treats float images by a different arithmetic)")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want:
+        raise ValueError("want is empty: 'pixel_values' and / or 'rgb'")
+    for wname in want:
+        if wname not in ("pixel_values", "rgb"):
+            raise ValueError(f"want={wname!r}: 'pixel_values' and / or 'rgb'")
+    if frames.dim() == 4:
+        frames = frames.unsqueeze(1)
+    p = _Plan(frames, layout)
+    tab = clip_resize_tables(p.H, p.W, image_size)
+    vmap = clip_value_map(mean, std)
+    if lengths is not None and (lengths.numel() if torch.is_tensor(lengths) else len(lengths)) != p.B:
+        raise ValueError(f"lengths holds {lengths.numel() if torch.is_tensor(lengths) else len(lengths)} entries for {p.B} clips")
+    dev = L.require_hip(frames)
+    S = tab["image_size"]
+    lens = _lengths(lengths, p.B, dev)
+    shapes = {"pixel_values": ((p.B, p.T, 3, S, S), torch.float32), "rgb": ((p.B, p.T, S, S, 3), torch.uint8)}
+    res = {}
+    for wname in want:
+        shape, dtype = shapes[wname]
+        t = None if out is None else out.get(wname)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"out[{wname!r}]: expected a contiguous {dtype} tensor of shape {shape} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        res[wname] = t
+    key = (p.H, p.W, S) + _dev_key(dev)
+    if key not in _clip_tables_dev_cache:
+        _clip_tables_dev_cache[key] = torch.from_numpy(tab["table"]).to(dev)
+    mkey = (vmap.tobytes(),) + _dev_key(dev)
+    if mkey not in _clip_map_dev_cache:
+        _clip_map_dev_cache[mkey] = torch.from_numpy(vmap).to(dev)
+    table, vm = _clip_tables_dev_cache[key], _clip_map_dev_cache[mkey]
+    L.check(L.lib().ufnd_clip_preprocess(frames.data_ptr(), *p.strides, L.ptr(lens), table.data_ptr(), vm.data_ptr(), L.ptr(res.get("pixel_values")),
+                                         L.ptr(res.get("rgb")), p.B, p.T, p.H, p.W, S, tab["h"]["k"].shape[1], tab["v"]["k"].shape[1], tab["x_lo"],
+                                         tab["x_span"], tab["tile_rows"], tab["lds_rows"], L.stream_ptr(dev)), "ufnd_clip_preprocess")
+    return res
