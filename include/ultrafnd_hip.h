@@ -945,12 +945,14 @@ int ufnd_vit_unpatchify_attribution(const float* dpatches, const float* x, const
 /* Wav2Vec2FeatureExtractor(do_normalize): out[b, i] = (wave[b, i] - mean_b) / sqrt(var_b + 1e-7) for i < lengths[b] (population
  * variance over the clip's own samples; samples past lengths[b] are neither read nor written).  wave, out (B, n_max) fp32;
  * lengths (B) int32 on the device, each in [UFND_AUDIO_MIN_SAMPLES, n_max]; ws: 3 B ceil(n_max / UFND_WAVE_CHUNK) floats.
- * Partials per chunk are {pivot, sum, sum of squares about the pivot} in fp32, combined in float64 (Chan). */
+ * Partials per chunk are {centre, sum, sum of squares about the centre} in fp32, the centre being the chunk's own fp32 mean (formed
+ * inside the workgroup first), combined in float64 (Chan): the accuracy does not depend on where in a chunk an outlier sits. */
 int ufnd_wave_normalize(const float* wave, const int32_t* lengths, float* out, float* ws, int B, int n_max, void* stream);
 
 /* Layer 0 of the feature extractor: Conv1d(1 -> 512, k = 10, s = 5, no bias) + GroupNorm(512, 512) (per clip and channel over
  * the clip's T1_b = (lengths[b] - 10) / 5 + 1 frames, biased variance, affine) + GELU.  Two passes that both recompute the conv
- * from the wave: the fp32 conv output is never stored.  wave (B, n_max) fp32 (normalised); w (512, 10); out_bf16 rows b S1 + t;
+ * from the wave: the fp32 conv output is never stored.  Statistics as in ufnd_wave_normalize, per chunk of UFND_CONV0_CHUNK frames
+ * about the conv of the chunk's mean window (the conv is linear: that is each channel's mean over the chunk).  wave (B, n_max) fp32 (normalised); w (512, 10); out_bf16 rows b S1 + t;
  * out_f32 (optional, tests): the same rows before the bf16 rounding.  ws: 3 B 512 ceil(S1 / UFND_CONV0_CHUNK) + 2 B 512 floats. */
 int ufnd_w2v2_conv0(const float* wave, const int32_t* lengths, const float* w, const float* gamma, const float* beta, void* out_bf16,
                     float* out_f32, float* ws, int B, int n_max, int S1, float eps, void* stream);

@@ -1,8 +1,9 @@
 // Audio encoder (wav2vec2-base geometry), the pieces that are not a GEMM, an attention or a LayerNorm launch:
 //   utterance normalisation, conv layer 0 + GroupNorm + GELU, the positional conv's pack / add kernels, the frame counts.
 // Frames are rows, channel-last, in per-clip slabs (include/ultrafnd_hip.h).  Every reduction is a fixed tree over the clip's own
-// samples / frames: fp32 partials per fixed-size chunk about a pivot (the chunk's first value), combined in chunk order in
-// float64 (Chan's update).  No atomics; a clip's results are the same bits alone and inside any batch, on every run.
+// samples / frames: fp32 partials per fixed-size chunk about the chunk's own fp32 mean (formed inside the workgroup first: a chunk
+// whose first value is a click is as accurate as any other), combined in chunk order in float64 (Chan's update).  No atomics; a
+// clip's results are the same bits alone and inside any batch, on every run.
 #include "rowwise.hpp"
 #include "gemm_f32.hpp"
 
@@ -31,18 +32,37 @@ __device__ __forceinline__ int clip_len(const int32_t* lengths, int b, int n_max
   return n < n_max ? n : n_max;
 }
 
-// ---- utterance normalisation.  Partials: grid (chunks, B); chunk c of clip b -> ws[(b nch + c) 3 ..] = {pivot, s, q}
+// ---- utterance normalisation.  Partials: grid (chunks, B); chunk c of clip b -> ws[(b nch + c) 3 ..] = {centre, s, q}
 __global__ __launch_bounds__(256) void wave_partials_kernel(const float* wave, const int32_t* lengths, float* ws, int n_max, int nch) {
   __shared__ float red[4];
   const int b = blockIdx.y, c = blockIdx.x, n = clip_len(lengths, b, n_max), i0 = c * WCH;
   if (i0 >= n) return;
   const float* x = wave + (size_t)b * n_max;
-  const float p = x[i0];
+  const int i1 = i0 + WCH < n ? i0 + WCH : n;
+  // the thread's 16 samples stay in registers (past the chunk's end: its first sample, whose difference from itself is 0)
+  static_assert(WCH == 16 * 256, "one workgroup of 256 threads holds a chunk in 16 registers per thread");
+  const float first = x[i0];
+  float v[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int i = i0 + threadIdx.x + 256 * j;
+    v[j] = i < i1 ? x[i] : first;
+  }
+  // pass 1: the chunk's own fp32 mean, from a sum about its first sample.  It only has to lie NEAR the mean: whatever it is, the
+  // {centre, s, q} below describe the chunk exactly up to the rounding of s and q
   float s = 0.0f, q = 0.0f;
-  for (int i = i0 + threadIdx.x; i < i0 + WCH && i < n; i += 256) {
-    const float d = x[i] - p;
-    s += d;
-    q += d * d;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) s += v[j] - first;
+  const float p = first + block_sum4(s, red) / (float)(i1 - i0);
+  // pass 2: the sums about that centre
+  s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    if (i0 + threadIdx.x + 256 * j < i1) {
+      const float d = v[j] - p;
+      s += d;
+      q += d * d;
+    }
   }
   s = block_sum4(s, red);
   q = block_sum4(q, red);
@@ -52,7 +72,7 @@ __global__ __launch_bounds__(256) void wave_partials_kernel(const float* wave, c
   }
 }
 
-// Chan's combination of chunk partials {pivot, s, q} with counts cnt(c), in chunk order, float64: mean and M2 of the whole
+// Chan's combination of chunk partials {centre, s, q} with counts cnt(c), in chunk order, float64: mean and M2 of the whole
 struct MeanM2 { double mean, m2; };
 template <typename Get, typename Cnt>
 __device__ __forceinline__ MeanM2 combine_chunks(int nchunks, Get get, Cnt cnt) {
@@ -93,11 +113,8 @@ __device__ __forceinline__ void conv0_load_w(const float* w, int cg, float (&wr)
 #pragma unroll
     for (int k = 0; k < 10; ++k) wr[j][k] = w[(8 * cg + j) * 10 + k];
 }
-// the 10-tap dot of frame t: one fixed fma chain per channel, the same in both passes
-__device__ __forceinline__ void conv0_frame(const float* x, int t, const float (&wr)[8][10], float (&y)[8]) {
-  float xv[10];
-#pragma unroll
-  for (int k = 0; k < 10; ++k) xv[k] = x[5 * t + k];
+// the 10-tap dot of a window: one fixed fma chain per channel, the same in both passes
+__device__ __forceinline__ void conv0_dot(const float (&xv)[10], const float (&wr)[8][10], float (&y)[8]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     float a = 0.0f;
@@ -106,8 +123,14 @@ __device__ __forceinline__ void conv0_frame(const float* x, int t, const float (
     y[j] = a;
   }
 }
+__device__ __forceinline__ void conv0_frame(const float* x, int t, const float (&wr)[8][10], float (&y)[8]) {
+  float xv[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) xv[k] = x[5 * t + k];
+  conv0_dot(xv, wr, y);
+}
 
-// partials: grid (frame chunks, B); ws[((b nch + c) 3 + {0,1,2}) 512 + channel] = {pivot, s, q} of the chunk's frames
+// partials: grid (frame chunks, B); ws[((b nch + c) 3 + {0,1,2}) 512 + channel] = {centre, s, q} of the chunk's frames
 __global__ __launch_bounds__(256) void conv0_partials_kernel(const float* wave, const int32_t* lengths, const float* w, float* ws, int n_max, int nch) {
   __shared__ float red[2][4][C0];
   const int b = blockIdx.y, c = blockIdx.x, T1 = (clip_len(lengths, b, n_max) - 10) / 5 + 1, t0 = c * FCH;
@@ -116,10 +139,29 @@ __global__ __launch_bounds__(256) void conv0_partials_kernel(const float* wave, 
   const float* x = wave + (size_t)b * n_max;
   float wr[8][10], piv[8], y[8], s[8], q[8];
   conv0_load_w(w, cg, wr);
-  conv0_frame(x, t0, wr, piv);
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.0f;
   const int t1 = t0 + FCH < T1 ? t0 + FCH : T1;
+  // the centre of a channel's sums: the conv is linear, so its mean over the chunk's frames is the conv of the MEAN WINDOW -- ten
+  // sample means over the chunk (thread i holds frame t0 + i; one fixed tree), the same for all 512 channels.  A centre only has
+  // to lie near the mean: whatever it is, {centre, s, q} describe the chunk exactly up to the rounding of s and q.
+  static_assert(FCH == 256, "one frame of the chunk per thread");
+  {
+    float xm[10];
+    const int tf = t0 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) xm[k] = wave_sum(tf < t1 ? x[5 * tf + k] : 0.0f);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int k = 0; k < 10; ++k) red[0][fq][k] = xm[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 10; ++k) xm[k] = ((red[0][0][k] + red[0][1][k]) + (red[0][2][k] + red[0][3][k])) / (float)(t1 - t0);
+    __syncthreads();
+    conv0_dot(xm, wr, piv);
+  }
+  // pass 2: the sums about that centre
   for (int t = t0 + fq; t < t1; t += 4) {
     conv0_frame(x, t, wr, y);
 #pragma unroll
