@@ -145,13 +145,16 @@ def _mha(x, wq, bq, wk, bk, wv, bv, heads: int, add_mask: Optional[torch.Tensor]
 def bert_last_hidden_state(w: Dict[str, torch.Tensor], input_ids, attention_mask,
                            heads: int = 12, eps: float = 1e-12, collect: Optional[dict] = None) -> torch.Tensor:
     """BertModel(...).last_hidden_state -- text_blocks.py:79.  collect (optional dict): filled with the hidden states after
-    each layer, {1: ..., 2: ...} (BertModel's output_hidden_states[1:]), for per-layer localisation in the tests."""
+    each layer, {1: ..., 2: ...} (BertModel's output_hidden_states[1:]), and the embeddings under 0, for per-layer localisation in the
+    tests.  The arithmetic runs in the weights' dtype: float64 weights make it the float64 yardstick."""
     B, L = input_ids.shape
     H = w["embeddings.word_embeddings.weight"].shape[1]
     x = (w["embeddings.word_embeddings.weight"][input_ids]
          + w["embeddings.position_embeddings.weight"][:L][None]
          + w["embeddings.token_type_embeddings.weight"][0][None, None])
     x = F.layer_norm(x, (H,), w["embeddings.LayerNorm.weight"], w["embeddings.LayerNorm.bias"], eps)
+    if collect is not None:
+        collect[0] = x
     add_mask = (1.0 - attention_mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
     i = 0
     while f"encoder.layer.{i}.attention.self.query.weight" in w:
@@ -197,15 +200,18 @@ def field_mean_l2(parts: torch.Tensor) -> torch.Tensor:
 def vit_pooled(w: Dict[str, torch.Tensor], pixels: torch.Tensor, heads: int = 12,
                eps: float = 1e-5, collect: Optional[dict] = None) -> torch.Tensor:
     """CLIPVisionModel(...).pooler_output: (N,3,224,224) -> (N,768).  collect (optional dict): the residual stream after each
-    layer, {1: ..., 2: ...} (CLIPVisionModel's hidden_states[1:])."""
+    layer, {1: ..., 2: ...} (CLIPVisionModel's hidden_states[1:]), and the embeddings (pre_layrnorm's output) under 0.  The arithmetic
+    runs in the weights' dtype: float64 weights make it the float64 yardstick."""
     V = "vision_model."
     pw = w[V + "embeddings.patch_embedding.weight"]
     H, patch = pw.shape[0], pw.shape[-1]
     N = pixels.shape[0]
-    x = F.conv2d(pixels.float(), pw, bias=None, stride=patch).flatten(2).transpose(1, 2)
+    x = F.conv2d(pixels.to(pw.dtype), pw, bias=None, stride=patch).flatten(2).transpose(1, 2)
     cls = w[V + "embeddings.class_embedding"].expand(N, 1, H)
     x = torch.cat([cls, x], dim=1) + w[V + "embeddings.position_embedding.weight"][None]
     x = F.layer_norm(x, (H,), w[V + "pre_layrnorm.weight"], w[V + "pre_layrnorm.bias"], eps)
+    if collect is not None:
+        collect[0] = x
     i = 0
     while V + f"encoder.layers.{i}.self_attn.q_proj.weight" in w:
         P = V + f"encoder.layers.{i}."

@@ -89,10 +89,11 @@ def case_weights(sd: Dict[str, torch.Tensor], seed: int = 23) -> Dict[str, torch
     return sd
 
 
-def hf_model(sd: Dict[str, torch.Tensor], layers: int, vocab: int = VOCAB, labels: int = LABELS):
+def hf_model(sd: Dict[str, torch.Tensor], layers: int, vocab: int = VOCAB, labels: int = LABELS, hidden: int = HIDDEN, heads: int = HEADS,
+             inter: int = INTER, max_pos: int = MAX_POS):
     from transformers import RobertaConfig, RobertaForSequenceClassification
-    cfg = RobertaConfig(vocab_size=vocab, num_hidden_layers=layers, hidden_size=HIDDEN, num_attention_heads=HEADS, intermediate_size=INTER,
-                        max_position_embeddings=MAX_POS, type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=PAD, num_labels=labels,
+    cfg = RobertaConfig(vocab_size=vocab, num_hidden_layers=layers, hidden_size=hidden, num_attention_heads=heads, intermediate_size=inter,
+                        max_position_embeddings=max_pos, type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=PAD, num_labels=labels,
                         hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, hidden_act="gelu")
     cfg._attn_implementation = "eager"
     m = RobertaForSequenceClassification(cfg).double().eval()
@@ -111,21 +112,12 @@ def _rb(t: torch.Tensor, on: bool) -> torch.Tensor:
     return t.to(torch.bfloat16).double() if on else t
 
 
-@torch.no_grad()
-def mirror(sd: Dict[str, torch.Tensor], ids: torch.Tensor, mask: torch.Tensor, layers: int, bf16: bool = True, form: str = "folded-bf16",
-           heads: int = HEADS, eps: float = 1e-5, pad: int = PAD) -> dict:
-    """form: which of the encoder's three forms is mirrored (FORMS).  A LayerNorm's consumer GEMM reads, unfolded, the rounded LayerNorm
-    output against the rounded weight; folded, the rounded un-normalised row against the rounded W * gamma, normalised with the
-    statistics of the unrounded row.  The residual operand is LayerNorm of the fp32 row, or (bf16 stream) of its rounding."""
+def _post_ln_stack(w: Dict[str, torch.Tensor], prefix: str, x: torch.Tensor, mask: torch.Tensor, layers: int, bf16: bool, form: str, heads: int,
+                   eps: float) -> list:
+    """hidden_states[1 ..] of the post-LN layers `prefix`{i}. (BERT's and RoBERTa's names) over the embeddings x, in the given form."""
     fold, stream = FORMS[form]
     fold, sb = fold and bf16, (stream == "bf16") and bf16
-    w = {k: v.double() for k, v in sd.items()}
-    R, B, L = "roberta.", *ids.shape
-    E = R + "embeddings."
-    H = w[E + "word_embeddings.weight"].shape[1]
-    x = w[E + "word_embeddings.weight"][ids] + w[E + "position_embeddings.weight"][position_ids(ids, pad)] + w[E + "token_type_embeddings.weight"][0]
-    x = F.layer_norm(x, (H,), w[E + "LayerNorm.weight"], w[E + "LayerNorm.bias"], eps)
-    embed = x.clone()
+    B, L, H = x.shape
     keep = (mask != 0)[:, None, None, :]
 
     def lin(a, name):
@@ -154,7 +146,7 @@ def mirror(sd: Dict[str, torch.Tensor], ids: torch.Tensor, mask: torch.Tensor, l
     hs = []
     y_prev, prev_ln = None, None      # the previous layer's feed-forward sums and the LayerNorm that follows them
     for i in range(layers):
-        P = R + f"encoder.layer.{i}."
+        P = prefix + f"{i}."
         if y_prev is None:      # layer 0 reads the embeddings' materialised LayerNorm
             qkv = [lin(x, P + f"attention.self.{n}") for n in ("query", "key", "value")]
             res = _rb(x, sb)
@@ -170,10 +162,44 @@ def mirror(sd: Dict[str, torch.Tensor], ids: torch.Tensor, mask: torch.Tensor, l
         y2 = lin(_rb(a, bf16), P + "output.dense") + residual(y1, P + "attention.output.LayerNorm")
         y_prev, prev_ln = y2, P + "output.LayerNorm"
         hs.append(ln(y2, prev_ln))      # hidden_states[i + 1], as last_hidden_state(n_layers = i + 1) materialises it: from the fp32 sums
+    return hs
+
+
+@torch.no_grad()
+def mirror(sd: Dict[str, torch.Tensor], ids: torch.Tensor, mask: torch.Tensor, layers: int, bf16: bool = True, form: str = "folded-bf16",
+           heads: int = HEADS, eps: float = 1e-5, pad: int = PAD) -> dict:
+    """form: which of the encoder's three forms is mirrored (FORMS).  A LayerNorm's consumer GEMM reads, unfolded, the rounded LayerNorm
+    output against the rounded weight; folded, the rounded un-normalised row against the rounded W * gamma, normalised with the
+    statistics of the unrounded row.  The residual operand is LayerNorm of the fp32 row, or (bf16 stream) of its rounding.  The
+    geometry is the weights' own (H from the word embeddings) and `heads`."""
+    w = {k: v.double() for k, v in sd.items()}
+    E = "roberta.embeddings."
+    H = w[E + "word_embeddings.weight"].shape[1]
+    x = w[E + "word_embeddings.weight"][ids] + w[E + "position_embeddings.weight"][position_ids(ids, pad)] + w[E + "token_type_embeddings.weight"][0]
+    x = F.layer_norm(x, (H,), w[E + "LayerNorm.weight"], w[E + "LayerNorm.bias"], eps)
+    hs = _post_ln_stack(w, "roberta.encoder.layer.", x, mask, layers, bf16, form, heads, eps)
     feat = hs[-1][:, 0]
     t = torch.tanh(feat @ w["classifier.dense.weight"].T + w["classifier.dense.bias"])
     logits = t @ w["classifier.out_proj.weight"].T + w["classifier.out_proj.bias"]
-    return {"embed": embed, "layers": hs, "logits": logits, "class_probs": torch.softmax(logits, dim=-1)}
+    return {"embed": x, "layers": hs, "logits": logits, "class_probs": torch.softmax(logits, dim=-1)}
+
+
+@torch.no_grad()
+def bert_mirror(sd: Dict[str, torch.Tensor], ids: torch.Tensor, mask: torch.Tensor, layers: int, bf16: bool = True, form: str = "folded-bf16",
+                heads: int = 12, eps: float = 1e-12) -> dict:
+    """BertTextEncoder's pass: the same layers under BERT's names, with BERT's position rule (position l is row l) and the masked
+    mean-pool + L2 normalisation of the reference (text_blocks.py:82-100; fp32 in the product, unrounded here).  Returns "embed",
+    "layers" and "feature" (B, H).  With bf16=False it is oracle/encoders_ref.text_features in float64."""
+    w = {k: v.double() for k, v in sd.items()}
+    E = "embeddings."
+    B, L = ids.shape
+    H = w[E + "word_embeddings.weight"].shape[1]
+    x = w[E + "word_embeddings.weight"][ids] + w[E + "position_embeddings.weight"][:L][None] + w[E + "token_type_embeddings.weight"][0]
+    x = F.layer_norm(x, (H,), w[E + "LayerNorm.weight"], w[E + "LayerNorm.bias"], eps)
+    hs = _post_ln_stack(w, "encoder.layer.", x, mask, layers, bf16, form, heads, eps)
+    m = (mask != 0).double()[:, :, None]
+    rep = (hs[-1] * m).sum(dim=1) / m.sum(dim=1).clamp_min(1e-6)
+    return {"embed": x, "layers": hs, "feature": rep / (rep.norm(dim=-1, keepdim=True) + 1e-9)}
 
 
 # ---- the head chain and the arousal, float64

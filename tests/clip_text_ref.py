@@ -36,7 +36,10 @@ VOCAB = 512
 EOS = VOCAB - 1
 # the lengths of the attention-op test (the issue's list): one row, two, the 16-row MFMA tile and its neighbours, the 32-query wave
 # tile, the 64-key block / 64-query workgroup edge from both sides, CLIP's own 77
-ATTN_LENGTHS = (1, 2, 16, 17, 32, 33, 63, 64, 65, 77)
+# ... and, past the tower's own 77 (long-context towers: max_position_embeddings = 248), the second and third key-block / query-workgroup
+# edges from both sides and 248 itself (four key blocks, the last ragged)
+ATTN_LENGTHS = (1, 2, 16, 17, 32, 33, 63, 64, 65, 77, 127, 128, 129, 191, 192, 193, 248)
+ATTN_HEADS = (4, 8, 16)      # the head counts of the widths 256, 512 and 1024
 # the pooled positions of the stage tests at L = 77: row 1, the tile edges 15 | 16, the key-block / workgroup edge 63 | 64, the last row
 STAGE_E = (1, 15, 16, 63, 64, 76)
 STAGE_BATCHES = ((1, 15, 16, 63, 64), (76, 1, 64, 16, 63))      # ... spread over two batches of B = 5
@@ -87,10 +90,15 @@ def case_weights(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return sd
 
 
-def hf_model(sd: Dict[str, torch.Tensor], layers: int, eos_token_id: int = EOS, vocab: int = VOCAB):
+def hf_model(sd: Dict[str, torch.Tensor], layers: int, eos_token_id: int = EOS, vocab: int = VOCAB, hidden: int = HIDDEN, heads: int = HEADS,
+             inter: int = INTER, proj: int = PROJ, max_pos: int = MAX_POS, attn: str = "eager"):
+    """attn: HF's attention implementation.  Its "eager" softmax runs in float32 whatever the model's dtype (modeling_clip.py,
+    eager_attention_forward: softmax(..., dtype=torch.float32)), which leaves the float64 model about one fp32 unit roundoff per layer
+    away from float64; "sdpa" keeps the model's dtype throughout (the geometry table's yardstick, tests/encoder_geometry_cases.py)."""
     from transformers import CLIPTextConfig, CLIPTextModelWithProjection
-    cfg = CLIPTextConfig(vocab_size=vocab, num_hidden_layers=layers, eos_token_id=eos_token_id)
-    cfg._attn_implementation = "eager"
+    cfg = CLIPTextConfig(vocab_size=vocab, num_hidden_layers=layers, eos_token_id=eos_token_id, hidden_size=hidden, num_attention_heads=heads,
+                         intermediate_size=inter, projection_dim=proj, max_position_embeddings=max_pos)
+    cfg._attn_implementation = attn
     m = CLIPTextModelWithProjection(cfg).double().eval()
     m.load_state_dict({k: v.double() for k, v in sd.items()}, strict=True)
     return m

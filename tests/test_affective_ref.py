@@ -49,6 +49,43 @@ def test_mirror_without_rounding_is_hf():
             assert not R.mirror_within_sanity(got, want), (form, R.mirror_within_sanity(got, want))
 
 
+def _geometry_params(kind):
+    from tests import encoder_geometry_cases as G
+    return [pytest.param(c, id=c.id) for c in (G.ROBERTA_CASES if kind == "roberta" else G.BERT_CASES)]
+
+
+@pytest.mark.parametrize("c", _geometry_params("roberta") + _geometry_params("bert"))
+def test_mirror_at_every_geometry_of_the_table(c):
+    """tests/encoder_geometry_cases.py: RoBERTa and BERT at the four widths, L = 40 and 128, in the form the encoder takes there (read
+    from the encoder: at hidden 1024 the unfolded fallback).  With the roundings off the mirror is the float64 yardstick -- HF's
+    RobertaForSequenceClassification at that geometry, oracle/encoders_ref in float64 for BERT -- and with them on it stays inside the
+    sanity band on every input of tests/test_gpu_encoder_geometry.py."""
+    from tests import encoder_geometry_cases as G
+    form = G.form_of(G.text_encoder(c), len(c.lengths), c.L)["form"]
+    assert form in R.FORMS
+    ref, exact = G.text_ref_mirror(c, form, False)
+    for name, got, want in G.stages(ref, exact) + [("embed", exact["embed"], ref["embed"])]:
+        assert torch.allclose(got, want, rtol=0, atol=1e-11), (form, name)
+    _, mir = G.text_ref_mirror(c, form)
+    for name, got, want in G.stages(ref, mir):
+        if name == "class_probs" and c.labels == 1:      # softmax over one label is the constant 1: nothing rounds, the GPU is held to it exactly
+            assert torch.equal(got, want) and bool((want == 1).all())
+            continue
+        assert not R.mirror_within_sanity(got, want), (form, name, R.mirror_within_sanity(got, want))
+
+
+@pytest.mark.parametrize("hidden,form", [(256, "folded-fp32"), (1024, "unfolded")])
+def test_encode_fields_mirror_at_the_tables_widths(hidden, form):
+    """encode_fields' input of tests/test_gpu_encoder_geometry.py (strict: the fp32 stream; unfolded at 1024): exact without roundings,
+    inside the sanity band with them; the record without parts is a zero row in both."""
+    from tests import encoder_geometry_cases as G
+    ref, exact = G.fields_ref_mirror(hidden, form, False)
+    assert torch.allclose(exact, ref, rtol=0, atol=1e-11) and not ref[2].any() and not exact[2].any()
+    assert torch.allclose(ref[:2].norm(dim=-1), torch.ones(2, dtype=torch.float64), atol=1e-8)
+    _, mir = G.fields_ref_mirror(hidden, form)
+    assert not R.mirror_within_sanity(mir[:2], ref[:2]), R.mirror_within_sanity(mir[:2], ref[:2])
+
+
 def test_head_restatement_reproduces_the_reference(golden_dir):
     z = np.load(golden_dir / "affective.npz")
     names = [str(n) for n in z["labels"]]

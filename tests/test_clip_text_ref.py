@@ -54,7 +54,7 @@ def test_fp32_mode_mirror_is_the_yardstick(sd, eos):
         assert float((mir["layers"][k][live] - ref["layers"][k][live]).abs().max()) <= R.EPS32 * scale, k
 
 
-@pytest.mark.parametrize("L", sorted(set(R.ATTN_LENGTHS) - {1}))
+@pytest.mark.parametrize("L", sorted(l for l in set(R.ATTN_LENGTHS) - {1} if l <= R.MAX_POS))
 def test_bf16_mirror_stays_inside_the_sanity_band_at_every_length(sd, L):
     """L = 1 has one row per sample, which IS its EOS: covered by e = 1 and by the stage inputs below."""
     e_list = sorted({1, L // 2, L - 1} - {0})
@@ -85,6 +85,28 @@ def test_bf16_mirror_stays_inside_the_sanity_band_on_the_stage_inputs(sd, eos, e
     for name, m, r in [(f"layer{k + 1}", mir["layers"][k][live], ref["layers"][k][live]) for k in range(LAYERS)] + \
                       [(n, mir[n], ref[n]) for n in ("pooled", "text_embeds", "feature")]:
         assert not R.mirror_within_sanity(m, r), (name, R.mirror_within_sanity(m, r))
+
+
+def _geometry_params():
+    from tests import encoder_geometry_cases as G
+    return [pytest.param(c, eos, k, id=f"{c.id}-eos{eos}-b{k}") for c in G.CLIP_TEXT_CASES for eos in G.EOS_RULES for k in range(len(c.batches))]
+
+
+@pytest.mark.parametrize("c,eos,k", _geometry_params())
+def test_mirror_at_every_geometry_of_the_table(c, eos, k):
+    """tests/encoder_geometry_cases.py: the four widths at L = 77 and the long tower (max_position_embeddings = 248) at L = 128 .. 248.
+    With the roundings off the mirror is HF's float64 model at that geometry (the tolerance of test_fp32_mode_mirror_is_the_yardstick);
+    with them on it stays inside the sanity band on every input of tests/test_gpu_encoder_geometry.py."""
+    from tests import encoder_geometry_cases as G
+    ids, mask = G.clip_text_batch(c, k)
+    live = mask.bool()
+    assert R.pooled_positions(ids, eos).tolist() == list(c.batches[k])
+    ref, exact = G.clip_text_ref_mirror(c, eos, k, False)
+    for name, got, want in G.stages(ref, exact, live) + [("embed", exact["embed"], ref["embed"])]:
+        assert float((got - want).abs().max()) <= R.EPS32 * float(want.abs().max()), name
+    _, mir = G.clip_text_ref_mirror(c, eos, k)
+    for name, got, want in G.stages(ref, mir, live):
+        assert not R.mirror_within_sanity(got, want), (name, R.mirror_within_sanity(got, want))
 
 
 def test_pooled_position_rule_matches_both_hf_branches():

@@ -74,22 +74,31 @@ def _hold_abs(name, got, ref, bound):
 @pytest.mark.parametrize("L", R.ATTN_LENGTHS)
 @pytest.mark.parametrize("B", (1, 3))
 def test_causal_attention_op_against_float64(B, L):
-    """heads = 8; the padded and the cu_seqlens form, each without a key mask and with a prefix mask (key 0 always kept)."""
+    """heads = 4, 8 and 16 (the widths 256, 512 and 1024); the padded and the cu_seqlens form, each without a key mask and with a prefix mask
+    (key 0 always kept).  The lengths run past the tower's own 77 to 248: two to four key blocks and query workgroups, every edge from
+    both sides.  The bound is the derived one at every length: its nblk = ceil(L / 64) follows the key blocks."""
+    for heads in R.ATTN_HEADS:
+        _causal_attention_op(B, L, heads)
+
+
+def _causal_attention_op(B, L, heads):
     from ultrafnd_git_amd import _lib as Lb
-    lib, heads = Lb.lib(), R.HEADS
+    lib = Lb.lib()
     H = heads * 64
     bits = R.attn_inputs(B, L, heads, seed=L)
     qkv = _bf16_dev(bits)
     s = Lb.stream_ptr(torch.device(DEV))
     for mask in (None, R.attn_prefix_mask(B, L)):
-        tag = f"attn.B{B}.L{L}.{'prefix' if mask is not None else 'nomask'}"
+        tag = f"attn.B{B}.L{L}.h{heads}.{'prefix' if mask is not None else 'nomask'}"
         mdev = None if mask is None else torch.from_numpy(mask).to(DEV)
         # ---- padded
         ref, bound = R.causal_attn_ref_bound(bits, mask, B, L, heads)
-        ctx = torch.full((B * L, H), float("nan"), dtype=torch.bfloat16, device=DEV)
+        ctx = torch.full((B * L + 4, H), float("nan"), dtype=torch.bfloat16, device=DEV)      # (four sentinel rows behind the output)
         Lb.check(lib.ufnd_attention_bf16_causal(qkv.data_ptr(), Lb.ptr(mdev), ctx.data_ptr(), B, L, heads, s), "ufnd_attention_bf16_causal")
         torch.cuda.synchronize()
-        ratio = FO.worst_ratio(FO.bf16_f32(_bits_host(ctx)), ref, bound)
+        got = FO.bf16_f32(_bits_host(ctx))
+        assert np.isnan(got[B * L:]).all(), (tag, "a row past B L was written")
+        ratio = FO.worst_ratio(got[:B * L], ref, bound)
         print(f"CLIP_TEXT_ERR {tag}.padded elementwise gpu={ratio:.3e} bound=1.000e+00 ratio_to_bound={ratio:.2f}")
         assert ratio <= 1.0, (tag, "padded", ratio)
         # ---- cu_seqlens: sample b keeps its first n_b rows (L, about half, 1, ...), packed back to back; keys masked by mask[b][key]

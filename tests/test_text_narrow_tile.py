@@ -37,8 +37,9 @@ def test_every_other_pass_keeps_the_librarys_choice(tenc):
 
 
 def test_another_width_keeps_the_librarys_choice():
-    """the rule was measured at N = 768; a narrower encoder (N = 192 is no multiple of the tile's 128 columns) is left alone"""
-    enc = BertTextEncoder(layers=1, hidden=192, heads=3, intermediate=768, vocab_size=64, max_position=128)
+    """the rule was measured at N = 768; a narrower encoder is left alone (N = 256, the narrowest width with row kernels: a width
+    without them no longer constructs, tests/test_encoder_geometry_args.py)"""
+    enc = BertTextEncoder(layers=1, hidden=256, heads=4, intermediate=1024, vocab_size=64, max_position=128)
     assert enc.live_tiles(True, 128, 128) == {} and _chosen(enc, True, 128, 128, "ffn2") == -1
 
 

@@ -32,7 +32,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _lib as L
-from .encoders import BertTextEncoder
+from .encoders import BertTextEncoder, check_geometry
 
 # the reference's substring rules (affective_forensics.py:94-97), in group order: 0 fear, 1 anger, 2 joy
 GROUP_RULES = (("fear", "anx", "worr", "scare"), ("anger", "annoy", "mad", "rage"), ("joy", "happi", "delight", "amuse"))
@@ -61,6 +61,8 @@ class RobertaEmotionClassifier(BertTextEncoder):
         if not 1 <= num_labels <= 32 or num_hidden_layers < 1 or pad_token_id < 0 or max_position_embeddings - pad_token_id - 1 < 1:
             raise ValueError(f"num_labels={num_labels} (1 .. 32), num_hidden_layers={num_hidden_layers} (>= 1), pad_token_id={pad_token_id}, "
                              f"max_position_embeddings={max_position_embeddings}")
+        check_geometry(hidden=("hidden_size", hidden_size), heads=("num_attention_heads", num_attention_heads),
+                       intermediate=("intermediate_size", intermediate_size))
         super().__init__(layers=num_hidden_layers, hidden=hidden_size, heads=num_attention_heads, intermediate=intermediate_size,
                          vocab_size=vocab_size, max_position=max_position_embeddings, type_vocab=type_vocab_size, eps=layer_norm_eps,
                          fold_ln=fold_ln, residual_dtype=residual_dtype)

@@ -95,6 +95,25 @@ def text_slot_bin_count(n_rows) -> int:
     return len(text_slot_bins(n_rows))
 
 
+SUPPORTED_HIDDEN = (256, 512, 768, 1024)      # the widths the row kernels are instantiated for (csrc/rowwise.hpp: h_ok, NI_LAUNCH)
+MAX_PROJECTION = 1024                         # ufnd_l2norm_frames' widest row
+
+
+def check_geometry(hidden=None, heads=None, intermediate=None, projection_dim=None) -> None:
+    """The frozen encoders' constructor arguments against what their kernels are built for, each given as (argument name, value):
+    a ValueError that names the argument and the supported values, instead of a C-ABI refusal at the first launch (DESIGN.md's
+    geometry table).  heads is checked against hidden: the attention kernels are built for a head dimension of 64."""
+    if hidden is not None and hidden[1] not in SUPPORTED_HIDDEN:
+        raise ValueError(f"{hidden[0]}={hidden[1]!r}: one of {SUPPORTED_HIDDEN}, the widths the row kernels are built for")
+    if heads is not None and hidden[1] != heads[1] * 64:
+        raise ValueError(f"{heads[0]}={heads[1]!r}: {hidden[0]} // 64 = {hidden[1] // 64}, head_dim must be 64 ({hidden[0]} == {heads[0]} * 64)")
+    if intermediate is not None and (intermediate[1] < 64 or intermediate[1] % 64):
+        raise ValueError(f"{intermediate[0]}={intermediate[1]!r}: a positive multiple of 64 (the bf16 GEMM's N and K)")
+    if projection_dim is not None and (projection_dim[1] < 64 or projection_dim[1] % 64 or projection_dim[1] > MAX_PROJECTION):
+        raise ValueError(f"{projection_dim[0]}={projection_dim[1]!r}: a multiple of 64 from 64 to {MAX_PROJECTION} (the projection GEMM's N; "
+                         "the L2 normalisation's widest row)")
+
+
 TEXT_TILE_ROWS, TEXT_TILE_SAMPLES, TEXT_TILE_MAX_B = 256, 16, 512      # ufnd_text_pack_tiles (UFND_TEXT_TILE_*)
 TEXT_TILE_INTS, TEXT_TILE_UNIT0, TEXT_TILE_ROWMAP, TEXT_TILE_KBIAS = 576, 36, 64, 320
 
@@ -450,6 +469,7 @@ class BertTextEncoder(_EncoderBase):
                  vocab_size: int = 30522, max_position: int = 512, type_vocab: int = 2, eps: float = 1e-12,
                  fold_ln: bool = True, residual_dtype: str = "bf16", hidden_dropout_prob: float = 0.0,
                  attention_probs_dropout_prob: float = 0.0):
+        check_geometry(hidden=("hidden", hidden), heads=("heads", heads), intermediate=("intermediate", intermediate))
         super().__init__(hidden, heads, fold_ln, residual_dtype)
         # train-mode dropout (HF BertConfig names): applied only by encoder_train.TextBackprop.forward_train and its backward, never
         # by forward() / encode_fields, whatever the module's mode
@@ -540,6 +560,10 @@ class BertTextEncoder(_EncoderBase):
         if Lq > self.max_position:
             raise RuntimeError(f"sequence length {Lq} exceeds max_position_embeddings {self.max_position}")
 
+    def _fuses(self, Lq: int) -> bool:
+        """Whether an L-token pass runs a layer's Q/K/V projection + attention as one launch (two otherwise)."""
+        return bool(self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0)
+
     def live_tiles(self, packed: bool, B: int, Lq: int) -> Dict[str, int]:
         """The tiles a (B, L) pass names for its own live-row launches (text_narrow_tile, above): fixed by the pass's form and shape
         alone, so a captured pass never reads the live row count back.  N = 768 only: the width the choice was measured at."""
@@ -562,7 +586,7 @@ class BertTextEncoder(_EncoderBase):
         mask = attention_mask.to(dev, torch.int32).contiguous()
         p, b = self._pack(), self._workbufs(B, Lq)
         M = B * Lq
-        fuse = self.fuse_qkv_attention and Lq == 128 and self.heads % 2 == 0      # a layer's Q/K/V projection + attention as one launch
+        fuse = self._fuses(Lq)
         cu = b["cu"] if packed else None                 # packed rows: sample b's are cu[b] .. cu[b+1] ...
         live = _live_ptr(cu) if packed else None         # ... and cu[B], their count, stays on the device: the pack kernel writes it
         self._live_tiles = self.live_tiles(packed, B, Lq)
@@ -723,6 +747,13 @@ class ClipVisualEncoder(_EncoderBase):
     def __init__(self, layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072, patch: int = 32,
                  image: int = 224, projection_dim: int = 512, eps: float = 1e-5, fold_ln: bool = True, residual_dtype: str = "bf16",
                  attention_dropout: float = 0.0):
+        check_geometry(hidden=("hidden", hidden), heads=("heads", heads), intermediate=("intermediate", intermediate),
+                       projection_dim=("projection_dim", projection_dim))
+        # ufnd_vit_patchify copies 8-pixel runs of whole patches; the patch GEMM's K = 3 patch^2 is a multiple of 64 with them
+        if patch < 8 or patch % 8:
+            raise ValueError(f"patch={patch!r}: a positive multiple of 8 (the patch GEMM's K = 3 patch^2 is then a multiple of 64)")
+        if image < patch or image % patch:
+            raise ValueError(f"image={image!r}: a positive multiple of patch={patch}")
         super().__init__(hidden, heads, fold_ln, residual_dtype)
         # train-mode dropout on the attention probabilities (HF CLIPVisionConfig name; CLIP has no hidden-state dropout): applied only by
         # encoder_train.VisualBackprop.forward_train and its backward
@@ -808,6 +839,10 @@ class ClipVisualEncoder(_EncoderBase):
         N = frames.shape[0] * frames.shape[1]
         return b["xf"].view(N, self.n_patches + 1, self.hidden)
 
+    def _fuses(self) -> bool:
+        """Whether a pass runs a layer's Q/K/V projection + attention as one launch (samples of at most 64 tokens; two otherwise)."""
+        return bool(self.fuse_qkv_attention and self.n_patches + 1 <= 64)
+
     def _embed(self, fr, p, b, N) -> None:
         """Patchify, patch GEMM, then class token + positions + pre-LayerNorm into the residual stream (folded: hb and its statistics st0)."""
         w, V, s = self._w, "vision_model.", L.stream_ptr(self.device)
@@ -871,7 +906,7 @@ class ClipVisualEncoder(_EncoderBase):
         layers = p["layers"] if n_layers is None else p["layers"][:max(1, int(n_layers))]
         N, T = B * Fr, self.n_patches + 1
         self._embed(fr, p, b, N)
-        if self.fuse_qkv_attention and T <= 64:
+        if self._fuses():
             attend = lambda A, W, bias, **fold: self._qkv_attn(A, W, bias, None, b["ctx"], N, T, self.heads, eps=self.eps, **fold)
         else:
             attend = self._two_launch(b, "ufnd_attention_bf16", operands=(None,), B=N, Lq=T)      # (no key mask: every patch is a key)

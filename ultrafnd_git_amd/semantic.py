@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .encoders import _CLIP_LAYER, ACT_QUICK_GELU, ClipVisualEncoder, _bf16, _EncoderBase, _live_ptr
+from .encoders import _CLIP_LAYER, ACT_QUICK_GELU, ClipVisualEncoder, _bf16, _EncoderBase, _live_ptr, check_geometry
 
 
 class ClipTextEncoder(_EncoderBase):
@@ -45,9 +45,10 @@ class ClipTextEncoder(_EncoderBase):
         setting of a model that is frozen here: accepted, never applied."""
         if hidden_act != "quick_gelu":
             raise ValueError(f"hidden_act={hidden_act!r}: ClipTextEncoder is built for CLIP's 'quick_gelu'")
-        if intermediate_size % 64 or projection_dim % 64 or num_hidden_layers < 1:
-            raise ValueError(f"intermediate_size={intermediate_size}, projection_dim={projection_dim} (multiples of 64), "
-                             f"num_hidden_layers={num_hidden_layers} (>= 1)")
+        check_geometry(hidden=("hidden_size", hidden_size), heads=("num_attention_heads", num_attention_heads),
+                       intermediate=("intermediate_size", intermediate_size), projection_dim=("projection_dim", projection_dim))
+        if num_hidden_layers < 1:
+            raise ValueError(f"num_hidden_layers={num_hidden_layers} (>= 1)")
         super().__init__(hidden_size, num_attention_heads, fold_ln=False, residual_dtype="fp32")      # the plain (unfolded-LayerNorm) layer form
         self.layers, self.inter, self.vocab, self.proj, self.eps = num_hidden_layers, intermediate_size, vocab_size, projection_dim, layer_norm_eps
         self.max_position, self.eos_token_id = max_position_embeddings, int(eos_token_id)
