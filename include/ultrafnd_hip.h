@@ -250,6 +250,18 @@ int ufnd_softmax_ce(const float* logits, const int64_t* labels, int B, float* lo
 int ufnd_softmax_ce_weighted(const float* logits, const int64_t* labels, int B, float w0, float w1, float label_smoothing,
                              float* loss_rows, float* d_logits, ufnd_step_state* state, void* stream);
 
+/* FocalLoss(alpha, gamma), mean reduction, optionally under mixup_criterion, + its gradient: the criterion of the raw-data trainer
+ * (src/training/run_train_eval.py:717,1245-1281).  Per row and label y, pt = p_y, q = the other class's softmax probability (taken
+ * directly from the row's softmax, not as 1 - pt) and ce = -log pt, by the expressions of ufnd_softmax_ce:
+ *   fl(z, y) = alpha q^gamma ce,    d fl / d z_c = alpha (q^gamma + gamma q^(gamma-1) pt ce) (p_c - [c == y]).
+ * labels_b NULL (then mix NULL): state->loss = sum_r fl(z_r, ya_r) / B.  Otherwise mix points at two device floats
+ * (fl32(lam), fl32(1 - lam)) and every row is mix[0] fl(z_r, ya_r) + mix[1] fl(z_r, yb_r): state->loss is their sum / B.  lam is read
+ * on the device: a captured launch serves every draw.  loss_rows (B) or NULL: each row's term, not divided by B; d_logits (B,2) or NULL:
+ * the gradient of state->loss.  alpha finite and > 0; gamma == 0 (no power is evaluated: with alpha = 1 and labels_b NULL every output
+ * has ufnd_softmax_ce's bits) or 1 <= gamma <= 5.  One workgroup, fixed summation order, no atomics. */
+int ufnd_softmax_focal(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* mix, int B, float alpha, float gamma,
+                       float* loss_rows, float* d_logits, ufnd_step_state* state, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * clip_grad_norm_ + AdamW.step over a flat fp32 arena    forensic_trainer.py:292-298,176
  *   grad/param/exp_avg/exp_avg_sq: n floats each (n % 4 == 0, 16-byte aligned).
@@ -545,6 +557,27 @@ typedef struct ufnd_gather_item {
   int64_t src_rows;
 } ufnd_gather_item;
 int ufnd_gather_rows(const int64_t* idx, int B, const ufnd_gather_item* items, int n_items, void* stream);
+
+/* The same launch with mixup_data (src/training/run_train_eval.py:1245-1257) folded in.  perm: n_groups x B int64 (values outside
+ * [0, B) are clamped), mix: n_groups x 2 floats (fl32(lam), fl32(1 - lam)), both in device memory; item i belongs to draw
+ * g = items[i].group.
+ *   kind 0, fp32 rows: dst[r] = fl32(mix[g][0] x[idx[r]]) + fl32(mix[g][1] x[idx[perm[g][r]]]) -- two rounded products and one
+ *           rounded sum, what torch computes for lam * x + (1 - lam) * x[index, :]; dst_b is ignored.  16-byte accesses when
+ *           row_bytes % 16 == 0 and src, dst are 16-B aligned, 8-byte ones otherwise.
+ *   kind 1, labels: dst[r] = src[idx[r]], dst_b[r] = src[idx[perm[g][r]]].
+ * Rows as in ufnd_gather_rows (a multiple of 8 bytes, 8-B aligned, dense; source indices clamped into [0, src_rows)).  No
+ * destination may overlap a source. */
+typedef struct ufnd_mix_item {
+  const void* src;
+  void* dst;
+  void* dst_b;
+  int64_t row_bytes;
+  int64_t src_rows;
+  int kind;
+  int group;
+} ufnd_mix_item;
+int ufnd_gather_mix_rows(const int64_t* idx, const int64_t* perm, const float* mix, int B, const ufnd_mix_item* items, int n_items, int n_groups,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * TemporalSyncNet.align, batched          src/core_blocks/temporal_blocks.py:102-140 (+ _cosine :10-13)

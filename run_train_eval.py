@@ -42,7 +42,22 @@ def parse_args():
                    help="graph behind gnn_feat when the cache has no gnn_Z: the trainer's OCR-Jaccard graph, or the graph builder's "
                         "cosine kNN graph with OCR-overlap and delay weights")
     p.add_argument("--gnn_knn_k", type=int, default=8, help="neighbours per post of --gnn_graph knn (1..64)")
+    # the raw-data trainer's recipe (the reference's train_and_evaluate): focal loss, feature mixup, warm restarts
+    p.add_argument("--criterion", choices=("ce", "focal"), default="ce", help="mean cross-entropy, or FocalLoss(--focal_alpha, --focal_gamma)")
+    p.add_argument("--focal_alpha", type=float, default=1.0)
+    p.add_argument("--focal_gamma", type=float, default=2.0, help="0, or 1..5")
+    p.add_argument("--mixup_alpha", type=float, default=0.0, help="lam ~ Beta(a, a) feature mixup of cached rows; 0 = off (the reference uses 0.2)")
+    p.add_argument("--mixup_prob", type=float, default=0.5, help="share of train batches that are mixed")
+    p.add_argument("--mixup_mode", choices=("shared", "per_modality"), default="shared",
+                   help="one (lam, permutation) per batch, or one per modality as the reference's loop draws them")
+    p.add_argument("--warm_restarts", nargs=3, metavar=("T_0", "T_MULT", "ETA_MIN"), default=None,
+                   help="CosineAnnealingWarmRestarts(T_0, T_mult, eta_min) instead of StepLR(3, 0.7)")
     return p.parse_args()
+
+
+def warm_restarts_arg(v):
+    """--warm_restarts T_0 T_MULT ETA_MIN -> (int, int, float) or None"""
+    return None if v is None else (int(v[0]), int(v[1]), float(v[2]))
 
 
 def main():
@@ -74,7 +89,9 @@ def main():
                       weight_decay=args.weight_decay, gnn_dim=args.gnn_dim, gnn_overlap_thresh=args.gnn_overlap_thresh,
                       seed=args.seed, use_mps=False, use_gnn=(not args.no_gnn), save_best=True, device=f"cuda:{local}",
                       use_graph=not args.no_graph, grad_accum_steps=args.grad_accum_steps,
-                      gnn_graph=args.gnn_graph, gnn_knn_k=args.gnn_knn_k)
+                      gnn_graph=args.gnn_graph, gnn_knn_k=args.gnn_knn_k, criterion=args.criterion, focal_alpha=args.focal_alpha,
+                      focal_gamma=args.focal_gamma, mixup_alpha=args.mixup_alpha, mixup_prob=args.mixup_prob, mixup_mode=args.mixup_mode,
+                      warm_restarts=warm_restarts_arg(args.warm_restarts))
     cache = synthetic_cache(args.synthetic, seed=args.seed, gnn_dim=args.gnn_dim) if args.synthetic else None
     trainer = ForensicTrainer(cfg, cache=cache)
     if not args.eval_only:

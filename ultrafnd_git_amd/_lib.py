@@ -58,6 +58,11 @@ class GatherItem(C.Structure):
     _fields_ = [("src", _FP), ("dst", _FP), ("row_bytes", C.c_int), ("src_rows", C.c_int64)]
 
 
+class MixItem(C.Structure):
+    """ufnd_mix_item: one cached tensor -> one static batch buffer, mixed with its partner row (kind 0) or gathered twice (kind 1)."""
+    _fields_ = [("src", _FP), ("dst", _FP), ("dst_b", _FP), ("row_bytes", C.c_int64), ("src_rows", C.c_int64), ("kind", C.c_int), ("group", C.c_int)]
+
+
 class TcnLayer(C.Structure):
     """ufnd_tcn_layer: one Conv1d + BatchNorm1d block of the sequence path."""
     _fields_ = [(n, _FP) for n in ("w", "b", "gamma", "beta", "running_mean", "running_var")]
@@ -171,6 +176,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.ufnd_softmax_ce.argtypes = [P, P, I, P, P, P, P]
     lib.ufnd_softmax_ce_weighted.argtypes = [P, P, I, C.c_float, C.c_float, C.c_float, P, P, P, P]
     lib.ufnd_softmax_ce_weighted.restype = I
+    lib.ufnd_softmax_focal.argtypes = [P, P, P, P, I, C.c_float, C.c_float, P, P, P, P]
+    lib.ufnd_softmax_focal.restype = I
     lib.ufnd_grad_norm.argtypes = [P, S, P, P, P]
     lib.ufnd_adamw_step.argtypes = [P, P, P, P, S, P, P]
     lib.ufnd_step_advance.argtypes = [P, P]
@@ -372,6 +379,8 @@ def _declare_encoders(lib: C.CDLL) -> None:
     lib.ufnd_vit_unpatchify_attribution.restype = I
     lib.ufnd_gather_rows.argtypes = [P, I, C.POINTER(GatherItem), I, P]
     lib.ufnd_gather_rows.restype = I
+    lib.ufnd_gather_mix_rows.argtypes = [P, P, P, I, C.POINTER(MixItem), I, I, P]
+    lib.ufnd_gather_mix_rows.restype = I
     lib.ufnd_tcn_weight_ld.argtypes = [I, I]
     lib.ufnd_tcn_weight_ld.restype = I
     lib.ufnd_tcn_workspace_floats.argtypes = [I, I, I, I, I]

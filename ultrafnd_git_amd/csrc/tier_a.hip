@@ -991,6 +991,69 @@ __global__ __launch_bounds__(256) void softmax_ce_ws_kernel(const float* logits,
   if (threadIdx.x == 0) st->loss = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / W;
 }
 
+// FocalLoss(alpha, gamma) of the raw-data trainer (run_train_eval.py:1263-1281), optionally under mixup_criterion (:1259-1261).
+// Per row and label y, with pt = p_y, q = the OTHER class's softmax probability (taken from ce_row, never as 1 - pt: that
+// difference has lost every bit once q < 2^-24) and ce = -log pt:
+//   fl = (alpha q^gamma) ce,      d fl / d z_c = (alpha (q^gamma + gamma q^(gamma-1) pt ce)) (p_c - [c == y]).
+// Every operation is rounded on its own (contraction off), in the order written.  gamma == 0 never evaluates a power; gamma == 2 is q q.
+struct FocalRow { float fl, g0, g1; };
+__device__ __forceinline__ FocalRow focal_row(const CeRow& ce, int y, float alpha, float gamma) {
+#pragma clang fp contract(off)
+  const float pt = y ? ce.p1 : ce.p0, q = y ? ce.p0 : ce.p1, n = y ? ce.n1 : ce.n0;
+  float w, k;
+  if (gamma == 0.0f) {
+    w = 1.0f;
+    k = 1.0f;
+  } else {
+    float dw;      // gamma q^(gamma - 1)
+    if (gamma == 2.0f) {
+      w = q * q;
+      dw = 2.0f * q;
+    } else if (gamma == 1.0f) {
+      w = q;
+      dw = 1.0f;
+    } else {
+      w = powf(q, gamma);
+      dw = gamma * powf(q, gamma - 1.0f);
+    }
+    k = w + (dw * pt) * n;
+  }
+  const float ak = alpha * k;
+  return FocalRow{(alpha * w) * n, ak * (ce.p0 - (y == 0 ? 1.f : 0.f)), ak * (ce.p1 - (y == 1 ? 1.f : 0.f))};
+}
+
+// One workgroup, the reduction of softmax_ce_kernel (same order: reruns are bit-identical, and gamma = 0, alpha = 1 without labels_b
+// reproduces that kernel's bits).  With labels_b the row is mix[0] fl(ya) + mix[1] fl(yb) -- two rounded products, one rounded sum --
+// and so is its gradient; mix = (fl32(lam), fl32(1 - lam)) is read from device memory, so one captured launch serves every draw.
+__global__ __launch_bounds__(256) void softmax_focal_kernel(const float* logits, const int64_t* labels_a, const int64_t* labels_b,
+                                                            const float* mix, int B, float alpha, float gamma, float* loss_rows,
+                                                            float* dlog, ufnd_step_state* st) {
+#pragma clang fp contract(off)
+  __shared__ float sh[4];
+  float part = 0;
+  const float lam = labels_b ? mix[0] : 1.0f, mb = labels_b ? mix[1] : 0.0f;
+  for (int r = threadIdx.x; r < B; r += 256) {
+    const CeRow ce = ce_row(logits[r * 2], logits[r * 2 + 1]);
+    FocalRow f = focal_row(ce, labels_a[r] ? 1 : 0, alpha, gamma);
+    if (labels_b) {
+      const FocalRow fb = focal_row(ce, labels_b[r] ? 1 : 0, alpha, gamma);
+      f.fl = lam * f.fl + mb * fb.fl;
+      f.g0 = lam * f.g0 + mb * fb.g0;
+      f.g1 = lam * f.g1 + mb * fb.g1;
+    }
+    if (loss_rows) loss_rows[r] = f.fl;
+    part += f.fl;
+    if (dlog) {
+      dlog[r * 2] = f.g0 / (float)B;
+      dlog[r * 2 + 1] = f.g1 / (float)B;
+    }
+  }
+  part = wave_sum(part);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) st->loss = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / (float)B;
+}
+
 // ---------------------------------------------------------------- explanations
 // deep_truth_classifier.py:189-272 (feature_importance, the smooth-grad branch of explain_shap)
 // The seed of the input-gradient backward, d target / d logits (two floats per row): onehot(c) for sum_b logits[b, c], or
@@ -1913,6 +1976,21 @@ extern "C" int ufnd_softmax_ce(const float* logits, const int64_t* labels, int B
   return UFND_OK;
 }
 
+extern "C" int ufnd_softmax_focal(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* mix, int B, float alpha,
+                                  float gamma, float* loss_rows, float* d_logits, ufnd_step_state* state, void* stream_) {
+  UFND_REQUIRE(logits && labels_a && state && B >= 1, "softmax_focal: null argument");
+  UFND_REQUIRE((labels_b == nullptr) == (mix == nullptr), "softmax_focal: labels_b and mix are given together (mixup) or both NULL");
+  UFND_REQUIRE(ufnd_aligned(labels_a, 8) && ufnd_aligned(labels_b, 8) && ufnd_aligned(state, 8) && ufnd_aligned(mix, 4),
+               "softmax_focal: labels_a, labels_b and state must be 8-B aligned, mix 4-B aligned");
+  UFND_REQUIRE(alpha > 0.0f && alpha <= __FLT_MAX__,"softmax_focal: alpha=%g (finite and > 0)", alpha);
+  UFND_REQUIRE(gamma == 0.0f || (gamma >= 1.0f && gamma <= 5.0f),
+               "softmax_focal: gamma=%g (0, or 1 <= gamma <= 5: the gradient of 0 < gamma < 1 is unbounded as pt -> 1)", gamma);
+  hipLaunchKernelGGL(softmax_focal_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, labels_a, labels_b, mix, B, alpha, gamma,
+                     loss_rows, d_logits, state);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Batch assembly: CachedTensorDataset.__getitem__ + default collate (forensic_trainer.py:60-83,232-234) and the
@@ -1951,6 +2029,92 @@ extern "C" int ufnd_gather_rows(const int64_t* idx, int B, const ufnd_gather_ite
     a.rows[i] = t.src_rows;
   }
   hipLaunchKernelGGL(gather_rows_kernel, dim3(B, n_items), dim3(128), 0, (hipStream_t)stream_, idx, a);
+  UFND_CHECK_LAUNCH();
+  return UFND_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same launch with mixup_data (run_train_eval.py:1245-1257) folded in: a feature row is gathered together with its partner's,
+//   dst[r] = fl32(mix[g][0] x[idx[r]]) + fl32(mix[g][1] x[idx[perm[g][r]]])
+// (two rounded products, one rounded sum: torch's lam * x + (1 - lam) * x[index, :] on fp32), a label row is gathered twice
+// (y_a = y[idx[r]], y_b = y[idx[perm[g][r]]]).  lam and the permutation are read from device memory: nothing of a draw is a
+// kernel argument, so the launch can be replayed.  Every destination differs from every source: no in-place hazard.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct MixArgs {
+  const char* src[UFND_GATHER_MAX_ITEMS];
+  char* dst[UFND_GATHER_MAX_ITEMS];
+  char* dst_b[UFND_GATHER_MAX_ITEMS];
+  long long rows[UFND_GATHER_MAX_ITEMS];
+  int words[UFND_GATHER_MAX_ITEMS];      // row size in 8-byte words
+  int kind[UFND_GATHER_MAX_ITEMS];       // 0: fp32 rows, narrow (8-byte accesses); 1: labels; 2: fp32 rows, 16-byte accesses
+  int group[UFND_GATHER_MAX_ITEMS];
+};
+
+__global__ __launch_bounds__(128) void gather_mix_rows_kernel(const int64_t* __restrict__ idx, const int64_t* __restrict__ perm,
+                                                              const float* __restrict__ mix, int B, MixArgs a) {
+#pragma clang fp contract(off)
+  const int r = blockIdx.x, it = blockIdx.y, g = a.group[it], words = a.words[it];
+  const long long rows = a.rows[it];
+  long long pr = perm[(size_t)g * B + r];
+  pr = pr < 0 ? 0 : (pr < B ? pr : B - 1);
+  long long i = idx[r], j = idx[pr];
+  i = i < 0 ? 0 : (i < rows ? i : rows - 1);
+  j = j < 0 ? 0 : (j < rows ? j : rows - 1);
+  const char* sa = a.src[it] + (size_t)i * words * 8;
+  const char* sb = a.src[it] + (size_t)j * words * 8;
+  char* d = a.dst[it] + (size_t)r * words * 8;
+  if (a.kind[it] == 1) {
+    uint64_t* db = reinterpret_cast<uint64_t*>(a.dst_b[it] + (size_t)r * words * 8);
+    for (int w = threadIdx.x; w < words; w += 128) {
+      reinterpret_cast<uint64_t*>(d)[w] = reinterpret_cast<const uint64_t*>(sa)[w];
+      db[w] = reinterpret_cast<const uint64_t*>(sb)[w];
+    }
+    return;
+  }
+  const float lam = mix[2 * g], mb = mix[2 * g + 1];
+  if (a.kind[it] == 2) {
+    for (int w = threadIdx.x; w < words / 2; w += 128) {
+      const f32x4 x = ld4(reinterpret_cast<const float*>(sa) + 4 * w), y = ld4(reinterpret_cast<const float*>(sb) + 4 * w);
+      f32x4 o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = lam * x[c] + mb * y[c];
+      st4(reinterpret_cast<float*>(d) + 4 * w, o);
+    }
+  } else {
+    for (int w = threadIdx.x; w < words; w += 128) {
+      const float2 x = reinterpret_cast<const float2*>(sa)[w], y = reinterpret_cast<const float2*>(sb)[w];
+      reinterpret_cast<float2*>(d)[w] = make_float2(lam * x.x + mb * y.x, lam * x.y + mb * y.y);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int ufnd_gather_mix_rows(const int64_t* idx, const int64_t* perm, const float* mix, int B, const ufnd_mix_item* items, int n_items,
+                                    int n_groups, void* stream_) {
+  UFND_REQUIRE(idx && perm && mix && items && B >= 1 && n_items >= 1 && n_items <= UFND_GATHER_MAX_ITEMS, "gather_mix_rows: B=%d items=%d", B,
+               n_items);
+  UFND_REQUIRE(n_groups >= 1 && n_groups <= UFND_GATHER_MAX_ITEMS, "gather_mix_rows: n_groups=%d", n_groups);
+  UFND_REQUIRE(ufnd_aligned(idx, 8) && ufnd_aligned(perm, 8) && ufnd_aligned(mix, 4), "gather_mix_rows: idx and perm must be 8-B aligned, mix 4-B aligned");
+  MixArgs a;
+  for (int i = 0; i < n_items; ++i) {
+    const ufnd_mix_item& t = items[i];
+    UFND_REQUIRE(t.src && t.dst && t.row_bytes >= 8 && t.row_bytes % 8 == 0 && t.row_bytes <= (int64_t)__INT_MAX__ && t.src_rows >= 1,
+                 "gather_mix_rows: item %d (row_bytes=%lld rows=%lld)", i, (long long)t.row_bytes, (long long)t.src_rows);
+    UFND_REQUIRE(t.kind == 0 || t.kind == 1, "gather_mix_rows: item %d kind=%d (0: fp32 rows, 1: labels)", i, t.kind);
+    UFND_REQUIRE(t.group >= 0 && t.group < n_groups, "gather_mix_rows: item %d group=%d of %d", i, t.group, n_groups);
+    UFND_REQUIRE(t.kind == 0 || t.dst_b, "gather_mix_rows: item %d (labels) needs dst_b", i);
+    UFND_REQUIRE(ufnd_aligned(t.src, 8) && ufnd_aligned(t.dst, 8) && ufnd_aligned(t.dst_b, 8), "gather_mix_rows: item %d must be 8-B aligned", i);
+    a.src[i] = static_cast<const char*>(t.src);
+    a.dst[i] = static_cast<char*>(t.dst);
+    a.dst_b[i] = static_cast<char*>(t.dst_b);
+    a.words[i] = (int)(t.row_bytes / 8);
+    a.rows[i] = t.src_rows;
+    a.kind[i] = t.kind;
+    if (t.kind == 0 && t.row_bytes % 16 == 0 && ufnd_aligned(t.src, 16) && ufnd_aligned(t.dst, 16)) a.kind[i] = 2;
+    a.group[i] = t.group;
+  }
+  hipLaunchKernelGGL(gather_mix_rows_kernel, dim3(B, n_items), dim3(128), 0, (hipStream_t)stream_, idx, perm, mix, B, a);
   UFND_CHECK_LAUNCH();
   return UFND_OK;
 }

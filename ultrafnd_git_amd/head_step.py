@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -28,7 +29,17 @@ class HeadStep:
         self.head_graph = bool(cfg.use_graph and cfg.head_graph)
         # the two-call fused form of the step (ufnd_head_forward_loss / ufnd_head_backward: 22 launches instead of 26, same bits) whenever
         # the criterion is the plain mean CE; the weighted / label-smoothed criterion keeps the five module-level calls
-        self.fused_entries = not (cfg.label_smoothing > 0.0 or cfg.class_weighting) and bool(getattr(cfg, "fused_head", True))
+        # the raw-data recipe (run_train_eval.py): focal criterion and / or feature mixup, through ufnd_softmax_focal on the five-call path
+        self.focal = getattr(cfg, "criterion", "ce") == "focal"
+        self.mixup = float(getattr(cfg, "mixup_alpha", 0.0)) > 0.0
+        self.mix_groups = 4 if getattr(cfg, "mixup_mode", "shared") == "per_modality" else 1
+        self.fused_entries = not (cfg.label_smoothing > 0.0 or cfg.class_weighting or self.focal or self.mixup) and \
+            bool(getattr(cfg, "fused_head", True))
+        # one generator per rank for the step's (lam, permutation) draws; `draw_source(B) -> (lams, perms)` replaces it (tests)
+        self.mix_rng = np.random.default_rng([int(getattr(cfg, "seed", 0)), int(getattr(reducer, "rank", 0))]) if self.mixup else None
+        self.draw_source: Optional[Callable[[int], Tuple[np.ndarray, np.ndarray]]] = None
+        self._draw_ring: list = []
+        self._draw_next = 0
         self._dw_stream: Optional[torch.cuda.Stream] = None
         self._iota: Optional[torch.Tensor] = None
         # aux columns the classifier reads per row: aux_dim with use_aux, else none (the reference ignores aux then,
@@ -64,6 +75,12 @@ class HeadStep:
                 "logits": torch.empty(B, 2, dtype=f32, device=dev), "probs": torch.empty(B, 2, dtype=f32, device=dev),
                 "forensic": torch.empty(3, B, dtype=f32, device=dev), "dlogits": torch.empty(B, 2, dtype=f32, device=dev),
                 "dfused": torch.empty(B, self.fusion.hidden, dtype=f32, device=dev), "graph": None}
+            if self.mixup and train:
+                # one device block [perm: groups x B int64 | mix: groups x 2 floats], filled by one copy per step (stage_draw)
+                G = self.mix_groups
+                draw = torch.empty(G * B * 8 + G * 2 * 4, dtype=torch.uint8, device=dev)
+                self.step_bufs[key].update({"draw": draw, "perm": draw[:G * B * 8].view(torch.int64).view(G, B),
+                                            "mix": draw[G * B * 8:].view(f32).view(G, 2), "label_b": torch.empty(B, dtype=torch.int64, device=dev)})
             if self.gnn_node_dim is not None:
                 self.step_bufs[key].update({"gnn_x": torch.empty(B, self.gnn_node_dim, dtype=f32, device=dev),
                                             "gnn_adj": torch.zeros(B, B, dtype=f32, device=dev),
@@ -82,9 +99,74 @@ class HeadStep:
             self._iota = torch.arange(max(B, 256), dtype=torch.int64, device=self.device)
         return self._iota
 
-    def gather_cached(self, b: dict, ds: CachedTensorDataset, idx: torch.Tensor) -> None:
-        """Cached features named by row index: one launch gathers every tensor (and gnn_Z, forensic_trainer.py:240-252)."""
+    # ------------------------------------------------------------------ mixup: the per-step draw and the mixing gather
+    def draw(self, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(lams (groups,) float64, perms (groups, B) int64) of one micro-batch: mixup_data's distribution (run_train_eval.py:1245-1257) --
+        with probability mixup_prob lam ~ Beta(a, a) and a uniform permutation, else lam = 1 and the identity (:816-825).  "shared":
+        one draw; "per_modality": four, in the order text, audio, visual, temporal, each with its own lam and permutation (:818-821)."""
+        if self.draw_source is not None:
+            lams, perms = self.draw_source(B)
+            return np.asarray(lams, dtype=np.float64).reshape(self.mix_groups), np.asarray(perms, dtype=np.int64).reshape(self.mix_groups, B)
+        rng, a = self.mix_rng, float(self.cfg.mixup_alpha)
+        lams, perms = np.ones(self.mix_groups), np.tile(np.arange(B, dtype=np.int64), (self.mix_groups, 1))
+        if rng.random() < float(self.cfg.mixup_prob):
+            for g in range(self.mix_groups):
+                lams[g] = rng.beta(a, a)
+                perms[g] = rng.permutation(B)
+        return lams, perms
+
+    def stage_draw(self, b: dict, B: int) -> None:
+        """This micro-batch's draw into the step's device block: packed into a pinned host buffer, ONE asynchronous copy on the step's
+        stream in front of the gather.  mix = (fl32(lam), fl32(1 - lam)), the difference formed in double and rounded once.  The pinned
+        buffers rotate; one is rewritten only after the copy that read it has completed (eight steps back: the host does not wait)."""
+        G, nbytes = self.mix_groups, b["draw"].numel()
+        lams, perms = self.draw(B)
+        if len(self._draw_ring) < 8:
+            self._draw_ring.append([torch.empty(0, dtype=torch.uint8).pin_memory(), torch.cuda.Event()])
+            slot = self._draw_ring[-1]
+        else:
+            slot = self._draw_ring[self._draw_next]
+            self._draw_next = (self._draw_next + 1) % 8
+            slot[1].synchronize()
+        if slot[0].numel() < nbytes:
+            slot[0] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        host = slot[0][:nbytes].numpy()
+        host[:G * B * 8].view(np.int64)[:] = perms.ravel()
+        host[G * B * 8:].view(np.float32)[:] = np.stack([lams, 1.0 - lams], 1).astype(np.float32).ravel()
+        b["draw"].copy_(slot[0][:nbytes], non_blocking=True)
+        slot[1].record(torch.cuda.current_stream(self.device))
+
+    def gather_mixed(self, b: dict, idx_ptr: int, n: int, items) -> None:
+        """items: (src_ptr, dst, dst_b or None, row_bytes, src_rows, kind, group) -> ONE ufnd_gather_mix_rows launch"""
+        arr = (L.MixItem * len(items))()
+        for it, (src_ptr, dst, dst_b, rb, rows, kind, group) in zip(arr, items):
+            it.src, it.dst, it.dst_b = src_ptr, dst.data_ptr(), None if dst_b is None else dst_b.data_ptr()
+            it.row_bytes, it.src_rows, it.kind, it.group = rb, rows, kind, group
+        L.check(L.lib().ufnd_gather_mix_rows(idx_ptr, b["perm"].data_ptr(), b["mix"].data_ptr(), n, arr, len(items), self.mix_groups,
+                                             L.stream_ptr(self.device)), "ufnd_gather_mix_rows")
+
+    def gather_cached(self, b: dict, ds: CachedTensorDataset, idx: torch.Tensor, mix: bool = False) -> None:
+        """Cached features named by row index: one launch gathers every tensor (and gnn_Z, forensic_trainer.py:240-252).  `mix` (train
+        batches, with mixup on): the same launch mixes every feature row with its partner's and gathers both label rows."""
         idx = idx.to(self.device, torch.int64).contiguous()
+        if mix and self.mixup and "perm" in b:
+            B = idx.numel()
+            if B != b["label"].numel():
+                raise RuntimeError(f"mixup: {B} indices for a step buffer of {b['label'].numel()} rows")
+            self.stage_draw(b, B)
+            items = []
+            per = self.mix_groups == 4      # per_modality: text, audio, visual, temporal draw 0..3; labels, gnn and aux follow the text draw
+            for src, dst, kind, group in ((ds.T, b["text"], 0, 0), (ds.A, b["audio"], 0, 1 if per else 0), (ds.V, b["visual"], 0, 2 if per else 0),
+                                          (ds.U, b["temporal"], 0, 3 if per else 0), (ds.AUX, b["aux"], 0, 0), (ds.y, b["label"], 1, 0),
+                                          (ds.G, b["gnn"], 0, 0)):
+                if dst is b["aux"] and not self.aux_dim:
+                    continue
+                rb = src[0].numel() * src.element_size()
+                if not src.is_contiguous() or src.dtype != dst.dtype or rb != dst[0].numel() * dst.element_size() or src.device != dst.device:
+                    raise RuntimeError(f"cached tensor {tuple(src.shape)} {src.dtype} does not match its batch buffer {tuple(dst.shape)} {dst.dtype}")
+                items.append((src.data_ptr(), dst, b["label_b"] if kind == 1 else None, rb, src.shape[0], kind, group))
+            self.gather_mixed(b, idx.data_ptr(), B, items)
+            return
         pairs = []
         for src, dst in ((ds.T, b["text"]), (ds.A, b["audio"]), (ds.V, b["visual"]), (ds.U, b["temporal"]), (ds.AUX, b["aux"]),
                          (ds.y, b["label"]), (ds.G, b["gnn"])):
@@ -158,7 +240,15 @@ class HeadStep:
         L.check(lib.ufnd_classifier_forward(C.byref(d), C.byref(self.clf.param_table()), b["xin"], b["ldx"],
                                             self._aux_ptr(b), B, int(train), b["cws"].data_ptr(), b["logits"].data_ptr(),
                                             b["probs"].data_ptr(), st, s), "ufnd_classifier_forward")
-        if self.cfg.label_smoothing > 0.0 or self.cfg.class_weighting:
+        if self.focal or self.mixup:
+            # with mixup and the CE criterion: gamma = 0, alpha = 1 (the kernel's CE arm).  Forward-only calls (validation, test, a
+            # train-split forward) and buffers without a draw never mix: labels_b = NULL.
+            mixed = with_loss_grad and "label_b" in b
+            alpha, gamma = (float(self.cfg.focal_alpha), float(self.cfg.focal_gamma)) if self.focal else (1.0, 0.0)
+            L.check(lib.ufnd_softmax_focal(b["logits"].data_ptr(), b["label"].data_ptr(), b["label_b"].data_ptr() if mixed else None,
+                                           b["mix"].data_ptr() if mixed else None, B, alpha, gamma, None,
+                                           b["dlogits"].data_ptr() if with_loss_grad else None, st, s), "ufnd_softmax_focal")
+        elif self.cfg.label_smoothing > 0.0 or self.cfg.class_weighting:
             L.check(lib.ufnd_softmax_ce_weighted(b["logits"].data_ptr(), b["label"].data_ptr(), B, self.ce_w[0], self.ce_w[1],
                                                  float(self.cfg.label_smoothing), None,
                                                  b["dlogits"].data_ptr() if with_loss_grad else None, st, s), "ufnd_softmax_ce_weighted")

@@ -14,6 +14,7 @@ mean over the k' micro-batches of the group (k' < k for a group cut short: `load
 """
 from __future__ import annotations
 
+import math
 from typing import List
 
 import torch
@@ -149,3 +150,31 @@ class CosineAnnealingLR:
         self.last_epoch += 1
         lr = self.eta_min + (self.base_lr - self.eta_min) * (1 + self._math.cos(self._math.pi * self.last_epoch / self.T_max)) / 2
         self.optim.set_lr(lr)
+
+
+class CosineAnnealingWarmRestarts:
+    """torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(optim, T_0, T_mult, eta_min) for FusedAdamW (closed form), the raw-data
+    trainer's schedule (run_train_eval.py:726,729: T_0 = 5 | 10, T_mult = 2, eta_min = 1e-6).  Stepped once per epoch; T_cur and
+    T_i are kept as torch's class keeps them when step() is called without an argument, and the expression is torch's, operation
+    by operation, so the learning rates agree to the last bit of the double."""
+
+    def __init__(self, optim: FusedAdamW, T_0: int, T_mult: int = 1, eta_min: float = 0.0):
+        if isinstance(T_0, bool) or not isinstance(T_0, int) or T_0 <= 0:
+            raise ValueError(f"T_0={T_0!r}: a positive integer (epochs of the first cycle)")
+        if isinstance(T_mult, bool) or not isinstance(T_mult, int) or T_mult < 1:
+            raise ValueError(f"T_mult={T_mult!r}: an integer >= 1 (cycle length multiplier)")
+        self.optim, self.T_0, self.T_i, self.T_mult, self.eta_min = optim, T_0, T_0, T_mult, float(eta_min)
+        self.base_lr = optim.param_groups[0]["initial_lr"]
+        self.T_cur = 0
+        self.last_epoch = 0
+
+    def get_last_lr(self):
+        return [self.optim.param_groups[0]["lr"]]
+
+    def step(self) -> None:
+        self.last_epoch += 1
+        self.T_cur += 1
+        if self.T_cur >= self.T_i:
+            self.T_cur -= self.T_i
+            self.T_i *= self.T_mult
+        self.optim.set_lr(self.eta_min + (self.base_lr - self.eta_min) * (1 + math.cos(math.pi * self.T_cur / self.T_i)) / 2)

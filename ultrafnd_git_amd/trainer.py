@@ -32,6 +32,7 @@ over the node features, re-weighted by phrase overlap and delay differences), wh
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import InitVar, dataclass
 from typing import Dict, List, Optional, Tuple
@@ -48,7 +49,7 @@ from .encoders import dropout_prob
 from .fusion import CrossModalTransformer
 from .head_step import HeadStep
 from .metrics import aggregate_epoch_metrics, pretty_print
-from .optim import CosineAnnealingLR, FusedAdamW, StepLR
+from .optim import CosineAnnealingLR, CosineAnnealingWarmRestarts, FusedAdamW, StepLR
 from .pipeline import EncoderPipeline
 
 
@@ -118,8 +119,23 @@ class TrainConfig:
     # attributes, like grad_accum_steps.
     gnn_graph: InitVar[str] = "ocr"
     gnn_knn_k: InitVar[int] = 8
+    # the raw-data trainer's recipe (run_train_eval.py::train_and_evaluate): criterion "ce" | "focal" (FocalLoss(focal_alpha, focal_gamma),
+    # :717,1263-1281); feature mixup (:816-825,1245-1261) with lam ~ Beta(mixup_alpha, mixup_alpha) applied to a batch with probability
+    # mixup_prob, 0 = off; mixup_mode "shared" (one (lam, permutation) for every input of the step) | "per_modality" (one draw each for
+    # text, audio, visual, temporal, as :818-821 does; labels, loss weights, gnn and aux follow the text draw);
+    # warm_restarts (T_0, T_mult, eta_min) = CosineAnnealingWarmRestarts (:726,729) instead of StepLR.  Init-only options kept as
+    # attributes, like grad_accum_steps; the defaults run no new code.
+    criterion: InitVar[str] = "ce"
+    focal_alpha: InitVar[float] = 1.0
+    focal_gamma: InitVar[float] = 2.0
+    mixup_alpha: InitVar[float] = 0.0
+    mixup_prob: InitVar[float] = 0.5
+    mixup_mode: InitVar[str] = "shared"
+    warm_restarts: InitVar[Optional[Tuple[int, int, float]]] = None
 
-    def __post_init__(self, encoder_dropout: Optional[float], grad_accum_steps: int = 1, gnn_graph: str = "ocr", gnn_knn_k: int = 8):
+    def __post_init__(self, encoder_dropout: Optional[float], grad_accum_steps: int = 1, gnn_graph: str = "ocr", gnn_knn_k: int = 8,
+                      criterion: str = "ce", focal_alpha: float = 1.0, focal_gamma: float = 2.0, mixup_alpha: float = 0.0,
+                      mixup_prob: float = 0.5, mixup_mode: str = "shared", warm_restarts=None):
         self.encoder_dropout = None if encoder_dropout is None else dropout_prob("encoder_dropout", encoder_dropout)
         k = grad_accum_steps
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
@@ -133,6 +149,46 @@ class TrainConfig:
             raise ValueError('gnn_graph="knn" with gnn_in_graph=True: the integrated variant builds a zero-diagonal OCR graph per '
                              'mini-batch; the kNN graph (unit diagonal) feeds the cached gnn_feat table only')
         self.gnn_graph, self.gnn_knn_k = gnn_graph, int(gnn_knn_k)
+        if criterion not in ("ce", "focal"):
+            raise ValueError(f'criterion={criterion!r}: "ce" (mean cross-entropy) or "focal" (FocalLoss(focal_alpha, focal_gamma))')
+        real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating)) and math.isfinite(float(x))
+        if not real(focal_alpha) or float(focal_alpha) <= 0.0:
+            raise ValueError(f"focal_alpha={focal_alpha!r}: a finite number > 0")
+        if not real(focal_gamma) or not (float(focal_gamma) == 0.0 or 1.0 <= float(focal_gamma) <= 5.0):
+            raise ValueError(f"focal_gamma={focal_gamma!r}: 0, or a number in [1, 5] (the gradient of 0 < gamma < 1 is unbounded as pt -> 1)")
+        if not real(mixup_alpha) or float(mixup_alpha) < 0.0:
+            raise ValueError(f"mixup_alpha={mixup_alpha!r}: a finite number >= 0 (0 = no mixup; lam ~ Beta(mixup_alpha, mixup_alpha))")
+        if not real(mixup_prob) or not 0.0 <= float(mixup_prob) <= 1.0:
+            raise ValueError(f"mixup_prob={mixup_prob!r}: a probability in [0, 1] (the share of batches that are mixed)")
+        if mixup_mode not in ("shared", "per_modality"):
+            raise ValueError(f'mixup_mode={mixup_mode!r}: "shared" (one draw per batch) or "per_modality" (one per text / audio / visual / temporal)')
+        if warm_restarts is not None:
+            wr = tuple(warm_restarts) if isinstance(warm_restarts, (tuple, list)) else ()
+            integer = lambda x: not isinstance(x, bool) and isinstance(x, (int, np.integer))
+            if len(wr) != 3 or not integer(wr[0]) or int(wr[0]) < 1 or not integer(wr[1]) or int(wr[1]) < 1 or not real(wr[2]) or float(wr[2]) < 0.0:
+                raise ValueError(f"warm_restarts={warm_restarts!r}: None or (T_0, T_mult, eta_min) with integers T_0 >= 1, T_mult >= 1 and eta_min >= 0")
+            warm_restarts = (int(wr[0]), int(wr[1]), float(wr[2]))
+        self.criterion, self.focal_alpha, self.focal_gamma = criterion, float(focal_alpha), float(focal_gamma)
+        self.mixup_alpha, self.mixup_prob, self.mixup_mode, self.warm_restarts = float(mixup_alpha), float(mixup_prob), mixup_mode, warm_restarts
+        check_recipe(self)
+
+
+def check_recipe(cfg: "TrainConfig") -> None:
+    """The combinations the raw-data recipe refuses, each by the names of its arguments (at construction of the config and again of the
+    trainer: fields can be set in between)."""
+    if cfg.mixup_alpha > 0.0:
+        if cfg.encode_inline:
+            raise ValueError("mixup_alpha > 0 with encode_inline=True: mixup mixes cached feature rows while they are gathered; features "
+                             "that the encoders produce inside the step are not mixed")
+        if cfg.train_encoders:
+            raise ValueError("mixup_alpha > 0 with train_encoders=True: the encoders' backward would need the transposed mix of the feature gradients")
+        if cfg.gnn_in_graph:
+            raise ValueError("mixup_alpha > 0 with gnn_in_graph=True: the mini-batch graph is built from unmixed posts")
+    if cfg.criterion == "focal" and (cfg.label_smoothing > 0.0 or cfg.class_weighting):
+        raise ValueError('criterion="focal" with label_smoothing > 0 or class_weighting=True: the focal criterion has neither '
+                         "(the reference's FocalLoss is unweighted and unsmoothed)")
+    if cfg.warm_restarts is not None and cfg.use_cosine:
+        raise ValueError("warm_restarts with use_cosine=True: one schedule at a time (CosineAnnealingWarmRestarts or CosineAnnealingLR)")
 
 
 def apply_encoder_dropout(cfg: "TrainConfig", text_encoder, visual_encoder) -> None:
@@ -155,6 +211,7 @@ class ForensicTrainer:
                              f'accumulate: grad_accum_steps={k_acc} needs grad_exchange "all_reduce" or "rs_ag"')
         if cfg.gnn_graph == "knn" and cfg.gnn_in_graph:       # (also refused at construction; fields can be set afterwards)
             raise ValueError('gnn_graph="knn" with gnn_in_graph=True: the mini-batch graph of the integrated variant expects a zero diagonal')
+        check_recipe(cfg)
         os.makedirs(cfg.out_dir, exist_ok=True)
         self.device = torch.device(cfg.device)
         if self.device.type != "cuda":
@@ -259,7 +316,10 @@ class ForensicTrainer:
                                 seed=cfg.seed + 1000 * self.rank, grad_scale=self.reducer.grad_scale, accum_steps=k_acc)
         if self.text_bp is not None:        # encoder dropout draws from the head's step state: one (seed, step) per rank and step
             self.text_bp.drop_state = self.vis_bp.drop_state = self.optim.state
-        if cfg.use_cosine:
+        if cfg.warm_restarts is not None:
+            T_0, T_mult, eta_min = cfg.warm_restarts
+            self.scheduler = CosineAnnealingWarmRestarts(self.optim, T_0=T_0, T_mult=T_mult, eta_min=eta_min)
+        elif cfg.use_cosine:
             self.scheduler = CosineAnnealingLR(self.optim, T_max=cfg.epochs, eta_min=cfg.lr * cfg.min_lr_scale)
         else:
             self.scheduler = StepLR(self.optim, step_size=3, gamma=0.7)
@@ -325,8 +385,11 @@ class ForensicTrainer:
         """Fill the step's static buffers from a batch; features come from the cache or from the encoders."""
         if type(batch) is IndexedBatch and batch.ds.G is not None and not dict.__contains__(batch, "gnn_feat") and \
                 not (self.cfg.encode_inline and "input_ids" in batch):
-            self.head.gather_cached(b, batch.ds, dict.__getitem__(batch, "index"))
+            self.head.gather_cached(b, batch.ds, dict.__getitem__(batch, "index"), mix=split == "train")
             return
+        if self.head.mixup and split == "train" and "perm" in b:
+            raise NotImplementedError("mixup_alpha > 0 mixes rows of the device-resident cache while they are gathered (IndexedBatch, as the "
+                                      "trainer's loaders yield them); a train batch that brings its own feature tensors is not mixed")
         inline = self.cfg.encode_inline and "input_ids" in batch
         if inline:
             if self.text_bp is not None and self._enc_dirty:      # the masters moved since the frozen path last packed its operands
